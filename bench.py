@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Benchmark: batched CBF-NMPC solves on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config 2] [--agents A]
+    python bench.py [--gpus N --steps K --warmup W] [--config 2] [--agents A] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps,
+writes the outputs if asked and prints the result line.  --full adds what takes runs of its own:
+the kernel times on the launch stream and the roofline figures built on them, and the CPU
+baselines (cpu_baseline; --no-cpu-baseline leaves those out again).  --dump-outputs DIR writes
+what the last timed step computed -- the arrays a caller of the timed path receives -- as
+DIR/<name>.npy (float64; at most 64 MB in all, beyond that a fixed seeded sample of the rows);
+the inputs are seeded, so two builds of the library compare output for output.
 
 --gpus N > 1 without a launcher starts N ranks itself (torch.distributed.run on 127.0.0.1, one
 process per GPU); under a launcher WORLD_SIZE must equal N or the run exits non-zero.
@@ -89,6 +97,26 @@ def host_threads():
     if env and env.isdigit() and int(env) > 0:
         return int(env)
     return max(1, os.cpu_count() or 1)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, world, rank):
+    """--dump-outputs: the output tensors of the last timed step as <path>/<name>.npy (float64;
+    <name>.rank<r>.npy for the shards of a multi-GPU run).  Beyond DUMP_LIMIT_BYTES per run every
+    array keeps the same fixed, seeded sample of its rows (one row per agent), in order."""
+    arrs = {k: np.ascontiguousarray(v.detach().cpu().numpy(), dtype=np.float64) for k, v in out.items() if v is not None}
+    rows = next(iter(arrs.values())).shape[0]
+    per_row = sum(a.nbytes for a in arrs.values()) // max(1, rows)
+    keep = DUMP_LIMIT_BYTES // world // max(1, per_row)
+    if keep < rows:
+        idx = np.sort(np.random.default_rng(20240521).choice(rows, size=keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["sample_rows"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}.npy" if world == 1 else f"{k}.rank{rank}.npy"), a)
 
 
 def cpu_baseline(cfg, b, budget_s):
@@ -231,7 +259,7 @@ def main_ll(args, world, rank, local_rank, dev):
         step()
     torch.cuda.synchronize(dev)
     kern = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):      # --full: kernel duration on its launch stream, for the roofline
         step()
         kern.append(ctrl.last_kernel_ms())
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
@@ -252,12 +280,21 @@ def main_ll(args, world, rank, local_rank, dev):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, world, rank)
     status = out["status"].cpu().numpy(); iters = out["iters"].cpu().numpy()
-    cnt = full["ind"][lo:hi].sum(1)
-    kms = float(np.median(kern))
-    flops = ll_executed_flops(cnt, iters)
-    achieved = flops / (kms * 1e-3) / 1e12
-    io = n_loc * (8 * (LL_IN_DOUBLES + 18 + LL_OUT_DOUBLES) + 16 + 8)
+    roofline = None
+    if args.full:
+        cnt = full["ind"][lo:hi].sum(1)
+        kms = float(np.median(kern))
+        flops = ll_executed_flops(cnt, iters)
+        achieved = flops / (kms * 1e-3) / 1e12
+        io = n_loc * (8 * (LL_IN_DOUBLES + 18 + LL_OUT_DOUBLES) + 16 + 8)
+        roofline = {"bound": "mfma", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                    "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic_from("ll", n_loc)[0],
+                    "traffic_source": traffic_from("ll", n_loc)[1], "kernel": "srb_ll_kernel",
+                    "kernel_ms": kms, "flop_model": "bench.ll_executed_flops (DESIGN.md 6b); latency-bound",
+                    "io_bytes_per_launch": io, "hbm_GBps": io / (kms * 1e-3) / 1e9}
     line = {
         "metric": LL_METRIC, "value": A_total * args.steps / elapsed, "unit": "solves/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps,
@@ -266,14 +303,9 @@ def main_ll(args, world, rank, local_rank, dev):
                    "agents_per_gpu": A_local, "agents_total": A_total, "parallelism": f"agents sharded x{world}"},
         "p50_ms": float(np.percentile(per_step, 50)), "p99_ms": float(np.percentile(per_step, 99)),
         "optimal_frac": float((status == 0).mean()), "iters_mean": float(iters.mean()),
-        "roofline": {"bound": "mfma", "achieved": achieved, "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic_from("ll", n_loc)[0],
-                     "traffic_source": traffic_from("ll", n_loc)[1], "kernel": "srb_ll_kernel",
-                     "kernel_ms": kms, "flop_model": "bench.ll_executed_flops (DESIGN.md 6b); latency-bound",
-                     "io_bytes_per_launch": io, "hbm_GBps": io / (kms * 1e-3) / 1e9},
-        "cpu_baseline": None,
+        "roofline": roofline, "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, ROOT)
         import oracle
         p = oracle.ll_params()
@@ -359,7 +391,7 @@ def main_srb12(args, world, rank, local_rank, dev):
         step()
     torch.cuda.synchronize(dev)
     kern = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):      # --full: kernel durations on the launch stream, for the roofline
         step()
         kern.append(solver.last_kernel_ms())
     # the timed loop runs without the library's own timing events (srb12_ctx_set_timing): each event
@@ -383,11 +415,20 @@ def main_srb12(args, world, rank, local_rank, dev):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, world, rank)
     status = out["status"].cpu().numpy(); iters = out["iters"].cpu().numpy()
-    sel_ms = float(np.median([k[0] for k in kern])); solve_ms = float(np.median([k[1] for k in kern]))
-    flops = srb12_executed_flops(N, Ko + Kn, iters)
-    achieved = flops / (solve_ms * 1e-3) / 1e12
-    io = n_loc * 8 * (12 + 24 * N + 12 * N + (24 * N + 1) + 1) + n_loc * 4 * (4 * N + 4)
+    roofline = None
+    if args.full:
+        sel_ms = float(np.median([k[0] for k in kern])); solve_ms = float(np.median([k[1] for k in kern]))
+        flops = srb12_executed_flops(N, Ko + Kn, iters)
+        achieved = flops / (solve_ms * 1e-3) / 1e12
+        io = n_loc * 8 * (12 + 24 * N + 12 * N + (24 * N + 1) + 1) + n_loc * 4 * (4 * N + 4)
+        roofline = {"bound": "mfma", "limiter": "latency", "achieved": achieved, "peak": FP64_PEAK_TFLOPS,
+                    "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic_from("s12", n_loc)[0],
+                    "traffic_source": traffic_from("s12", n_loc)[1], "kernel": "srb12_kernel",
+                    "kernel_ms": solve_ms, "select_ms": sel_ms, "io_bytes_per_launch": io,
+                    "flop_model": "bench.srb12_executed_flops (Riccati IPM, DESIGN.md 11); latency-bound"}
     line = {
         "metric": "SRB-12 NMPC solves/sec (extension mode, DESIGN.md section 11)", "value": A_total * args.steps / elapsed,
         "unit": "solves/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -399,14 +440,9 @@ def main_srb12(args, world, rank, local_rank, dev):
         "p50_ms": float(np.percentile(per_step, 50)), "p99_ms": float(np.percentile(per_step, 99)),
         "optimal_frac": float((np.isin(status[:, 0], (0, 4)) & (status[:, 1] == 0)).mean()), "iters_mean": iters.mean(0).tolist(),
         "iters_max": iters.max(0).tolist(),
-        "roofline": {"bound": "mfma", "limiter": "latency", "achieved": achieved, "peak": FP64_PEAK_TFLOPS,
-                     "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic_from("s12", n_loc)[0],
-                     "traffic_source": traffic_from("s12", n_loc)[1], "kernel": "srb12_kernel",
-                     "kernel_ms": solve_ms, "select_ms": sel_ms, "io_bytes_per_launch": io,
-                     "flop_model": "bench.srb12_executed_flops (Riccati IPM, DESIGN.md 11); latency-bound"},
-        "cpu_baseline": None,
+        "roofline": roofline, "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, ROOT)
         import oracle
         op = oracle.params12(N, K_obs=Ko_, K_nbr=Kn_)
@@ -483,7 +519,12 @@ def main():
     ap.add_argument("--config", type=int, default=3)
     ap.add_argument("--agents", type=int, default=0, help="agents per GPU (override)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the kernel times on the launch stream with the "
+                         "roofline figures built on them, and the CPU baselines (cpu_baseline)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the output arrays of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--waves", type=int, default=0, help="waves per agent (0 automatic; srb_ctx_set_waves)")
     ap.add_argument("--qp-init", type=int, default=1,
                     help="QP-stage start: 1 scaled (default), 0 iSWIFT's kkt_initialize (srb_ctx_set_qp_init)")
@@ -596,7 +637,7 @@ def main():
         step()
     torch.cuda.synchronize(dev)
     kern, pol = [], []
-    for _ in range(3):            # kernel duration on the stream it runs on (HIP events in the C ABI)
+    for _ in range(3 if args.full else 0):  # --full: kernel duration on the stream it runs on (HIP events in the C ABI)
         step()
         kern.append(solver.last_kernel_ms())
         pol.append(solver.last_polish_ms())
@@ -628,27 +669,46 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     value = (hi - lo) * world * args.steps / elapsed if args.emulate_shards > 1 else A_total * args.steps / elapsed
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, world, rank)
     status = out["status"].cpu().numpy(); iters = out["iters"].cpu().numpy()
-    solve_ms = float(np.median([k[1] for k in kern]))
-    flops = executed_flops(p, iters, cfg["K_obs"] + cfg["K_nbr"])
-    achieved = flops / (solve_ms * 1e-3) / 1e12
     dense_per_solve = dense_equiv_flops(p, iters) / max(1, iters.shape[0])
-    cyc_iter = solve_ms * 1e-3 * SCLK_GHZ * 1e9 / max(1, int(iters.sum(1).max()))
-    traffic = traffic_polish = None
-    fused = solver.polish_fused_active()
-    if args.traffic_json is None:           # this round's PMC summary of the config, else round 5's
-        args.traffic_json = next((f for f in (os.path.join(ROOT, "profiles", f"{r}_pmc_traffic_c{args.config}.json")
-                                              for r in ("r06", "r05")) if os.path.exists(f)),
-                                 os.path.join(ROOT, "profiles", f"r06_pmc_traffic_c{args.config}.json"))
-    if os.path.exists(args.traffic_json):
-        try:
-            tj = json.load(open(args.traffic_json))
-            if tj.get("config") == args.config and tj.get("agents") == n_loc and \
-                    tj.get("polish_fused", 0) == int(fused):
-                traffic = tj.get("hbm_bytes_per_launch")
-                traffic_polish = tj.get("kernels", {}).get("srb_polish_kernel", {}).get("hbm_bytes")
-        except Exception:
-            traffic = None
+    roofline = None
+    if args.full:
+        solve_ms = float(np.median([k[1] for k in kern]))
+        flops = executed_flops(p, iters, cfg["K_obs"] + cfg["K_nbr"])
+        achieved = flops / (solve_ms * 1e-3) / 1e12
+        cyc_iter = solve_ms * 1e-3 * SCLK_GHZ * 1e9 / max(1, int(iters.sum(1).max()))
+        traffic = traffic_polish = None
+        fused = solver.polish_fused_active()
+        if args.traffic_json is None:           # this round's PMC summary of the config, else round 5's
+            args.traffic_json = next((f for f in (os.path.join(ROOT, "profiles", f"{r}_pmc_traffic_c{args.config}.json")
+                                                  for r in ("r06", "r05")) if os.path.exists(f)),
+                                     os.path.join(ROOT, "profiles", f"r06_pmc_traffic_c{args.config}.json"))
+        if os.path.exists(args.traffic_json):
+            try:
+                tj = json.load(open(args.traffic_json))
+                if tj.get("config") == args.config and tj.get("agents") == n_loc and \
+                        tj.get("polish_fused", 0) == int(fused):
+                    traffic = tj.get("hbm_bytes_per_launch")
+                    traffic_polish = tj.get("kernels", {}).get("srb_polish_kernel", {}).get("hbm_bytes")
+            except Exception:
+                traffic = None
+        roofline = {"bound": "mfma", "limiter": "latency", "achieved": achieved, "peak": FP64_PEAK_TFLOPS,
+                    "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic,
+                    "traffic_source": os.path.relpath(args.traffic_json, ROOT) if traffic is not None else None,
+                    "cycles_per_iter": cyc_iter,
+                    "cycles_per_iter_note": "solve-kernel HIP-event time x 2.4 GHz / IPM iterations (QP + NLP) of "
+                                            "the slowest agent: the critical-path cost of one iteration; per-phase "
+                                            "split in profiles/r06_c3_stamps.txt (r05_*_stamps.txt)",
+                    "kernel": "srb_nmpc_kernel", "waves_per_agent": solver.waves(), "kernel_ms": solve_ms, "knn_ms": float(np.median([k[0] for k in kern])),
+                    "flop_model": "executed fp64 flops of the condensed IPM (bench.executed_flops, DESIGN.md 6) over "
+                                  "the fp64 peak; the kernel is latency-bound (dependent FMA / cross-lane chains per "
+                                  "agent), neither MFMA- nor HBM-throughput-bound",
+                    "polish_ms": float(np.median(pol)),
+                    "polish_kernel": "fused into srb_nmpc_kernel" if fused else "srb_polish_kernel",
+                    "polish_traffic": traffic_polish,
+                    "io_bytes_per_launch": io_bytes(p, n_loc, sh["obstacles"].shape[0], A_total if cfg["K_nbr"] else 0)}
     kkt32 = args.kkt_fp32_mu > 0 and solver.get_option("last_kkt_fp32") == 1.0
     line = {
         "metric": METRIC, "value": value, "unit": "solves/s", "n_gpus": world, "steps": args.steps,
@@ -670,24 +730,10 @@ def main():
         "dense_kkt_flops_note": "SURVEY.md 8(d) work-equivalence figure: (2/3) d^3 + 4 d^2 per IPM iteration of the "
                                 "unreduced dense KKT (d = nv + neq) x this batch's iterations, per solve; a "
                                 "comparison with a dense-KKT solver, not executed flops and not a rate",
-        "roofline": {"bound": "mfma", "limiter": "latency", "achieved": achieved, "peak": FP64_PEAK_TFLOPS,
-                     "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS, "traffic": traffic,
-                     "traffic_source": os.path.relpath(args.traffic_json, ROOT) if traffic is not None else None,
-                     "cycles_per_iter": cyc_iter,
-                     "cycles_per_iter_note": "solve-kernel HIP-event time x 2.4 GHz / IPM iterations (QP + NLP) of "
-                                             "the slowest agent: the critical-path cost of one iteration; per-phase "
-                                             "split in profiles/r06_c3_stamps.txt (r05_*_stamps.txt)",
-                     "kernel": "srb_nmpc_kernel", "waves_per_agent": solver.waves(), "kernel_ms": solve_ms, "knn_ms": float(np.median([k[0] for k in kern])),
-                     "flop_model": "executed fp64 flops of the condensed IPM (bench.executed_flops, DESIGN.md 6) over "
-                                   "the fp64 peak; the kernel is latency-bound (dependent FMA / cross-lane chains per "
-                                   "agent), neither MFMA- nor HBM-throughput-bound",
-                     "polish_ms": float(np.median(pol)),
-                     "polish_kernel": "fused into srb_nmpc_kernel" if fused else "srb_polish_kernel",
-                     "polish_traffic": traffic_polish,
-                     "io_bytes_per_launch": io_bytes(p, n_loc, sh["obstacles"].shape[0], A_total if cfg["K_nbr"] else 0)},
+        "roofline": roofline,
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(cfg, sh, args.cpu_seconds)
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -21,6 +21,9 @@ Fixtures written (data only -- inputs and expected outputs):
                       contact sets trot / stand / three legs / flight, and the genuine-iSWIFT
                       solution of each agent's QP with and without the CLF row
                       (numpy .npz, plain arrays, loads with allow_pickle=False)
+  ll_iswift_random.npz  the genuine-iSWIFT solution (x, flag, iterations) of the low-level CLF-QP of
+                      the 24 seeded agents ll_workload.make_batch(24, seed=5), which
+                      tests/test_ll_oracle.py rebuilds (python tests/golden/make_goldens.py llrand)
 """
 import json
 import os
@@ -248,10 +251,26 @@ def ll_ctrl():
     print("wrote ll_ctrl.npz")
 
 
+def ll_random():
+    b = ll_workload.make_batch(24, seed=5)
+    p = oracle.ll_params()
+    X = np.zeros((24, 32)); NX = np.zeros(24, np.int32); F = np.zeros(24, np.int32); IT = np.zeros(24, np.int32)
+    for a in range(24):
+        Pd, c, A, bb, G, h, *_ = oracle.ll_build_qp(p, b, a)
+        x, f, it = oracle.iswift_ref(Pd, c, A, bb, G, h, "md")
+        X[a, :x.size] = x; NX[a] = x.size; F[a] = f; IT[a] = it
+    np.savez_compressed(os.path.join(HERE, "ll_iswift_random.npz"), iswift_x=X, iswift_n=NX, iswift_flag=F,
+                        iswift_iters=IT)
+    print("wrote ll_iswift_random.npz")
+
+
 if __name__ == "__main__":
     oracle.build()
     if sys.argv[1:] == ["ll"]:
         ll_ctrl()
+        sys.exit(0)
+    if sys.argv[1:] == ["llrand"]:
+        ll_random()
         sys.exit(0)
     if sys.argv[1:] == ["qpmd"]:
         qp_md()

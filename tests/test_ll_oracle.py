@@ -136,16 +136,23 @@ def test_ll_epilogue_matches_numpy():
         np.testing.assert_allclose(o["q"][a], qn, rtol=1e-10, atol=1e-12)
 
 
-@pytest.mark.skipif(not oracle.ref_available(), reason="oracle/_ref (genuine iSWIFT) not built")
 def test_ll_oracle_vs_genuine_iswift_random():
+    """The genuine iSWIFT's answers are the stored ones (tests/golden/ll_iswift_random.npz, written by
+    make_goldens.py llrand from the same seeded batch); where oracle/_ref is built, it must reproduce them."""
     b = ll_workload.make_batch(24, seed=5)
     p = oracle.ll_params()
     o = oracle.ll_calc_torque(p, b)
+    g = np.load(os.path.join(os.path.dirname(GOLD), "ll_iswift_random.npz"), allow_pickle=False)
     for a in range(24):
-        Pd, c, A, bb, G, h, *_ = oracle.ll_build_qp(p, b, a)
-        x, f, it = oracle.iswift_ref(Pd, c, A, bb, G, h, "md")
+        n = int(g["iswift_n"][a])
+        x, f, it = g["iswift_x"][a, :n], g["iswift_flag"][a], g["iswift_iters"][a]
+        if oracle.ref_available():
+            Pd, c, A, bb, G, h, *_ = oracle.ll_build_qp(p, b, a)
+            xr, fr, itr = oracle.iswift_ref(Pd, c, A, bb, G, h, "md")
+            assert (fr, itr, xr.size) == (f, it, n)
+            np.testing.assert_array_equal(xr, x)
         assert f == o["status"][a] and it == o["iters"][a]
-        assert np.abs(x - o["x"][a, :x.size]).max() < 1e-8
+        assert np.abs(x - o["x"][a, :n]).max() < 1e-8
 
 
 def test_ll_no_trap_variant_differs_from_iswift_only_when_it_traps():

@@ -1,5 +1,5 @@
 """Summarise rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes (separate runs, MI355X_MICROARCH.md
-HBM section) into per-launch HBM traffic figures that bench.py reports as roofline.traffic.
+HBM section) into per-launch HBM traffic figures that bench.py --full reports as roofline.traffic.
 
     python tools/pmc_traffic.py calib <fetch_dir> <write_dir> <out.json>
         the counters of tools/ubench/fetch_calib (1 GiB touched once per dispatch by 8-B/lane
