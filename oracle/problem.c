@@ -8,7 +8,7 @@
 #include "oracle.h"
 
 #ifndef ORC_POLISH_DEFAULT
-#define ORC_POLISH_DEFAULT 1           /* the kernel's SRB_POLISH_ON */
+#define ORC_POLISH_DEFAULT 1           /* the context default of SRB_OPT_POLISH */
 #endif
 
 void orc_params_default(orc_params *p, int N, int C)

@@ -10,36 +10,17 @@
 #include <string>
 #include "srbnmpc.h"
 #include "srb_kernel_params.h"
+#include "srb_kernel_decls.h"
+#include "srb_host.h"
 
 #define SRB12_DBG_LEN (2 * 64 * 8 + 16 + 128)   // trace, stamp sums, state checks (srb12_kernels.hip)
 
-int srb_internal_fail(int code, const char *msg);
-int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
-                        const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                        int obstacles_version, int *sel, hipStream_t s);
-int srb_internal_mark_done(srb_ctx *c, hipStream_t s);
-
 typedef void (*srb12_fn)(Srb12KParams, int, const double *, const double *, const double *, const int *,
                          const double *, const double *, const int *, double *, double *, double *, int *, int *);
-#define DECL12(TL, TO, NC, K1)                                                                                  \
-    extern "C" __global__ void srb12_kernel_##TL##_##TO##_##NC##_##K1(Srb12KParams, int, const double *, const double *,      \
-                                                        const double *, const int *, const double *,             \
-                                                        const double *, const int *, double *, double *,         \
-                                                        double *, int *, int *);
-SRB12_INSTANCES(DECL12)
-#undef DECL12
-extern "C" __global__ void srb12_pos_kernel(int n_agents, const double *x0g, double *pos);
 struct srb12_inst { int tl, to, nc, k1; srb12_fn fn; };
 #define ENTRY12(TL, TO, NC, K1) {TL, TO, NC, K1, srb12_kernel_##TL##_##TO##_##NC##_##K1},
 static const srb12_inst g_inst12[] = {SRB12_INSTANCES(ENTRY12)};
 #undef ENTRY12
-
-#define H12CHK(expr)                                                                                    \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return srb_internal_fail(SRB_ERR_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 struct srb12_ctx {
     srb12_params p;
@@ -47,9 +28,8 @@ struct srb12_ctx {
     srb_ctx *sel_ctx;              // LIP-mode context: selection kernels, grids, default sel buffer
     hipStream_t stream;
     hipEvent_t ev[3];
-    hipEvent_t done;
-    hipStream_t last;
-    bool timed, any;
+    SrbCallOrder order;            // submission-order chaining of the calls on this context
+    bool timed;
     int timing;                    // srb12_ctx_set_timing (default 1)
     double *pos;                   // [max_agents][4] CoM rows for the selection
     int *sel;                      // [max_agents][2 SRB_KNN_MAX]
@@ -140,9 +120,9 @@ extern "C" int srb12_ctx_create(const srb12_params *p, int max_agents, int devic
     int rc = validate12(p);
     if (rc) return rc;
     int ndev = 0;
-    H12CHK(hipGetDeviceCount(&ndev));
+    HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return srb_internal_fail(SRB_ERR_ARG, "device index out of range");
-    H12CHK(hipSetDevice(device));
+    HIPCHK(hipSetDevice(device));
     srb_params sp;
     srb_params_default(&sp, 2, 2);
     sp.K_obs = p->K_obs; sp.K_nbr = p->K_nbr;
@@ -152,20 +132,12 @@ extern "C" int srb12_ctx_create(const srb12_params *p, int max_agents, int devic
     std::memset(c, 0, sizeof *c);
     // a failure after this point unwinds through srb12_ctx_destroy (it null-checks every buffer and
     // destroys the selection context); *out stays untouched
-#define CREATE_CHK(expr)                                                                                \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) {                                                                         \
-            const int rc_ = srb_internal_fail(SRB_ERR_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-            srb12_ctx_destroy(c);   /* sets no error: the message above stays */                      \
-            return rc_;                                                                                 \
-        }                                                                                               \
-    } while (0)
     c->p = *p; c->max_agents = max_agents; c->device = device; c->sel_ctx = sc;
     const size_t A = (size_t)max_agents, N = (size_t)p->N, nv = 24 * N + 1;
+#define CREATE_CHK(expr) HIPCHK_UNWIND_(expr, #expr, srb12_ctx_destroy(c))
     CREATE_CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (int i = 0; i < 3; i++) CREATE_CHK(hipEventCreate(&c->ev[i]));
-    CREATE_CHK(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
+    CREATE_CHK(hipEventCreateWithFlags(&c->order.done, hipEventDisableTiming));
     CREATE_CHK(hipMalloc(&c->pos, A * 4 * sizeof(double)));
     CREATE_CHK(hipMalloc(&c->sel, A * 2 * SRB_KNN_MAX * sizeof(int)));
     CREATE_CHK(hipMalloc(&c->x0, A * 12 * sizeof(double)));
@@ -178,8 +150,8 @@ extern "C" int srb12_ctx_create(const srb12_params *p, int max_agents, int devic
     CREATE_CHK(hipMalloc(&c->status, A * 2 * sizeof(int)));
     CREATE_CHK(hipMalloc(&c->iters, A * 2 * sizeof(int)));
     CREATE_CHK(hipMalloc(&c->dbg, SRB12_DBG_LEN * sizeof(double)));
-    c->dbg_agent = -1; c->timing = 1;
 #undef CREATE_CHK
+    c->dbg_agent = -1; c->timing = 1;
     *out = c;
     return SRB_OK;
 }
@@ -189,23 +161,17 @@ extern "C" int srb12_ctx_destroy(srb12_ctx *c)
     if (!c) return SRB_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->any) (void)hipEventSynchronize(c->done);
+    (void)c->order.wait_idle();
     void *bufs[] = {c->dbg, c->pos, c->sel, c->x0, c->xref, c->foot, c->contact, c->obstacles, c->nbr, c->x_qp, c->x, c->obj,
                     c->status, c->iters};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (int i = 0; i < 3; i++)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    if (c->done) (void)hipEventDestroy(c->done);
+    if (c->order.done) (void)hipEventDestroy(c->order.done);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     srb_ctx_destroy(c->sel_ctx);
     delete c;
-    return SRB_OK;
-}
-
-static int order12(srb12_ctx *c, hipStream_t s)
-{
-    if (c->any && s != c->last) H12CHK(hipStreamWaitEvent(s, c->done, 0));
     return SRB_OK;
 }
 
@@ -240,10 +206,10 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     if (!in) return srb_internal_fail(SRB_ERR_SIZE, "no SRB-12 kernel instance covers the row slots");
     const size_t lds = (size_t)srb12_lds_doubles(p->N, Ko + Kn) * sizeof(double);
     int *sel = d->sel ? d->sel : c->sel;
-    if (c->timing) H12CHK(hipEventRecord(c->ev[0], s));
+    if (c->timing) HIPCHK(hipEventRecord(c->ev[0], s));
     if (Ko + Kn > 0) {
         hipLaunchKernelGGL(srb12_pos_kernel, dim3((n_agents + 255) / 256), dim3(256), 0, s, n_agents, d->x0, c->pos);
-        H12CHK(hipGetLastError());
+        HIPCHK(hipGetLastError());
         int rc = srb_internal_select(c->sel_ctx, n_agents, c->pos, d->obstacles, Ko > 0 ? d->n_obs : 0, d->nbr_state,
                                      Kn > 0 ? d->n_all : 0, d->agent_offset, Ko, Kn, d->obstacles_version, sel, s);
         if (rc) return rc;
@@ -251,11 +217,11 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         // this launch (grid_reserve waits on it)
         if ((rc = srb_internal_mark_done(c->sel_ctx, s))) return rc;
     }
-    if (c->timing) H12CHK(hipEventRecord(c->ev[1], s));
+    if (c->timing) HIPCHK(hipEventRecord(c->ev[1], s));
     hipLaunchKernelGGL(in->fn, dim3(n_agents), dim3(64), lds, s, k, n_agents, d->x0, d->xref, d->foot, d->contact,
                        d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters);
-    H12CHK(hipGetLastError());
-    if (c->timing) H12CHK(hipEventRecord(c->ev[2], s));
+    HIPCHK(hipGetLastError());
+    if (c->timing) HIPCHK(hipEventRecord(c->ev[2], s));
     c->timed = c->timing != 0;
     return SRB_OK;
 }
@@ -265,23 +231,20 @@ extern "C" int srb12_solve_batch_device(srb12_ctx *c, int n_agents, const srb12_
     if (d && d->struct_size != (int)sizeof(srb12_batch))
         return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
     if (!c || !d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
-    H12CHK(hipSetDevice(c->device));
+    HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
-    int rc = order12(c, s);
+    int rc = c->order.order_after_last(s);
     if (!rc) rc = launch12(c, n_agents, d, s);
-    if (!rc && n_agents > 0) {
-        H12CHK(hipEventRecord(c->done, s));
-        c->last = s; c->any = true;
-    }
+    if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
 }
 
 static int reserve(void **buf, size_t *cap, size_t bytes, srb12_ctx *c)
 {
     if (bytes <= *cap) return SRB_OK;
-    if (c->any) H12CHK(hipEventSynchronize(c->done));
-    if (*buf) H12CHK(hipFree(*buf));
-    H12CHK(hipMalloc(buf, bytes));
+    if (int rc = c->order.wait_idle()) return rc;
+    if (*buf) HIPCHK(hipFree(*buf));
+    HIPCHK(hipMalloc(buf, bytes));
     *cap = bytes;
     return SRB_OK;
 }
@@ -295,14 +258,14 @@ extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *
     if (n_agents == 0) return SRB_OK;
     if (!h->x0 || !h->xref || !h->foot || !h->contact || !h->x || !h->obj || !h->status || !h->iters)
         return srb_internal_fail(SRB_ERR_ARG, "missing buffer");
-    H12CHK(hipSetDevice(c->device));
+    HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    if (int rc0 = order12(c, s)) return rc0;
+    if (int rc0 = c->order.order_after_last(s)) return rc0;
     const size_t A = (size_t)n_agents, N = (size_t)c->p.N, nv = 24 * N + 1;
-    H12CHK(hipMemcpyAsync(c->x0, h->x0, A * 12 * sizeof(double), hipMemcpyHostToDevice, s));
-    H12CHK(hipMemcpyAsync(c->xref, h->xref, A * 12 * N * sizeof(double), hipMemcpyHostToDevice, s));
-    H12CHK(hipMemcpyAsync(c->foot, h->foot, A * 12 * N * sizeof(double), hipMemcpyHostToDevice, s));
-    H12CHK(hipMemcpyAsync(c->contact, h->contact, A * 4 * N * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->x0, h->x0, A * 12 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->xref, h->xref, A * 12 * N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->foot, h->foot, A * 12 * N * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->contact, h->contact, A * 4 * N * sizeof(int), hipMemcpyHostToDevice, s));
     srb12_batch d = *h;
     d.x0 = c->x0; d.xref = c->xref; d.foot = c->foot; d.contact = c->contact;
     d.x_qp = c->x_qp; d.x = c->x; d.obj = c->obj; d.status = c->status; d.iters = c->iters;
@@ -312,33 +275,32 @@ extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *
         size_t cap = c->cap_obs;
         if (int rc = reserve((void **)&c->obstacles, &cap, (size_t)h->n_obs * 2 * sizeof(double), c)) return rc;
         c->cap_obs = cap;
-        H12CHK(hipMemcpyAsync(c->obstacles, h->obstacles, (size_t)h->n_obs * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->obstacles, h->obstacles, (size_t)h->n_obs * 2 * sizeof(double), hipMemcpyHostToDevice, s));
         d.obstacles = c->obstacles;
     }
     if (h->n_all > 0 && h->nbr_state) {
         size_t cap = c->cap_nbr;
         if (int rc = reserve((void **)&c->nbr, &cap, (size_t)h->n_all * 4 * sizeof(double), c)) return rc;
         c->cap_nbr = cap;
-        H12CHK(hipMemcpyAsync(c->nbr, h->nbr_state, (size_t)h->n_all * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(c->nbr, h->nbr_state, (size_t)h->n_all * 4 * sizeof(double), hipMemcpyHostToDevice, s));
         d.nbr_state = c->nbr;
     }
     d.obstacles_version = 0;               // staging copies: no grid reuse across calls
     int rc = launch12(c, n_agents, &d, s);
+    if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
-    H12CHK(hipEventRecord(c->done, s));
-    c->last = s; c->any = true;
-    if (h->x_qp) H12CHK(hipMemcpyAsync(h->x_qp, c->x_qp, A * nv * sizeof(double), hipMemcpyDeviceToHost, s));
-    H12CHK(hipMemcpyAsync(h->x, c->x, A * nv * sizeof(double), hipMemcpyDeviceToHost, s));
-    H12CHK(hipMemcpyAsync(h->obj, c->obj, A * sizeof(double), hipMemcpyDeviceToHost, s));
-    H12CHK(hipMemcpyAsync(h->status, c->status, A * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    H12CHK(hipMemcpyAsync(h->iters, c->iters, A * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (h->x_qp) HIPCHK(hipMemcpyAsync(h->x_qp, c->x_qp, A * nv * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h->x, c->x, A * nv * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h->obj, c->obj, A * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h->status, c->status, A * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h->iters, c->iters, A * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     if (h->sel) {
         int Ko = 0, Kn = 0;
         clamp_rows(&c->p, h, &Ko, &Kn);
         const int Kt = Ko + Kn;
-        if (Kt > 0) H12CHK(hipMemcpyAsync(h->sel, c->sel, A * Kt * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (Kt > 0) HIPCHK(hipMemcpyAsync(h->sel, c->sel, A * Kt * sizeof(int), hipMemcpyDeviceToHost, s));
     }
-    H12CHK(hipStreamSynchronize(s));
+    HIPCHK(hipStreamSynchronize(s));
     return SRB_OK;
 }
 
@@ -352,10 +314,10 @@ extern "C" int srb12_ctx_set_timing(srb12_ctx *c, int on)
 extern "C" int srb12_last_kernel_ms(srb12_ctx *c, float *select_ms, float *solve_ms)
 {
     if (!c || !c->timed) return srb_internal_fail(SRB_ERR_ARG, "no timed launch");
-    H12CHK(hipEventSynchronize(c->ev[2]));
+    HIPCHK(hipEventSynchronize(c->ev[2]));
     float a = 0, b = 0;
-    H12CHK(hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
-    H12CHK(hipEventElapsedTime(&b, c->ev[1], c->ev[2]));
+    HIPCHK(hipEventElapsedTime(&a, c->ev[0], c->ev[1]));
+    HIPCHK(hipEventElapsedTime(&b, c->ev[1], c->ev[2]));
     if (select_ms) *select_ms = a;
     if (solve_ms) *solve_ms = b;
     return SRB_OK;
@@ -367,13 +329,13 @@ extern "C" int srb12_last_kernel_ms(srb12_ctx *c, float *select_ms, float *solve
 extern "C" int srb12_debug_trace(srb12_ctx *c, int agent, double *out)
 {
     if (!c) return srb_internal_fail(SRB_ERR_ARG, "null ctx");
-    H12CHK(hipSetDevice(c->device));
+    HIPCHK(hipSetDevice(c->device));
     if (out) {
-        if (c->any) H12CHK(hipEventSynchronize(c->done));
-        H12CHK(hipMemcpy(out, c->dbg, (2 * 64 * 8 + 16) * sizeof(double), hipMemcpyDeviceToHost));
+        if (int rc = c->order.wait_idle()) return rc;
+        HIPCHK(hipMemcpy(out, c->dbg, (2 * 64 * 8 + 16) * sizeof(double), hipMemcpyDeviceToHost));
     }
     c->dbg_agent = agent;
-    H12CHK(hipMemset(c->dbg, 0, SRB12_DBG_LEN * sizeof(double)));
+    HIPCHK(hipMemset(c->dbg, 0, SRB12_DBG_LEN * sizeof(double)));
     return SRB_OK;
 }
 
@@ -382,8 +344,8 @@ extern "C" int srb12_debug_trace(srb12_ctx *c, int agent, double *out)
 extern "C" int srb12_debug_check(srb12_ctx *c, double *out)
 {
     if (!c || !out) return srb_internal_fail(SRB_ERR_ARG, "null argument");
-    H12CHK(hipSetDevice(c->device));
-    if (c->any) H12CHK(hipEventSynchronize(c->done));
-    H12CHK(hipMemcpy(out, c->dbg + (2 * 64 * 8 + 16), 128 * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipSetDevice(c->device));
+    if (int rc = c->order.wait_idle()) return rc;
+    HIPCHK(hipMemcpy(out, c->dbg + (2 * 64 * 8 + 16), 128 * sizeof(double), hipMemcpyDeviceToHost));
     return SRB_OK;
 }

@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "srb_kernel_params.h"
+#include "srb_kernel_decls.h"
 
 #ifndef SRB12_REFINE_PREDICTOR        // 1: refine the predictor's solve too (round-3 behaviour)
 #define SRB12_REFINE_PREDICTOR 0

@@ -13,27 +13,8 @@
 #include <string>
 #include "srbnmpc.h"
 #include "srb_kernel_params.h"
-
-#define DECL_NMPC(NZL, TS, NW, NC, CC, KC)                                                                    \
-    extern "C" __global__ void srb_nmpc_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                     \
-        SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
-        const double *obstacles, int n_obs, const double *nbr_state, int n_all, int agent_offset,              \
-        double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
-        const double *alpha_buf, double *alpha_out, const int *sel_g, float *zpol_g, int zstride);            \
-    extern "C" __global__ void srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                   \
-        SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
-        const double *obstacles, const double *nbr_state, double *x_out, double *obj_out, int *status_out,     \
-        const double *alpha_buf, double *alpha_out, const int *sel_g, const float *zpol_g, int zstride);
-SRB_KERNEL_INSTANCES(DECL_NMPC)
-#undef DECL_NMPC
-#define DECL_NMPC_F32(NZL, TS, NW, NC, CC, KC)                                                                \
-    extern "C" __global__ void srb_nmpc_kernel_f32_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                 \
-        SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
-        const double *obstacles, int n_obs, const double *nbr_state, int n_all, int agent_offset,              \
-        double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
-        const double *alpha_buf, double *alpha_out, const int *sel_g, float *zpol_g, int zstride);
-SRB_KF32_INSTANCES(DECL_NMPC_F32)
-#undef DECL_NMPC_F32
+#include "srb_kernel_decls.h"
+#include "srb_host.h"
 
 typedef void (*srb_kernel_fn)(SrbKParams, int, const double *, const double *, const double *, const double *, int,
                               const double *, int, int, double *, double *, double *, int *, int *, const double *,
@@ -41,29 +22,20 @@ typedef void (*srb_kernel_fn)(SrbKParams, int, const double *, const double *, c
 typedef void (*srb_polish_fn)(SrbKParams, int, const double *, const double *, const double *, const double *,
                               const double *, double *, double *, int *, const double *, double *, const int *,
                               const float *, int);
-struct SrbGrid;
-extern "C" __global__ void srb_knn_kernel(int n_agents, const double *x0g, const double *obstacles, int n_obs,
-                                          const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                                          int *sel_out, int sel_stride, const SrbGrid *gob, const int *oob, const double2 *pob,
-                                          const int *iob, const SrbGrid *gnb, const int *onb, const double2 *pnb,
-                                          const int *inb);
-extern "C" __global__ void srb_grid_build_kernel(const double *tab0, int stride0, int n0, SrbGrid *g0, int *off0,
-                                                 double2 *spos0, int *sidx0, const double *tab1, int stride1, int n1,
-                                                 SrbGrid *g1, int *off1, double2 *spos1, int *sidx1);
 struct srb_instance { int nzl, ts, nw, nc, cc, kc; srb_kernel_fn fn; srb_polish_fn polish; };
-#define ENTRY_NMPC(NZL, TS, NW, NC, CC, KC)                                                                   \
-    {NZL, TS, NW, NC, CC, KC, srb_nmpc_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC,                       \
-     srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC},
+// solve kernel (INFIX empty, or f32_) and polish kernel of one instance
+#define ENTRY_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC) NZL, TS, NW, NC, CC, KC, srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
+#define ENTRY_POLISH_(NZL, TS, NW, NC, CC, KC) srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
+#define ENTRY_NMPC(...) {ENTRY_NMPC_(, __VA_ARGS__), ENTRY_POLISH_(__VA_ARGS__)},
+#define ENTRY_F32(...) {ENTRY_NMPC_(f32_, __VA_ARGS__), nullptr},
 static const srb_instance g_instances[] = {SRB_KERNEL_INSTANCES(ENTRY_NMPC)};
+// the fp32-factor variant of an instance (SRB_OPT_KKT_FP32_MU > 0), or null; these entries carry no polish kernel
+static const srb_instance g_instances_f32[] = {SRB_KF32_INSTANCES(ENTRY_F32)};
 #undef ENTRY_NMPC
-// the fp32-factor variant of an instance (SRB_OPT_KKT_FP32_MU > 0), or null
-struct srb_instance_f32 { int nzl, ts, nw, nc, cc, kc; srb_kernel_fn fn; };
-#define ENTRY_F32(NZL, TS, NW, NC, CC, KC) {NZL, TS, NW, NC, CC, KC, srb_nmpc_kernel_f32_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC},
-static const srb_instance_f32 g_instances_f32[] = {SRB_KF32_INSTANCES(ENTRY_F32)};
 #undef ENTRY_F32
 static srb_kernel_fn f32_variant(const srb_instance *in)
 {
-    for (const srb_instance_f32 &v : g_instances_f32)
+    for (const srb_instance &v : g_instances_f32)
         if (v.nzl == in->nzl && v.ts == in->ts && v.nw == in->nw && v.nc == in->nc && v.cc == in->cc && v.kc == in->kc) return v.fn;
     return nullptr;
 }
@@ -109,23 +81,15 @@ static int fail(int code, const std::string &msg)
     return code;
 }
 
-// shared with srb_ll_capi.cpp
+// shared with srb12_capi.cpp and srb_ll_capi.cpp (srb_host.h, whose HIPCHK reports through it)
 int srb_internal_fail(int code, const char *msg) { return fail(code, msg); }
-
-#define HIPCHK(expr)                                                                   \
-    do {                                                                               \
-        hipError_t e_ = (expr);                                                        \
-        if (e_ != hipSuccess) return fail(SRB_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
 
 struct srb_ctx {
     srb_params p;
     int max_agents, device;
     hipStream_t stream;
     hipEvent_t ev[4];
-    hipEvent_t done;               // recorded after every call's work (submission-order chaining)
-    hipStream_t last;              // stream of the previous call
-    bool any;                      // a call has been submitted (done is valid)
+    SrbCallOrder order;            // submission-order chaining of the calls on this context
     // device staging
     double *x0, *ref, *foot, *obstacles, *nbr, *x_qp, *x, *obj, *abuf, *alpha;
     int *status, *iters;
@@ -151,27 +115,10 @@ struct srb_ctx {
     int zstride;
     float polish_ms;
     // selection grids (table 0: static obstacles, 1: neighbour snapshot), rebuilt per launch
-    struct grid_buf { void *g; int *off; double2 *spos; int *sidx; size_t cap; } grid[2];
+    struct grid_buf { SrbGrid *g; int *off; double2 *spos; int *sidx; size_t cap; } grid[2];
     const double *grid_src;        // obstacle table, row count and version the obstacle grid was built from
     int grid_n, grid_ver;
 };
-
-// Calls on one context run in submission order (include/srbnmpc.h, "Ordering"): a call on
-// another stream than the previous one first waits for that call's work, so the context's
-// scratch (grids, the default sel buffer, staging, timing events) never serves two launches
-// in flight.
-static int order_after_last(srb_ctx *c, hipStream_t s)
-{
-    if (c->any && s != c->last) HIPCHK(hipStreamWaitEvent(s, c->done, 0));
-    return SRB_OK;
-}
-
-static int mark_done(srb_ctx *c, hipStream_t s)
-{
-    HIPCHK(hipEventRecord(c->done, s));
-    c->last = s; c->any = true;
-    return SRB_OK;
-}
 
 // device buffers of selection grid t for a table of n rows (grown on demand; the header
 // starts with ok = 0, so a grid is never read before a build has filled it)
@@ -184,7 +131,7 @@ static int grid_reserve(srb_ctx *c, int t, size_t n)
         HIPCHK(hipMalloc(&b.off, (SRB_GRID_CELLS + 1) * sizeof(int)));
     }
     if (n > b.cap) {
-        if (c->any) HIPCHK(hipEventSynchronize(c->done));   // the previous launch may still read them
+        if (int rc = c->order.wait_idle()) return rc;       // the previous launch may still read them
         if (b.spos) HIPCHK(hipFree(b.spos));
         if (b.sidx) HIPCHK(hipFree(b.sidx));
         HIPCHK(hipMalloc(&b.spos, n * sizeof(double2)));
@@ -320,30 +267,21 @@ extern "C" int srb_ctx_create(const srb_params *p, int max_agents, int device, s
     if (rc) return rc;
     srb_ctx *c = new srb_ctx();           // value-initialised: every buffer null until allocated
     // a failure after this point unwinds through srb_ctx_destroy; *out stays untouched
-#define CREATE_CHK(expr)                                                                               \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) {                                                                        \
-            const int rc_ = fail(SRB_ERR_HIP, std::string(#expr ": ") + hipGetErrorString(e_));          \
-            srb_ctx_destroy(c);                                                                        \
-            return rc_;                                                                                \
-        }                                                                                              \
-    } while (0)
     c->p = *p; c->max_agents = max_agents; c->device = device;
     c->cap_obs = 0; c->cap_nbr = 0; c->obstacles = nullptr; c->nbr = nullptr; c->timed = false; c->nw = 0; c->last_nw = 0;
     for (auto &g : c->grid) g = srb_ctx::grid_buf{nullptr, nullptr, nullptr, nullptr, 0};
     c->grid_src = nullptr; c->grid_n = 0; c->grid_ver = 0;
-    c->last = nullptr; c->any = false;
     c->qp_init = 1; c->polish_ms = 0.0f;
-    c->polish = SRB_POLISH_ON; c->polish_rho = SRB_POLISH_RHO; c->qp_warm_tol = SRB_QP_WARM_TOL; c->polish_waves = 0; c->polish_fused = 1; c->last_polish = 0; c->timing = 1; c->selection = 1;
+    c->polish = 1; c->polish_rho = SRB_POLISH_RHO; c->qp_warm_tol = SRB_QP_WARM_TOL; c->polish_waves = 0; c->polish_fused = 1; c->last_polish = 0; c->timing = 1; c->selection = 1;
     c->kkt32_mu = 0.0; c->kkt32_ref = 3;
     c->grid_min_rows = SRB_GRID_MIN_ROWS; c->grid_min_rows_static = SRB_GRID_MIN_ROWS_STATIC;
     c->zstride = 2 * srb_r4(srb_slots(p->N, p->C, p->K_obs + p->K_nbr));
     const int N = p->N, C = p->C, nv = srb_nv(p);
     const size_t A = (size_t)max_agents;
+#define CREATE_CHK(expr) HIPCHK_UNWIND_(expr, #expr, srb_ctx_destroy(c))
     CREATE_CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     for (int i = 0; i < 4; i++) CREATE_CHK(hipEventCreate(&c->ev[i]));
-    CREATE_CHK(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
+    CREATE_CHK(hipEventCreateWithFlags(&c->order.done, hipEventDisableTiming));
     CREATE_CHK(hipMalloc(&c->x0, A * 4 * sizeof(double)));
     CREATE_CHK(hipMalloc(&c->ref, A * 4 * N * sizeof(double)));
     CREATE_CHK(hipMalloc(&c->foot, A * 2 * C * N * sizeof(double)));
@@ -366,17 +304,17 @@ extern "C" int srb_ctx_destroy(srb_ctx *c)
     if (!c) return SRB_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->any) (void)hipEventSynchronize(c->done);     // the last launch may be on another stream
+    (void)c->order.wait_idle();                         // the last launch may be on another stream
     void *bufs[] = {c->x0, c->ref, c->foot, c->x_qp, c->x, c->obj, c->status, c->iters, c->obstacles, c->nbr,
                     c->abuf, c->alpha, c->sel, c->zpol};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (auto &g : c->grid)
-        for (void *b : {g.g, (void *)g.off, (void *)g.spos, (void *)g.sidx})
+        for (void *b : {(void *)g.g, (void *)g.off, (void *)g.spos, (void *)g.sidx})
             if (b) (void)hipFree(b);
     for (int i = 0; i < 4; i++)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    if (c->done) (void)hipEventDestroy(c->done);
+    if (c->order.done) (void)hipEventDestroy(c->order.done);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SRB_OK;
@@ -405,15 +343,15 @@ static int launch_select(srb_ctx *c, int n_agents, const double *x0, const doubl
                                   obstacles == c->grid_src && n_obs == c->grid_n);
     if (go_build || gn) {
         hipLaunchKernelGGL(srb_grid_build_kernel, dim3(2), dim3(1024), 0, s,
-                           obstacles, 2, n_obs, go_build ? (SrbGrid *)G0.g : nullptr, G0.off, G0.spos, G0.sidx,
-                           nbr_state, 4, n_all, gn ? (SrbGrid *)G1.g : nullptr, G1.off, G1.spos, G1.sidx);
+                           obstacles, 2, n_obs, go_build ? G0.g : nullptr, G0.off, G0.spos, G0.sidx,
+                           nbr_state, 4, n_all, gn ? G1.g : nullptr, G1.off, G1.spos, G1.sidx);
         HIPCHK(hipGetLastError());
     }
     if (go_build) { c->grid_src = obstacles; c->grid_n = n_obs; c->grid_ver = obstacles_version; }
     hipLaunchKernelGGL(srb_knn_kernel, dim3(n_agents), dim3(64 * SRB_KNN_WAVES), 0, s, n_agents, x0, obstacles, n_obs,
                        nbr_state, n_all, agent_offset, K_obs, K_nbr, sel, sel_stride,
-                       go ? (const SrbGrid *)G0.g : nullptr, G0.off, G0.spos, G0.sidx,
-                       gn ? (const SrbGrid *)G1.g : nullptr, G1.off, G1.spos, G1.sidx);
+                       go ? G0.g : nullptr, G0.off, G0.spos, G0.sidx,
+                       gn ? G1.g : nullptr, G1.off, G1.spos, G1.sidx);
     HIPCHK(hipGetLastError());
     return SRB_OK;
 }
@@ -426,7 +364,7 @@ int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double
                          obstacles_version, sel, s);
 }
 
-int srb_internal_mark_done(srb_ctx *c, hipStream_t s) { return mark_done(c, s); }
+int srb_internal_mark_done(srb_ctx *c, hipStream_t s) { return c->order.mark_done(s); }
 
 static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, int use_nlp)
 {
@@ -603,9 +541,9 @@ extern "C" int srb_solve_batch_device(srb_ctx *c, int n_agents, const srb_batch 
     if (!c || !dev_io) return fail(SRB_ERR_ARG, "null argument");
     hipStream_t s = (hipStream_t)stream;          // NULL: the HIP null stream (ordered with blocking streams)
     HIPCHK(hipSetDevice(c->device));
-    int rc = order_after_last(c, s);
+    int rc = c->order.order_after_last(s);
     if (!rc) rc = launch(c, n_agents, dev_io, s, c->p.use_nlp);
-    if (!rc && n_agents > 0) rc = mark_done(c, s);
+    if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
 }
 
@@ -632,20 +570,14 @@ extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, i
         return fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
-    int rc = order_after_last(c, s);
+    int rc = c->order.order_after_last(s);
     const int ko = (tables & 1) ? Ko : 0, kn = (tables & 2) ? Kn : 0;
     if (!rc && ko + kn > 0)
         rc = launch_select(c, n_agents, d->x0, d->obstacles, ko ? d->n_obs : 0, d->nbr_state, kn ? d->n_all : 0,
                            d->agent_offset, ko, kn, d->obstacles_version, d->sel + (ko ? 0 : Ko), s, Ko + Kn);
-    if (!rc) rc = mark_done(c, s);
+    if (!rc) rc = c->order.mark_done(s);
     return rc;
 }
-
-extern "C" __global__ void srb_prepare_kernel(int n_agents, int N, int C, int n_rows, int T, int agent_offset,
-                                              const double *Pr, const double *Prd, const int *agent_id,
-                                              const int *gait_domain, const int *contact, const double *toe,
-                                              const double *start, const double *q, const double *dq, double *x0,
-                                              double *ref, double *foot, double *last_state, int *status);
 
 extern "C" int srb_prepare_batch_device(srb_ctx *c, int n_agents, const srb_prep *d, void *stream)
 {
@@ -667,13 +599,6 @@ extern "C" int srb_prepare_batch_device(srb_ctx *c, int n_agents, const srb_prep
     HIPCHK(hipGetLastError());
     return SRB_OK;
 }
-
-extern "C" __global__ void srb_hlplan_kernel(int NA, const double *Pstart, const double *Pobs, int n_obs, int loop,
-                                             double *Pr, double *Prd);
-
-extern "C" __global__ void srb_hlplan_step_kernel(int NA, int i, int loop, const double *Pobs, int n_obs,
-                                                  const double *pos_cur, double *pos_next, double *st, double *Pr,
-                                                  double *Prd);
 
 // swarms up to this many agents run as one persistent workgroup (srb_hlplan_kernel); larger ones
 // one launch per step over NA / 64 workgroups (srb_hlplan_step_kernel)
@@ -785,7 +710,7 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp)
     const size_t A = (size_t)n_agents;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    if (int rc0 = order_after_last(c, s)) return rc0;   // after the last device launch on this context
+    if (int rc0 = c->order.order_after_last(s)) return rc0;   // after the last device launch on this context
     if (!h->x0 || !h->ref || !h->foot || !h->x || !h->obj || !h->status || !h->iters)
         return fail(SRB_ERR_ARG, "missing buffer");
     HIPCHK(hipMemcpyAsync(c->x0, h->x0, A * 4 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -823,7 +748,7 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp)
     d.sel = nullptr;                       // the context's scratch; copied out below when asked for
     d.obstacles_version = 0;               // staged copy: rebuilt every call
     int rc = launch(c, n_agents, &d, s, use_nlp);
-    if (!rc) rc = mark_done(c, s);
+    if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->sel && use_nlp) {
         const int Ko = std::min(p->K_obs, std::max(h->n_obs, 0)), Kn = h->nbr_state ? std::min(p->K_nbr, std::max(h->n_all - 1, 0)) : 0;

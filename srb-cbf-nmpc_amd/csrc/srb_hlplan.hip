@@ -10,6 +10,7 @@
 // two columns are the unsampled states T and T+1 (T = loop / 40), reproduced (:1047-1067).
 #include <hip/hip_runtime.h>
 #include "srbnmpc.h"
+#include "srb_kernel_decls.h"
 
 #pragma clang fp contract(off)
 

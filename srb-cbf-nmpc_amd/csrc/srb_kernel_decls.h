@@ -1,0 +1,84 @@
+// What the host launch code and the device code must agree on, defined once: the structs passed to kernels by
+// value or by pointer, and the prototype of every extern "C" kernel.  Included by the .hip file that defines a
+// kernel and by the C-ABI file that launches it, so a parameter list that drifts is a conflicting declaration at
+// compile time instead of undefined behaviour at launch.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "srb_kernel_params.h"
+
+// device pointers of one low-level batch (srb_ll_io order; srb_ll_capi.cpp to_dev, srb_llctrl.hip)
+struct SrbLLDev {
+    const int *ind;
+    const double *q, *dq, *Dinv, *B, *Hv, *Jc, *dJc, *Js, *Jtoe, *Jhip, *toePos, *hipPos, *H0, *dH0, *y, *dy, *hd,
+        *dhd, *fDes;
+    double *tau, *QP_force, *ddq, *dq_out, *q_out, *V, *dV, *x;
+    int *status, *iters;
+};
+
+// Uniform grid over the rows of a table (SURVEY 8(a) row a10 at swarm scale): built on the
+// device each launch by srb_grid_build_kernel for tables of SRB_GRID_MIN_ROWS rows or more.
+// Cells row-major (cy * nx + cx), rows of finite coordinates sorted by cell (the order inside
+// a cell is arbitrary -- the selection order of srb_knn.h is exact whatever it is).
+struct SrbGrid {
+    double x0, y0, inv_h, h;       // origin and cell size
+    int nx, ny, n;                 // cells per axis, rows in the grid
+    int ok;                        // 0: not built (brute-force scan)
+};
+
+// ---- srb_kernels.hip: the solve kernel (INFIX empty, or f32_ for the fp32-factor instances) and the polish kernel
+#define SRB_DECL_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC)                                                         \
+    extern "C" __global__ void srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(               \
+        SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
+        const double *obstacles, int n_obs, const double *nbr_state, int n_all, int agent_offset,              \
+        double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
+        const double *alpha_buf, double *alpha_out, const int *sel_g, float *zpol_g, int zstride);
+#define SRB_DECL_POLISH(NZL, TS, NW, NC, CC, KC)                                                              \
+    extern "C" __global__ void srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                   \
+        SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
+        const double *obstacles, const double *nbr_state, double *x_out, double *obj_out, int *status_out,     \
+        const double *alpha_buf, double *alpha_out, const int *sel_g, const float *zpol_g, int zstride);
+#define SRB_DECL_NMPC(...) SRB_DECL_NMPC_(, __VA_ARGS__) SRB_DECL_POLISH(__VA_ARGS__)
+#define SRB_DECL_NMPC_F32(...) SRB_DECL_NMPC_(f32_, __VA_ARGS__)
+SRB_KERNEL_INSTANCES(SRB_DECL_NMPC)
+#ifndef SRB_DEV_INSTANCES
+SRB_KF32_INSTANCES(SRB_DECL_NMPC_F32)
+#endif
+#undef SRB_DECL_NMPC_
+#undef SRB_DECL_POLISH
+#undef SRB_DECL_NMPC
+#undef SRB_DECL_NMPC_F32
+
+// ---- srb_select.hip (compiled as part of srb_kernels.hip)
+extern "C" __global__ void srb_knn_kernel(int n_agents, const double *x0g, const double *obstacles, int n_obs,
+                                          const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
+                                          int *sel_out, int sel_stride, const SrbGrid *gob, const int *oob, const double2 *pob,
+                                          const int *iob, const SrbGrid *gnb, const int *onb, const double2 *pnb,
+                                          const int *inb);
+extern "C" __global__ void srb_grid_build_kernel(const double *tab0, int stride0, int n0, SrbGrid *g0, int *off0,
+                                                 double2 *spos0, int *sidx0, const double *tab1, int stride1, int n1,
+                                                 SrbGrid *g1, int *off1, double2 *spos1, int *sidx1);
+
+// ---- srb_prepare.hip, srb_hlplan.hip
+extern "C" __global__ void srb_prepare_kernel(int n_agents, int N, int C, int n_rows, int T, int agent_offset,
+                                              const double *Pr, const double *Prd, const int *agent_id,
+                                              const int *gait_domain, const int *contact, const double *toe,
+                                              const double *start, const double *q, const double *dq, double *x0,
+                                              double *ref, double *foot, double *last_state, int *status);
+extern "C" __global__ void srb_hlplan_kernel(int NA, const double *Pstart, const double *Pobs, int n_obs, int loop,
+                                             double *Pr, double *Prd);
+extern "C" __global__ void srb_hlplan_step_kernel(int NA, int i, int loop, const double *Pobs, int n_obs,
+                                                  const double *pos_cur, double *pos_next, double *st, double *Pr,
+                                                  double *Prd);
+
+// ---- srb_llctrl.hip
+extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDev io);
+
+// ---- srb12_kernels.hip
+#define SRB_DECL12(TL, TO, NC, K1)                                                                             \
+    extern "C" __global__ void srb12_kernel_##TL##_##TO##_##NC##_##K1(                                       \
+        Srb12KParams prm, int n_agents, const double *x0g, const double *xrefg, const double *footg,           \
+        const int *contactg, const double *obstacles, const double *nbr_state, const int *sel_g,              \
+        double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out);
+SRB12_INSTANCES(SRB_DECL12)
+#undef SRB_DECL12
+extern "C" __global__ void srb12_pos_kernel(int n_agents, const double *x0g, double *pos);

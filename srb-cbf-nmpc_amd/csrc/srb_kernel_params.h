@@ -3,9 +3,7 @@
 #pragma once
 
 #define SRB_KNN_MAX 16    // nearest static obstacles / neighbours per agent (each)
-#ifndef SRB_REFINE
-#define SRB_REFINE 1      // iterative-refinement steps per reduced Newton solve
-#endif
+#define SRB_REFINE 1      // iterative-refinement steps per reduced Newton solve (the KF instances: run-time, kkt32_ref)
 #ifndef SRB_KNN_WAVES
 #define SRB_KNN_WAVES 2   // waves per agent in the selection kernel (srb_knn_kernel; 2: 1 % faster configs[2] step than 4, round 4)
 #endif
@@ -46,9 +44,7 @@
 // 1/RHO; at most PASSES active sets (the most negative multiplier leaves, violated rows join).
 // Accepted (-> OPTIMAL) only if every row is within PTOL of its bound, the active rows hold to PTOL,
 // z_A >= -1e-9 max|z_A| and the last Newton correction is <= DXTOL.
-#ifndef SRB_POLISH_ON
-#define SRB_POLISH_ON 1
-#endif
+// (on by default; SRB_OPT_POLISH turns it off at run time)
 // instances whose solve kernel carries the fused polish (srb_kernels.hip; srb_capi.cpp launches the
 // polish kernel for the others).  Round 5: up to NZL 24 -- with the obstacle positions moved into the
 // Z'Z buffer (SRB_OBS_IN_ZZ) two N = 20 agents with the fused polish's buffer fit one CU's LDS, and
@@ -69,7 +65,8 @@
 #endif
 #define SRB_POLISH_PTOL 1e-9
 #define SRB_POLISH_DXTOL 1e-7
-// and only where the equality rows (LIP dynamics, CoP, sum lambda) hold to this (lip_eq_res, srb_kernels.hip)
+// and only where the equality rows (LIP dynamics, CoP, sum lambda) hold to this (lip_eq_res, srb_kernels.hip; a
+// diagnostic build without the test: -DSRB_POLISH_EQTOL=1e300)
 #ifndef SRB_POLISH_EQTOL
 #define SRB_POLISH_EQTOL 1e-8
 #endif
@@ -78,9 +75,6 @@
 // bench workloads, round 6)
 #ifndef SRB_POLISH_STOL
 #define SRB_POLISH_STOL 1e-6
-#endif
-#ifndef SRB_POLISH_EQCHECK        // 0: diagnostic builds without the equality test
-#define SRB_POLISH_EQCHECK 1
 #endif
 // a Newton step <= DX1 after which every active row holds to CTOL (its quadratic remainder) ends the
 // pass as converged without the verifying step (oracle ORC_POLISH_DX1 / ORC_POLISH_CTOL)

@@ -41,6 +41,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "srb_kernel_params.h"
+#include "srb_kernel_decls.h"
 
 #define WAVE 64
 // Barrier of the NW-wave workgroup.  NW = 1 (one agent per wave, the large-batch instances): the LDS
@@ -67,6 +68,7 @@ __device__ __forceinline__ void srb_sync()
 #define SYNC() srb_sync<NW>()
 
 #include "srb_wave.h"
+#include "srb_gj.h"
 
 
 // --------------------------------------------------------------------------- diagnostic stamps
@@ -88,20 +90,6 @@ __device__ unsigned long long srb_stamp_buf[SRB_NSTAMP];
 #define STAMP_END(slot) do {} while (0)
 #define STAMP_STAGE(s) do {} while (0)
 #define STAMP_FLUSH(agent) do {} while (0)
-#endif
-
-// --------------------------------------------------------------------------- fp32 storage (diagnostic)
-// Built only with -DSRB_DIAG_ROUND32 (make lipvar TAG=r32): every term row and every entry of the
-// assembled reduced matrix rounded to fp32 where it is stored -- the arithmetic effect of storing them in fp32 with
-// fp64 accumulation and the fp64 refinement (which then refines against the rounded matrix).  The LDS it would save
-// buys no occupancy (config 5 is register-bound at two agents per CU), so only the accuracy is measured.
-#ifdef SRB_DIAG_ROUND32
-#ifndef SRB_DIAG_BUILD
-#error "SRB_DIAG_ROUND32 is a diagnostic-build option"
-#endif
-#define R32(v) ((double)(float)(v))
-#else
-#define R32(v) (v)
 #endif
 
 // --------------------------------------------------------------------------- LDS bounds (diagnostic)
@@ -198,12 +186,12 @@ __device__ __forceinline__ void ul_add(const double *R, const double *W, const d
     const int c1 = F.C - 1, np = F.N * c1 * c1, rl = F.rU + 2 * F.N, rs = F.rU + F.n - 1 - 4 * F.N;
     if (GRAM) {
         for (int e = tid0; e <= np; e += step) {
-            if (e == np) { H[0] = R32(H[0] + W[rs]); continue; }  // slack row: Z = e_0
+            if (e == np) { H[0] = H[0] + W[rs]; continue; }  // slack row: Z = e_0
             const int j = e / (c1 * c1), rem = e - j * c1 * c1, a = 1 + j * c1 + rem / c1, b = 1 + j * c1 + rem % c1;
             double v = 0.0;
             for (int d = 0; d < 2; d++) { const int r = F.rU + 2 * j + d; v = fma(W[r] * R[r * LDR + a], R[r * LDR + b], v); }
             for (int i = 0; i < F.C; i++) { const int r = rl + F.C * j + i; v = fma(W[r] * R[r * LDR + a], R[r * LDR + b], v); }
-            H[a * LDH + b] = R32(H[a * LDH + b] + v);
+            H[a * LDH + b] = H[a * LDH + b] + v;
         }
     }
     if (RHS) {
@@ -440,7 +428,7 @@ __device__ __forceinline__ void gram_rhs(const double *R, const double *W, const
         // wave 0 stores its tiles; with two waves, wave 1 then adds its own in place (a fixed
         // order: bit-reproducible, and no partial-Gram scratch in LDS)
         auto put = [&](int i, int j, double v, bool add) {
-            if (i < NZL && j < NZL) H[i * LDH + j] = R32(add ? H[i * LDH + j] + v : v);
+            if (i < NZL && j < NZL) H[i * LDH + j] = add ? H[i * LDH + j] + v : v;
         };
 #pragma unroll
         for (int ph = 0; ph < NW; ph++) {
@@ -480,7 +468,6 @@ __device__ __forceinline__ void gram_rhs(const double *R, const double *W, const
 #pragma unroll
             for (int w2 = 0; w2 < NW; w2++) v += part[((w2 * NT + t) * 4 + q) * 64 + ln];
             const int r = (ln >> 4) + 4 * q, cl = ln & 15;
-            v = R32(v);
             if (t == 0) { if (r < NZL && cl < NZL) H[r * LDH + cl] = v; }
             else if (t == 1) { if (16 + cl < NZL) { H[r * LDH + 16 + cl] = v; H[(16 + cl) * LDH + r] = v; } }
             else if (16 + r < NZL && 16 + cl < NZL) H[(16 + r) * LDH + 16 + cl] = v;
@@ -648,7 +635,7 @@ __device__ __forceinline__ void obs_relin(double *R, double *OJ, int rO, int o, 
         double *dst = R + (rO + o) * LDR;
         const double *zx = R + i0 * LDR, *zy = R + i1 * LDR;
 #pragma unroll
-        for (int a = 0; a < NZL; a++) dst[a] = R32(fma(jx, zx[a], fma(jy, zy[a], (a == 0) ? -1.0 : 0.0)));
+        for (int a = 0; a < NZL; a++) dst[a] = fma(jx, zx[a], fma(jy, zy[a], (a == 0) ? -1.0 : 0.0));
     } else {
         OJ[2 * o] = jx; OJ[2 * o + 1] = jy;
     }
@@ -686,27 +673,6 @@ __device__ __forceinline__ void gj_load(double (&A)[NZL], const double *H, const
     }
 }
 
-// Inverse of the reduced Newton matrix (replicated layout from gj_load): gj_invert.  The
-// column-split elimination (gj_invert_split, -DSRB_GJ_SPLIT=1) is bit-identical and issues
-// fewer cross-lane moves, but measured slower on MI355X (configs[2] kernel 0.42 vs 0.40 ms,
-// configs[1] 0.244 vs 0.206 ms; profiles/r02_gj_split_ab.txt): column k reaches the other
-// rows of the wave through two permlane-swap stages on every step's critical path.
-#ifndef SRB_GJ_SPLIT
-#define SRB_GJ_SPLIT 0
-#endif
-#if SRB_GJ_SPLIT
-template <int NZL, int NZE = NZL>
-__device__ __forceinline__ int gj_reduced(double (&A)[NZL], int nz, int lane, int regularise)
-{
-    if constexpr (NZL <= 16 && NZL % 4 == 0 && SRB_USE_DPP && !SRB_KKT_FP32)
-        return gj_invert_split<NZL>(A, lane, regularise);
-    else
-        return gj_invert<NZL, NZE>(A, nz, lane, regularise);
-}
-#else
-#define gj_reduced gj_invert
-#endif
-
 // Newton solve in the reduced space: out = (Hs + dl Zs)^-1 g with one step of iterative refinement
 // (y = M g; y += M (g - Hs y)): the explicit inverse alone is not backward stable, and near
 // the end of an interior-point solve Hs carries barrier weights of 1e8..1e12.
@@ -727,8 +693,7 @@ __device__ __forceinline__ void la_solve(const double (&M)[NZL], const double *H
         double y0 = 0.0;
 #pragma unroll
         for (int j = 0; j < NZE; j++) y0 = fma(M[j], bc16(gi, j), y0);
-        // SRB_REFINE steps of iterative refinement with fp64 residuals (1 in the product build;
-        // the fp32-factor diagnostic build uses more)
+        // SRB_REFINE steps of iterative refinement with fp64 residuals (the KF instances: nref)
         double y1 = y0;
         const int nr = KF ? nref : SRB_REFINE;
 #pragma unroll
@@ -1019,7 +984,6 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
                                                   double *vd, const double (&Mi)[NZL], const double *H0, int nz, int tid,
                                                   double *part, uint64_t bmask, double *red, int N, int n, int TT, int srow)
 {
-    double gmax = 0.0;
     SYNC();                                              // every lane's reads of R / OJ / CF / vg of the last step are done
     // the obstacle rows linearised at the polished point itself (the last Newton step, up to 1e-4 when the
     // active rows then hold to 1e-10, ran on rows taken before it: J'z would be off by 2 |dx| |z| there)
@@ -1034,7 +998,6 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
             if (kd == K_VAR) {
                 const int v = q.i0;
                 const double a0 = var_weight(prm, v), gf = fma(a0, xs[v], (v < 4 * N) ? -a0 * ref[v] : 0.0);
-                gmax = fmax(gmax, fabs(gf));
                 CF[q.wr] = gf + zj;
             } else if (kd == K_COP || kd == K_OBS) {
                 CF[q.wr] = zj;
@@ -1078,7 +1041,6 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
         }
     double rv[2] = {-zmin, zmax};
     wred_x<2, 3u, NW>(rv, red + 5 * 8 * NW, tid);
-    (void)gmax;
     // (rho |c_A| <= rho SRB_POLISH_PTOL = 1 is the resolution of that update: the tolerance)
     return (-rv[0] >= -(prm.polish_rho * SRB_POLISH_PTOL + 1e-9 * rv[1])) ? dm : 1e300;
 }
@@ -1141,7 +1103,7 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
     float *zpl = (float *)p; p += SRB_FUSED_POLISH_OK(NZL) ? rnd4(S) : 0;   /* fused polish: the exported active set (2 floats a slot) */ \
     const int RROWS = SRB_OBS_STORED(NZL) ? TT : rO;   /* term rows stored in R */ \
     LCK_INIT(); \
-    LCK((int)(p - lds) <= srb_lds_doubles(prm, NZL, NW) - (SRB_FUSED_POLISH_OK(NZL) ? 0 : 0), 0); \
+    LCK((int)(p - lds) <= srb_lds_doubles(prm, NZL, NW), 0); \
     LCK(rU <= RROWS && (!SRB_OBS_STORED(NZL) || rO + NKP <= TT), 4); \
     (void)RROWS; \
     do {} while (0)
@@ -1180,13 +1142,13 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
         if (!is_null) \
             _Pragma("unroll") for (int i = 0; i < 4; i++) \
                 if (i < C) { g0 += foot[(j * 2 + 0) * C + i] * lam[i]; g1 += foot[(j * 2 + 1) * C + i] * lam[i]; } \
-        _Pragma("unroll") for (int i = 0; i < 4; i++) if (i < C) R[TL.zr(6 * N + C * j + i) * LDR + col] = R32(lam[i]); \
-        R[TL.zr(4 * N + 2 * j) * LDR + col] = R32(g0); \
-        R[TL.zr(4 * N + 2 * j + 1) * LDR + col] = R32(g1); \
+        _Pragma("unroll") for (int i = 0; i < 4; i++) if (i < C) R[TL.zr(6 * N + C * j + i) * LDR + col] = lam[i]; \
+        R[TL.zr(4 * N + 2 * j) * LDR + col] = g0; \
+        R[TL.zr(4 * N + 2 * j + 1) * LDR + col] = g1; \
         double v[4]; \
         for (int d = 0; d < 4; d++) v[d] = prm.Bd[d * 2] * g0 + prm.Bd[d * 2 + 1] * g1; \
         for (int k = j; k < N; k++) { \
-            for (int d = 0; d < 4; d++) R[(4 * k + d) * LDR + col] = R32(v[d]); \
+            for (int d = 0; d < 4; d++) R[(4 * k + d) * LDR + col] = v[d]; \
             double tt[4]; \
             for (int d = 0; d < 4; d++) tt[d] = prm.Ad[d * 4] * v[0] + prm.Ad[d * 4 + 1] * v[1] + prm.Ad[d * 4 + 2] * v[2] + prm.Ad[d * 4 + 3] * v[3]; \
             for (int d = 0; d < 4; d++) v[d] = tt[d]; \
@@ -1198,7 +1160,7 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
     /* CoM-CoP term rows M_e = Z_p - Z_u (p: CoM of grid i, u: CoP of grid i+1); xs = xbar */ \
     if (tid < NE) { \
         const int i = tid >> 1, d = tid & 1, pp = 4 * i + 2 * d, uu = 4 * N + 2 * (i + 1) + d; \
-        for (int a = 0; a < NZL; a++) Rt[tid * LDR + a] = R32(R[pp * LDR + a] - R[TL.zr(uu) * LDR + a]); \
+        for (int a = 0; a < NZL; a++) Rt[tid * LDR + a] = R[pp * LDR + a] - R[TL.zr(uu) * LDR + a]; \
     } \
     for (int v = tid; v < n; v += NTH) xs[v] = xb[v]; \
     do {} while (0)
@@ -1327,7 +1289,7 @@ _Pragma("unroll")                                                               
             SYNC();                                                                                                                           \
             if (pass == 0 && pit == 0) POLDBG_MAT(H0, LDH, vg, nz);                                                                           \
             gj_load<NZL, NZE>(Mi, H0, ZZ, 0.0, nz, lane);                                                                                          \
-            if (gj_reduced<NZL, NZE>(Mi, nz, lane, 0) != 0) { bad = true; break; } /* not PD: reject */                                            \
+            if (gj_invert<NZL, NZE>(Mi, nz, lane, 0) != 0) { bad = true; break; } /* not PD: reject */                                            \
             la_solve<NZL, NW, NZE>(Mi, H0, ZZ, 0.0, vg, vy, vr, vd, dxi, nz, lane);                                                                    \
             double mdx = 0.0;                                                                                                                 \
 _Pragma("unroll")                                                                                                                             \
@@ -1374,7 +1336,7 @@ _Pragma("unroll")                                                               
                         else if (q.m[r] != 0.0) vi = fmax(vi, v);                                                                             \
                     }                                                                                                                         \
                 }                                                                                                                             \
-            double rv[6] = {pv, cv, nzmin, zm, vi, SRB_POLISH_EQCHECK ? lip_eq_res(prm, x0, xs, foot, N, C, tid, NTH) : 0.0};                \
+            double rv[6] = {pv, cv, nzmin, zm, vi, lip_eq_res(prm, x0, xs, foot, N, C, tid, NTH)};                                   \
             wred_x<6, 0x3Fu, NW>(rv, red + 7 * 8 * NW, tid);                                                                                  \
             pv = rv[0]; cv = rv[1]; nzmin = rv[2]; zm = rv[3]; vi = rv[4]; eqr = rv[5];                                                       \
         }                                                                                                                                     \
@@ -1511,7 +1473,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
             gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, H0, vg, nz, tid, part, bmask);
             SYNC();
             gj_load<NZL, NZE>(Mi, H0, ZZ, 0.0, nz, lane);
-            if (gj_reduced<NZL, NZE>(Mi, nz, lane, 1) != 0) {
+            if (gj_invert<NZL, NZE>(Mi, nz, lane, 1) != 0) {
                 qp_flag = 1;                                  // x stays xbar (last iterate is returned)
                 continue;
             }
@@ -1645,7 +1607,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
             gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, ZZ, vg, nz, tid, part, bmask);
             SYNC();
             gj_load<NZL, NZE>(Mi, ZZ, ZZ, 0.0, nz, lane);
-            gj_reduced<NZL, NZE>(Mi, nz, lane, 0);
+            gj_invert<NZL, NZE>(Mi, nz, lane, 0);
             la_solve<NZL, NW, NZE>(Mi, ZZ, ZZ, 0.0, vg, vy, vr, vd, dxi, nz, lane);
 #pragma unroll
             for (int t = 0; t < TS; t++)
@@ -1854,7 +1816,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                     LCK(nl || delta == 0.0, 7);
                     gj_load<NZL, NZE>(Mi, H0, ZZ, delta, nz, lane);    // H0 + delta Z'Z (the solves shift on the fly too)
                     // KF instances: the inverse in fp32 while mu > kkt32_mu (then nref fp64 refinement steps per solve)
-                    const int cf = (KF && f32) ? gj_invert_f32<NZL>(Mi, mrow<NZL>(lane), !nl) : gj_reduced<NZL, NZE>(Mi, nz, lane, !nl);
+                    const int cf = (KF && f32) ? gj_invert_f32<NZL>(Mi, mrow<NZL>(lane), !nl) : gj_invert<NZL, NZE>(Mi, nz, lane, !nl);
                     if (cf == 0) { ok = 1; break; }
                     delta = (delta == 0.0) ? dstart : delta * 10.0;
                 }
@@ -2168,9 +2130,13 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
 
 }
 
-#define SRB_NMPC_KERNEL(NZL, TS, NW, NC, CC, KC)                                                               \
+// Kernel entries.  The solve kernel of an instance: INFIX empty and KF = 0, or INFIX f32_ and KF = 1 for the
+// fp32-factor instances (SRB_OPT_KKT_FP32_MU > 0 selects them): configs[4]'s "fp32 KKT with fp64 iterative-refine
+// residuals" -- the reduced Newton matrix assembled and refined against in fp64, inverted in fp32 while the
+// complementarity mu is above prm.kkt32_mu, in fp64 below
+#define SRB_NMPC_ENTRY(INFIX, KF, NZL, TS, NW, NC, CC, KC)                                                     \
     extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
-    srb_nmpc_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                                                 \
+    srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                                          \
         SrbKParams prm, int n_agents, const double *__restrict__ x0g, const double *__restrict__ refg,          \
         const double *__restrict__ footg, const double *__restrict__ obstacles, int n_obs,                       \
         const double *__restrict__ nbr_state, int n_all, int agent_offset, double *__restrict__ x_qp_out,        \
@@ -2181,10 +2147,11 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
-        nmpc_agent<NZL, TS, NW, NC, CC, KC>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
+        nmpc_agent<NZL, TS, NW, NC, CC, KC, KF>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
                                 x_qp_out, x_out, obj_out, status_out, iters_out, alpha_buf, alpha_out, sel_g, \
                                 zpol_g, zstride, lds);                                                         \
-    }                                                                                                          \
+    }
+#define SRB_POLISH_ENTRY(NZL, TS, NW, NC, CC, KC)                                                              \
     extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
     srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                                               \
         SrbKParams prm, int n_agents, const double *__restrict__ x0g, const double *__restrict__ refg,          \
@@ -2199,27 +2166,8 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         polish_agent<NZL, TS, NW, NC, CC, KC>(prm, agent, x0g, refg, footg, obstacles, nbr_state, x_out, obj_out,          \
                                   status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, lds);             \
     }
-
-// fp32-factor instances (KF = 1; SRB_OPT_KKT_FP32_MU > 0 selects them): configs[4]'s "fp32 KKT with fp64
-// iterative-refine residuals" -- the reduced Newton matrix assembled and refined against in fp64, inverted in
-// fp32 while the complementarity mu is above prm.kkt32_mu, in fp64 below
-#define SRB_NMPC_KERNEL_F32(NZL, TS, NW, NC, CC, KC)                                                           \
-    extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
-    srb_nmpc_kernel_f32_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                                             \
-        SrbKParams prm, int n_agents, const double *__restrict__ x0g, const double *__restrict__ refg,          \
-        const double *__restrict__ footg, const double *__restrict__ obstacles, int n_obs,                       \
-        const double *__restrict__ nbr_state, int n_all, int agent_offset, double *__restrict__ x_qp_out,        \
-        double *__restrict__ x_out, double *__restrict__ obj_out, int *__restrict__ status_out,                 \
-        int *__restrict__ iters_out, const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,       \
-        const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride)                               \
-    {                                                                                                          \
-        extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
-        const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
-        if (agent >= n_agents) return;                                                                         \
-        nmpc_agent<NZL, TS, NW, NC, CC, KC, 1>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
-                                x_qp_out, x_out, obj_out, status_out, iters_out, alpha_buf, alpha_out, sel_g, \
-                                zpol_g, zstride, lds);                                                         \
-    }
+#define SRB_NMPC_KERNEL(...) SRB_NMPC_ENTRY(, 0, __VA_ARGS__) SRB_POLISH_ENTRY(__VA_ARGS__)
+#define SRB_NMPC_KERNEL_F32(...) SRB_NMPC_ENTRY(f32_, 1, __VA_ARGS__)
 
 #if defined(SRB_PART) && !defined(SRB_DEV_INSTANCES)
 #if SRB_PART == 0
@@ -2240,154 +2188,10 @@ SRB_KF32_INSTANCES(SRB_NMPC_KERNEL_F32)
 #endif
 #endif
 
+// The selection kernels (srb_select.hip) are compiled into the code object of part 0 (or of the single-unit
+// builds), not one of their own: as a separate object, with every kernel's machine code unchanged, the default
+// bench step measured 0.3-0.6 % slower in three of three A/B runs against the library before the move (the
+// selection kernel runs right before the solve kernel of part 0 every step), and not with this layout.
 #if !defined(SRB_PART) || SRB_PART == 0
-
-// Obstacle and neighbour selection (MPC_dist.cpp:371-396, generalised to K): one workgroup per
-// agent, the K_obs nearest static obstacles (with the reference's 1000 m sentinel) and the
-// K_nbr nearest other agents to the agent's own CoM, indices to sel_out[agent][K_obs + K_nbr]
-// (-1: no neighbour row).  A kernel of its own rather than a phase of the solve: there the
-// scan ran at the solve kernel's occupancy, one or two waves per CU, and took a quarter of
-// the solve (profiles/r01_c3_stamps.txt).  Tables of SRB_GRID_MIN_ROWS rows or more come with
-// a uniform grid (srb_grid_build_kernel) and only the cells around the agent are scanned.
-extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_WAVES) srb_knn_kernel(int n_agents,
-                const double *__restrict__ x0g, const double *__restrict__ obstacles, int n_obs,
-                const double *__restrict__ nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                int *__restrict__ sel_out, int sel_stride, const SrbGrid *__restrict__ gob, const int *__restrict__ oob,
-                const double2 *__restrict__ pob, const int *__restrict__ iob, const SrbGrid *__restrict__ gnb,
-                const int *__restrict__ onb, const double2 *__restrict__ pnb, const int *__restrict__ inb)
-{
-    __shared__ double wd_lds[SRB_KNN_WAVES];
-    __shared__ int wi_lds[SRB_KNN_WAVES];
-    const int agent = xcd_agent(blockIdx.x, gridDim.x), tid = threadIdx.x;
-    if (agent >= n_agents) return;                 // whole workgroup: the barriers stay uniform
-    const double px = x0g[4 * (size_t)agent], py = x0g[4 * (size_t)agent + 2];
-    // sel_stride = Ko + Kn of the whole selection; a pass over one table (srb_select_device) hands over
-    // K_obs or K_nbr alone and sel_out already offset to its columns
-    int *sel = sel_out + (size_t)agent * sel_stride;
-    if (SRB_KNN_WAVES == 2 && K_obs > 0 && K_nbr > 0) {
-        // the two tables on the two waves at once, each selection wave-local (DPP argmins, no barrier):
-        // configs[2] selection 23.5 -> 20.9 us a step (HIP events, round 5; round 6's thresholded scan and ballot
-        // argmin in srb_wave.h: 20.5 -> 13.4 us); the same rows.  (Selecting
-        // inside the solve kernel's setup instead measured no faster at configs[2] -- the solve kernel
-        // grew by what the launch saved -- and 4.6 % slower at N = 20, where four rounds of agents each
-        // wait for their selection; round 5)
-        const int lane = tid & 63;
-        if (tid < 64)
-            knn_select<1>(lane, px, py, obstacles, 2, n_obs, -1, K_obs, 1, sel, wd_lds, wi_lds, gob, oob, pob, iob);
-        else
-            knn_select<1>(lane, px, py, nbr_state, 4, n_all, agent_offset + agent, K_nbr, 0, sel + K_obs, wd_lds, wi_lds,
-                          gnb, onb, pnb, inb);
-        return;
-    }
-    // one table (srb_select_device's passes, or a batch without neighbour rows): a table that one wave scans
-    // with the threshold pass (knn_thresh) or through a grid runs on wave 0 alone -- the two-wave form pays two
-    // barriers per pop round (round 6: the neighbour pass of the multi-GPU step 19.3 us with both waves)
-    if (SRB_KNN_WAVES == 2 && (K_obs > 0) != (K_nbr > 0)) {
-        const bool o = K_obs > 0;
-        const SrbGrid *g = o ? gob : gnb;
-        if ((o ? n_obs : n_all) <= 64 * SRB_KNN_RB || (g && g->ok)) {
-            if (tid >= 64) return;                     // whole wave: no barrier follows on the one-wave path
-            if (o) knn_select<1>(tid, px, py, obstacles, 2, n_obs, -1, K_obs, 1, sel, wd_lds, wi_lds, gob, oob, pob, iob);
-            else knn_select<1>(tid, px, py, nbr_state, 4, n_all, agent_offset + agent, K_nbr, 0, sel + K_obs, wd_lds, wi_lds,
-                               gnb, onb, pnb, inb);
-            return;
-        }
-    }
-    if (K_obs > 0)
-        knn_select<SRB_KNN_WAVES>(tid, px, py, obstacles, 2, n_obs, -1, K_obs, 1, sel, wd_lds, wi_lds, gob, oob, pob, iob);
-    if (K_nbr > 0)
-        knn_select<SRB_KNN_WAVES>(tid, px, py, nbr_state, 4, n_all, agent_offset + agent, K_nbr, 0, sel + K_obs, wd_lds,
-                                  wi_lds, gnb, onb, pnb, inb);
-}
-
-// Uniform grid over one table per workgroup (block 0: table 0, block 1: table 1), rebuilt every
-// launch (the neighbour snapshot moves every cycle): bounds of the finite rows, about two rows
-// per cell (at most SRB_GRID_CELLS cells), counts by LDS atomics, one exclusive scan, scatter of
-// the rows into cell order.  One workgroup of 1024 threads per table: a few microseconds for the
-// tens of thousands of rows of an 8-GPU swarm, against a brute-force scan per agent.
-__device__ __forceinline__ int grid_cell(double x, double y, double x0, double y0, double inv_h, int nx, int ny)
-{
-    const int cx = min(max((int)((x - x0) * inv_h), 0), nx - 1);
-    const int cy = min(max((int)((y - y0) * inv_h), 0), ny - 1);
-    return cy * nx + cx;
-}
-
-extern "C" __global__ void __launch_bounds__(1024) srb_grid_build_kernel(
-    const double *__restrict__ tab0, int stride0, int n0, SrbGrid *g0, int *off0, double2 *spos0, int *sidx0,
-    const double *__restrict__ tab1, int stride1, int n1, SrbGrid *g1, int *off1, double2 *spos1, int *sidx1)
-{
-    __shared__ int cnt[SRB_GRID_CELLS];
-    __shared__ double red[4][16];
-    __shared__ int part[1024];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const double *tab = blockIdx.x ? tab1 : tab0;
-    const int stride = blockIdx.x ? stride1 : stride0, n = blockIdx.x ? n1 : n0;
-    SrbGrid *g = blockIdx.x ? g1 : g0;
-    int *off = blockIdx.x ? off1 : off0;
-    double2 *spos = blockIdx.x ? spos1 : spos0;
-    int *sidx = blockIdx.x ? sidx1 : sidx0;
-    if (!g) return;
-    // bounds of the finite rows
-    double mnx = __builtin_inf(), mny = __builtin_inf(), mxx = -__builtin_inf(), mxy = -__builtin_inf();
-    for (int i = tid; i < n; i += 1024) {
-        const double x = tab[(size_t)stride * i], y = tab[(size_t)stride * i + 1];
-        if (isfinite(x) && isfinite(y)) { mnx = fmin(mnx, x); mny = fmin(mny, y); mxx = fmax(mxx, x); mxy = fmax(mxy, y); }
-    }
-    mnx = wmin(mnx); mny = wmin(mny); mxx = wmax(mxx); mxy = wmax(mxy);
-    if (lane == 0) { red[0][wv] = mnx; red[1][wv] = mny; red[2][wv] = mxx; red[3][wv] = mxy; }
-    __syncthreads();
-    mnx = red[0][0]; mny = red[1][0]; mxx = red[2][0]; mxy = red[3][0];
-    for (int w = 1; w < 16; w++) {
-        mnx = fmin(mnx, red[0][w]); mny = fmin(mny, red[1][w]); mxx = fmax(mxx, red[2][w]); mxy = fmax(mxy, red[3][w]);
-    }
-    if (!(mnx <= mxx)) {                           // no finite row: selection falls back to the scan
-        if (tid == 0) g->ok = 0;
-        return;
-    }
-    const double W = mxx - mnx, H = mxy - mny;
-    const int target = min(max(n / 2, 1), SRB_GRID_CELLS);
-    double h = sqrt(fmax(W * H, 1e-300) / target);
-    if (!(h > 0.0) || !isfinite(h)) h = 1.0;
-    h = fmax(h, fmax(W, H) / 4096.0);             // keeps nx, ny in range
-    int nx = (int)(W / h) + 1, ny = (int)(H / h) + 1;
-    while ((long long)nx * ny > SRB_GRID_CELLS) { h *= 1.25; nx = (int)(W / h) + 1; ny = (int)(H / h) + 1; }
-    const double inv_h = 1.0 / h;
-    const int C = nx * ny;
-    for (int c = tid; c < C; c += 1024) cnt[c] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += 1024) {
-        const double x = tab[(size_t)stride * i], y = tab[(size_t)stride * i + 1];
-        if (isfinite(x) && isfinite(y)) atomicAdd(&cnt[grid_cell(x, y, mnx, mny, inv_h, nx, ny)], 1);
-    }
-    __syncthreads();
-    // exclusive scan: per-thread chunk sums, a scan of the 1024 partials, chunk-local offsets
-    const int chunk = (C + 1023) / 1024, c0 = tid * chunk, c1 = min(c0 + chunk, C);
-    int sum = 0;
-    for (int c = c0; c < c1; c++) sum += cnt[c];
-    part[tid] = sum;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-        const int v = (tid >= o) ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - sum;                     // exclusive prefix of this chunk
-    for (int c = c0; c < c1; c++) { const int v = cnt[c]; cnt[c] = run; off[c] = run; run += v; }
-    if (tid == 1023) off[C] = part[1023];
-    __syncthreads();
-    for (int i = tid; i < n; i += 1024) {
-        const double x = tab[(size_t)stride * i], y = tab[(size_t)stride * i + 1];
-        if (isfinite(x) && isfinite(y)) {
-            const int at = atomicAdd(&cnt[grid_cell(x, y, mnx, mny, inv_h, nx, ny)], 1);
-            spos[at] = make_double2(x, y);
-            sidx[at] = i;
-        }
-    }
-    if (tid == 0) {
-        SrbGrid r;
-        r.x0 = mnx; r.y0 = mny; r.inv_h = inv_h; r.h = h; r.nx = nx; r.ny = ny; r.n = part[1023]; r.ok = 1;
-        *g = r;
-    }
-}
-#endif   // SRB_PART 0: selection kernels
+#include "srb_select.hip"
+#endif

@@ -10,24 +10,8 @@
 #include <string>
 #include "srbnmpc.h"
 #include "srb_kernel_params.h"
-
-int srb_internal_fail(int code, const char *msg);
-
-struct SrbLLDev {   // must match srb_llctrl.hip
-    const int *ind;
-    const double *q, *dq, *Dinv, *B, *Hv, *Jc, *dJc, *Js, *Jtoe, *Jhip, *toePos, *hipPos, *H0, *dH0, *y, *dy, *hd,
-        *dhd, *fDes;
-    double *tau, *QP_force, *ddq, *dq_out, *q_out, *V, *dV, *x;
-    int *status, *iters;
-};
-extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDev io);
-
-#define LLCHK(expr)                                                                                     \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return srb_internal_fail(SRB_ERR_HIP, (std::string(#expr ": ") + hipGetErrorString(e_)).c_str()); \
-    } while (0)
+#include "srb_kernel_decls.h"
+#include "srb_host.h"
 
 // per-agent element counts of every srb_ll_io array, in SrbLLDev order
 static const int kInCount[] = {18, 18, 18 * 18, 12 * 18, 18, 18 * 12, 12, 18 * 12, 18 * 12, 18 * 12, 12, 12,
@@ -41,9 +25,8 @@ struct srb_ll_ctx {
     int max_agents, device;
     hipStream_t stream;
     hipEvent_t ev[2];
-    hipEvent_t done;               // recorded after every call's work (submission-order chaining)
-    hipStream_t last;              // stream of the previous call
-    bool timed, any;
+    SrbCallOrder order;            // submission-order chaining of the calls on this context
+    bool timed;
     int *ind, *status, *iters;
     double *in[LL_NIN], *outb[LL_NOUT];
 };
@@ -92,21 +75,24 @@ extern "C" int srb_ll_ctx_create(const srb_ll_params *p, int max_agents, int dev
     int rc = validate_ll(p);
     if (rc) return rc;
     int ndev = 0;
-    LLCHK(hipGetDeviceCount(&ndev));
+    HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return srb_internal_fail(SRB_ERR_ARG, "device index out of range");
-    LLCHK(hipSetDevice(device));
+    HIPCHK(hipSetDevice(device));
     srb_ll_ctx *c = new srb_ll_ctx();
     std::memset(c, 0, sizeof *c);
     c->p = *p; c->max_agents = max_agents; c->device = device;
     const size_t A = (size_t)max_agents;
-    LLCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) LLCHK(hipEventCreate(&c->ev[i]));
-    LLCHK(hipEventCreateWithFlags(&c->done, hipEventDisableTiming));
-    LLCHK(hipMalloc(&c->ind, A * 4 * sizeof(int)));
-    LLCHK(hipMalloc(&c->status, A * sizeof(int)));
-    LLCHK(hipMalloc(&c->iters, A * sizeof(int)));
-    for (int i = 0; i < LL_NIN; i++) LLCHK(hipMalloc(&c->in[i], A * kInCount[i] * sizeof(double)));
-    for (int i = 0; i < LL_NOUT; i++) LLCHK(hipMalloc(&c->outb[i], A * kOutCount[i] * sizeof(double)));
+    // a failure after this point unwinds through srb_ll_ctx_destroy (it null-checks every handle); *out stays untouched
+#define CREATE_CHK(expr) HIPCHK_UNWIND_(expr, #expr, srb_ll_ctx_destroy(c))
+    CREATE_CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++) CREATE_CHK(hipEventCreate(&c->ev[i]));
+    CREATE_CHK(hipEventCreateWithFlags(&c->order.done, hipEventDisableTiming));
+    CREATE_CHK(hipMalloc(&c->ind, A * 4 * sizeof(int)));
+    CREATE_CHK(hipMalloc(&c->status, A * sizeof(int)));
+    CREATE_CHK(hipMalloc(&c->iters, A * sizeof(int)));
+    for (int i = 0; i < LL_NIN; i++) CREATE_CHK(hipMalloc(&c->in[i], A * kInCount[i] * sizeof(double)));
+    for (int i = 0; i < LL_NOUT; i++) CREATE_CHK(hipMalloc(&c->outb[i], A * kOutCount[i] * sizeof(double)));
+#undef CREATE_CHK
     *out = c;
     return SRB_OK;
 }
@@ -115,14 +101,19 @@ extern "C" int srb_ll_ctx_destroy(srb_ll_ctx *c)
 {
     if (!c) return SRB_OK;
     (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    if (c->any) (void)hipEventSynchronize(c->done);     // the last launch may be on another stream
-    (void)hipFree(c->ind); (void)hipFree(c->status); (void)hipFree(c->iters);
-    for (int i = 0; i < LL_NIN; i++) (void)hipFree(c->in[i]);
-    for (int i = 0; i < LL_NOUT; i++) (void)hipFree(c->outb[i]);
-    for (int i = 0; i < 2; i++) (void)hipEventDestroy(c->ev[i]);
-    (void)hipEventDestroy(c->done);
-    (void)hipStreamDestroy(c->stream);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    (void)c->order.wait_idle();                         // the last launch may be on another stream
+    void *bufs[] = {c->ind, c->status, c->iters};
+    for (void *b : bufs)
+        if (b) (void)hipFree(b);
+    for (double *b : c->in)
+        if (b) (void)hipFree(b);
+    for (double *b : c->outb)
+        if (b) (void)hipFree(b);
+    for (int i = 0; i < 2; i++)
+        if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
+    if (c->order.done) (void)hipEventDestroy(c->order.done);
+    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return SRB_OK;
 }
@@ -142,21 +133,6 @@ static SrbLLDev to_dev(const srb_ll_io *d)
     return k;
 }
 
-// calls on one context run in submission order (include/srbnmpc.h, "Ordering"): a call on
-// another stream than the previous one first waits for that call's work
-static int ll_order(srb_ll_ctx *c, hipStream_t s)
-{
-    if (c->any && s != c->last) LLCHK(hipStreamWaitEvent(s, c->done, 0));
-    return SRB_OK;
-}
-
-static int ll_done(srb_ll_ctx *c, hipStream_t s)
-{
-    LLCHK(hipEventRecord(c->done, s));
-    c->last = s; c->any = true;
-    return SRB_OK;
-}
-
 static int ll_launch(srb_ll_ctx *c, int n_agents, SrbLLDev k, hipStream_t s)
 {
     const void *need[] = {k.ind, k.q, k.dq, k.Dinv, k.B, k.Hv, k.Jc, k.dJc, k.Js, k.Jtoe, k.Jhip, k.toePos,
@@ -166,10 +142,10 @@ static int ll_launch(srb_ll_ctx *c, int n_agents, SrbLLDev k, hipStream_t s)
         if (!b) return srb_internal_fail(SRB_ERR_ARG, "missing srb_ll_io buffer");
     SrbLLKParams prm = make_llk(&c->p);
     prm.dbg_agent = srb_ll_dbg_agent();
-    LLCHK(hipEventRecord(c->ev[0], s));
+    HIPCHK(hipEventRecord(c->ev[0], s));
     hipLaunchKernelGGL(srb_ll_kernel, dim3(n_agents), dim3(64), 0, s, prm, n_agents, k);
-    LLCHK(hipGetLastError());
-    LLCHK(hipEventRecord(c->ev[1], s));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev[1], s));
     c->timed = true;
     return SRB_OK;
 }
@@ -181,13 +157,13 @@ extern "C" int srb_ll_calc_torque_device(srb_ll_ctx *c, int n_agents, const srb_
     if (!c || !d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
-    LLCHK(hipSetDevice(c->device));
+    HIPCHK(hipSetDevice(c->device));
     SrbLLDev k = to_dev(d);
     if (!k.x) k.x = c->outb[7];   // x is optional: the context's buffer absorbs it
     hipStream_t s = (hipStream_t)stream;                         // NULL: the HIP null stream
-    int rc = ll_order(c, s);
+    int rc = c->order.order_after_last(s);
     if (!rc) rc = ll_launch(c, n_agents, k, s);
-    if (!rc) rc = ll_done(c, s);
+    if (!rc) rc = c->order.mark_done(s);
     return rc;
 }
 
@@ -198,9 +174,9 @@ extern "C" int srb_ll_calc_torque(srb_ll_ctx *c, int n_agents, const srb_ll_io *
     if (!c || !h) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
-    LLCHK(hipSetDevice(c->device));
+    HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    if (int rc0 = ll_order(c, s)) return rc0;
+    if (int rc0 = c->order.order_after_last(s)) return rc0;
     const size_t A = (size_t)n_agents;
     const double *hin[LL_NIN] = {h->q, h->dq, h->Dinv, h->B, h->H, h->Jc, h->dJc, h->Js, h->Jtoe, h->Jhip,
                                  h->toePos, h->hipPos, h->H0, h->dH0, h->y, h->dy, h->hd, h->dhd, h->fDes};
@@ -210,10 +186,10 @@ extern "C" int srb_ll_calc_torque(srb_ll_ctx *c, int n_agents, const srb_ll_io *
         if (!hin[i]) return srb_internal_fail(SRB_ERR_ARG, "missing srb_ll_io input buffer");
     for (int i = 0; i < LL_NOUT - 1; i++)
         if (!hout[i]) return srb_internal_fail(SRB_ERR_ARG, "missing srb_ll_io output buffer");
-    LLCHK(hipMemcpyAsync(c->ind, h->ind, A * 4 * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->ind, h->ind, A * 4 * sizeof(int), hipMemcpyHostToDevice, s));
     for (int i = 0; i < LL_NIN; i++)
-        LLCHK(hipMemcpyAsync(c->in[i], hin[i], A * kInCount[i] * sizeof(double), hipMemcpyHostToDevice, s));
-    LLCHK(hipMemcpyAsync(c->outb[0], h->tau, A * 18 * sizeof(double), hipMemcpyHostToDevice, s));   // tau is in/out
+        HIPCHK(hipMemcpyAsync(c->in[i], hin[i], A * kInCount[i] * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(c->outb[0], h->tau, A * 18 * sizeof(double), hipMemcpyHostToDevice, s));   // tau is in/out
     srb_ll_io d;
     d.struct_size = sizeof d;
     d.ind = c->ind;
@@ -224,30 +200,30 @@ extern "C" int srb_ll_calc_torque(srb_ll_ctx *c, int n_agents, const srb_ll_io *
     d.tau = c->outb[0]; d.QP_force = c->outb[1]; d.ddq = c->outb[2]; d.dq_out = c->outb[3]; d.q_out = c->outb[4];
     d.V = c->outb[5]; d.dV = c->outb[6]; d.x = c->outb[7]; d.status = c->status; d.iters = c->iters;
     int rc = ll_launch(c, n_agents, to_dev(&d), s);
-    if (!rc) rc = ll_done(c, s);
+    if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     for (int i = 0; i < LL_NOUT; i++)
-        if (hout[i]) LLCHK(hipMemcpyAsync(hout[i], c->outb[i], A * kOutCount[i] * sizeof(double), hipMemcpyDeviceToHost, s));
-    LLCHK(hipMemcpyAsync(h->status, c->status, A * sizeof(int), hipMemcpyDeviceToHost, s));
-    LLCHK(hipMemcpyAsync(h->iters, c->iters, A * sizeof(int), hipMemcpyDeviceToHost, s));
-    LLCHK(hipStreamSynchronize(s));
+        if (hout[i]) HIPCHK(hipMemcpyAsync(hout[i], c->outb[i], A * kOutCount[i] * sizeof(double), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h->status, c->status, A * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(h->iters, c->iters, A * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     return SRB_OK;
 }
 
 extern "C" int srb_ll_sync(srb_ll_ctx *c)
 {
     if (!c) return srb_internal_fail(SRB_ERR_ARG, "null ctx");
-    LLCHK(hipSetDevice(c->device));
-    LLCHK(hipDeviceSynchronize());
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
     return SRB_OK;
 }
 
 extern "C" int srb_ll_last_kernel_ms(srb_ll_ctx *c, float *ms)
 {
     if (!c || !c->timed) return srb_internal_fail(SRB_ERR_ARG, "no timed launch");
-    LLCHK(hipEventSynchronize(c->ev[1]));
+    HIPCHK(hipEventSynchronize(c->ev[1]));
     float t = 0;
-    LLCHK(hipEventElapsedTime(&t, c->ev[0], c->ev[1]));
+    HIPCHK(hipEventElapsedTime(&t, c->ev[0], c->ev[1]));
     if (ms) *ms = t;
     return SRB_OK;
 }

@@ -27,7 +27,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "srb_kernel_params.h"
+#include "srb_kernel_decls.h"
 #include "srb_wave.h"
+#include "srb_gj.h"
 
 #define NQ SRB_LL_NQ
 #define NU SRB_LL_NU
@@ -35,14 +37,6 @@
 #define LDA 25      // row stride of the dense (F, tau) part of A
 #define ZS 63       // index of the always-zero slot of the 64-entry LDS vectors
 #define SYNC() __syncthreads()
-
-struct SrbLLDev {
-    const int *ind;
-    const double *q, *dq, *Dinv, *B, *Hv, *Jc, *dJc, *Js, *Jtoe, *Jhip, *toePos, *hipPos, *H0, *dH0, *y, *dy, *hd,
-        *dhd, *fDes;
-    double *tau, *QP_force, *ddq, *dq_out, *q_out, *V, *dV, *x;
-    int *status, *iters;
-};
 
 struct LLShared {
     double D[NQ * NQ];                    // Dinv, column-major as given

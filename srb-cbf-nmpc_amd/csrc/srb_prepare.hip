@@ -8,6 +8,7 @@
 // neighbour-snapshot row (get_lastState) that the multi-GPU all-gather exchanges.
 #include <hip/hip_runtime.h>
 #include "srbnmpc.h"
+#include "srb_kernel_decls.h"
 
 // MPC_dist.cpp:1206-1209: FR, FL, RR, RL offsets from the start position
 __constant__ double c_init_foot[4][2] = {{0.2188, -0.1320}, {0.2188, 0.1320}, {-0.1472, -0.1320}, {-0.1472, 0.1320}};

@@ -424,7 +424,7 @@ def test_knn_matches_bruteforce(Ko, Kn):
 
 @pytest.mark.parametrize("n_tab", [5, 64, 256, 257, 1024, 1025, 2048, 2049, 5000])
 def test_knn_threshold_pass_table_sizes(n_tab):
-    """Round 6's thresholded scan (srb_wave.h knn_thresh: 4, 16 or 32 register slots a lane by the table's size,
+    """Round 6's thresholded scan (srb_knn.h knn_thresh: 4, 16 or 32 register slots a lane by the table's size,
     the batched scan beyond 2048 rows) at every size boundary, through srb_select_device on one table and on both
     (one wave each): the reference's order exactly (oracle.select_idx) -- with exact-distance ties (a table
     snapped to a quarter-metre lattice around lattice-aligned agents), NaN rows, the agent's own row, and K

@@ -7,7 +7,7 @@
 #include <cmath>
 #define WAVE 64
 #include "../../srb-cbf-nmpc_amd/csrc/srb_kernel_params.h"
-#include "../../srb-cbf-nmpc_amd/csrc/srb_wave.h"
+#include "../../srb-cbf-nmpc_amd/csrc/srb_gj.h"
 
 // value of lane k of this lane's 16-lane row (k folds to an immediate after unrolling)
 __device__ __forceinline__ double bc16(double v, int k)

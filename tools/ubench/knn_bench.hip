@@ -5,7 +5,7 @@
 #include <cstdio>
 #include <vector>
 #include "srb_kernel_params.h"
-#include "srb_wave.h"
+#include "srb_knn.h"
 
 template <int KW, int MODE>
 __global__ void __launch_bounds__(64 * KW) kb(int n_agents, const double *x0g, const double *obst, int n_obs,

@@ -6,7 +6,7 @@
 #include <cstdio>
 #include <vector>
 #include "srb_kernel_params.h"
-#include "srb_wave.h"
+#include "srb_knn.h"
 
 // MODE bits: 1 no sqrt (the key is d^2), 2 no insertion (lane min only), 4 no pop rounds, 8 no table loads
 // (rows from registers), 16 empty kernel (store only)
