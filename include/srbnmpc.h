@@ -42,7 +42,7 @@ extern "C" {
  * the SRB_ABI_VERSION the library was built with (bumped on any layout change).
  *   srb_batch b = {sizeof(srb_batch)};      (C)      srb_batch b{}; b.struct_size = sizeof b;  (C++)
  */
-#define SRB_ABI_VERSION 5
+#define SRB_ABI_VERSION 6
 int srb_abi_version(void);
 
 /* solver exit codes (iSWIFT GlobalOptions.h:31-34) */
@@ -108,6 +108,18 @@ int srb_nv(const srb_params *p);     /* (6+C)N+1 */
  *                           lower index on ties; a static round with nothing closer than 1000 m
  *                           selects obstacle 0, as min_dist = 1000 / min_i = 0 do).  NULL = the
  *                           context's own scratch buffer.
+ * Neighbour plans (the inter-agent CBF rows against what the neighbours plan to do), both optional:
+ *   nbr_plan  [n_all][N][2] in: row i, grid k is global agent i's predicted (x, y) at time (k+1) Ts from the
+ *                           instant of x0 -- the grid times of obstacle row k.  NULL: the neighbour rows are
+ *                           the constant-velocity guess p + v Ts (k+1) from nbr_state.  Read only by the NLP
+ *                           stage and only for the neighbour columns of sel; needs nbr_state (the selection's
+ *                           snapshot) and, with K_nbr > 0, agent_offset + n_agents <= n_all.  Row
+ *                           agent_offset + a is agent a's own previous plan: the horizon-aware selection
+ *                           (SRB_OPT_PLAN_SELECTION) reads it, the CBF rows never do.
+ *   plan      [A][N][2]     out: (x[4k], x[4k+2]) of the returned x for every agent, whatever its status (written
+ *                           by the kernel that writes the final x: always a gather of x).  srb_solve_qp
+ *                           writes it from the QP x.  Must not overlap the nbr_plan table: workgroups read the
+ *                           table while others write their plans, so an iteration over plans needs two buffers.
  */
 typedef struct srb_batch {
     int struct_size;         /* sizeof(srb_batch) (ABI check, see SRB_ABI_VERSION) */
@@ -121,6 +133,8 @@ typedef struct srb_batch {
     int obstacles_version;   /* != 0: the obstacle table is unchanged since the last call that passed
                                 this version, pointer and n_obs (the reference's Pobs_real is set once,
                                 MPC_dist::setPobs_real): its selection grid is reused; 0: rebuilt */
+    const double *nbr_plan;  /* [n_all][N][2] neighbour plans, or NULL (constant velocity) */
+    double *plan;            /* [A][N][2] this batch's plans, or NULL */
 } srb_batch;
 
 typedef struct srb_ctx srb_ctx;
@@ -170,7 +184,14 @@ int srb_ctx_waves(srb_ctx *ctx);
  *                                matrix (assembled in fp64) is inverted in fp32 while the complementarity mu is
  *                                above this value, each solve then refined SRB_OPT_KKT_FP32_REFINE times (default
  *                                3) against the fp64 matrix; fp64 below it
- *   SRB_OPT_LAST_KKT_FP32        read only: 1 if the last launch ran an fp32-factor instance */
+ *   SRB_OPT_LAST_KKT_FP32        read only: 1 if the last launch ran an fp32-factor instance
+ *   SRB_OPT_PLAN_SELECTION       0 (default): neighbours are selected from the snapshot (nbr_state), nearest now.
+ *                                1: by closest predicted approach over the horizon (srb_knn_plan_kernel): the key
+ *                                of table row i for agent g = agent_offset + a is the square root of the smallest
+ *                                squared distance over the snapshot pair (x0 against nbr_state[i]) and the N grid
+ *                                pairs nbr_plan[g][k] against nbr_plan[i][k]; same order, ties, NaN and -1 rules,
+ *                                brute force.  Needs batch.nbr_plan (SRB_ERR_ARG without it); the static columns
+ *                                are selected as before */
 #define SRB_OPT_POLISH 1
 #define SRB_OPT_POLISH_RHO 2
 #define SRB_OPT_POLISH_WAVES 3
@@ -184,6 +205,7 @@ int srb_ctx_waves(srb_ctx *ctx);
 #define SRB_OPT_KKT_FP32_MU 11
 #define SRB_OPT_KKT_FP32_REFINE 12
 #define SRB_OPT_LAST_KKT_FP32 13
+#define SRB_OPT_PLAN_SELECTION 14
 int srb_ctx_set_option(srb_ctx *ctx, int opt, double value);
 int srb_ctx_get_option(srb_ctx *ctx, int opt, double *value);
 
@@ -217,6 +239,7 @@ int srb_solve_batch_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, 
 
 /* The selection alone (MPC_dist.cpp:371-396 generalised to K), asynchronous on `stream`: tables = 1 the static
  * obstacles (columns 0 .. Ko-1 of dev_io->sel), 2 the neighbour snapshot (columns Ko .. Ko+Kn-1), 3 both.
+ * With SRB_OPT_PLAN_SELECTION = 1, tables & 2 is the horizon-aware selection and needs dev_io->nbr_plan.
  * dev_io->sel is required; the other members are read as srb_solve_batch_device reads them.  Multi-GPU use
  * (bench.py): select the static obstacles while the neighbour all-gather is in flight, the neighbours after
  * it, then solve with SRB_OPT_SELECTION = 0.  Indices are identical to the solve's own selection. */

@@ -18,10 +18,10 @@
 
 typedef void (*srb_kernel_fn)(SrbKParams, int, const double *, const double *, const double *, const double *, int,
                               const double *, int, int, double *, double *, double *, int *, int *, const double *,
-                              double *, const int *, float *, int);
+                              double *, const int *, float *, int, const double *, double *);
 typedef void (*srb_polish_fn)(SrbKParams, int, const double *, const double *, const double *, const double *,
                               const double *, double *, double *, int *, const double *, double *, const int *,
-                              const float *, int);
+                              const float *, int, const double *, double *);
 struct srb_instance { int nzl, ts, nw, nc, cc, kc; srb_kernel_fn fn; srb_polish_fn polish; };
 // solve kernel (INFIX empty, or f32_) and polish kernel of one instance
 #define ENTRY_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC) NZL, TS, NW, NC, CC, KC, srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
@@ -92,6 +92,9 @@ struct srb_ctx {
     SrbCallOrder order;            // submission-order chaining of the calls on this context
     // device staging
     double *x0, *ref, *foot, *obstacles, *nbr, *x_qp, *x, *obj, *abuf, *alpha;
+    double *nbr_plan, *plan;       // neighbour plan table [cap_plan][N][2], this batch's plans [max_agents][N][2]
+    size_t cap_plan;
+    int plan_selection;            // SRB_OPT_PLAN_SELECTION: 1 neighbours by closest predicted approach
     int *status, *iters;
     int *sel;                      // [max_agents][2 SRB_KNN_MAX] selected obstacle / neighbour rows
     size_t cap_obs, cap_nbr;
@@ -274,6 +277,7 @@ extern "C" int srb_ctx_create(const srb_params *p, int max_agents, int device, s
     c->qp_init = 1; c->polish_ms = 0.0f;
     c->polish = 1; c->polish_rho = SRB_POLISH_RHO; c->qp_warm_tol = SRB_QP_WARM_TOL; c->polish_waves = 0; c->polish_fused = 1; c->last_polish = 0; c->timing = 1; c->selection = 1;
     c->kkt32_mu = 0.0; c->kkt32_ref = 3;
+    c->nbr_plan = nullptr; c->cap_plan = 0; c->plan_selection = 0;
     c->grid_min_rows = SRB_GRID_MIN_ROWS; c->grid_min_rows_static = SRB_GRID_MIN_ROWS_STATIC;
     c->zstride = 2 * srb_r4(srb_slots(p->N, p->C, p->K_obs + p->K_nbr));
     const int N = p->N, C = p->C, nv = srb_nv(p);
@@ -292,6 +296,7 @@ extern "C" int srb_ctx_create(const srb_params *p, int max_agents, int device, s
     CREATE_CHK(hipMalloc(&c->iters, A * 2 * sizeof(int)));
     CREATE_CHK(hipMalloc(&c->abuf, A * 4 * sizeof(double)));
     CREATE_CHK(hipMalloc(&c->alpha, A * 20 * sizeof(double)));
+    CREATE_CHK(hipMalloc(&c->plan, A * 2 * N * sizeof(double)));
     CREATE_CHK(hipMalloc(&c->sel, A * 2 * SRB_KNN_MAX * sizeof(int)));
     CREATE_CHK(hipMalloc(&c->zpol, A * (size_t)c->zstride * sizeof(float)));
 #undef CREATE_CHK
@@ -306,7 +311,7 @@ extern "C" int srb_ctx_destroy(srb_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->order.wait_idle();                         // the last launch may be on another stream
     void *bufs[] = {c->x0, c->ref, c->foot, c->x_qp, c->x, c->obj, c->status, c->iters, c->obstacles, c->nbr,
-                    c->abuf, c->alpha, c->sel, c->zpol};
+                    c->abuf, c->alpha, c->sel, c->zpol, c->nbr_plan, c->plan};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (auto &g : c->grid)
@@ -325,9 +330,23 @@ extern "C" int srb_ctx_destroy(srb_ctx *c)
 // (stride 4); shared with the SRB-12 mode (srb12_capi.cpp), which hands over its CoM positions so.
 static int launch_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                          const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                         int obstacles_version, int *sel, hipStream_t s, int sel_stride = -1)
+                         int obstacles_version, int *sel, hipStream_t s, int sel_stride = -1,
+                         const double *nbr_plan = nullptr, int N = 0)
 {
     if (sel_stride < 0) sel_stride = K_obs + K_nbr;
+    // SRB_OPT_PLAN_SELECTION (the caller hands over nbr_plan only then): the neighbour columns by closest predicted
+    // approach (srb_knn_plan_kernel, brute force, no grid); the static columns from srb_knn_kernel as ever
+    if (nbr_plan && K_nbr > 0) {
+        if (K_obs > 0) {
+            int rc = launch_select(c, n_agents, x0, obstacles, n_obs, nullptr, 0, agent_offset, K_obs, 0, obstacles_version,
+                                   sel, s, sel_stride);
+            if (rc) return rc;
+        }
+        hipLaunchKernelGGL(srb_knn_plan_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents, x0, nbr_state, nbr_plan,
+                           n_all, N, agent_offset, K_nbr, sel + K_obs, sel_stride);
+        HIPCHK(hipGetLastError());
+        return SRB_OK;
+    }
     // long tables (a swarm sharded over GPUs: the whole neighbour snapshot, obstacles scaled
     // with the arena) get a uniform grid so each agent scans only the cells around it
     // (a versioned static obstacle table builds its grid once, so it pays off at fewer rows;
@@ -366,6 +385,26 @@ int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double
 
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s) { return c->order.mark_done(s); }
 
+// The argument errors of the plan members (srb_batch.nbr_plan / plan), before anything is launched.  select: the
+// call would run the neighbour selection (the horizon-aware one then needs the table).
+static int check_plans(srb_ctx *c, int n_agents, const srb_batch *d, bool select)
+{
+    const srb_params *p = &c->p;
+    if (d->nbr_plan && !d->nbr_state) return fail(SRB_ERR_ARG, "nbr_plan needs nbr_state (the selection's snapshot)");
+    if (d->nbr_plan && p->K_nbr > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
+        return fail(SRB_ERR_ARG, "nbr_plan: agent_offset + n_agents exceeds n_all (the plan table's rows)");
+    if (d->nbr_plan && d->plan) {
+        const char *t0 = (const char *)d->nbr_plan, *t1 = t0 + (size_t)std::max(d->n_all, 0) * 2 * p->N * sizeof(double);
+        const char *o0 = (const char *)d->plan, *o1 = o0 + (size_t)n_agents * 2 * p->N * sizeof(double);
+        if (o0 < t1 && t0 < o1)
+            return fail(SRB_ERR_ARG, "plan overlaps the nbr_plan table (workgroups read the table while others write their "
+                                     "plans: use two buffers)");
+    }
+    if (select && c->plan_selection && !d->nbr_plan && d->nbr_state && std::min(p->K_nbr, d->n_all - 1) > 0)
+        return fail(SRB_ERR_ARG, "SRB_OPT_PLAN_SELECTION = 1 needs nbr_plan (the horizon-aware selection reads the plan table)");
+    return SRB_OK;
+}
+
 static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, int use_nlp)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
@@ -380,6 +419,10 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         return fail(SRB_ERR_ARG, "obstacles missing");
     if (use_nlp && p->K_nbr > 0 && d->nbr_state && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
+    // (the QP-only solve ignores nbr_plan: it has no obstacle rows)
+    if (use_nlp)
+        if (int rc = check_plans(c, n_agents, d, c->selection != 0)) return rc;
+    const double *nbr_plan = (use_nlp && p->K_nbr > 0) ? d->nbr_plan : nullptr;
     SrbKParams k = make_kparams(p, use_nlp);
     k.qp_init = c->qp_init;
     k.polish_rho = c->polish_rho;
@@ -405,7 +448,7 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     // around a collective, bench.py's multi-GPU step)
     if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection) {
         int rc = launch_select(c, n_agents, d->x0, d->obstacles, n_obs, d->nbr_state, n_all, d->agent_offset, k.K_obs,
-                               k.K_nbr, d->obstacles_version, sel, s);
+                               k.K_nbr, d->obstacles_version, sel, s, -1, c->plan_selection ? nbr_plan : nullptr, k.N);
         if (rc) return rc;
     }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[2], s));
@@ -426,7 +469,7 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     hipLaunchKernelGGL(fn, dim3(n_agents), dim3(64 * in->nw), lds, s, k, n_agents, d->x0, d->ref, d->foot, d->obstacles,
                        n_obs, d->nbr_state, n_all, d->agent_offset, d->x_qp, d->x, d->obj, d->status, d->iters,
                        d->alpha ? d->alpha_buf : nullptr, d->alpha_buf ? d->alpha : nullptr, (const int *)sel,
-                       polish ? c->zpol : nullptr, c->zstride);
+                       polish ? c->zpol : nullptr, c->zstride, k.K_nbr > 0 ? nbr_plan : nullptr, d->plan);
     HIPCHK(hipGetLastError());
     if (c->timing) HIPCHK(hipEventRecord(c->ev[3], s));
     if (polish) {
@@ -441,7 +484,8 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         const size_t plds = (size_t)srb_lds_doubles(k, pin->nzl, pin->nw) * sizeof(double);
         hipLaunchKernelGGL(pin->polish, dim3(n_agents), dim3(64 * pin->nw), plds, s, k, n_agents, d->x0, d->ref, d->foot,
                            d->obstacles, d->nbr_state, d->x, d->obj, d->status, d->alpha ? d->alpha_buf : nullptr,
-                           d->alpha_buf ? d->alpha : nullptr, (const int *)sel, (const float *)c->zpol, c->zstride);
+                           d->alpha_buf ? d->alpha : nullptr, (const int *)sel, (const float *)c->zpol, c->zstride,
+                           k.K_nbr > 0 ? nbr_plan : nullptr, d->plan);
         HIPCHK(hipGetLastError());
     }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[1], s));
@@ -494,6 +538,9 @@ extern "C" int srb_ctx_set_option(srb_ctx *c, int opt, double v)
         c->kkt32_ref = (int)v; return SRB_OK;
     case SRB_OPT_LAST_KKT_FP32:
         return fail(SRB_ERR_ARG, "SRB_OPT_LAST_KKT_FP32 is read only");
+    case SRB_OPT_PLAN_SELECTION:
+        if (v != 0.0 && v != 1.0) return fail(SRB_ERR_ARG, "SRB_OPT_PLAN_SELECTION: 0 (snapshot) or 1 (closest predicted approach)");
+        c->plan_selection = (int)v; return SRB_OK;
     case SRB_OPT_GRID_MIN_ROWS:
     case SRB_OPT_GRID_MIN_ROWS_STATIC:
         if (!whole || v < 1.0 || v > 2147483647.0) return fail(SRB_ERR_ARG, "SRB_OPT_GRID_MIN_ROWS*: a row count >= 1");
@@ -521,6 +568,7 @@ extern "C" int srb_ctx_get_option(srb_ctx *c, int opt, double *v)
     case SRB_OPT_KKT_FP32_MU: *v = c->kkt32_mu; return SRB_OK;
     case SRB_OPT_KKT_FP32_REFINE: *v = c->kkt32_ref; return SRB_OK;
     case SRB_OPT_LAST_KKT_FP32: *v = c->last_f32; return SRB_OK;
+    case SRB_OPT_PLAN_SELECTION: *v = c->plan_selection; return SRB_OK;
     default: return fail(SRB_ERR_ARG, "unknown option");
     }
 }
@@ -568,13 +616,15 @@ extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, i
     if ((tables & 1) && Ko > 0 && !d->obstacles) return fail(SRB_ERR_ARG, "obstacles missing");
     if ((tables & 2) && Kn > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
+    if (int rc0 = check_plans(c, n_agents, d, (tables & 2) != 0)) return rc0;
+    const double *nbr_plan = (c->plan_selection && (tables & 2)) ? d->nbr_plan : nullptr;
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
     int rc = c->order.order_after_last(s);
     const int ko = (tables & 1) ? Ko : 0, kn = (tables & 2) ? Kn : 0;
     if (!rc && ko + kn > 0)
         rc = launch_select(c, n_agents, d->x0, d->obstacles, ko ? d->n_obs : 0, d->nbr_state, kn ? d->n_all : 0,
-                           d->agent_offset, ko, kn, d->obstacles_version, d->sel + (ko ? 0 : Ko), s, Ko + Kn);
+                           d->agent_offset, ko, kn, d->obstacles_version, d->sel + (ko ? 0 : Ko), s, Ko + Kn, nbr_plan, p->N);
     if (!rc) rc = c->order.mark_done(s);
     return rc;
 }
@@ -745,6 +795,22 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp)
         HIPCHK(hipMemcpyAsync(c->nbr, h->nbr_state, (size_t)h->n_all * 4 * sizeof(double), hipMemcpyHostToDevice, s));
         d.nbr_state = c->nbr;
     }
+    // the plan members: the table staged like nbr_state (NLP stage only), the plans like x
+    d.nbr_plan = nullptr;
+    if (use_nlp)                           // the overlap rule holds for the caller's own (host) buffers
+        if (int rc0 = check_plans(c, n_agents, h, false)) return rc0;
+    if (use_nlp && h->nbr_plan && d.nbr_state) {
+        const size_t rows = (size_t)h->n_all * 2 * N;
+        if ((size_t)h->n_all > c->cap_plan) {
+            if (c->nbr_plan) HIPCHK(hipFree(c->nbr_plan));
+            c->nbr_plan = nullptr; c->cap_plan = 0;
+            HIPCHK(hipMalloc(&c->nbr_plan, rows * sizeof(double)));
+            c->cap_plan = h->n_all;
+        }
+        HIPCHK(hipMemcpyAsync(c->nbr_plan, h->nbr_plan, rows * sizeof(double), hipMemcpyHostToDevice, s));
+        d.nbr_plan = c->nbr_plan;
+    }
+    d.plan = h->plan ? c->plan : nullptr;
     d.sel = nullptr;                       // the context's scratch; copied out below when asked for
     d.obstacles_version = 0;               // staged copy: rebuilt every call
     int rc = launch(c, n_agents, &d, s, use_nlp);
@@ -760,6 +826,7 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp)
     HIPCHK(hipMemcpyAsync(h->status, c->status, A * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h->iters, c->iters, A * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     if (d.alpha) HIPCHK(hipMemcpyAsync(h->alpha, c->alpha, A * 20 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (d.plan) HIPCHK(hipMemcpyAsync(h->plan, c->plan, A * 2 * N * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return SRB_OK;
 }

@@ -31,12 +31,14 @@ struct SrbGrid {
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
         const double *obstacles, int n_obs, const double *nbr_state, int n_all, int agent_offset,              \
         double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
-        const double *alpha_buf, double *alpha_out, const int *sel_g, float *zpol_g, int zstride);
+        const double *alpha_buf, double *alpha_out, const int *sel_g, float *zpol_g, int zstride,             \
+        const double *nbr_plan, double *plan_out);
 #define SRB_DECL_POLISH(NZL, TS, NW, NC, CC, KC)                                                              \
     extern "C" __global__ void srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                   \
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
         const double *obstacles, const double *nbr_state, double *x_out, double *obj_out, int *status_out,     \
-        const double *alpha_buf, double *alpha_out, const int *sel_g, const float *zpol_g, int zstride);
+        const double *alpha_buf, double *alpha_out, const int *sel_g, const float *zpol_g, int zstride,       \
+        const double *nbr_plan, double *plan_out);
 #define SRB_DECL_NMPC(...) SRB_DECL_NMPC_(, __VA_ARGS__) SRB_DECL_POLISH(__VA_ARGS__)
 #define SRB_DECL_NMPC_F32(...) SRB_DECL_NMPC_(f32_, __VA_ARGS__)
 SRB_KERNEL_INSTANCES(SRB_DECL_NMPC)
@@ -54,6 +56,9 @@ extern "C" __global__ void srb_knn_kernel(int n_agents, const double *x0g, const
                                           int *sel_out, int sel_stride, const SrbGrid *gob, const int *oob, const double2 *pob,
                                           const int *iob, const SrbGrid *gnb, const int *onb, const double2 *pnb,
                                           const int *inb);
+extern "C" __global__ void srb_knn_plan_kernel(int n_agents, const double *x0g, const double *nbr_state,
+                                               const double *nbr_plan, int n_all, int N, int agent_offset, int K_nbr,
+                                               int *sel_out, int sel_stride);
 extern "C" __global__ void srb_grid_build_kernel(const double *tab0, int stride0, int n0, SrbGrid *g0, int *off0,
                                                  double2 *spos0, int *sidx0, const double *tab1, int stride1, int n1,
                                                  SrbGrid *g1, int *off1, double2 *spos1, int *sidx1);

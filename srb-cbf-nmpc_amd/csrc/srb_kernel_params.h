@@ -7,7 +7,8 @@
 #ifndef SRB_KNN_WAVES
 #define SRB_KNN_WAVES 2   // waves per agent in the selection kernel (srb_knn_kernel; 2: 1 % faster configs[2] step than 4, round 4)
 #endif
-#define SRB_GRID_CELLS 16384      // cells of the selection grid (LDS counters of srb_grid_build_kernel)
+#define SRB_KNN_PLAN_WAVES 4   // waves per agent in the horizon-aware selection kernel (srb_knn_plan_kernel)
+#define SRB_GRID_CELLS 16384     // cells of the selection grid (LDS counters of srb_grid_build_kernel)
 #define SRB_GRID_MIN_ROWS 8192    // tables this long get a grid (shorter: brute-force scan)
 #define SRB_GRID_MIN_ROWS_STATIC 4096   // versioned static obstacle tables (grid built once, reused):
                                          // configs[2]'s 5120 rows: selection 37.8 -> 31.3 us (profiles/r02_grid_threshold.txt)

@@ -1052,8 +1052,9 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
 //   SRB_AGENT_LAYOUT     sizes, term-row layout, slot ranges, the LDS carve (srb_lds_doubles)
 //   SRB_AGENT_SETUP      inputs (a1/a2/a3: x0, reference window, footholds), Z, xbar, CoM-CoP rows
 //   SRB_AGENT_OBSTACLES  the K selected rows per grid (srb_knn_kernel's sel; MPC_dist.cpp:371-396
-//                        generalised, neighbours predicted at constant velocity o_k = p + v Ts (k+1))
-//   SRB_AGENT_OUTPUTS    x, objective, alpha_COM
+//                        generalised; neighbours at their planned positions nbr_plan[sel][k], or without a plan
+//                        table predicted at constant velocity o_k = p + v Ts (k+1))
+//   SRB_AGENT_OUTPUTS    x, the agent's plan (the CoM positions of x), objective, alpha_COM
 #define SRB_AGENT_LAYOUT \
     constexpr int NZM = ((NZL + 15) / 16) * 16; \
     constexpr int LDR = NZL + 1, LDH = NZL + 1; \
@@ -1178,10 +1179,17 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
                 const int bi = sel[j]; \
                 const double tt = st ? 0.0 : prm.Ts * (k + 1); \
                 const size_t bj = (bi >= 0) ? bi : 0; \
-                const double *srcp = st ? obstacles + 2 * bj : nbr_state + 4 * bj; \
-                /* no selection (-1): a row 1000 m along +x, as the oracle */ \
-                ox_[t] = (bi >= 0) ? srcp[0] + (st ? 0.0 : srcp[2] * tt) : x0[0] + 1000.0; \
-                oy_[t] = (bi >= 0) ? srcp[1] + (st ? 0.0 : srcp[3] * tt) : x0[2]; \
+                if (nbr_plan) {   /* a kernel argument: the branch is wave-uniform */ \
+                    /* neighbour rows from the plan table: row sel[j], grid k is that agent's (x, y) at Ts (k + 1) */ \
+                    const double *srcp = st ? obstacles + 2 * bj : nbr_plan + 2 * (bj * (size_t)N + k); \
+                    ox_[t] = (bi >= 0) ? srcp[0] : x0[0] + 1000.0; \
+                    oy_[t] = (bi >= 0) ? srcp[1] : x0[2]; \
+                } else { \
+                    const double *srcp = st ? obstacles + 2 * bj : nbr_state + 4 * bj; \
+                    /* no selection (-1): a row 1000 m along +x, as the oracle */ \
+                    ox_[t] = (bi >= 0) ? srcp[0] + (st ? 0.0 : srcp[2] * tt) : x0[0] + 1000.0; \
+                    oy_[t] = (bi >= 0) ? srcp[1] + (st ? 0.0 : srcp[3] * tt) : x0[2]; \
+                } \
             } \
         } \
         _Pragma("unroll") for (int t = 0; t < TS; t++) { \
@@ -1198,6 +1206,8 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
     for (int v = tid; v < n; v += NTH) { \
         const double xv = xs[v]; \
         x_out[(size_t)agent * n + v] = xv; \
+        /* the plan: (x, y) of grid k = x[4k], x[4k + 2], the even entries of X */ \
+        if (plan_out && v < 4 * N && !(v & 1)) plan_out[(size_t)agent * 2 * N + (v >> 1)] = xv; \
         const double a0 = var_weight(prm, v), a1 = (v < 4 * N) ? -a0 * ref[v] : 0.0; \
         f += fma(0.5 * a0 * xv, xv, a1 * xv); \
     } \
@@ -1393,7 +1403,8 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 double *__restrict__ x_qp_out, double *__restrict__ x_out,
                 double *__restrict__ obj_out, int *__restrict__ status_out, int *__restrict__ iters_out,
                 const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,
-                const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride, double *lds)
+                const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride,
+                const double *__restrict__ nbr_plan, double *__restrict__ plan_out, double *lds)
 {
     SRB_AGENT_LAYOUT;
 #ifdef SRB_STAMPS
@@ -2051,7 +2062,8 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
                 const double *__restrict__ obstacles, const double *__restrict__ nbr_state,
                 double *__restrict__ x_out, double *__restrict__ obj_out, int *__restrict__ status_out,
                 const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,
-                const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride, double *lds)
+                const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride,
+                const double *__restrict__ nbr_plan, double *__restrict__ plan_out, double *lds)
 {
     SRB_AGENT_LAYOUT;
 #ifdef SRB_STAMPS
@@ -2142,14 +2154,15 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         const double *__restrict__ nbr_state, int n_all, int agent_offset, double *__restrict__ x_qp_out,        \
         double *__restrict__ x_out, double *__restrict__ obj_out, int *__restrict__ status_out,                 \
         int *__restrict__ iters_out, const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,       \
-        const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride)                               \
+        const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride,                               \
+        const double *__restrict__ nbr_plan, double *__restrict__ plan_out)                                    \
     {                                                                                                          \
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         nmpc_agent<NZL, TS, NW, NC, CC, KC, KF>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
                                 x_qp_out, x_out, obj_out, status_out, iters_out, alpha_buf, alpha_out, sel_g, \
-                                zpol_g, zstride, lds);                                                         \
+                                zpol_g, zstride, nbr_plan, plan_out, lds);                                     \
     }
 #define SRB_POLISH_ENTRY(NZL, TS, NW, NC, CC, KC)                                                              \
     extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
@@ -2158,13 +2171,14 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         const double *__restrict__ footg, const double *__restrict__ obstacles,                                 \
         const double *__restrict__ nbr_state, double *__restrict__ x_out, double *__restrict__ obj_out,          \
         int *__restrict__ status_out, const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,     \
-        const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride)                         \
+        const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride,                         \
+        const double *__restrict__ nbr_plan, double *__restrict__ plan_out)                                    \
     {                                                                                                          \
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         polish_agent<NZL, TS, NW, NC, CC, KC>(prm, agent, x0g, refg, footg, obstacles, nbr_state, x_out, obj_out,          \
-                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, lds);             \
+                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, lds); \
     }
 #define SRB_NMPC_KERNEL(...) SRB_NMPC_ENTRY(, 0, __VA_ARGS__) SRB_POLISH_ENTRY(__VA_ARGS__)
 #define SRB_NMPC_KERNEL_F32(...) SRB_NMPC_ENTRY(f32_, 1, __VA_ARGS__)

@@ -24,6 +24,10 @@ __device__ __forceinline__ void knn_insert(double (&bd)[KM], int (&bi)[KM], doub
     }
 }
 
+template <int KW, int KM>
+__device__ __forceinline__ void knn_pop(int tid, double (&bd)[KM], int (&bi)[KM], int K, int cap, int *sel,
+                                        double *wd_lds, int *wi_lds);
+
 // The thresholded brute-force pass of knn_select_k (round 6) over a table of at most RB rows a lane: every
 // row's d^2 kept in registers (row tid + r STEP in slot r; NaN for the agent itself, rows past the table and
 // rows with NaN coordinates, which are never selected), then a bound T on the K-th smallest d^2 from the lanes'
@@ -205,6 +209,16 @@ __device__ __forceinline__ void knn_select_k(int tid, double px, double py, cons
                 if (i0 + u * STEP < n_rows) offer(tx[u], ty[u], i0 + u * STEP);
         }
     }
+    knn_pop<KW, KM>(tid, bd, bi, K, cap, sel, wd_lds, wi_lds);
+}
+
+// The K pop rounds over the lanes' sorted lists (knn_select_k, and srb_knn_plan_kernel's lists keyed by closest
+// predicted approach): the global (distance, index) order into sel[0..K).
+template <int KW, int KM>
+__device__ __forceinline__ void knn_pop(int tid, double (&bd)[KM], int (&bi)[KM], int K, int cap, int *sel,
+                                        double *wd_lds, int *wi_lds)
+{
+    const int lane = tid & 63, wv = tid >> 6;
     // round j's winner is kept by lane j and stored after the last round: a store inside the
     // loop would make every barrier wait for it (s_waitcnt vmcnt(0) before s_barrier)
     int mine = -1;

@@ -64,6 +64,62 @@ extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_WAVES) srb_knn_kernel(
                                   wi_lds, gnb, onb, pnb, inb);
 }
 
+// Horizon-aware neighbour selection (SRB_OPT_PLAN_SELECTION = 1): the K_nbr table rows of closest predicted
+// approach to global agent g = agent_offset + agent.  The key of row i is sqrt(min_k d_k^2) over the N + 1 pairs
+// k = 0 the snapshot (x0 against nbr_state[i].xy) and k >= 1 the plans nbr_plan[g][k-1] against nbr_plan[i][k-1];
+// order, ties, the excluded row g, NaN rows and the -1 fill are knn_select_k's (no 1000 m cap: that rule is the
+// static table's).  Brute force, one workgroup per agent: the agent's own N + 1 points in LDS, every thread scans
+// rows tid, tid + 64 KW, .. and keeps a sorted list (knn_insert); knn_pop merges them.  Only the neighbour
+// columns are written (sel_out points at them; rows of stride sel_stride).
+template <int KM>
+__device__ __forceinline__ void knn_plan_select(int tid, const double *own, const double *__restrict__ nbr_state,
+                                                const double *__restrict__ nbr_plan, int n_all, int N, int self, int K,
+                                                int *sel, double *wd_lds, int *wi_lds)
+{
+#pragma clang fp contract(off)
+    double bd[KM]; int bi[KM];
+#pragma unroll
+    for (int j = 0; j < KM; j++) { bd[j] = __builtin_inf(); bi[j] = 0x7fffffff; }
+    double wq = __builtin_inf();                   // filter bound on the squared key (knn_select_k's)
+    for (int i = tid; i < n_all; i += 64 * SRB_KNN_PLAN_WAVES) {
+        if (i == self) continue;
+        const double *row = nbr_plan + 2 * (size_t)i * N;
+        const double dx0 = own[0] - nbr_state[4 * (size_t)i], dy0 = own[1] - nbr_state[4 * (size_t)i + 1];
+        double m = dx0 * dx0 + dy0 * dy0;
+        for (int k = 0; k < N; k++) {
+            const double dx = own[2 * k + 2] - row[2 * k], dy = own[2 * k + 3] - row[2 * k + 1];
+            const double d2 = dx * dx + dy * dy;
+            m = (d2 < m || d2 != d2) ? d2 : m;       // the minimum; a NaN pair makes the key NaN for good
+        }
+        if (!(m <= wq)) continue;                  // NaN keys fail: such rows are never selected
+        knn_insert<KM>(bd, bi, sqrt(m), i, K);
+#pragma unroll
+        for (int j = 0; j < KM; j++)
+            if (j == K - 1) wq = bd[j] * bd[j] * (1.0 + 1e-14);
+    }
+    knn_pop<SRB_KNN_PLAN_WAVES, KM>(tid, bd, bi, K, 0, sel, wd_lds, wi_lds);
+}
+
+extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_PLAN_WAVES) srb_knn_plan_kernel(int n_agents,
+                const double *__restrict__ x0g, const double *__restrict__ nbr_state,
+                const double *__restrict__ nbr_plan, int n_all, int N, int agent_offset, int K_nbr,
+                int *__restrict__ sel_out, int sel_stride)
+{
+    __shared__ double wd_lds[SRB_KNN_PLAN_WAVES];
+    __shared__ int wi_lds[SRB_KNN_PLAN_WAVES];
+    __shared__ double own[2 * (SRB_MAX_N + 1)];
+    const int agent = xcd_agent(blockIdx.x, gridDim.x), tid = threadIdx.x;
+    if (agent >= n_agents) return;                 // whole workgroup: the barriers stay uniform
+    const int g = agent_offset + agent;
+    if (tid < 2) own[tid] = x0g[4 * (size_t)agent + 2 * tid];
+    else if (tid < 2 * N + 2) own[tid] = nbr_plan[2 * (size_t)g * N + tid - 2];
+    __syncthreads();
+    int *sel = sel_out + (size_t)agent * sel_stride;
+    if (K_nbr <= 4) knn_plan_select<4>(tid, own, nbr_state, nbr_plan, n_all, N, g, K_nbr, sel, wd_lds, wi_lds);
+    else if (K_nbr <= 8) knn_plan_select<8>(tid, own, nbr_state, nbr_plan, n_all, N, g, K_nbr, sel, wd_lds, wi_lds);
+    else knn_plan_select<SRB_KNN_MAX>(tid, own, nbr_state, nbr_plan, n_all, N, g, K_nbr, sel, wd_lds, wi_lds);
+}
+
 // Uniform grid over one table per workgroup (block 0: table 0, block 1: table 1), rebuilt every
 // launch (the neighbour snapshot moves every cycle): bounds of the finite rows, about two rows
 // per cell (at most SRB_GRID_CELLS cells), counts by LDS atomics, one exclusive scan, scatter of

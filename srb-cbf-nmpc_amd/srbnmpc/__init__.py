@@ -13,6 +13,7 @@ constructing a solver raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -34,8 +35,8 @@ QP_WARM = 4
 # srb_ctx_set_option codes (SRB_OPT_* of include/srbnmpc.h)
 OPTIONS = {"polish": 1, "polish_rho": 2, "polish_waves": 3, "grid_min_rows": 4, "grid_min_rows_static": 5,
            "polish_fused": 6, "last_polish": 7, "timing": 8, "qp_warm_tol": 9, "selection": 10,
-           "kkt_fp32_mu": 11, "kkt_fp32_refine": 12, "last_kkt_fp32": 13}
-ABI_VERSION = 5                                               # SRB_ABI_VERSION of include/srbnmpc.h
+           "kkt_fp32_mu": 11, "kkt_fp32_refine": 12, "last_kkt_fp32": 13, "plan_selection": 14}
+ABI_VERSION = 6                                               # SRB_ABI_VERSION of include/srbnmpc.h
 
 
 class Params(ctypes.Structure):
@@ -60,7 +61,8 @@ class Batch(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int), ("x0", _dp), ("ref", _dp), ("foot", _dp), ("obstacles", _dp), ("nbr_state", _dp),
                 ("n_obs", ctypes.c_int), ("n_all", ctypes.c_int), ("agent_offset", ctypes.c_int),
                 ("x_qp", _dp), ("x", _dp), ("obj", _dp), ("status", _ip), ("iters", _ip),
-                ("alpha_buf", _dp), ("alpha", _dp), ("sel", _ip), ("obstacles_version", ctypes.c_int)]
+                ("alpha_buf", _dp), ("alpha", _dp), ("sel", _ip), ("obstacles_version", ctypes.c_int),
+                ("nbr_plan", _dp), ("plan", _dp)]
 
     def __init__(self, *args, **kw):
         super().__init__(ctypes.sizeof(Batch), *args, **kw)
@@ -190,10 +192,13 @@ class BatchSolver:
         return min(p.K_obs, max(n_obs, 0)), (min(p.K_nbr, max(n_all - 1, 0)) if n_all > 0 else 0)
 
     def solve(self, x0, ref, foot, obstacles=None, nbr_state=None, agent_offset: int = 0, qp_only: bool = False,
-              alpha_buf=None):
+              alpha_buf=None, nbr_plan=None, plan=None):
         """Host arrays in, dict of outputs back.  alpha_buf ([A][4], the Bezier buffer state)
         additionally returns alpha ([A][4][5], get_alphaCOM) from the fused fit.  With the NLP
-        stage, sel ([A][Ko + Kn]) holds the selected obstacle / neighbour rows."""
+        stage, sel ([A][Ko + Kn]) holds the selected obstacle / neighbour rows.  nbr_plan
+        ([n_all][N][2], float64, C-contiguous) makes the neighbour rows follow the neighbours' plans
+        instead of the constant-velocity guess; plan ([A][N][2], the same) receives this batch's plans
+        (out["plan"]; allocated here when None)."""
         p = self.params
         x0 = _f64(x0).reshape(-1, 4)
         A = x0.shape[0]
@@ -209,24 +214,34 @@ class BatchSolver:
             out["alpha"] = np.zeros((A, 4, 5))
         Ko, Kn = self.n_selected(ob.shape[0], nb.shape[0] if nb is not None else 0)
         out["sel"] = np.full((A, Ko + Kn), -2, np.int32)
+        if nbr_plan is not None:
+            # (without nbr_state the row count is the table's own: the library refuses that call by name)
+            _check_plan_array(nbr_plan, (nb.shape[0] if nb is not None else len(nbr_plan), p.N, 2), "nbr_plan", np.float64)
+        if plan is None:
+            plan = np.zeros((A, p.N, 2))
+        _check_plan_array(plan, (A, p.N, 2), "plan", np.float64)
+        out["plan"] = plan
         b = Batch(_p(x0), _p(ref), _p(foot), _p(ob) if ob.size else None, _p(nb) if nb is not None else None,
                   ob.shape[0], nb.shape[0] if nb is not None else 0, int(agent_offset),
                   _p(out["x_qp"]), _p(out["x"]), _p(out["obj"]), _p(out["status"]), _p(out["iters"]),
                   _p(ab) if ab is not None else None, _p(out["alpha"]) if ab is not None else None,
-                  _p(out["sel"]) if out["sel"].size and not qp_only else None)
+                  _p(out["sel"]) if out["sel"].size and not qp_only else None, 0, _p(nbr_plan), _p(plan))
         fn = lib().srb_solve_qp if qp_only else lib().srb_solve_batch
         _check(fn(self._h, A, ctypes.byref(b)))
         return out
 
     # --------------------------------------------------------------- device path
     def solve_device(self, x0, ref, foot, obstacles, nbr_state, out, agent_offset: int = 0, stream=None,
-                     alpha_buf=None, obstacles_version: int = 0):
+                     alpha_buf=None, obstacles_version: int = 0, nbr_plan=None, plan=None):
         """All arguments torch tensors on this solver's device (float64 / int32), contiguous.
         `out` is a dict with x_qp (or None), x, obj, status, iters and, with alpha_buf [A][4],
         alpha [A][20]; an optional int32 out["sel"] [A][Ko + Kn] receives the selected rows
         (otherwise the context's scratch is used: one stream per context at a time).
         obstacles_version != 0 marks the obstacle tensor as unchanged since the last call with
         that version (its selection grid is reused; the reference's obstacles are static).
+        nbr_plan ([n_all][N][2] float64, contiguous): the neighbours' plans for the inter-agent rows
+        (None: constant velocity); plan (or out["plan"], [A][N][2] float64): receives this batch's plans,
+        and must not overlap nbr_plan.
         Asynchronous on `stream` (a hipStream_t handle), by default torch's current stream on
         this device, so the launch is ordered after the torch work that filled the inputs."""
         def dptr(t):
@@ -244,33 +259,89 @@ class BatchSolver:
             raise ValueError(f"out['sel'] must be a contiguous int32 tensor of shape ({A}, {Ko + Kn}) "
                              f"(K_obs, K_nbr clamped to the table sizes: BatchSolver.n_selected), got "
                              f"{tuple(sel.shape)} {sel.dtype}")
+        if plan is None:
+            plan = out.get("plan")
+        N = self.params.N
+        if nbr_plan is not None:
+            _check_plan_array(nbr_plan, (nbr_plan.shape[0] if nbr_state is None else nbr_state.shape[0], N, 2), "nbr_plan",
+                              torch_float64())
+        if plan is not None:
+            _check_plan_array(plan, (A, N, 2), "plan", torch_float64())
         b = Batch(dptr(x0), dptr(ref), dptr(foot), dptr(obstacles), dptr(nbr_state),
                   0 if obstacles is None else obstacles.shape[0], 0 if nbr_state is None else nbr_state.shape[0],
                   int(agent_offset), dptr(out.get("x_qp")), dptr(out["x"]), dptr(out["obj"]),
                   iptr(out["status"]), iptr(out["iters"]), dptr(alpha_buf),
                   dptr(out.get("alpha") if alpha_buf is not None else None),
-                  iptr(out["sel"]) if out.get("sel") is not None else None, int(obstacles_version))
+                  iptr(out["sel"]) if out.get("sel") is not None else None, int(obstacles_version),
+                  dptr(nbr_plan), dptr(plan))
         _check(lib().srb_solve_batch_device(self._h, A, ctypes.byref(b), self._stream(stream)))
 
     def select_device(self, x0, obstacles, nbr_state, sel, tables: int = 3, agent_offset: int = 0, stream=None,
-                      obstacles_version: int = 0):
+                      obstacles_version: int = 0, nbr_plan=None):
         """The obstacle / neighbour selection alone (srb_select_device) into the int32 tensor sel [A][Ko + Kn]:
         tables 1 the static obstacles, 2 the neighbour snapshot, 3 both.  With the option "selection" set
         to 0, solve_device then uses out["sel"] as filled here (bench.py selects the static obstacles while
-        the neighbour all-gather is in flight).  Asynchronous on `stream` like solve_device."""
+        the neighbour all-gather is in flight).  With the option "plan_selection" set to 1, tables & 2 is the
+        horizon-aware selection (closest predicted approach) and needs nbr_plan [n_all][N][2].
+        Asynchronous on `stream` like solve_device."""
         A = x0.shape[0]
         Ko, Kn = self.n_selected(0 if obstacles is None else obstacles.shape[0],
                                  0 if nbr_state is None else nbr_state.shape[0])
         if sel.dtype != torch_int32() or tuple(sel.shape) != (A, Ko + Kn) or not sel.is_contiguous():
             raise ValueError(f"sel must be a contiguous int32 tensor of shape ({A}, {Ko + Kn}), got {tuple(sel.shape)} {sel.dtype}")
+        if nbr_plan is not None:
+            _check_plan_array(nbr_plan, (nbr_plan.shape[0] if nbr_state is None else nbr_state.shape[0], self.params.N, 2), "nbr_plan",
+                              torch_float64())
 
         def dptr(t):
             return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
         b = Batch(dptr(x0), None, None, dptr(obstacles), dptr(nbr_state),
                   0 if obstacles is None else obstacles.shape[0], 0 if nbr_state is None else nbr_state.shape[0],
                   int(agent_offset), None, None, None, None, None, None, None,
-                  ctypes.cast(ctypes.c_void_p(sel.data_ptr()), _ip), int(obstacles_version))
+                  ctypes.cast(ctypes.c_void_p(sel.data_ptr()), _ip), int(obstacles_version), dptr(nbr_plan), None)
         _check(lib().srb_select_device(self._h, A, ctypes.byref(b), int(tables), self._stream(stream)))
+
+    def solve_coupled_device(self, x0, ref, foot, obstacles, nbr_state, out, outer: int = 2, exchange=None,
+                             nbr_plan=None, agent_offset: int = 0, stream=None, alpha_buf=None,
+                             obstacles_version: int = 0):
+        """Jacobi iteration over the agents' plans: `outer` solves of the same cycle, each against the plans
+        the agents wrote in the round before.  Round 0 solves against nbr_plan (None: the constant-velocity
+        rows); every later round r exchanges the plans of round r - 1 -- table = exchange(plan), a
+        dist.PlanExchange, or on one GPU (exchange None: the batch is the whole team, agent_offset 0) the plan
+        tensor itself -- and solves again.  The plans ping-pong between out["plan"] ([A][N][2], required) and
+        a second buffer of this solver, so the table a round reads is never the buffer it writes; the last
+        round's results, its plans included, are in `out`.  Returns plan_change, a device tensor [outer - 1]:
+        max |plan_r - plan_{r-1}| per round (torch reductions; nothing synchronises with the host inside the
+        loop).  No damping and no convergence test: the plain Jacobi round.  Other arguments as solve_device."""
+        import torch
+        outer = int(outer)
+        if outer < 1:
+            raise ValueError("outer must be >= 1")
+        plan = out.get("plan")
+        if plan is None:
+            raise ValueError("solve_coupled_device needs out['plan'] ([A][N][2] float64)")
+        A, N = x0.shape[0], self.params.N
+        _check_plan_array(plan, (A, N, 2), "out['plan']", torch.float64)
+        if exchange is None and outer > 1 and (nbr_state is None or nbr_state.shape[0] != A or agent_offset != 0):
+            raise ValueError("solve_coupled_device without an exchange iterates over this batch's own plans: "
+                             "nbr_state must hold exactly the batch's agents (agent_offset 0)")
+        other = getattr(self, "_plan_pong", None)
+        if outer > 1 and (other is None or other.shape != plan.shape or other.device != plan.device):
+            other = self._plan_pong = torch.empty_like(plan)
+        ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream)) if stream is not None else contextlib.nullcontext()
+        change = torch.zeros(max(outer - 1, 0), dtype=torch.float64, device=plan.device)
+        with ctx:
+            table, prev = nbr_plan, None
+            for r in range(outer):
+                cur = plan if (outer - 1 - r) % 2 == 0 else other      # the last round writes out["plan"]
+                if r > 0:
+                    table = exchange(prev) if exchange is not None else prev
+                self.solve_device(x0, ref, foot, obstacles, nbr_state, out, agent_offset=agent_offset, stream=stream,
+                                  alpha_buf=alpha_buf, obstacles_version=obstacles_version, nbr_plan=table, plan=cur)
+                if r > 0:
+                    change[r - 1] = (cur - prev).abs().max()
+                prev = cur
+        return change
 
     def _stream(self, stream):
         """hipStream_t for a launch: the caller's, else torch's current stream on this device
@@ -306,7 +377,8 @@ class BatchSolver:
 
     def set_option(self, name: str, value: float):
         """Context option (srb_ctx_set_option): name one of OPTIONS ("polish", "polish_rho",
-        "polish_waves", "grid_min_rows", "grid_min_rows_static", "polish_fused"; "last_polish" is read only)."""
+        "polish_waves", "grid_min_rows", "grid_min_rows_static", "polish_fused", "plan_selection", ..;
+        "last_polish" is read only)."""
         _check(lib().srb_ctx_set_option(self._h, OPTIONS[name], float(value)))
 
     def get_option(self, name: str) -> float:
@@ -341,6 +413,20 @@ class BatchSolver:
 def torch_int32():
     import torch
     return torch.int32
+
+
+def torch_float64():
+    import torch
+    return torch.float64
+
+
+def _check_plan_array(a, shape, name, dtype):
+    """Shape, dtype and contiguity of a plan array (numpy on the host path, torch on the device path), as
+    out['sel'] is checked: the library reads rows of exactly this layout."""
+    contiguous = a.is_contiguous() if hasattr(a, "is_contiguous") else a.flags["C_CONTIGUOUS"]
+    if a.dtype != dtype or tuple(a.shape) != tuple(shape) or not contiguous:
+        raise ValueError(f"{name} must be a contiguous float64 array of shape {tuple(shape)}, got "
+                         f"{tuple(a.shape)} {a.dtype}")
 
 
 def hl_plan(Pstart, Pobs, loop: int = 100000, device: int = 0):
