@@ -34,7 +34,7 @@ extern "C" {
 #define SRB_ERR_SIZE (-3)
 
 /*
- * ABI versioning.  Every I/O struct (srb_batch, srb_prep, srb_ll_io) starts with
+ * ABI versioning.  Every I/O struct (srb_batch, srb_prep, srb_sim, srb_ll_io) starts with
  * `int struct_size`, which the caller sets to sizeof(struct) of the header it was compiled
  * against; the library rejects any other value with SRB_ERR_ARG (srb_last_error() names
  * the struct), so a caller built against an older or newer layout fails loudly instead of
@@ -275,6 +275,82 @@ typedef struct srb_prep {
     int *status;
 } srb_prep;
 int srb_prepare_batch_device(srb_ctx *ctx, int n_agents, const srb_prep *dev_io, void *stream);
+
+/*
+ * Closed-loop team rollout on the device: the step from one cycle's solution to the next cycle's inputs, and the
+ * team's safety log, so that T control cycles run without a host round trip.  One cycle is
+ * one gait domain of NDOMAIN = 4 grids (global_loco_opts.h:9), so N >= 4.  The plant is nominal: the state that
+ * starts cycle c + 1 is the X the solve of cycle c predicted at grid index 3, the domain's end -- what the
+ * reference buffers (MPC_dist.cpp:798) -- whatever that solve's status.  All pointers are device pointers, fp64
+ * unless noted; cycles count from c_first, and log rows are indexed by c - c_first.
+ *
+ * srb_sim_advance_device(ctx, A, sim, c, stream), cycle c >= c_first:
+ *   state       [A][4]       x, xdot, y, ydot.  c == c_first: read (the caller's start state); later cycles:
+ *                            written from x[a][12..15]
+ *   goal        [A][2]       in: each agent's goal
+ *   phase       [A] int      in, optional: added to c for the trot parity
+ *   vref                     reference speed (the synthetic workload's: 0.27)
+ *   x, status, iters         in: the previous solve's outputs (srb_batch layout); x is required when c != c_first
+ *   x0 [A][4], ref [A][4N], foot [A][N][2][C]  out: the srb_batch inputs of cycle c.  ref is the straight line
+ *                            from the current position to the goal at v = min(vref, dist / (Ts N)), so it never
+ *                            overshoots and an agent at its goal gets a standing reference; foot is the default
+ *                            stance (MPC_dist.cpp:1206-1209) around the reference position at each domain's
+ *                            start, legs {FR,RL} when c + phase + k / 4 is even, {FL,RR} when odd (C = 2), all
+ *                            four for C = 4
+ *   last_state  [A][4]       out: x, y, xdot, ydot -- the neighbour-snapshot row (get_lastState)
+ *   alpha_buf   [A][4]       out, optional: the state, as the Bezier buffer of the solve
+ *   plan_table  [A][N][2]    out, optional, c != c_first only: the previous solve's plans (x[4k], x[4k+2]) shifted
+ *                            by 4 grids; past the horizon the last finite difference continues,
+ *                            last + m (last - previous).  At c_first the caller's content stands
+ *   traj        [T+1][A][4]  out, optional: row c - c_first gets the state
+ *   status_log, iters_log [T][A][2] int, x_log [T][A][nv]  out, optional, c != c_first only: row c - c_first - 1
+ *                            gets the previous solve's status, iters, x
+ * srb_sim_metrics_device(ctx, A, sim, c, stream): the safety metrics of `state` at the start of cycle c, brute
+ * force and independent of the solver's own selection:
+ *   obstacles [n_obs][2], nbr_state [n_all][4], agent_offset   in: as in srb_batch (row agent_offset + a is the
+ *                            agent itself and is left out); either table may be empty
+ *   d_obs, d_agent [A]       out, optional: distance to the nearest obstacle / other agent at this cycle; a table
+ *                            row holding a NaN never wins, an empty table gives +inf
+ *   min_d_obs, min_d_agent [A]  out, optional: their minima over the cycles c_first .. c
+ *   fail_cycle [A] int, distance_to_fail [A]  out, optional: the first cycle with d_obs < 0.5 (else -1) and
+ *                            sqrt(x^2 + y^2) at that cycle (else 0): updateDistance_to_fail, MPC_dist.cpp:21-40;
+ *                            once set they are never overwritten.  The running results are initialised by the
+ *                            call with c == c_first
+ * Both are asynchronous on `stream` and ordered by the context like srb_solve_batch_device.
+ *
+ * srb_rollout_device(ctx, A, batch, sim, cycles, stream): `cycles` whole cycles of one team on one GPU.  For
+ * c = c_first .. c_first + cycles - 1 it enqueues advance, metrics and solve, then one final advance that
+ * flushes the last logs and the end state -- plain launches, no graph capture, no host synchronisation.  The two
+ * structs are wired together here: the solve reads sim's x0, ref, foot, alpha_buf (when batch.alpha is set) and
+ * sim.last_state as its nbr_state with n_all = A, agent_offset = 0; the advance reads batch's x, status, iters;
+ * the metrics read batch's obstacles / n_obs and sim.last_state.  The members of either struct that this
+ * replaces are ignored; batch.n_all / agent_offset must be A / 0 or both 0 (a shard cannot roll out alone: its
+ * neighbours move too).  The first solve reads batch.nbr_plan (or none); with sim.plan_table set every later
+ * solve reads that table as nbr_plan, so it must not overlap batch.plan.
+ */
+typedef struct srb_sim {
+    int struct_size;         /* sizeof(srb_sim) (ABI check) */
+    double *state;
+    const double *goal;
+    const int *phase;
+    double vref;
+    int c_first;
+    const double *x;
+    const int *status, *iters;
+    double *x0, *ref, *foot, *last_state, *alpha_buf, *plan_table;
+    double *traj;
+    int *status_log, *iters_log;
+    double *x_log;
+    const double *obstacles, *nbr_state;
+    int n_obs, n_all, agent_offset;
+    double *d_obs, *d_agent, *min_d_obs, *min_d_agent;
+    int *fail_cycle;
+    double *distance_to_fail;
+} srb_sim;
+int srb_sim_advance_device(srb_ctx *ctx, int n_agents, const srb_sim *dev_io, int cycle, void *stream);
+int srb_sim_metrics_device(srb_ctx *ctx, int n_agents, const srb_sim *dev_io, int cycle, void *stream);
+int srb_rollout_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_sim *sim, int cycles,
+                       void *stream);
 
 /*
  * HL reference planner (generateReferenceTrajectory, MPC_dist.cpp:930-1104; SURVEY.md 8(f)

@@ -650,6 +650,120 @@ extern "C" int srb_prepare_batch_device(srb_ctx *c, int n_agents, const srb_prep
     return SRB_OK;
 }
 
+// ---- closed-loop rollout (srb_sim.hip): the argument checks that need no context come first, in a fixed order
+// (struct_size, goal, x), so that tests/test_rollout.py reaches them without a GPU
+static int check_sim(const srb_sim *d, int cycle, bool advance)
+{
+    if (d && d->struct_size != (int)sizeof(srb_sim))
+        return fail(SRB_ERR_ARG, "srb_sim.struct_size != sizeof(srb_sim): caller built against another ABI");
+    if (!d) return fail(SRB_ERR_ARG, "null argument");
+    if (cycle < d->c_first) return fail(SRB_ERR_ARG, "srb_sim: cycle precedes c_first");
+    if (!advance) return SRB_OK;
+    if (!d->goal) return fail(SRB_ERR_ARG, "srb_sim.goal missing");
+    if (!d->x && cycle != d->c_first)
+        return fail(SRB_ERR_ARG, "srb_sim.x missing (the previous solve's x: required when cycle != c_first)");
+    return SRB_OK;
+}
+
+static int launch_advance(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s)
+{
+    const srb_params *p = &c->p;
+    if (p->N < 4) return fail(SRB_ERR_ARG, "the rollout needs N >= 4 (one cycle is one gait domain of 4 grids)");
+    if (!d->state || !d->x0 || !d->ref || !d->foot || !d->last_state)
+        return fail(SRB_ERR_ARG, "srb_sim: missing buffer (state, x0, ref, foot, last_state)");
+    hipLaunchKernelGGL(srb_sim_advance_kernel, dim3((n_agents + 255) / 256), dim3(256), 0, s, n_agents, p->N, p->C,
+                       srb_nv(p), p->Ts, d->vref, cycle, d->c_first, d->state, d->goal, d->phase, d->x, d->status,
+                       d->iters, d->x0, d->ref, d->foot, d->last_state, d->alpha_buf, d->plan_table, d->traj,
+                       d->status_log, d->iters_log, d->x_log);
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s)
+{
+    if (!d->state) return fail(SRB_ERR_ARG, "srb_sim: missing buffer (state)");
+    if (d->n_obs < 0 || d->n_all < 0 || (d->n_obs > 0 && !d->obstacles) || (d->n_all > 0 && !d->nbr_state))
+        return fail(SRB_ERR_ARG, "srb_sim: obstacles / nbr_state missing for n_obs / n_all rows");
+    hipLaunchKernelGGL(srb_sim_metrics_kernel, dim3((n_agents + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK),
+                       dim3(256), 0, s, n_agents, cycle, d->c_first,
+                       (const double *)d->state, d->obstacles, d->n_obs, d->nbr_state, d->n_all, d->agent_offset, d->d_obs,
+                       d->d_agent, d->min_d_obs, d->min_d_agent, d->fail_cycle, d->distance_to_fail);
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream, bool advance)
+{
+    if (int rc = check_sim(d, cycle, advance)) return rc;
+    if (!c) return fail(SRB_ERR_ARG, "null argument");
+    if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
+    if (n_agents == 0) return SRB_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->order.order_after_last(s);
+    if (!rc) rc = advance ? launch_advance(c, n_agents, d, cycle, s) : launch_metrics(c, n_agents, d, cycle, s);
+    if (!rc) rc = c->order.mark_done(s);
+    return rc;
+}
+
+extern "C" int srb_sim_advance_device(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream)
+{
+    return sim_call(c, n_agents, d, cycle, stream, true);
+}
+
+extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream)
+{
+    return sim_call(c, n_agents, d, cycle, stream, false);
+}
+
+extern "C" int srb_rollout_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, int cycles, void *stream)
+{
+    if (b && b->struct_size != (int)sizeof(srb_batch))
+        return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    // (the layout and null checks of check_sim only: the driver's first cycle is c_first itself)
+    if (int rc = check_sim(d, d && d->struct_size == (int)sizeof(srb_sim) ? d->c_first : 0, false)) return rc;
+    if (!b) return fail(SRB_ERR_ARG, "null argument");
+    if (!d->goal) return fail(SRB_ERR_ARG, "srb_sim.goal missing");
+    if (!c) return fail(SRB_ERR_ARG, "null argument");
+    if (cycles < 0) return fail(SRB_ERR_ARG, "negative cycles");
+    if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
+    if (b->agent_offset != 0 || d->agent_offset != 0 || (b->n_all != 0 && b->n_all != n_agents) ||
+        (d->n_all != 0 && d->n_all != n_agents))
+        return fail(SRB_ERR_ARG, "srb_rollout_device rolls out a whole team on one GPU: a sharded batch (agent_offset != 0 "
+                                 "or n_all != n_agents) needs the neighbour exchange between advance and metrics");
+    if (d->plan_table && b->plan) {
+        const size_t bytes = (size_t)n_agents * 2 * c->p.N * sizeof(double);
+        const char *t0 = (const char *)d->plan_table, *o0 = (const char *)b->plan;
+        if (o0 < t0 + bytes && t0 < o0 + bytes)
+            return fail(SRB_ERR_ARG, "srb_sim.plan_table overlaps srb_batch.plan (the solve reads the table while it "
+                                     "writes its plans: use two buffers)");
+    }
+    if (n_agents == 0) return SRB_OK;
+    // the two structs wired together (include/srbnmpc.h): the solve reads what the advance wrote and back
+    srb_sim sim = *d;
+    sim.x = b->x; sim.status = b->status; sim.iters = b->iters;
+    sim.obstacles = b->obstacles; sim.n_obs = b->n_obs;
+    sim.nbr_state = d->last_state; sim.n_all = n_agents; sim.agent_offset = 0;
+    srb_batch bat = *b;
+    bat.x0 = d->x0; bat.ref = d->ref; bat.foot = d->foot;
+    bat.nbr_state = d->last_state; bat.n_all = n_agents; bat.agent_offset = 0;
+    bat.alpha_buf = b->alpha ? d->alpha_buf : nullptr;
+    if (!sim.x) return fail(SRB_ERR_ARG, "srb_batch.x missing");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->order.order_after_last(s);
+    for (int i = 0; i <= cycles && !rc; i++) {
+        const int cyc = d->c_first + i;
+        rc = launch_advance(c, n_agents, &sim, cyc, s);
+        if (rc || i == cycles) break;
+        rc = launch_metrics(c, n_agents, &sim, cyc, s);
+        if (i > 0 && d->plan_table) bat.nbr_plan = d->plan_table;
+        if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp);
+    }
+    if (!rc) rc = c->order.mark_done(s);
+    return rc;
+}
+
 // swarms up to this many agents run as one persistent workgroup (srb_hlplan_kernel); larger ones
 // one launch per step over NA / 64 workgroups (srb_hlplan_step_kernel)
 #define SRB_HL_ONE_WG 1024

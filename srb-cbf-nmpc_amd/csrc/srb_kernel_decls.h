@@ -75,6 +75,19 @@ extern "C" __global__ void srb_hlplan_step_kernel(int NA, int i, int loop, const
                                                   const double *pos_cur, double *pos_next, double *st, double *Pr,
                                                   double *Prd);
 
+// ---- srb_sim.hip
+extern "C" __global__ void srb_sim_advance_kernel(int n_agents, int N, int C, int nv, double Ts, double vref, int c,
+                                                  int c_first, double *state, const double *goal, const int *phase,
+                                                  const double *x, const int *status, const int *iters, double *x0,
+                                                  double *ref, double *foot, double *last_state, double *alpha_buf,
+                                                  double *plan_table, double *traj, int *status_log, int *iters_log,
+                                                  double *x_log);
+#define SRB_SIM_AGENTS_PER_BLOCK 16      // srb_sim_metrics_kernel: agents per block of 256 threads (16 threads each)
+extern "C" __global__ void srb_sim_metrics_kernel(int n_agents, int c, int c_first, const double *state,
+                                                  const double *obstacles, int n_obs, const double *nbr_state, int n_all,
+                                                  int agent_offset, double *d_obs, double *d_agent, double *min_d_obs,
+                                                  double *min_d_agent, int *fail_cycle, double *distance_to_fail);
+
 // ---- srb_llctrl.hip
 extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDev io);
 

@@ -5,6 +5,7 @@ gfx950).  There is no CPU fallback: if the library is missing, or no GPU is visi
 constructing a solver raises.
 
     BatchSolver   -- whole agent batch per call (host numpy or device torch buffers)
+    Rollout       -- closed-loop team rollout of a BatchSolver on the device (srbnmpc.rollout)
     MPCDist       -- per-agent object with the reference's MPC_dist call surface
                      (/root/reference/include/MPC_dist.hpp:137-190)
     workload      -- synthetic agent batches with the SURVEY.md §8d distributions
@@ -79,6 +80,21 @@ class Prep(ctypes.Structure):
         super().__init__(ctypes.sizeof(Prep), *args, **kw)
 
 
+class Sim(ctypes.Structure):
+    """Mirror of srb_sim (the closed-loop rollout; struct_size filled in)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("state", _dp), ("goal", _dp), ("phase", _ip), ("vref", ctypes.c_double),
+                ("c_first", ctypes.c_int), ("x", _dp), ("status", _ip), ("iters", _ip),
+                ("x0", _dp), ("ref", _dp), ("foot", _dp), ("last_state", _dp), ("alpha_buf", _dp), ("plan_table", _dp),
+                ("traj", _dp), ("status_log", _ip), ("iters_log", _ip), ("x_log", _dp),
+                ("obstacles", _dp), ("nbr_state", _dp),
+                ("n_obs", ctypes.c_int), ("n_all", ctypes.c_int), ("agent_offset", ctypes.c_int),
+                ("d_obs", _dp), ("d_agent", _dp), ("min_d_obs", _dp), ("min_d_agent", _dp), ("fail_cycle", _ip),
+                ("distance_to_fail", _dp)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(ctypes.sizeof(Sim), *args, **kw)
+
+
 _lib = None
 
 
@@ -120,6 +136,10 @@ def lib():
         L.srb_last_polish_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
         L.srb_hl_plan.argtypes = [ctypes.c_int, ctypes.c_int, _dp, _dp, ctypes.c_int, ctypes.c_int, _dp, _dp]
         L.srb_prepare_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Prep), ctypes.c_void_p]
+        for f in ("srb_sim_advance_device", "srb_sim_metrics_device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Sim), ctypes.c_int, ctypes.c_void_p]
+        L.srb_rollout_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim),
+                                         ctypes.c_int, ctypes.c_void_p]
         L.srb_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.srb_fit_bezier.argtypes = [_dp, _dp, _dp]
         L.srb_last_error.restype = ctypes.c_char_p
@@ -461,3 +481,4 @@ from .mpc_dist import MPCDist  # noqa: E402
 from . import workload  # noqa: E402
 from . import ll_workload  # noqa: E402
 from .lowlevel import LowLevelCtrl  # noqa: E402
+from .rollout import Rollout  # noqa: E402

@@ -1,0 +1,214 @@
+"""Closed-loop team rollout on the device (srb_sim_advance_device / srb_sim_metrics_device /
+srb_rollout_device, include/srbnmpc.h): T control cycles of a whole agent batch with the nominal plant, the
+goal-directed reference of workload.make_batch re-centred every cycle, and the team's safety log.
+
+    r = Rollout(solver, goal, plans=True, obstacles=obstacles)
+    r.reset(state)              # [A][4] x, xdot, y, ydot
+    r.run(50)                   # the C driver: no host round trip inside
+    out = r.results()           # traj, status, iters, min_d_agent, min_d_obs, fail_cycle, ...
+
+step() is one cycle from Python (advance, [neighbour all-gather,] metrics, solve) and gives the same bits as
+run(); shards of a team step in lockstep, each with its dist.NeighbourExchange.
+"""
+from __future__ import annotations
+
+import ctypes
+
+from . import Batch, Sim, _check, _dp, _ip, lib
+
+
+def _dptr(t):
+    return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
+
+
+def _iptr(t):
+    return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _ip)
+
+
+def _check_tensor(t, shape, name, dtype, device):
+    """Shape, dtype, contiguity (as _check_plan_array) and device of a tensor the library reads by pointer."""
+    if not hasattr(t, "is_contiguous") or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)}, got "
+                         f"{tuple(getattr(t, 'shape', ()))} {getattr(t, 'dtype', type(t))}")
+    if t.device != device:
+        raise ValueError(f"{name} must be on {device}, got {t.device}")
+
+
+class Rollout:
+    """The closed loop of `solver` (a BatchSolver with N >= 4) for the agents whose goals are `goal` [A][2].
+
+    vref      reference speed of the goal-directed line (workload.VREF)
+    phase     [A] int32 or None: added to the cycle index for the trot parity
+    plans     True: from the second cycle on, the inter-agent rows follow the neighbours' previous plans shifted
+              by one gait domain (srb_batch.nbr_plan) instead of the constant-velocity guess
+    log_x     True: keep every cycle's decision vectors (results()["x"], [T][A][nv])
+    obstacles [n_obs][2] or None: the static obstacles, for the solve and for d_obs / fail_cycle
+    agent_offset, n_all   a shard of a larger team: this batch is rows agent_offset .. agent_offset + A of the
+              n_all-row neighbour table that step(exchange) gathers (default: the whole team)
+    All tensors are float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
+
+    def __init__(self, solver, goal, vref: float = 0.27, phase=None, plans: bool = False, log_x: bool = False, *,
+                 obstacles=None, agent_offset: int = 0, n_all: int | None = None):
+        import torch
+        self.solver = solver
+        p = solver.params
+        if p.N < 4:
+            raise ValueError("Rollout needs N >= 4 (one cycle is one gait domain of 4 grids)")
+        self.device = torch.device("cuda", solver.device)
+        if not hasattr(goal, "shape") or len(goal.shape) != 2:
+            raise ValueError("goal must be a [A][2] tensor")
+        A = self.A = int(goal.shape[0])
+        if A < 1 or A > solver.max_agents:
+            raise ValueError(f"goal holds {A} agents, the solver takes 1 .. {solver.max_agents}")
+        _check_tensor(goal, (A, 2), "goal", torch.float64, self.device)
+        if phase is not None:
+            _check_tensor(phase, (A,), "phase", torch.int32, self.device)
+        if obstacles is not None:
+            _check_tensor(obstacles, (obstacles.shape[0], 2), "obstacles", torch.float64, self.device)
+            if obstacles.shape[0] == 0:
+                obstacles = None
+        self.goal, self.phase, self.obstacles = goal, phase, obstacles
+        self.vref, self.plans, self.log_x = float(vref), bool(plans), bool(log_x)
+        self.agent_offset = int(agent_offset)
+        self.n_all = A if n_all is None else int(n_all)
+        if self.agent_offset < 0 or self.agent_offset + A > self.n_all:
+            raise ValueError("agent_offset + A exceeds n_all")
+        self.sharded = self.agent_offset != 0 or self.n_all != A
+        N, C, nv = p.N, p.C, p.nv
+        f8 = dict(dtype=torch.float64, device=self.device)
+        i4 = dict(dtype=torch.int32, device=self.device)
+        self.state = torch.zeros((A, 4), **f8)
+        self.x0, self.last_state, self.alpha_buf = (torch.zeros((A, 4), **f8) for _ in range(3))
+        self.ref = torch.zeros((A, 4 * N), **f8)
+        self.foot = torch.zeros((A, N, 2, C), **f8)
+        self.plan_table = torch.zeros((A, N, 2), **f8) if self.plans else None
+        self.out = dict(x=torch.zeros((A, nv), **f8), obj=torch.zeros(A, **f8), status=torch.zeros((A, 2), **i4),
+                        iters=torch.zeros((A, 2), **i4), alpha=torch.zeros((A, 20), **f8))
+        if self.plans:
+            self.out["plan"] = torch.zeros((A, N, 2), **f8)
+        self.metrics = dict(d_obs=torch.zeros(A, **f8), d_agent=torch.zeros(A, **f8), min_d_obs=torch.zeros(A, **f8),
+                            min_d_agent=torch.zeros(A, **f8), fail_cycle=torch.full((A,), -1, **i4),
+                            distance_to_fail=torch.zeros(A, **f8))
+        self.cap = 0
+        self.traj = self.status_log = self.iters_log = self.x_log = None
+        self.c = 0
+        self.flushed = True
+        self._ready = False
+
+    # ------------------------------------------------------------------ buffers
+    def _reserve(self, cycles: int):
+        """Log rows for `cycles` cycles (traj one more); grown by copying, so earlier rows stay."""
+        import torch
+        if cycles <= self.cap:
+            return
+        cap = max(cycles, 2 * self.cap, 8)
+        A, nv = self.A, self.solver.params.nv
+
+        def grow(old, rows, tail, dtype):
+            new = torch.zeros((rows,) + tail, dtype=dtype, device=self.device)
+            if old is not None:
+                new[:old.shape[0]] = old
+            return new
+        self.traj = grow(self.traj, cap + 1, (A, 4), torch.float64)
+        self.status_log = grow(self.status_log, cap, (A, 2), torch.int32)
+        self.iters_log = grow(self.iters_log, cap, (A, 2), torch.int32)
+        if self.log_x:
+            self.x_log = grow(self.x_log, cap, (A, nv), torch.float64)
+        self.cap = cap
+
+    def _sim(self, nbr_state=None) -> Sim:
+        nbr = self.last_state if nbr_state is None else nbr_state
+        m, o = self.metrics, self.out
+        return Sim(_dptr(self.state), _dptr(self.goal), _iptr(self.phase), self.vref, 0,
+                   _dptr(o["x"]), _iptr(o["status"]), _iptr(o["iters"]),
+                   _dptr(self.x0), _dptr(self.ref), _dptr(self.foot), _dptr(self.last_state), _dptr(self.alpha_buf),
+                   _dptr(self.plan_table), _dptr(self.traj), _iptr(self.status_log), _iptr(self.iters_log),
+                   _dptr(self.x_log), _dptr(self.obstacles), _dptr(nbr),
+                   0 if self.obstacles is None else self.obstacles.shape[0], nbr.shape[0], self.agent_offset,
+                   _dptr(m["d_obs"]), _dptr(m["d_agent"]), _dptr(m["min_d_obs"]), _dptr(m["min_d_agent"]),
+                   _iptr(m["fail_cycle"]), _dptr(m["distance_to_fail"]))
+
+    # ------------------------------------------------------------------ driving
+    def reset(self, state):
+        """Start state [A][4] (x, xdot, y, ydot); the cycle count and the logs start over."""
+        import torch
+        _check_tensor(state, (self.A, 4), "state", torch.float64, self.device)
+        self.state.copy_(state)
+        self.c = 0
+        self.flushed = True
+        self._ready = True
+
+    def advance(self, stream=None):
+        """The advance of the current cycle alone: state, x0, ref, foot, last_state (and the previous cycle's logs).
+        step() runs it itself; calling it first as well changes nothing (it rewrites the same values) and lets
+        shards driven from one process fill their snapshot rows before a stand-in exchange gathers them."""
+        if not self._ready:
+            raise RuntimeError("Rollout.advance before reset(state)")
+        s = self.solver
+        self._reserve(self.c + 1)
+        _check(lib().srb_sim_advance_device(s._h, self.A, ctypes.byref(self._sim()), self.c, s._stream(stream)))
+
+    def step(self, exchange=None, plan_exchange=None, stream=None):
+        """One cycle: advance, metrics, solve.  exchange (a dist.NeighbourExchange, or any callable
+        [A][4] -> [n_all][4]): the all-gather of the snapshot rows between advance and metrics, for a shard;
+        with plans, plan_exchange (a dist.PlanExchange) gathers the shifted plans likewise."""
+        if not self._ready:
+            raise RuntimeError("Rollout.step before reset(state)")
+        if self.sharded and exchange is None:
+            raise ValueError("a shard (agent_offset / n_all) steps with its neighbour exchange")
+        if self.plans and exchange is not None and plan_exchange is None:
+            raise ValueError("plans across shards need a plan_exchange (dist.PlanExchange)")
+        s = self.solver
+        self._reserve(self.c + 1)
+        self.advance(stream)
+        nbr = self.last_state if exchange is None else exchange(self.last_state)
+        import torch
+        _check_tensor(nbr, (self.n_all, 4), "the exchanged neighbour table", torch.float64, self.device)
+        _check(lib().srb_sim_metrics_device(s._h, self.A, ctypes.byref(self._sim(nbr)), self.c, s._stream(stream)))
+        table = None
+        if self.plans and self.c > 0:
+            table = self.plan_table if plan_exchange is None else plan_exchange(self.plan_table)
+        s.solve_device(self.x0, self.ref, self.foot, self.obstacles, nbr, self.out, agent_offset=self.agent_offset,
+                       stream=stream, alpha_buf=self.alpha_buf, nbr_plan=table)
+        self.c += 1
+        self.flushed = False
+
+    def run(self, T: int, stream=None):
+        """T cycles by the C driver (srb_rollout_device), right after reset(): one call, nothing synchronises
+        with the host inside.  A whole team only."""
+        T = int(T)
+        if not self._ready or self.c != 0:
+            raise RuntimeError("Rollout.run starts from reset(state) (use step() to go on)")
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        if self.sharded:
+            raise ValueError("run() rolls out a whole team; a shard steps with its exchange (step)")
+        s, o = self.solver, self.out
+        self._reserve(T)
+        b = Batch(None, None, None, _dptr(self.obstacles), None,
+                  0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
+                  None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]),
+                  None, _dptr(o["alpha"]), None, 0, None, _dptr(o.get("plan")))
+        _check(lib().srb_rollout_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), T, s._stream(stream)))
+        self.c = T
+        self.flushed = True
+
+    def results(self, stream=None):
+        """The logs and metrics so far, as tensors (views of this object's buffers; asynchronous like the
+        launches -- synchronise before reading on the host): traj [T+1][A][4], status / iters [T][A][2],
+        x [T][A][nv] (log_x), state [A][4] (the end state), cycles, and d_obs, d_agent, min_d_obs,
+        min_d_agent, fail_cycle, distance_to_fail [A]."""
+        if not self._ready:
+            raise RuntimeError("Rollout.results before reset(state)")
+        T = self.c
+        self._reserve(max(T, 1))
+        if not self.flushed:
+            self.advance(stream)                 # the final advance: the last logs and the end state
+            self.flushed = True
+        elif T == 0:
+            self.advance(stream)
+        out = dict(cycles=T, traj=self.traj[:T + 1], status=self.status_log[:T], iters=self.iters_log[:T],
+                   state=self.state, **self.metrics)
+        if self.log_x:
+            out["x"] = self.x_log[:T]
+        return out
