@@ -151,6 +151,25 @@ int srb_ctx_destroy(srb_ctx *ctx);
 int srb_ctx_set_waves(srb_ctx *ctx, int nw);
 int srb_ctx_waves(srb_ctx *ctx);
 
+/* Scenes: the batch is a set of independent teams of scene_agents agents, each with scene_obs obstacle rows.
+ * Global agent g = agent_offset + a belongs to scene g / scene_agents.  Its static rows are selected from
+ * obstacles[scene*scene_obs .. +scene_obs), its neighbour rows from nbr_state (and nbr_plan) rows
+ * [scene*scene_agents .. +scene_agents), itself excluded.  sel holds GLOBAL row indices (-1 as before).
+ * (0, 0) = off (default): one team, today's behaviour bit for bit.
+ * Tables stay flat and scene-major; n_obs and n_all stay the total row counts.  Honoured by srb_solve_batch,
+ * srb_solve_qp, srb_solve_batch_device, srb_select_device (tables 1, 2, 3 and the horizon-aware selection),
+ * srb_sim_metrics_device (nearest obstacle / other agent of the agent's scene) and srb_rollout_device.
+ * K_obs clamps to scene_obs and K_nbr to scene_agents - 1 (batch-uniform, like the n_obs / n_all - 1 clamps);
+ * the static 1000 m rule selects the scene's row 0 (global scene*scene_obs).  Scene tables are scanned brute
+ * force: no selection grid is built or consulted, and a cached static grid stays as it is.
+ * A call is refused (SRB_ERR_ARG, before anything is launched) when n_all is not a multiple of scene_agents,
+ * when n_obs != scenes * scene_obs with both tables in use, when agent_offset + n_agents lies beyond the last
+ * scene, and, for srb_rollout_device, when n_agents is not a multiple of scene_agents.  A shard (agent_offset,
+ * n_all > n_agents) may start and end inside a scene.  set refuses a negative value and scene_agents == 0 with
+ * scene_obs != 0.  The SRB-12 mode and the MPC_dist shims have no scenes. */
+int srb_ctx_set_scenes(srb_ctx *ctx, int scene_agents, int scene_obs);
+int srb_ctx_scenes(srb_ctx *ctx, int *scene_agents, int *scene_obs);
+
 /* Context options (no environment variable changes what the library computes; every knob is one
  * of these, per context).  set returns SRB_ERR_ARG for an unknown option or a value out of range.
  *   SRB_OPT_POLISH               1 (default) polish the NLP result to the exact KKT point of its active

@@ -121,6 +121,7 @@ struct srb_ctx {
     struct grid_buf { SrbGrid *g; int *off; double2 *spos; int *sidx; size_t cap; } grid[2];
     const double *grid_src;        // obstacle table, row count and version the obstacle grid was built from
     int grid_n, grid_ver;
+    int scene_agents, scene_obs;   // srb_ctx_set_scenes: agents / obstacle rows per scene (0, 0: one team)
 };
 
 // device buffers of selection grid t for a table of n rows (grown on demand; the header
@@ -325,6 +326,52 @@ extern "C" int srb_ctx_destroy(srb_ctx *c)
     return SRB_OK;
 }
 
+// ---- scenes (srb_ctx_set_scenes).  A table is in use by a call when the call hands it over: the obstacles with
+// n_obs > 0, the neighbour snapshot with a pointer (the metrics: n_all > 0).
+// "Up to K nearest" of what exists for an agent: the whole tables, or with scenes its scene's (batch-uniform).
+static void clamp_K(const srb_ctx *c, int n_obs, bool has_nbr, int n_all, int *Ko, int *Kn)
+{
+    int rows = n_obs > 0 ? n_obs : 0, others = has_nbr ? n_all - 1 : 0;
+    if (c->scene_agents > 0) {
+        rows = std::min(rows, c->scene_obs);
+        others = has_nbr ? c->scene_agents - 1 : 0;
+    }
+    if (*Ko > rows) *Ko = rows;
+    if (*Kn > others) *Kn = others > 0 ? others : 0;
+}
+
+// The per-call refusals of a scene partition, before anything is launched; *n_scenes (optional) receives the
+// number of scenes of the call's tables.  Nothing to check with scenes off, or without a table.
+static int check_scenes(const srb_ctx *c, int n_agents, int n_obs, bool has_nbr, int n_all, int agent_offset,
+                        int *n_scenes = nullptr)
+{
+    const int sa = c->scene_agents, so = c->scene_obs;
+    if (n_scenes) *n_scenes = 0;
+    const bool has_obs = n_obs > 0;
+    if (sa <= 0 || (!has_obs && !has_nbr)) return SRB_OK;
+    int ns;
+    if (has_nbr) {
+        if (n_all < 0 || n_all % sa != 0)
+            return fail(SRB_ERR_ARG, "scenes: n_all (" + std::to_string(n_all) + ") is not a multiple of scene_agents (" +
+                                     std::to_string(sa) + ")");
+        ns = n_all / sa;
+        if (has_obs && (long long)n_obs != (long long)ns * so)
+            return fail(SRB_ERR_ARG, "scenes: n_obs (" + std::to_string(n_obs) + ") != scenes * scene_obs (" +
+                                     std::to_string(ns) + " * " + std::to_string(so) + ")");
+    } else {
+        if (so == 0 || n_obs % so != 0)
+            return fail(SRB_ERR_ARG, "scenes: n_obs (" + std::to_string(n_obs) + ") != scenes * scene_obs (scene_obs " +
+                                     std::to_string(so) + ")");
+        ns = n_obs / so;
+    }
+    if (agent_offset < 0 || (long long)agent_offset + n_agents > (long long)ns * sa)
+        return fail(SRB_ERR_ARG, "scenes: agent_offset + n_agents (" + std::to_string(agent_offset) + " + " +
+                                 std::to_string(n_agents) + ") lies beyond the last scene (" + std::to_string(ns) +
+                                 " scenes of " + std::to_string(sa) + " agents)");
+    if (n_scenes) *n_scenes = ns;
+    return SRB_OK;
+}
+
 // Obstacle / neighbour selection for a batch (srb_knn_kernel; with a uniform grid per long table,
 // srb_grid_build_kernel): K_obs, K_nbr already clamped to the tables.  x0 rows are [x, ., y, .]
 // (stride 4); shared with the SRB-12 mode (srb12_capi.cpp), which hands over its CoM positions so.
@@ -334,6 +381,23 @@ static int launch_select(srb_ctx *c, int n_agents, const double *x0, const doubl
                          const double *nbr_plan = nullptr, int N = 0)
 {
     if (sel_stride < 0) sel_stride = K_obs + K_nbr;
+    // scenes: every agent's scene sub-tables brute force, no grid built or consulted (the cached static grid of
+    // obstacles_version stays for a later call with scenes off); the plan selection on the scene's rows
+    if (c->scene_agents > 0) {
+        const bool by_plan = nbr_plan && K_nbr > 0;
+        if (K_obs > 0 || !by_plan) {
+            hipLaunchKernelGGL(srb_knn_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_WAVES), 0, s, n_agents, x0, obstacles,
+                               nbr_state, agent_offset, c->scene_agents, c->scene_obs, K_obs, by_plan ? 0 : K_nbr, sel,
+                               sel_stride);
+            HIPCHK(hipGetLastError());
+        }
+        if (by_plan) {
+            hipLaunchKernelGGL(srb_knn_plan_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents, x0,
+                               nbr_state, nbr_plan, N, agent_offset, c->scene_agents, K_nbr, sel + K_obs, sel_stride);
+            HIPCHK(hipGetLastError());
+        }
+        return SRB_OK;
+    }
     // SRB_OPT_PLAN_SELECTION (the caller hands over nbr_plan only then): the neighbour columns by closest predicted
     // approach (srb_knn_plan_kernel, brute force, no grid); the static columns from srb_knn_kernel as ever
     if (nbr_plan && K_nbr > 0) {
@@ -415,6 +479,7 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     if ((d->alpha != nullptr) != (d->alpha_buf != nullptr))
         return fail(SRB_ERR_ARG, "alpha and alpha_buf go together (both or neither)");
     if (d->alpha && p->N < 4) return fail(SRB_ERR_ARG, "the Bezier fit needs N >= 4 (X_0..X_3)");
+    if (int rc = check_scenes(c, n_agents, d->n_obs, d->nbr_state != nullptr, d->n_all, d->agent_offset)) return rc;
     if (use_nlp && p->K_obs > 0 && (d->n_obs < 0 || (d->n_obs > 0 && !d->obstacles)))
         return fail(SRB_ERR_ARG, "obstacles missing");
     if (use_nlp && p->K_nbr > 0 && d->nbr_state && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
@@ -430,9 +495,8 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     k.kkt32_mu = c->kkt32_mu;
     k.kkt32_ref = c->kkt32_ref;
     // "up to K nearest": clamp to what exists (batch-uniform), so no row is ever a dummy
-    if (k.K_obs > d->n_obs) k.K_obs = d->n_obs > 0 ? d->n_obs : 0;
-    const int others = d->nbr_state ? d->n_all - 1 : 0;
-    if (k.K_nbr > others) k.K_nbr = others > 0 ? others : 0;
+    // (with scenes: to the agent's scene)
+    clamp_K(c, d->n_obs, d->nbr_state != nullptr, d->n_all, &k.K_obs, &k.K_nbr);
     const srb_instance *in = pick_instance(k, wanted_waves(n_agents, srb_slots(k.N, k.C, k.K_obs + k.K_nbr), c->nw));
     if (!in) return fail(SRB_ERR_SIZE, "no kernel instance covers this problem");
     const size_t lds = (size_t)srb_lds_doubles(k, in->nzl, in->nw) * sizeof(double);
@@ -501,6 +565,25 @@ extern "C" int srb_ctx_set_waves(srb_ctx *c, int nw)
 }
 
 extern "C" int srb_ctx_waves(srb_ctx *c) { return c ? c->last_nw : 0; }
+
+extern "C" int srb_ctx_set_scenes(srb_ctx *c, int scene_agents, int scene_obs)
+{
+    if (!c) return fail(SRB_ERR_ARG, "null ctx");
+    if (scene_agents < 0 || scene_obs < 0) return fail(SRB_ERR_ARG, "scenes: scene_agents and scene_obs must not be negative");
+    if (scene_agents == 0 && scene_obs != 0)
+        return fail(SRB_ERR_ARG, "scenes: scene_agents == 0 (off) goes with scene_obs == 0");
+    c->scene_agents = scene_agents;
+    c->scene_obs = scene_obs;
+    return SRB_OK;
+}
+
+extern "C" int srb_ctx_scenes(srb_ctx *c, int *scene_agents, int *scene_obs)
+{
+    if (!c) return fail(SRB_ERR_ARG, "null ctx");
+    if (scene_agents) *scene_agents = c->scene_agents;
+    if (scene_obs) *scene_obs = c->scene_obs;
+    return SRB_OK;
+}
 
 extern "C" int srb_ctx_set_option(srb_ctx *c, int opt, double v)
 {
@@ -610,9 +693,8 @@ extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, i
     if (n_agents == 0) return SRB_OK;
     const srb_params *p = &c->p;
     int Ko = p->K_obs, Kn = p->K_nbr;                     // clamped exactly as the solve does
-    if (Ko > d->n_obs) Ko = d->n_obs > 0 ? d->n_obs : 0;
-    const int others = d->nbr_state ? d->n_all - 1 : 0;
-    if (Kn > others) Kn = others > 0 ? others : 0;
+    clamp_K(c, d->n_obs, d->nbr_state != nullptr, d->n_all, &Ko, &Kn);
+    if (int rc0 = check_scenes(c, n_agents, d->n_obs, d->nbr_state != nullptr, d->n_all, d->agent_offset)) return rc0;
     if ((tables & 1) && Ko > 0 && !d->obstacles) return fail(SRB_ERR_ARG, "obstacles missing");
     if ((tables & 2) && Kn > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
@@ -684,6 +766,19 @@ static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
     if (!d->state) return fail(SRB_ERR_ARG, "srb_sim: missing buffer (state)");
     if (d->n_obs < 0 || d->n_all < 0 || (d->n_obs > 0 && !d->obstacles) || (d->n_all > 0 && !d->nbr_state))
         return fail(SRB_ERR_ARG, "srb_sim: obstacles / nbr_state missing for n_obs / n_all rows");
+    // scenes: blocks of one scene each, from the scene of the batch's first agent to that of its last
+    int n_scenes = 0;
+    if (int rc = check_scenes(c, n_agents, d->n_obs, d->n_all > 0, d->n_all, d->agent_offset, &n_scenes)) return rc;
+    if (n_scenes > 0) {
+        const int sa = c->scene_agents, bps = (sa + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK;
+        const int s0 = d->agent_offset / sa, s1 = (d->agent_offset + n_agents - 1) / sa;
+        hipLaunchKernelGGL(srb_sim_scene_metrics_kernel, dim3((s1 - s0 + 1) * bps), dim3(256), 0, s, n_agents, cycle,
+                           d->c_first, (const double *)d->state, d->obstacles, d->n_obs > 0 ? c->scene_obs : 0, d->nbr_state,
+                           d->n_all > 0 ? sa : 0, sa, d->agent_offset, s0, bps, d->d_obs, d->d_agent, d->min_d_obs,
+                           d->min_d_agent, d->fail_cycle, d->distance_to_fail);
+        HIPCHK(hipGetLastError());
+        return SRB_OK;
+    }
     hipLaunchKernelGGL(srb_sim_metrics_kernel, dim3((n_agents + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK),
                        dim3(256), 0, s, n_agents, cycle, d->c_first,
                        (const double *)d->state, d->obstacles, d->n_obs, d->nbr_state, d->n_all, d->agent_offset, d->d_obs,
@@ -737,6 +832,12 @@ extern "C" int srb_rollout_device(srb_ctx *c, int n_agents, const srb_batch *b, 
         if (o0 < t0 + bytes && t0 < o0 + bytes)
             return fail(SRB_ERR_ARG, "srb_sim.plan_table overlaps srb_batch.plan (the solve reads the table while it "
                                      "writes its plans: use two buffers)");
+    }
+    if (c->scene_agents > 0) {
+        if (n_agents % c->scene_agents != 0)
+            return fail(SRB_ERR_ARG, "scenes: srb_rollout_device rolls out whole scenes, n_agents (" + std::to_string(n_agents) +
+                                     ") is not a multiple of scene_agents (" + std::to_string(c->scene_agents) + ")");
+        if (int rc = check_scenes(c, n_agents, b->n_obs, true, n_agents, 0)) return rc;
     }
     if (n_agents == 0) return SRB_OK;
     // the two structs wired together (include/srbnmpc.h): the solve reads what the advance wrote and back
@@ -875,6 +976,8 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp)
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     if (int rc0 = c->order.order_after_last(s)) return rc0;   // after the last device launch on this context
+    if (int rc0 = check_scenes(c, n_agents, h->obstacles ? h->n_obs : 0, h->n_all > 0 && h->nbr_state, h->n_all, h->agent_offset))
+        return rc0;                                           // before the staging copies
     if (!h->x0 || !h->ref || !h->foot || !h->x || !h->obj || !h->status || !h->iters)
         return fail(SRB_ERR_ARG, "missing buffer");
     HIPCHK(hipMemcpyAsync(c->x0, h->x0, A * 4 * sizeof(double), hipMemcpyHostToDevice, s));
@@ -931,7 +1034,8 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp)
     if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->sel && use_nlp) {
-        const int Ko = std::min(p->K_obs, std::max(h->n_obs, 0)), Kn = h->nbr_state ? std::min(p->K_nbr, std::max(h->n_all - 1, 0)) : 0;
+        int Ko = p->K_obs, Kn = p->K_nbr;
+        clamp_K(c, h->n_obs, h->nbr_state && h->n_all > 0, h->n_all, &Ko, &Kn);       // as launch() did on the staged tables
         if (Ko + Kn > 0) HIPCHK(hipMemcpyAsync(h->sel, c->sel, A * (Ko + Kn) * sizeof(int), hipMemcpyDeviceToHost, s));
     }
     if (h->x_qp) HIPCHK(hipMemcpyAsync(h->x_qp, c->x_qp, A * nv * sizeof(double), hipMemcpyDeviceToHost, s));

@@ -88,6 +88,23 @@ extern "C" __global__ void srb_sim_metrics_kernel(int n_agents, int c, int c_fir
                                                   int agent_offset, double *d_obs, double *d_agent, double *min_d_obs,
                                                   double *min_d_agent, int *fail_cycle, double *distance_to_fail);
 
+// ---- srb_scenes.hip (srb_ctx_set_scenes): the selections over the sub-tables of the agent's scene, global indices
+// out; the metrics with block b serving agents (b % blocks_per_scene) SRB_SIM_AGENTS_PER_BLOCK .. of scene
+// scene0 + b / blocks_per_scene and staging only that scene's rows (obs_rows / nbr_rows a scene: scene_obs /
+// scene_agents, or 0 without the table)
+extern "C" __global__ void srb_knn_scene_kernel(int n_agents, const double *x0g, const double *obstacles,
+                                                const double *nbr_state, int agent_offset, int scene_agents,
+                                                int scene_obs, int K_obs, int K_nbr, int *sel_out, int sel_stride);
+extern "C" __global__ void srb_knn_plan_scene_kernel(int n_agents, const double *x0g, const double *nbr_state,
+                                                     const double *nbr_plan, int N, int agent_offset, int scene_agents,
+                                                     int K_nbr, int *sel_out, int sel_stride);
+extern "C" __global__ void srb_sim_scene_metrics_kernel(int n_agents, int c, int c_first, const double *state,
+                                                        const double *obstacles, int obs_rows, const double *nbr_state,
+                                                        int nbr_rows, int scene_agents, int agent_offset, int scene0,
+                                                        int blocks_per_scene, double *d_obs, double *d_agent,
+                                                        double *min_d_obs, double *min_d_agent, int *fail_cycle,
+                                                        double *distance_to_fail);
+
 // ---- srb_llctrl.hip
 extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDev io);
 

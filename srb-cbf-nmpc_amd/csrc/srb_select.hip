@@ -70,36 +70,8 @@ extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_WAVES) srb_knn_kernel(
 // order, ties, the excluded row g, NaN rows and the -1 fill are knn_select_k's (no 1000 m cap: that rule is the
 // static table's).  Brute force, one workgroup per agent: the agent's own N + 1 points in LDS, every thread scans
 // rows tid, tid + 64 KW, .. and keeps a sorted list (knn_insert); knn_pop merges them.  Only the neighbour
-// columns are written (sel_out points at them; rows of stride sel_stride).
-template <int KM>
-__device__ __forceinline__ void knn_plan_select(int tid, const double *own, const double *__restrict__ nbr_state,
-                                                const double *__restrict__ nbr_plan, int n_all, int N, int self, int K,
-                                                int *sel, double *wd_lds, int *wi_lds)
-{
-#pragma clang fp contract(off)
-    double bd[KM]; int bi[KM];
-#pragma unroll
-    for (int j = 0; j < KM; j++) { bd[j] = __builtin_inf(); bi[j] = 0x7fffffff; }
-    double wq = __builtin_inf();                   // filter bound on the squared key (knn_select_k's)
-    for (int i = tid; i < n_all; i += 64 * SRB_KNN_PLAN_WAVES) {
-        if (i == self) continue;
-        const double *row = nbr_plan + 2 * (size_t)i * N;
-        const double dx0 = own[0] - nbr_state[4 * (size_t)i], dy0 = own[1] - nbr_state[4 * (size_t)i + 1];
-        double m = dx0 * dx0 + dy0 * dy0;
-        for (int k = 0; k < N; k++) {
-            const double dx = own[2 * k + 2] - row[2 * k], dy = own[2 * k + 3] - row[2 * k + 1];
-            const double d2 = dx * dx + dy * dy;
-            m = (d2 < m || d2 != d2) ? d2 : m;       // the minimum; a NaN pair makes the key NaN for good
-        }
-        if (!(m <= wq)) continue;                  // NaN keys fail: such rows are never selected
-        knn_insert<KM>(bd, bi, sqrt(m), i, K);
-#pragma unroll
-        for (int j = 0; j < KM; j++)
-            if (j == K - 1) wq = bd[j] * bd[j] * (1.0 + 1e-14);
-    }
-    knn_pop<SRB_KNN_PLAN_WAVES, KM>(tid, bd, bi, K, 0, sel, wd_lds, wi_lds);
-}
-
+// columns are written (sel_out points at them; rows of stride sel_stride).  The scan itself is knn_plan_select
+// (srb_knn.h), shared with the per-scene kernel of srb_scenes.hip.
 extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_PLAN_WAVES) srb_knn_plan_kernel(int n_agents,
                 const double *__restrict__ x0g, const double *__restrict__ nbr_state,
                 const double *__restrict__ nbr_plan, int n_all, int N, int agent_offset, int K_nbr,

@@ -6,7 +6,8 @@
 //                            the new position, last cycle's plans shifted by one domain, and the logs
 //   srb_sim_metrics_kernel   brute force over the obstacle table and the neighbour snapshot: nearest obstacle,
 //                            nearest other agent, their running minima and the reference's distance_to_fail
-//                            (updateDistance_to_fail, MPC_dist.cpp:21-40)
+//                            (updateDistance_to_fail, MPC_dist.cpp:21-40); its scan and its update rules are in
+//                            srb_sim_scan.h, shared with the per-scene kernel of srb_scenes.hip
 // One cycle is one gait domain of NDOMAIN = 4 grids (global_loco_opts.h:9).  All arithmetic is fp64 with
 // contraction off and every expression is written with the grouping of tests/sim_oracle.py, which restates both
 // kernels in numpy bit for bit.
@@ -124,33 +125,7 @@ extern "C" __global__ void __launch_bounds__(256) srb_sim_advance_kernel(
     }
 }
 
-#define SIM_TILE 256
-#define SIM_AG SRB_SIM_AGENTS_PER_BLOCK            // agents per block
-#define SIM_SL (SIM_TILE / SIM_AG)                 // threads per agent: each scans every SIM_SL-th row of a tile
-
-// this thread's share of the smallest squared distance from (px, py) to the rows of tab (row stride `stride`
-// doubles, columns 0 and 1), row `skip` left out.  The block stages the rows through LDS in tiles of SIM_TILE and
-// thread (agent, slice) scans rows slice, slice + SIM_SL, .. of each tile, so every thread of the block calls this
-// (threads past the batch's end included).  A squared distance that is NaN never compares smaller.
-__device__ static __forceinline__ double sim_nearest2(const double *__restrict__ tab, int n, int stride, int skip,
-                                                      double px, double py, double2 *tile)
-{
-    const int slice = (int)threadIdx.x / SIM_AG;
-    double best = INFINITY;
-    for (int t0 = 0; t0 < n; t0 += SIM_TILE) {
-        const int row = t0 + (int)threadIdx.x;
-        __syncthreads();                                  // the previous tile has been read
-        if (row < n) tile[threadIdx.x] = make_double2(tab[(size_t)row * stride], tab[(size_t)row * stride + 1]);
-        __syncthreads();
-        const int m = n - t0 < SIM_TILE ? n - t0 : SIM_TILE;
-        for (int i = slice; i < m; i += SIM_SL) {
-            const double dx = px - tile[i].x, dy = py - tile[i].y;
-            const double d2 = dx * dx + dy * dy;
-            if (t0 + i != skip && d2 < best) best = d2;
-        }
-    }
-    return best;
-}
+#include "srb_sim_scan.h"      // SIM_TILE, SIM_AG, SIM_SL and sim_nearest2, the tiled scan (shared with srb_scenes.hip)
 
 // SIM_AG agents per block of SIM_TILE threads, SIM_SL threads per agent.  (One thread per agent leaves a
 // 1024-agent team on 4 CUs, each thread walking every row: 0.156 ms at 5120 obstacles + 1024 agents, half a
@@ -177,21 +152,6 @@ extern "C" __global__ void __launch_bounds__(SIM_TILE) srb_sim_metrics_kernel(
         if (part[0][s][al] < b_ob) b_ob = part[0][s][al];
         if (part[1][s][al] < b_ag) b_ag = part[1][s][al];
     }
-    const double dob = sqrt(b_ob), dag = sqrt(b_ag);
-    const bool first = c == c_first;
-    if (d_obs) d_obs[a] = dob;
-    if (d_agent) d_agent[a] = dag;
-    if (min_d_obs) min_d_obs[a] = (first || dob < min_d_obs[a]) ? dob : min_d_obs[a];
-    if (min_d_agent) min_d_agent[a] = (first || dag < min_d_agent[a]) ? dag : min_d_agent[a];
-    // updateDistance_to_fail (MPC_dist.cpp:21-40): the first cycle inside 0.5 m of an obstacle, and the distance
-    // from the origin there; once set they stay (isSuccess)
-    if (fail_cycle) {
-        int fc = first ? -1 : fail_cycle[a];
-        if (first && distance_to_fail) distance_to_fail[a] = 0.0;
-        if (fc < 0 && dob < 0.5) {
-            fc = c;
-            if (distance_to_fail) distance_to_fail[a] = sqrt(px * px + py * py);
-        }
-        fail_cycle[a] = fc;
-    }
+    sim_metrics_store(a, c, c_first, px, py, b_ob, b_ag, d_obs, d_agent, min_d_obs, min_d_agent, fail_cycle,
+                      distance_to_fail);
 }

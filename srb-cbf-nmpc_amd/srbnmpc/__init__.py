@@ -130,6 +130,8 @@ def lib():
         L.srb_sync.argtypes = [ctypes.c_void_p]
         L.srb_ctx_set_waves.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.srb_ctx_waves.argtypes = [ctypes.c_void_p]
+        L.srb_ctx_set_scenes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.srb_ctx_scenes.argtypes = [ctypes.c_void_p, _ip, _ip]
         L.srb_ctx_set_qp_init.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.srb_ctx_set_option.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double]
         L.srb_ctx_get_option.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
@@ -192,6 +194,7 @@ class BatchSolver:
         h = ctypes.c_void_p()
         _check(lib().srb_ctx_create(ctypes.byref(params), self.max_agents, self.device, ctypes.byref(h)))
         self._h = h
+        self._scenes = (0, 0)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -209,6 +212,9 @@ class BatchSolver:
         """(Ko, Kn): selected static obstacles / neighbours per agent for tables of these sizes
         ("up to K nearest", the clamp the C ABI applies)."""
         p = self.params
+        sa, so = self.scenes
+        if sa > 0:                                            # per scene: the agent's own sub-tables
+            return min(p.K_obs, max(n_obs, 0), so), (min(p.K_nbr, sa - 1) if n_all > 0 else 0)
         return min(p.K_obs, max(n_obs, 0)), (min(p.K_nbr, max(n_all - 1, 0)) if n_all > 0 else 0)
 
     def solve(self, x0, ref, foot, obstacles=None, nbr_state=None, agent_offset: int = 0, qp_only: bool = False,
@@ -394,6 +400,20 @@ class BatchSolver:
     def set_waves(self, nw: int = 0):
         """Waves per agent (0 automatic, 1, 2, 4; srb_ctx_set_waves)."""
         _check(lib().srb_ctx_set_waves(self._h, int(nw)))
+
+    def set_scenes(self, scene_agents: int = 0, scene_obs: int = 0):
+        """The batch as independent teams (srb_ctx_set_scenes): scene_agents agents and scene_obs obstacle rows
+        per scene, tables flat and scene-major; agent g selects and is measured within scene g // scene_agents,
+        sel holds global rows.  (0, 0): off, one team."""
+        _check(lib().srb_ctx_set_scenes(self._h, int(scene_agents), int(scene_obs)))
+        a, o = ctypes.c_int(), ctypes.c_int()
+        _check(lib().srb_ctx_scenes(self._h, ctypes.byref(a), ctypes.byref(o)))
+        self._scenes = (a.value, o.value)
+
+    @property
+    def scenes(self):
+        """(scene_agents, scene_obs) as last set through set_scenes; (0, 0) when off."""
+        return self._scenes
 
     def set_option(self, name: str, value: float):
         """Context option (srb_ctx_set_option): name one of OPTIONS ("polish", "polish_rho",

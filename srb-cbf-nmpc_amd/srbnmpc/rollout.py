@@ -9,6 +9,10 @@ goal-directed reference of workload.make_batch re-centred every cycle, and the t
 
 step() is one cycle from Python (advance, [neighbour all-gather,] metrics, solve) and gives the same bits as
 run(); shards of a team step in lockstep, each with its dist.NeighbourExchange.
+
+With the solver's scene partition on (BatchSolver.set_scenes(team, n_obs); inputs from workload.make_scenes) the
+batch is many independent teams rolled out by the same launches -- obstacles is then the scene-major table
+[n_scenes * n_obs][2] -- and scene_results() reduces the metrics per scene.
 """
 from __future__ import annotations
 
@@ -183,6 +187,9 @@ class Rollout:
             raise ValueError("T must be >= 0")
         if self.sharded:
             raise ValueError("run() rolls out a whole team; a shard steps with its exchange (step)")
+        sa = self.solver.scenes[0]
+        if sa > 0 and self.A % sa != 0:
+            raise ValueError(f"run() rolls out whole scenes: {self.A} agents are not a multiple of scene_agents = {sa}")
         s, o = self.solver, self.out
         self._reserve(T)
         b = Batch(None, None, None, _dptr(self.obstacles), None,
@@ -212,3 +219,33 @@ class Rollout:
         if self.log_x:
             out["x"] = self.x_log[:T]
         return out
+
+    def scene_results(self, stream=None):
+        """results() reduced per scene of the solver's partition (BatchSolver.set_scenes; a whole number of scenes),
+        as device tensors [n_scenes]: min_d_agent and min_d_obs (the smallest over the scene's agents), n_failed
+        (agents with fail_cycle >= 0) and n_not_converged (solves of the logged cycles that did not converge: QP
+        stage neither OPTIMAL nor QP_WARM, or NLP stage not OPTIMAL); plus scene_agents and n_scenes.
+        Asynchronous like results()."""
+        sa = self.solver.scenes[0]
+        if sa <= 0:
+            raise ValueError("scene_results needs the solver's scene partition (BatchSolver.set_scenes)")
+        if self.sharded or self.A % sa != 0:
+            raise ValueError(f"scene_results reduces whole scenes: {self.A} agents (a shard: {self.sharded}) "
+                             f"are not a whole number of scenes of {sa}")
+        return reduce_scenes(self.results(stream), sa)
+
+
+def reduce_scenes(res, scene_agents: int):
+    """The per-scene reductions of Rollout.scene_results from a results() dict (torch tensors, any device):
+    views [n_scenes][scene_agents] of the per-agent metrics, reduced along the scene."""
+    sa = int(scene_agents)
+    A = res["min_d_agent"].shape[0]
+    if sa <= 0 or A % sa != 0:
+        raise ValueError(f"{A} agents are not a whole number of scenes of {sa}")
+    S = A // sa
+    st = res["status"]                                       # [T][A][2]
+    ok = ((st[..., 0] == 0) | (st[..., 0] == 4)) & (st[..., 1] == 0)
+    return dict(n_scenes=S, scene_agents=sa,
+                min_d_agent=res["min_d_agent"].view(S, sa).amin(1), min_d_obs=res["min_d_obs"].view(S, sa).amin(1),
+                n_failed=(res["fail_cycle"].view(S, sa) >= 0).sum(1),
+                n_not_converged=(~ok).view(st.shape[0], S, sa).sum((0, 2)))

@@ -83,6 +83,68 @@ def make_batch(n_agents: int, N: int = 10, C: int = 2, seed: int = 0, n_obs: int
     return dict(x0=x0, ref=ref.reshape(A, 4 * N), foot=foot, obstacles=obstacles, nbr_state=nbr_state)
 
 
+SCENE_MAX_ATTEMPTS = 1000     # start draws per scene (make_scenes) before the clearance counts as impossible
+
+
+def make_scenes(n_scenes: int, team: int, N: int = 10, C: int = 2, seed: int = 0, n_obs: int = 20,
+                clearance: float = 0.5):
+    """n_scenes independent teams of `team` agents for BatchSolver.set_scenes(team, n_obs), scene-major:
+    dict(x0 [S*team,4], ref [S*team,4N], foot [S*team,N,2,C], obstacles [S*n_obs,2], nbr_state [S*team,4],
+    goal [S*team,2], phase [S*team] int32).  Every scene is its own draw of the reference's arena at
+    arena_scale(team) with make_batch's distributions, from a generator seeded by (seed, scene index) alone, so
+    scene s is the same whatever n_scenes is.  A start closer than `clearance` to an obstacle of its scene or to an
+    earlier start of its scene is drawn again (host-side rejection, deterministic); after SCENE_MAX_ATTEMPTS draws
+    in one scene a ValueError names the scene."""
+    S, A = int(n_scenes), int(team)
+    if S < 1 or A < 1 or n_obs < 0:
+        raise ValueError("make_scenes: n_scenes >= 1, team >= 1, n_obs >= 0")
+    sc = arena_scale(A)
+    goal1 = GOAL * np.array([sc, 1.0])
+    k = np.arange(N)
+    out = dict(x0=np.zeros((S * A, 4)), ref=np.zeros((S * A, N, 4)), foot=np.zeros((S * A, N, 2, C)),
+               obstacles=np.zeros((S * n_obs, 2)), nbr_state=np.zeros((S * A, 4)), goal=np.tile(goal1, (S * A, 1)),
+               phase=np.zeros(S * A, np.int32))
+    for s in range(S):
+        rng = np.random.default_rng([int(seed), s])
+        obstacles = make_obstacles(rng, n_obs, sc)
+        p0 = np.zeros((A, 2))
+        attempts = 0
+        for a in range(A):
+            while True:
+                if attempts >= SCENE_MAX_ATTEMPTS:
+                    raise ValueError(f"make_scenes: scene {s}: no start {clearance} m clear of the scene's {n_obs} "
+                                     f"obstacles and {a} earlier starts after {attempts} draws")
+                attempts += 1
+                q = np.array([rng.uniform(0, 9.0 * sc), rng.uniform(-2.0 * sc, 2.0 * sc)])
+                taken = np.concatenate([obstacles, p0[:a]])
+                if not taken.size or np.sqrt(((taken - q) ** 2).sum(1)).min() >= clearance:
+                    break
+            p0[a] = q
+        d = goal1 - p0
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        v0 = d * rng.uniform(0, 0.3, (A, 1)) + rng.uniform(-0.05, 0.05, (A, 2))
+        phase = rng.integers(0, 4, A)
+        r = slice(s * A, (s + 1) * A)
+        out["x0"][r] = np.stack([p0[:, 0], v0[:, 0], p0[:, 1], v0[:, 1]], 1)
+        ref = out["ref"][r]
+        ref[:, :, 0] = p0[:, None, 0] + d[:, None, 0] * VREF * TS * (k + 1)
+        ref[:, :, 1] = d[:, None, 0] * VREF
+        ref[:, :, 2] = p0[:, None, 1] + d[:, None, 1] * VREF * TS * (k + 1)
+        ref[:, :, 3] = d[:, None, 1] * VREF
+        for a in range(A):                                      # the trot schedule of make_batch
+            for kk in range(N):
+                dom = (kk + phase[a]) // 4
+                k_start = max(4 * dom - phase[a], 0)
+                centre = p0[a] + d[a] * VREF * TS * k_start
+                legs = TROT_PAIRS[dom % 2] if C == 2 else [0, 1, 2, 3]
+                out["foot"][s * A + a, kk] = STANCE[:, legs] + centre[:, None]
+        out["obstacles"][s * n_obs:(s + 1) * n_obs] = obstacles
+        out["nbr_state"][r] = np.stack([p0[:, 0], p0[:, 1], v0[:, 0], v0[:, 1]], 1)
+        out["phase"][r] = phase
+    out["ref"] = out["ref"].reshape(S * A, 4 * N)
+    return out
+
+
 HCOM12 = 0.3      # SRB-12 mode: nominal CoM height of the synthetic batches
 
 
