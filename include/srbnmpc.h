@@ -166,7 +166,8 @@ int srb_ctx_waves(srb_ctx *ctx);
  * when n_obs != scenes * scene_obs with both tables in use, when agent_offset + n_agents lies beyond the last
  * scene, and, for srb_rollout_device, when n_agents is not a multiple of scene_agents.  A shard (agent_offset,
  * n_all > n_agents) may start and end inside a scene.  set refuses a negative value and scene_agents == 0 with
- * scene_obs != 0.  The SRB-12 mode and the MPC_dist shims have no scenes. */
+ * scene_obs != 0.  The SRB-12 mode has the same partition on its own context (srb12_ctx_set_scenes); the
+ * MPC_dist shims have no scenes. */
 int srb_ctx_set_scenes(srb_ctx *ctx, int scene_agents, int scene_obs);
 int srb_ctx_scenes(srb_ctx *ctx, int *scene_agents, int *scene_obs);
 
@@ -529,6 +530,92 @@ int srb12_last_kernel_ms(srb12_ctx *ctx, float *select_ms, float *solve_ms);
 /* 1 (default): HIP events around the selection and solve kernels (srb12_last_kernel_ms); 0: none */
 int srb12_ctx_set_timing(srb12_ctx *ctx, int on);
 int srb12_lds_bytes(const srb12_params *p);
+
+/* Scenes in the SRB-12 mode: srb_ctx_set_scenes / srb_ctx_scenes forwarded to the context's selection.  The rules,
+ * the per-call refusals and their messages are those of the LIP mode (see srb_ctx_set_scenes); they are honoured by
+ * srb12_solve_batch, srb12_solve_batch_device, srb12_sim_metrics_device and srb12_rollout_device.  "Up to K nearest"
+ * clamps to the agent's scene (K_obs to scene_obs, K_nbr to scene_agents - 1), and `sel` holds global row indices. */
+int srb12_ctx_set_scenes(srb12_ctx *ctx, int scene_agents, int scene_obs);
+int srb12_ctx_scenes(srb12_ctx *ctx, int *scene_agents, int *scene_obs);
+
+/*
+ * Closed-loop team rollout of the SRB-12 mode on the device: srb_sim's step and safety log for
+ * the 12-state body.  One cycle is one gait domain of NDOMAIN = 4 grids, so N >= 4.  The plant is nominal: the state
+ * that starts cycle c + 1 is the X the solve of cycle c predicted at grid index 3, x[a][36..47], whatever that
+ * solve's status.  All pointers are device pointers, fp64 unless noted; cycles count from c_first, and log rows are
+ * indexed by c - c_first.
+ *
+ * srb12_sim_advance_device(ctx, A, sim, c, stream), cycle c >= c_first:
+ *   state       [A][12]      p(3), roll/pitch/yaw(3), v(3), omega(3).  c == c_first: read (the caller's start
+ *                            state); later cycles: written from x[a][36..47]
+ *   goal        [A][2]       in: each agent's goal
+ *   phase       [A] int      in, optional: added to c for the trot parity
+ *   vref                     reference speed (the synthetic workload's: 0.27)
+ *   hcom                     reference height of the CoM (the synthetic workload's: 0.3)
+ *   yaw_step, hold_radius    the yaw reference: with e the bearing of the goal minus the yaw, wrapped to
+ *                            [-pi, pi] (e -= 2 pi rint(e / 2 pi)) and clamped to +-yaw_step, yaw_ref = yaw + e
+ *                            when the goal is farther than hold_radius, else the yaw itself.  A function of the
+ *                            state alone, so a logged state reproduces it.  (Python defaults: 0.1 rad, the heading
+ *                            offset workload.make_batch12 draws, and 0.05 m)
+ *   gait                     0 trot, 1 stand
+ *   x, status, iters         in: the previous solve's outputs (srb12_batch layout); x is required when c != c_first
+ *   x0 [A][12], xref [A][N][12], foot [A][N][4][3], contact [A][N][4] int   out: the srb12_batch inputs of cycle c.
+ *                            With d = goal - (x, y), dist = |d|, w = (d / dist) min(vref, dist / (Ts N)) (0 at the
+ *                            goal: a standing reference that never overshoots) and t = Ts (k + 1), xref grid k is
+ *                            columns 0, 1 = p + w t, 2 = hcom, 5 = yaw_ref, 6, 7 = w, every other column 0.  foot
+ *                            grid k, domain j = k / 4: leg l (FR, FL, RR, RL) at centre + R(yaw_ref) STANCE[l], z = 0,
+ *                            centre = p + w (Ts 4 j), STANCE the default stance (MPC_dist.cpp:1206-1209).  contact:
+ *                            stand sets all four legs; trot {FR,RL} when c + phase + j is even, {FL,RR} when odd
+ *   last_state  [A][4]       out: x, y, xdot, ydot -- the neighbour-snapshot row (get_lastState)
+ *   com         [A][4]       out: x, xdot, y, ydot -- the row the selection and the metrics scan read
+ *   traj        [T+1][A][12] out, optional: row c - c_first gets the state
+ *   status_log, iters_log [T][A][2] int, x_log [T][A][24N+1]  out, optional, c != c_first only: row c - c_first - 1
+ *                            gets the previous solve's status, iters, x
+ * srb12_sim_metrics_device(ctx, A, sim, c, stream): the safety metrics of the `com` rows at the start of cycle c --
+ * the kernels, the scan and the update rules of srb_sim_metrics_device, brute force and independent of the solver's
+ * own selection:
+ *   obstacles [n_obs][2], nbr_state [n_all][4], agent_offset   in: as in srb12_batch (row agent_offset + a is the
+ *                            agent itself and is left out); either table may be empty
+ *   d_obs, d_agent, min_d_obs, min_d_agent [A], fail_cycle [A] int, distance_to_fail [A]   out, optional: exactly
+ *                            as in srb_sim (a NaN row never wins, an empty table gives +inf, the first cycle with
+ *                            d_obs < 0.5 is kept); the running results are initialised by the call with c == c_first
+ * Both are asynchronous on `stream` and ordered by the context like srb12_solve_batch_device.
+ *
+ * srb12_rollout_device(ctx, A, batch, sim, cycles, stream): `cycles` whole cycles of one team on one GPU.  For
+ * c = c_first .. c_first + cycles - 1 it enqueues advance, metrics and solve, then one final advance that flushes
+ * the last logs and the end state -- plain launches, no graph capture, no host synchronisation.  The two structs
+ * are wired together here: the solve reads sim's x0, xref, foot, contact and sim.last_state as its nbr_state with
+ * n_all = A, agent_offset = 0; the advance reads batch's x, status, iters; the metrics read batch's obstacles /
+ * n_obs and sim.last_state.  The members of either struct that this replaces are ignored; batch.n_all /
+ * agent_offset must be A / 0 or both 0 (a shard cannot roll out alone: its neighbours move too).  With scenes,
+ * A must be a whole number of scenes.  The solve has no nbr_plan input: the inter-agent rows use the
+ * constant-velocity guess in every cycle.
+ */
+typedef struct srb12_sim {
+    int struct_size;         /* sizeof(srb12_sim) (ABI check) */
+    double *state;
+    const double *goal;
+    const int *phase;
+    double vref, hcom, yaw_step, hold_radius;
+    int gait, c_first;
+    const double *x;
+    const int *status, *iters;
+    double *x0, *xref, *foot;
+    int *contact;
+    double *last_state, *com;
+    double *traj;
+    int *status_log, *iters_log;
+    double *x_log;
+    const double *obstacles, *nbr_state;
+    int n_obs, n_all, agent_offset;
+    double *d_obs, *d_agent, *min_d_obs, *min_d_agent;
+    int *fail_cycle;
+    double *distance_to_fail;
+} srb12_sim;
+int srb12_sim_advance_device(srb12_ctx *ctx, int n_agents, const srb12_sim *dev_io, int cycle, void *stream);
+int srb12_sim_metrics_device(srb12_ctx *ctx, int n_agents, const srb12_sim *dev_io, int cycle, void *stream);
+int srb12_rollout_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim, int cycles,
+                         void *stream);
 
 const char *srb_last_error(void);
 

@@ -176,15 +176,20 @@ extern "C" int srb12_ctx_destroy(srb12_ctx *c)
 }
 
 // "up to K nearest": the rows selected per agent, clamped to what the tables hold (batch-uniform, as
-// the LIP mode) and 0 without the NLP stage -- the launch and the host copy-back of sel use this one rule
-static void clamp_rows(const srb12_params *p, const srb12_batch *d, int *Ko, int *Kn)
+// the LIP mode; with scenes to the agent's scene: scene_obs rows, scene_agents - 1 others) and 0 without
+// the NLP stage -- the launch and the host copy-back of sel use this one rule
+static void clamp_rows(const srb12_ctx *c, const srb12_batch *d, int *Ko, int *Kn)
 {
-    int ko = p->K_obs, kn = p->K_nbr;
-    if (ko > d->n_obs) ko = d->n_obs > 0 ? d->n_obs : 0;
-    const int others = d->nbr_state ? d->n_all - 1 : 0;
-    if (kn > others) kn = others > 0 ? others : 0;
-    if (!p->use_nlp) ko = kn = 0;
+    int ko = c->p.K_obs, kn = c->p.K_nbr;
+    srb_internal_clamp_K(c->sel_ctx, d->n_obs, d->nbr_state != nullptr, d->n_all, &ko, &kn);
+    if (!c->p.use_nlp) ko = kn = 0;
     *Ko = ko; *Kn = kn;
+}
+
+// the per-call refusals of the scene partition (srb12_ctx_set_scenes), the LIP mode's with its messages
+static int check_scenes12(const srb12_ctx *c, int n_agents, const srb12_batch *d)
+{
+    return srb_internal_check_scenes(c->sel_ctx, n_agents, d->n_obs, d->nbr_state != nullptr, d->n_all, d->agent_offset);
 }
 
 static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_t s)
@@ -198,8 +203,9 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         return srb_internal_fail(SRB_ERR_ARG, "obstacles missing");
     if (p->use_nlp && p->K_nbr > 0 && d->nbr_state && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return srb_internal_fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
+    if (int rc = check_scenes12(c, n_agents, d)) return rc;
     int Ko = 0, Kn = 0;
-    clamp_rows(p, d, &Ko, &Kn);
+    clamp_rows(c, d, &Ko, &Kn);
     Srb12KParams k = make_k12(p, Ko, Kn);
     k.dbg_agent = c->dbg_agent; k.dbg = c->dbg;
     const srb12_inst *in = pick12(p->N, Ko + Kn);
@@ -258,6 +264,9 @@ extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *
     if (n_agents == 0) return SRB_OK;
     if (!h->x0 || !h->xref || !h->foot || !h->contact || !h->x || !h->obj || !h->status || !h->iters)
         return srb_internal_fail(SRB_ERR_ARG, "missing buffer");
+    if (int rc0 = srb_internal_check_scenes(c->sel_ctx, n_agents, h->obstacles ? h->n_obs : 0, h->n_all > 0 && h->nbr_state,
+                                            h->n_all, h->agent_offset))
+        return rc0;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
     if (int rc0 = c->order.order_after_last(s)) return rc0;
@@ -296,7 +305,7 @@ extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *
     HIPCHK(hipMemcpyAsync(h->iters, c->iters, A * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     if (h->sel) {
         int Ko = 0, Kn = 0;
-        clamp_rows(&c->p, h, &Ko, &Kn);
+        clamp_rows(c, &d, &Ko, &Kn);
         const int Kt = Ko + Kn;
         if (Kt > 0) HIPCHK(hipMemcpyAsync(h->sel, c->sel, A * Kt * sizeof(int), hipMemcpyDeviceToHost, s));
     }
@@ -321,6 +330,143 @@ extern "C" int srb12_last_kernel_ms(srb12_ctx *c, float *select_ms, float *solve
     if (select_ms) *select_ms = a;
     if (solve_ms) *solve_ms = b;
     return SRB_OK;
+}
+
+// ---- scenes: the partition lives in the selection context, whose kernels and checks serve both modes
+extern "C" int srb12_ctx_set_scenes(srb12_ctx *c, int scene_agents, int scene_obs)
+{
+    if (!c) return srb_internal_fail(SRB_ERR_ARG, "null ctx");
+    return srb_ctx_set_scenes(c->sel_ctx, scene_agents, scene_obs);
+}
+
+extern "C" int srb12_ctx_scenes(srb12_ctx *c, int *scene_agents, int *scene_obs)
+{
+    if (!c) return srb_internal_fail(SRB_ERR_ARG, "null ctx");
+    return srb_ctx_scenes(c->sel_ctx, scene_agents, scene_obs);
+}
+
+// ---- closed-loop rollout (srb12_sim.hip): the argument checks that need no context come first, in a fixed order
+// (struct_size, c_first, goal, x), as check_sim of srb_capi.cpp
+static int check_sim12(const srb12_sim *d, int cycle, bool advance)
+{
+    if (d && d->struct_size != (int)sizeof(srb12_sim))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.struct_size != sizeof(srb12_sim): caller built against another ABI");
+    if (!d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
+    if (cycle < d->c_first) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim: cycle precedes c_first");
+    if (!advance) return SRB_OK;
+    if (!d->goal) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.goal missing");
+    if (!d->x && cycle != d->c_first)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.x missing (the previous solve's x: required when cycle != c_first)");
+    return SRB_OK;
+}
+
+static int launch_advance12(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, hipStream_t s)
+{
+    const srb12_params *p = &c->p;
+    if (p->N < 4) return srb_internal_fail(SRB_ERR_ARG, "the rollout needs N >= 4 (one cycle is one gait domain of 4 grids)");
+    if (!d->state || !d->x0 || !d->xref || !d->foot || !d->contact || !d->last_state || !d->com)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_sim: missing buffer (state, x0, xref, foot, contact, last_state, com)");
+    if (d->gait != 0 && d->gait != 1) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.gait: 0 trot, 1 stand");
+    const int threads = n_agents * p->N;                  // one per (agent, grid): at most max_agents * 24
+    hipLaunchKernelGGL(srb12_sim_advance_kernel, dim3((threads + 255) / 256), dim3(256), 0, s, n_agents, p->N, p->Ts,
+                       d->vref, d->hcom, d->yaw_step, d->hold_radius, d->gait, cycle, d->c_first, d->state, d->goal,
+                       d->phase, d->x, d->status, d->iters, d->x0, d->xref, d->foot, d->contact, d->last_state, d->com,
+                       d->traj, d->status_log, d->iters_log, d->x_log);
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+// the metrics of the LIP rollout (srb_sim_metrics_kernel, with scenes srb_sim_scene_metrics_kernel) on the com rows
+static int launch_metrics12(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, hipStream_t s)
+{
+    if (!d->com) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim: missing buffer (com)");
+    if (d->n_obs < 0 || d->n_all < 0 || (d->n_obs > 0 && !d->obstacles) || (d->n_all > 0 && !d->nbr_state))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_sim: obstacles / nbr_state missing for n_obs / n_all rows");
+    srb_sim m;
+    std::memset(&m, 0, sizeof m);
+    m.struct_size = (int)sizeof m;
+    m.state = d->com; m.c_first = d->c_first;
+    m.obstacles = d->obstacles; m.nbr_state = d->nbr_state;
+    m.n_obs = d->n_obs; m.n_all = d->n_all; m.agent_offset = d->agent_offset;
+    m.d_obs = d->d_obs; m.d_agent = d->d_agent; m.min_d_obs = d->min_d_obs; m.min_d_agent = d->min_d_agent;
+    m.fail_cycle = d->fail_cycle; m.distance_to_fail = d->distance_to_fail;
+    return srb_internal_sim_metrics(c->sel_ctx, n_agents, &m, cycle, s);
+}
+
+static int sim12_call(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream, bool advance)
+{
+    if (int rc = check_sim12(d, cycle, advance)) return rc;
+    if (!c) return srb_internal_fail(SRB_ERR_ARG, "null argument");
+    if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
+    if (n_agents == 0) return SRB_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->order.order_after_last(s);
+    if (!rc) rc = advance ? launch_advance12(c, n_agents, d, cycle, s) : launch_metrics12(c, n_agents, d, cycle, s);
+    if (!rc) rc = c->order.mark_done(s);
+    return rc;
+}
+
+extern "C" int srb12_sim_advance_device(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream)
+{
+    return sim12_call(c, n_agents, d, cycle, stream, true);
+}
+
+extern "C" int srb12_sim_metrics_device(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream)
+{
+    return sim12_call(c, n_agents, d, cycle, stream, false);
+}
+
+extern "C" int srb12_rollout_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, int cycles,
+                                    void *stream)
+{
+    if (b && b->struct_size != (int)sizeof(srb12_batch))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    // (the layout and null checks of check_sim12 only: the driver's first cycle is c_first itself)
+    if (int rc = check_sim12(d, d && d->struct_size == (int)sizeof(srb12_sim) ? d->c_first : 0, false)) return rc;
+    if (!b) return srb_internal_fail(SRB_ERR_ARG, "null argument");
+    if (!d->goal) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.goal missing");
+    if (!c) return srb_internal_fail(SRB_ERR_ARG, "null argument");
+    if (cycles < 0) return srb_internal_fail(SRB_ERR_ARG, "negative cycles");
+    if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
+    if (b->agent_offset != 0 || d->agent_offset != 0 || (b->n_all != 0 && b->n_all != n_agents) ||
+        (d->n_all != 0 && d->n_all != n_agents))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_rollout_device rolls out a whole team on one GPU: a sharded batch "
+                                              "(agent_offset != 0 or n_all != n_agents) needs the neighbour exchange "
+                                              "between advance and metrics");
+    int sa = 0, so = 0;
+    if (int rc = srb_ctx_scenes(c->sel_ctx, &sa, &so)) return rc;
+    if (sa > 0) {
+        if (n_agents % sa != 0)
+            return srb_internal_fail(SRB_ERR_ARG, ("scenes: srb12_rollout_device rolls out whole scenes, n_agents (" +
+                                                   std::to_string(n_agents) + ") is not a multiple of scene_agents (" +
+                                                   std::to_string(sa) + ")").c_str());
+        if (int rc = srb_internal_check_scenes(c->sel_ctx, n_agents, b->n_obs, true, n_agents, 0)) return rc;
+    }
+    if (n_agents == 0) return SRB_OK;
+    // the two structs wired together (include/srbnmpc.h): the solve reads what the advance wrote and back
+    srb12_sim sim = *d;
+    sim.x = b->x; sim.status = b->status; sim.iters = b->iters;
+    sim.obstacles = b->obstacles; sim.n_obs = b->n_obs;
+    sim.nbr_state = d->last_state; sim.n_all = n_agents; sim.agent_offset = 0;
+    srb12_batch bat = *b;
+    bat.x0 = d->x0; bat.xref = d->xref; bat.foot = d->foot; bat.contact = d->contact;
+    bat.nbr_state = d->last_state; bat.n_all = n_agents; bat.agent_offset = 0;
+    if (!b->x || !b->obj || !b->status || !b->iters)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_batch: missing buffer (x, obj, status, iters)");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->order.order_after_last(s);
+    if (rc) return rc;
+    for (int i = 0; i <= cycles && !rc; i++) {
+        const int cyc = d->c_first + i;
+        rc = launch_advance12(c, n_agents, &sim, cyc, s);
+        if (rc || i == cycles) break;
+        rc = launch_metrics12(c, n_agents, &sim, cyc, s);
+        if (!rc) rc = launch12(c, n_agents, &bat, s);
+    }
+    const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier cycles run
+    return rc ? rc : rc_mark;
 }
 
 // diagnostics (not in the public header): agent >= 0 records a per-iteration trace on the next

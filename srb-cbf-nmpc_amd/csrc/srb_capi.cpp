@@ -449,6 +449,16 @@ int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double
 
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s) { return c->order.mark_done(s); }
 
+int srb_internal_check_scenes(const srb_ctx *c, int n_agents, int n_obs, bool has_nbr, int n_all, int agent_offset)
+{
+    return check_scenes(c, n_agents, n_obs, has_nbr, n_all, agent_offset);
+}
+
+void srb_internal_clamp_K(const srb_ctx *c, int n_obs, bool has_nbr, int n_all, int *Ko, int *Kn)
+{
+    clamp_K(c, n_obs, has_nbr, n_all, Ko, Kn);
+}
+
 // The argument errors of the plan members (srb_batch.nbr_plan / plan), before anything is launched.  select: the
 // call would run the neighbour selection (the horizon-aware one then needs the table).
 static int check_plans(srb_ctx *c, int n_agents, const srb_batch *d, bool select)
@@ -785,6 +795,11 @@ static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
                        d->d_agent, d->min_d_obs, d->min_d_agent, d->fail_cycle, d->distance_to_fail);
     HIPCHK(hipGetLastError());
     return SRB_OK;
+}
+
+int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s)
+{
+    return launch_metrics(c, n_agents, d, cycle, s);
 }
 
 static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream, bool advance)

@@ -117,3 +117,12 @@ extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDe
 SRB12_INSTANCES(SRB_DECL12)
 #undef SRB_DECL12
 extern "C" __global__ void srb12_pos_kernel(int n_agents, const double *x0g, double *pos);
+
+// ---- srb12_sim.hip: one thread per (agent, grid), n_agents N threads
+extern "C" __global__ void srb12_sim_advance_kernel(int n_agents, int N, double Ts, double vref, double hcom,
+                                                    double yaw_step, double hold_radius, int gait, int c, int c_first,
+                                                    double *state, const double *goal, const int *phase,
+                                                    const double *x, const int *status, const int *iters, double *x0,
+                                                    double *xref, double *foot, int *contact, double *last_state,
+                                                    double *com, double *traj, int *status_log, int *iters_log,
+                                                    double *x_log);

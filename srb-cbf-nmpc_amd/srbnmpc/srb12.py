@@ -5,6 +5,10 @@ The reference declares this solver (FastMPC::runMPC / MPC_Cost / MPC_Constraints
 getLinearDynamics, /root/reference/include/fast_MPC.hpp:98-103) without a body, so there is no
 reference call surface to mirror: Solver12 follows BatchSolver's shape (host numpy solve, device
 torch solve on a stream).  Problem statement: DESIGN.md section 11; checker: oracle/srb12.c.
+
+Team features, as the LIP mode's: Solver12.set_scenes partitions a batch into independent teams
+(srb12_ctx_set_scenes; inputs from workload.make_scenes12), and Rollout12 is the closed-loop rollout on the
+device (csrc/srb12_sim.hip, srb12_rollout_device; DESIGN.md sections 9 and 10.4).
 """
 from __future__ import annotations
 
@@ -12,7 +16,7 @@ import ctypes
 
 import numpy as np
 
-from . import _check, _dp, _ip, _p, lib
+from . import _check, _dp, _ip, _p, lib, workload
 
 _p12_fields = [("N", ctypes.c_int), ("K_obs", ctypes.c_int), ("K_nbr", ctypes.c_int),
                ("Ts", ctypes.c_double), ("mass", ctypes.c_double), ("Ib", ctypes.c_double * 9),
@@ -44,6 +48,25 @@ class Batch12(ctypes.Structure):
         super().__init__(ctypes.sizeof(Batch12), *args, **kw)
 
 
+class Sim12(ctypes.Structure):
+    """Mirror of srb12_sim (the closed-loop rollout of the SRB-12 mode; struct_size filled in)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("state", _dp), ("goal", _dp), ("phase", _ip),
+                ("vref", ctypes.c_double), ("hcom", ctypes.c_double), ("yaw_step", ctypes.c_double),
+                ("hold_radius", ctypes.c_double), ("gait", ctypes.c_int), ("c_first", ctypes.c_int),
+                ("x", _dp), ("status", _ip), ("iters", _ip),
+                ("x0", _dp), ("xref", _dp), ("foot", _dp), ("contact", _ip), ("last_state", _dp), ("com", _dp),
+                ("traj", _dp), ("status_log", _ip), ("iters_log", _ip), ("x_log", _dp),
+                ("obstacles", _dp), ("nbr_state", _dp),
+                ("n_obs", ctypes.c_int), ("n_all", ctypes.c_int), ("agent_offset", ctypes.c_int),
+                ("d_obs", _dp), ("d_agent", _dp), ("min_d_obs", _dp), ("min_d_agent", _dp), ("fail_cycle", _ip),
+                ("distance_to_fail", _dp)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(ctypes.sizeof(Sim12), *args, **kw)
+
+
+GAITS = {"trot": 0, "stand": 1}       # srb12_sim.gait
+
 _bound = False
 
 
@@ -60,6 +83,12 @@ def _lib():
         L.srb12_solve_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12), ctypes.c_void_p]
         L.srb12_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.srb12_ctx_set_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.srb12_ctx_set_scenes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+        L.srb12_ctx_scenes.argtypes = [ctypes.c_void_p, _ip, _ip]
+        for f in ("srb12_sim_advance_device", "srb12_sim_metrics_device"):
+            getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Sim12), ctypes.c_int, ctypes.c_void_p]
+        L.srb12_rollout_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12), ctypes.POINTER(Sim12),
+                                           ctypes.c_int, ctypes.c_void_p]
         _bound = True
     return L
 
@@ -76,10 +105,14 @@ def lds_bytes(p: Params12) -> int:
     return _lib().srb12_lds_bytes(ctypes.byref(p))
 
 
-def n_selected(p: Params12, n_obs: int, n_all: int):
-    """(Ko, Kn) rows selected per agent for tables of these sizes (clamped as the C ABI does)."""
-    Ko = min(p.K_obs, max(n_obs, 0)) if p.use_nlp else 0
-    Kn = min(p.K_nbr, max(n_all - 1, 0)) if p.use_nlp else 0
+def n_selected(p: Params12, n_obs: int, n_all: int, scenes=(0, 0)):
+    """(Ko, Kn) rows selected per agent for tables of these sizes (clamped as the C ABI does; with a scene
+    partition (scene_agents, scene_obs) to the agent's scene)."""
+    rows, others = max(n_obs, 0), max(n_all - 1, 0)
+    if scenes[0] > 0:
+        rows, others = min(rows, scenes[1]), (scenes[0] - 1 if n_all > 0 else 0)
+    Ko = min(p.K_obs, rows) if p.use_nlp else 0
+    Kn = min(p.K_nbr, others) if p.use_nlp else 0
     return Ko, Kn
 
 
@@ -93,6 +126,28 @@ class Solver12:
         h = ctypes.c_void_p()
         _check(_lib().srb12_ctx_create(ctypes.byref(params), self.max_agents, self.device, ctypes.byref(h)))
         self._h = h
+        self._scenes = (0, 0)
+
+    def _stream(self, stream):
+        """hipStream_t for a launch: the caller's, else torch's current stream on this device."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        return ctypes.c_void_p(stream)
+
+    def set_scenes(self, scene_agents: int = 0, scene_obs: int = 0):
+        """The batch as independent teams (srb12_ctx_set_scenes): scene_agents agents and scene_obs obstacle rows
+        per scene, tables flat and scene-major; agent g selects and is measured within scene g // scene_agents,
+        sel holds global rows.  (0, 0): off, one team."""
+        _check(_lib().srb12_ctx_set_scenes(self._h, int(scene_agents), int(scene_obs)))
+        a, o = ctypes.c_int(), ctypes.c_int()
+        _check(_lib().srb12_ctx_scenes(self._h, ctypes.byref(a), ctypes.byref(o)))
+        self._scenes = (a.value, o.value)
+
+    @property
+    def scenes(self):
+        """(scene_agents, scene_obs) as last set through set_scenes; (0, 0) when off."""
+        return self._scenes
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -114,7 +169,7 @@ class Solver12:
         contact = np.ascontiguousarray(contact, np.int32)
         ob = np.ascontiguousarray(obstacles if obstacles is not None else np.zeros((0, 2)), np.float64)
         nb = np.ascontiguousarray(nbr_state, np.float64) if nbr_state is not None else None
-        Ko, Kn = n_selected(p, ob.shape[0], nb.shape[0] if nb is not None else 0)
+        Ko, Kn = n_selected(p, ob.shape[0], nb.shape[0] if nb is not None else 0, self._scenes)
         out = dict(x_qp=np.zeros((A, p.nv)), x=np.zeros((A, p.nv)), obj=np.zeros(A),
                    status=np.zeros((A, 2), np.int32), iters=np.zeros((A, 2), np.int32),
                    sel=np.full((A, Ko + Kn), -2, np.int32))
@@ -137,20 +192,18 @@ class Solver12:
         A = x0.shape[0]
         import torch
         Ko, Kn = n_selected(self.params, 0 if obstacles is None else obstacles.shape[0],
-                            0 if nbr_state is None else nbr_state.shape[0])
+                            0 if nbr_state is None else nbr_state.shape[0], self._scenes)
         sel = out.get("sel")
         # the kernel writes rows of stride Ko + Kn (clamped to the tables, 0 without the NLP stage):
         # anything else would be overrun or read misaligned (BatchSolver.solve_device, same check)
         if sel is not None and (sel.dtype != torch.int32 or tuple(sel.shape) != (A, Ko + Kn) or not sel.is_contiguous()):
             raise ValueError(f"out['sel'] must be a contiguous int32 tensor of shape ({A}, {Ko + Kn}) "
                              f"(n_selected(params, n_obs, n_all)), got {tuple(sel.shape)} {sel.dtype}")
-        if stream is None:
-            stream = torch.cuda.current_stream(self.device).cuda_stream
         b = Batch12(dptr(x0), dptr(xref), dptr(foot), iptr(contact), dptr(obstacles), dptr(nbr_state),
                     0 if obstacles is None else obstacles.shape[0], 0 if nbr_state is None else nbr_state.shape[0],
                     int(agent_offset), dptr(out.get("x_qp")), dptr(out["x"]), dptr(out["obj"]), iptr(out["status"]),
                     iptr(out["iters"]), iptr(out.get("sel")), int(obstacles_version))
-        _check(_lib().srb12_solve_batch_device(self._h, A, ctypes.byref(b), ctypes.c_void_p(stream)))
+        _check(_lib().srb12_solve_batch_device(self._h, A, ctypes.byref(b), self._stream(stream)))
 
     def last_kernel_ms(self):
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -167,3 +220,194 @@ def split(p: Params12, x):
     N = p.N
     return (x[..., :12 * N].reshape(x.shape[:-1] + (N, 12)), x[..., 12 * N:24 * N].reshape(x.shape[:-1] + (N, 4, 3)),
             x[..., 24 * N])
+
+
+class Rollout12:
+    """The closed loop of `solver` (a Solver12 with N >= 4) for the agents whose goals are `goal` [A][2]
+    (srb12_sim_advance_device / srb12_sim_metrics_device / srb12_rollout_device): srbnmpc.Rollout for the 12-state
+    body, with the nominal plant, the goal-directed reference of workload.make_batch12 re-centred every cycle and
+    the team's safety log.
+
+        r = Rollout12(solver, goal, obstacles=obstacles)
+        r.reset(state)              # [A][12] p, roll/pitch/yaw, v, omega
+        r.run(50)                   # the C driver: no host round trip inside
+        out = r.results()           # traj, status, iters, min_d_agent, min_d_obs, fail_cycle, ...
+
+    vref        reference speed of the goal-directed line (workload.VREF)
+    phase       [A] int32 or None: added to the cycle index for the trot parity
+    gait        "trot" (one diagonal per gait domain) or "stand" (all four legs)
+    log_x       True: keep every cycle's decision vectors (results()["x"], [T][A][24N+1])
+    obstacles   [n_obs][2] or None: the static obstacles, for the solve and for d_obs / fail_cycle; with the
+                solver's scene partition on (Solver12.set_scenes, inputs from workload.make_scenes12) the
+                scene-major table [n_scenes * n_obs][2]
+    hcom        reference CoM height
+    yaw_step, hold_radius   the yaw reference turns towards the goal's bearing by at most yaw_step a cycle and
+                keeps the yaw within hold_radius of the goal
+    A whole team on one GPU (the SRB-12 mode has no sharded stepping and no neighbour plans).  All tensors are
+    float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
+
+    def __init__(self, solver, goal, vref: float = 0.27, phase=None, gait: str = "trot", log_x: bool = False,
+                 obstacles=None, hcom: float = workload.HCOM12, yaw_step: float = 0.1, hold_radius: float = 0.05):
+        import torch
+        from .rollout import _check_tensor
+        self.solver = solver
+        p = solver.params
+        if p.N < 4:
+            raise ValueError("Rollout12 needs N >= 4 (one cycle is one gait domain of 4 grids)")
+        if gait not in GAITS:
+            raise ValueError(f"gait must be one of {sorted(GAITS)}, got {gait!r}")
+        self.device = torch.device("cuda", solver.device)
+        if not hasattr(goal, "shape") or len(goal.shape) != 2:
+            raise ValueError("goal must be a [A][2] tensor")
+        A = self.A = int(goal.shape[0])
+        if A < 1 or A > solver.max_agents:
+            raise ValueError(f"goal holds {A} agents, the solver takes 1 .. {solver.max_agents}")
+        _check_tensor(goal, (A, 2), "goal", torch.float64, self.device)
+        if phase is not None:
+            _check_tensor(phase, (A,), "phase", torch.int32, self.device)
+        if obstacles is not None:
+            _check_tensor(obstacles, (obstacles.shape[0], 2), "obstacles", torch.float64, self.device)
+            if obstacles.shape[0] == 0:
+                obstacles = None
+        self.goal, self.phase, self.obstacles = goal, phase, obstacles
+        self.vref, self.gait, self.log_x = float(vref), gait, bool(log_x)
+        self.hcom = float(hcom)
+        self.yaw_step, self.hold_radius = float(yaw_step), float(hold_radius)
+        N, nv = p.N, p.nv
+        f8 = dict(dtype=torch.float64, device=self.device)
+        i4 = dict(dtype=torch.int32, device=self.device)
+        self.state, self.x0 = torch.zeros((A, 12), **f8), torch.zeros((A, 12), **f8)
+        self.last_state, self.com = torch.zeros((A, 4), **f8), torch.zeros((A, 4), **f8)
+        self.xref = torch.zeros((A, N, 12), **f8)
+        self.foot = torch.zeros((A, N, 4, 3), **f8)
+        self.contact = torch.zeros((A, N, 4), **i4)
+        self.out = dict(x=torch.zeros((A, nv), **f8), obj=torch.zeros(A, **f8), status=torch.zeros((A, 2), **i4),
+                        iters=torch.zeros((A, 2), **i4))
+        self.metrics = dict(d_obs=torch.zeros(A, **f8), d_agent=torch.zeros(A, **f8), min_d_obs=torch.zeros(A, **f8),
+                            min_d_agent=torch.zeros(A, **f8), fail_cycle=torch.full((A,), -1, **i4),
+                            distance_to_fail=torch.zeros(A, **f8))
+        self.cap = 0
+        self.traj = self.status_log = self.iters_log = self.x_log = None
+        self.c = 0
+        self.flushed = True
+        self._ready = False
+
+    # ------------------------------------------------------------------ buffers
+    def _reserve(self, cycles: int):
+        """Log rows for `cycles` cycles (traj one more); grown by copying, so earlier rows stay."""
+        import torch
+        if cycles <= self.cap:
+            return
+        cap = max(cycles, 2 * self.cap, 8)
+        A, nv = self.A, self.solver.params.nv
+
+        def grow(old, rows, tail, dtype):
+            new = torch.zeros((rows,) + tail, dtype=dtype, device=self.device)
+            if old is not None:
+                new[:old.shape[0]] = old
+            return new
+        self.traj = grow(self.traj, cap + 1, (A, 12), torch.float64)
+        self.status_log = grow(self.status_log, cap, (A, 2), torch.int32)
+        self.iters_log = grow(self.iters_log, cap, (A, 2), torch.int32)
+        if self.log_x:
+            self.x_log = grow(self.x_log, cap, (A, nv), torch.float64)
+        self.cap = cap
+
+    def _sim(self) -> Sim12:
+        from .rollout import _dptr, _iptr
+        m, o = self.metrics, self.out
+        return Sim12(_dptr(self.state), _dptr(self.goal), _iptr(self.phase), self.vref, self.hcom, self.yaw_step,
+                     self.hold_radius, GAITS[self.gait], 0, _dptr(o["x"]), _iptr(o["status"]), _iptr(o["iters"]),
+                     _dptr(self.x0), _dptr(self.xref), _dptr(self.foot), _iptr(self.contact), _dptr(self.last_state),
+                     _dptr(self.com), _dptr(self.traj), _iptr(self.status_log), _iptr(self.iters_log),
+                     _dptr(self.x_log), _dptr(self.obstacles), _dptr(self.last_state),
+                     0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
+                     _dptr(m["d_obs"]), _dptr(m["d_agent"]), _dptr(m["min_d_obs"]), _dptr(m["min_d_agent"]),
+                     _iptr(m["fail_cycle"]), _dptr(m["distance_to_fail"]))
+
+    # ------------------------------------------------------------------ driving
+    def reset(self, state):
+        """Start state [A][12] (p, roll/pitch/yaw, v, omega); the cycle count and the logs start over."""
+        import torch
+        from .rollout import _check_tensor
+        _check_tensor(state, (self.A, 12), "state", torch.float64, self.device)
+        self.state.copy_(state)
+        self.c = 0
+        self.flushed = True
+        self._ready = True
+
+    def advance(self, stream=None):
+        """The advance of the current cycle alone: state, x0, xref, foot, contact, last_state, com (and the previous
+        cycle's logs).  step() runs it itself; calling it first as well rewrites the same values."""
+        if not self._ready:
+            raise RuntimeError("Rollout12.advance before reset(state)")
+        s = self.solver
+        self._reserve(self.c + 1)
+        _check(_lib().srb12_sim_advance_device(s._h, self.A, ctypes.byref(self._sim()), self.c, s._stream(stream)))
+
+    def step(self, stream=None):
+        """One cycle: advance, metrics, solve."""
+        if not self._ready:
+            raise RuntimeError("Rollout12.step before reset(state)")
+        s = self.solver
+        self._reserve(self.c + 1)
+        self.advance(stream)
+        _check(_lib().srb12_sim_metrics_device(s._h, self.A, ctypes.byref(self._sim()), self.c, s._stream(stream)))
+        s.solve_device(self.x0, self.xref, self.foot, self.contact, self.obstacles, self.last_state, self.out,
+                       stream=stream)
+        self.c += 1
+        self.flushed = False
+
+    def run(self, T: int, stream=None):
+        """T cycles by the C driver (srb12_rollout_device), right after reset(): one call, nothing synchronises
+        with the host inside."""
+        from .rollout import _dptr, _iptr
+        T = int(T)
+        if not self._ready or self.c != 0:
+            raise RuntimeError("Rollout12.run starts from reset(state) (use step() to go on)")
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        sa = self.solver.scenes[0]
+        if sa > 0 and self.A % sa != 0:
+            raise ValueError(f"run() rolls out whole scenes: {self.A} agents are not a multiple of scene_agents = {sa}")
+        s, o = self.solver, self.out
+        self._reserve(T)
+        b = Batch12(None, None, None, None, _dptr(self.obstacles), None,
+                    0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
+                    None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]), None, 0)
+        _check(_lib().srb12_rollout_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), T, s._stream(stream)))
+        self.c = T
+        self.flushed = True
+
+    def results(self, stream=None):
+        """The logs and metrics so far, as tensors (views of this object's buffers; asynchronous like the
+        launches -- synchronise before reading on the host): traj [T+1][A][12], status / iters [T][A][2],
+        x [T][A][24N+1] (log_x), state [A][12] (the end state), cycles, and d_obs, d_agent, min_d_obs,
+        min_d_agent, fail_cycle, distance_to_fail [A]."""
+        if not self._ready:
+            raise RuntimeError("Rollout12.results before reset(state)")
+        T = self.c
+        self._reserve(max(T, 1))
+        if not self.flushed:
+            self.advance(stream)                 # the final advance: the last logs and the end state
+            self.flushed = True
+        elif T == 0:
+            self.advance(stream)
+        out = dict(cycles=T, traj=self.traj[:T + 1], status=self.status_log[:T], iters=self.iters_log[:T],
+                   state=self.state, **self.metrics)
+        if self.log_x:
+            out["x"] = self.x_log[:T]
+        return out
+
+    def scene_results(self, stream=None):
+        """results() reduced per scene of the solver's partition (Solver12.set_scenes; a whole number of scenes):
+        rollout.reduce_scenes -- min_d_agent, min_d_obs, n_failed, n_not_converged [n_scenes], scene_agents and
+        n_scenes.  Asynchronous like results()."""
+        from .rollout import reduce_scenes
+        sa = self.solver.scenes[0]
+        if sa <= 0:
+            raise ValueError("scene_results needs the solver's scene partition (Solver12.set_scenes)")
+        if self.A % sa != 0:
+            raise ValueError(f"scene_results reduces whole scenes: {self.A} agents are not a whole number of scenes "
+                             f"of {sa}")
+        return reduce_scenes(self.results(stream), sa)

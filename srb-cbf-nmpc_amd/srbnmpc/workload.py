@@ -196,3 +196,73 @@ def make_batch12(n_agents: int, N: int = 10, gait: str = "trot", seed: int = 0, 
     obstacles = make_obstacles(rng, n_obs, sc)
     nbr_state = np.stack([x0[:, 0], x0[:, 1], x0[:, 6], x0[:, 7]], 1)
     return dict(x0=x0, xref=xref, foot=foot, contact=contact, obstacles=obstacles, nbr_state=nbr_state)
+
+
+def make_scenes12(n_scenes: int, team: int, N: int = 10, gait: str = "trot", seed: int = 0, n_obs: int = 20,
+                  clearance: float = 0.5):
+    """make_scenes lifted to the SRB-12 mode as make_batch12 lifts make_batch: n_scenes independent teams of `team`
+    agents for Solver12.set_scenes(team, n_obs), scene-major: dict(x0 [S*team,12], xref [S*team,N,12],
+    foot [S*team,N,4,3], contact [S*team,N,4] int32, obstacles [S*n_obs,2], nbr_state [S*team,4], goal [S*team,2],
+    phase [S*team] int32).  Every scene is its own draw of the arena at arena_scale(team) from a generator seeded
+    by (seed, scene index) alone, so scene s is the same whatever n_scenes is; starts keep `clearance` from the
+    scene's obstacles and earlier starts by make_scenes' rejection rule (SCENE_MAX_ATTEMPTS draws a scene)."""
+    S, A = int(n_scenes), int(team)
+    if S < 1 or A < 1 or n_obs < 0:
+        raise ValueError("make_scenes12: n_scenes >= 1, team >= 1, n_obs >= 0")
+    sc = arena_scale(A)
+    goal1 = GOAL * np.array([sc, 1.0])
+    k = np.arange(1, N + 1)
+    out = dict(x0=np.zeros((S * A, 12)), xref=np.zeros((S * A, N, 12)), foot=np.zeros((S * A, N, 4, 3)),
+               contact=np.zeros((S * A, N, 4), np.int32), obstacles=np.zeros((S * n_obs, 2)),
+               nbr_state=np.zeros((S * A, 4)), goal=np.tile(goal1, (S * A, 1)), phase=np.zeros(S * A, np.int32))
+    for s in range(S):
+        rng = np.random.default_rng([int(seed), s])
+        obstacles = make_obstacles(rng, n_obs, sc)
+        p0 = np.zeros((A, 2))
+        attempts = 0
+        for a in range(A):
+            while True:
+                if attempts >= SCENE_MAX_ATTEMPTS:
+                    raise ValueError(f"make_scenes12: scene {s}: no start {clearance} m clear of the scene's {n_obs} "
+                                     f"obstacles and {a} earlier starts after {attempts} draws")
+                attempts += 1
+                q = np.array([rng.uniform(0, 9.0 * sc), rng.uniform(-2.0 * sc, 2.0 * sc)])
+                taken = np.concatenate([obstacles, p0[:a]])
+                if not taken.size or np.sqrt(((taken - q) ** 2).sum(1)).min() >= clearance:
+                    break
+            p0[a] = q
+        d = goal1 - p0
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        head = np.arctan2(d[:, 1], d[:, 0])
+        v0 = d * rng.uniform(0, 0.3, (A, 1)) + rng.uniform(-0.05, 0.05, (A, 2))
+        r = slice(s * A, (s + 1) * A)
+        x0 = out["x0"][r]
+        x0[:, 0:2] = p0
+        x0[:, 2] = HCOM12 + rng.uniform(-0.01, 0.01, A)
+        x0[:, 3:5] = rng.uniform(-0.02, 0.02, (A, 2))
+        x0[:, 5] = head + rng.uniform(-0.1, 0.1, A)
+        x0[:, 6:8] = v0
+        x0[:, 9:12] = rng.uniform(-0.05, 0.05, (A, 3))
+        xref = out["xref"][r]
+        xref[:, :, 0] = p0[:, None, 0] + d[:, None, 0] * VREF * TS * k
+        xref[:, :, 1] = p0[:, None, 1] + d[:, None, 1] * VREF * TS * k
+        xref[:, :, 2] = HCOM12
+        xref[:, :, 5] = head[:, None]
+        xref[:, :, 6] = d[:, None, 0] * VREF
+        xref[:, :, 7] = d[:, None, 1] * VREF
+        phase = rng.integers(0, 4, A)
+        cs, sn = np.cos(head), np.sin(head)
+        for a in range(A):                                      # the trot schedule of make_batch12
+            Rm = np.array([[cs[a], -sn[a]], [sn[a], cs[a]]])
+            off = (Rm @ STANCE).T
+            for kk in range(N):
+                dom = (kk + phase[a]) // 4
+                k_start = max(4 * dom - phase[a], 0)
+                centre = p0[a] + d[a] * VREF * TS * k_start
+                out["foot"][s * A + a, kk, :, :2] = centre[None, :] + off
+                legs = TROT_PAIRS[dom % 2] if gait == "trot" else [0, 1, 2, 3]
+                out["contact"][s * A + a, kk, legs] = 1
+        out["obstacles"][s * n_obs:(s + 1) * n_obs] = obstacles
+        out["nbr_state"][r] = np.stack([x0[:, 0], x0[:, 1], x0[:, 6], x0[:, 7]], 1)
+        out["phase"][r] = phase
+    return out

@@ -1,0 +1,183 @@
+"""Closed-loop rollout of the SRB-12 mode at the shape of bench.py --path srb12 (1024 agents, N = 10, trot, 3 static
++ 8 neighbour rows, workload.make_batch12 seed 1234) on one GPU: cycles per second of the C driver
+(Rollout12.run(T): advance, metrics and solve enqueued from one call), of T x Rollout12.step() from Python, of the
+plain solve_device loop that re-solves the same inputs (no advance, no metrics, no state carried), and of a
+scene-batched rollout (128 scenes x 8 agents x 20 obstacles, workload.make_scenes12); the advance and metrics
+kernels alone, next to the LIP mode's advance at the same agent count; and the separation the team keeps.
+
+Method (as tools/bench_rollout.py): every mode is warmed up, then the modes are timed in interleaved rounds -- one
+window of T cycles per mode per round, host clock around work that ends in a device synchronise, the library's
+timing events off -- and the median over the rounds is reported with each mode's spread (min, max).  Every window of
+a rollout mode starts from the same reset state and runs the same T cycles.  The kernels alone are timed the same
+way, a window being T back-to-back calls at cycle 1 (the later-cycle path, with the logs).
+
+    python tools/bench_rollout12.py [--cycles 20] [--rounds 7] [--out profiles/bench_rollout12.json]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "srb-cbf-nmpc_amd")]
+import srbnmpc  # noqa: E402
+from srbnmpc import srb12, workload  # noqa: E402
+
+EDGES = [0.0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.75, 1.0, 1.5, 2.0, 3.0, 5.0, 1e9]
+
+
+def hist(v):
+    v = np.asarray(v)
+    return {"edges_m": EDGES[:-1] + ["inf"], "counts": [int(c) for c in np.histogram(v, EDGES)[0]],
+            "min": float(v.min()), "median": float(np.median(v)), "max": float(v.max())}
+
+
+def safety_of(r):
+    st = r["status"].cpu().numpy()
+    fc = r["fail_cycle"].cpu().numpy()
+    z = r["traj"][:, :, 2].cpu().numpy()
+    return {"min_d_agent": hist(r["min_d_agent"].cpu().numpy()), "min_d_obs": hist(r["min_d_obs"].cpu().numpy()),
+            "agents_inside_0.5m_of_an_obstacle": {"at_cycle_0": int((fc == 0).sum()), "later": int((fc > 0).sum()),
+                                                  "never": int((fc < 0).sum())},
+            "height_m": {"min": float(z.min()), "max": float(z.max())},
+            "non_optimal_frac_per_cycle": [float(1.0 - (np.isin(s[:, 0], (0, 4)) & (s[:, 1] == 0)).mean()) for s in st]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--cycles", type=int, default=20, help="T: cycles per window")
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=1, help="untimed windows per mode")
+    ap.add_argument("--agents", type=int, default=1024)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_rollout12.py needs a GPU (no CPU fallback)")
+    dev = torch.device("cuda", 0)
+    A, N, Ko, Kn, T = args.agents, 10, 3, 8, args.cycles
+    team, scene_obs = 8, 20
+    S = A // team
+    D = lambda v, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(v), dtype=dt, device=dev)
+
+    b = workload.make_batch12(A, N, "trot", seed=1234)
+    t = {k: D(v, torch.int32 if k == "contact" else torch.float64) for k, v in b.items()}
+    goal = D(np.tile(workload.GOAL * np.array([workload.arena_scale(A), 1.0]), (A, 1)))
+    p = srb12.default_params(N, K_obs=Ko, K_nbr=Kn)
+    solver = srb12.Solver12(p, A, 0)
+    solver.set_timing(False)
+    roll = srb12.Rollout12(solver, goal, vref=workload.VREF, obstacles=t["obstacles"])
+    plain_out = dict(x_qp=None, x=torch.zeros((A, p.nv), dtype=torch.float64, device=dev),
+                     obj=torch.zeros(A, dtype=torch.float64, device=dev),
+                     status=torch.zeros((A, 2), dtype=torch.int32, device=dev),
+                     iters=torch.zeros((A, 2), dtype=torch.int32, device=dev))
+
+    # the scene-batched team of the same size on a context of its own (the partition is a context setting)
+    sb = workload.make_scenes12(S, team, N, "trot", seed=1234, n_obs=scene_obs)
+    ssolver = srb12.Solver12(p, S * team, 0)
+    ssolver.set_timing(False)
+    ssolver.set_scenes(team, scene_obs)
+    sroll = srb12.Rollout12(ssolver, D(sb["goal"]), vref=workload.VREF, phase=D(sb["phase"], torch.int32),
+                            obstacles=D(sb["obstacles"]))
+    sx0 = D(sb["x0"])
+
+    # the LIP advance at the same agent count (the yardstick of the advance kernel: DESIGN.md 10.2)
+    lb = workload.make_batch(A, N, 2, seed=1234)
+    lsolver = srbnmpc.BatchSolver(srbnmpc.default_params(N, 2, K_obs=Ko, K_nbr=Kn), A, 0)
+    lsolver.set_option("timing", 0)
+    lroll = srbnmpc.Rollout(lsolver, goal, vref=workload.VREF, obstacles=t["obstacles"])
+    lroll.reset(D(lb["x0"]))
+    lroll.step()
+    roll.reset(t["x0"])
+    roll.step()
+    lib, lib12 = srbnmpc.lib(), srb12._lib()
+
+    def run():
+        roll.reset(t["x0"])
+        roll.run(T)
+
+    def steps():
+        roll.reset(t["x0"])
+        for _ in range(T):
+            roll.step()
+
+    def plain():
+        for _ in range(T):
+            solver.solve_device(t["x0"], t["xref"], t["foot"], t["contact"], t["obstacles"], t["nbr_state"], plain_out)
+
+    def scenes():
+        sroll.reset(sx0)
+        sroll.run(T)
+
+    def advance12():                     # cycle 1 of the rollout left by the last rollout window: logs included
+        sim, st = roll._sim(), solver._stream(None)
+        for _ in range(T):
+            lib12.srb12_sim_advance_device(solver._h, A, ctypes.byref(sim), 1, st)
+
+    def metrics12():
+        sim, st = roll._sim(), solver._stream(None)
+        for _ in range(T):
+            lib12.srb12_sim_metrics_device(solver._h, A, ctypes.byref(sim), 1, st)
+
+    def advance_lip():
+        sim, st = lroll._sim(), lsolver._stream(None)
+        for _ in range(T):
+            lib.srb_sim_advance_device(lsolver._h, A, ctypes.byref(sim), 1, st)
+
+    modes = [("run", run), ("step", steps), ("plain_solve_loop", plain), ("scenes_run", scenes),
+             ("advance12_kernel", advance12), ("metrics12_kernel", metrics12), ("advance_lip_kernel", advance_lip)]
+    for _ in range(args.warmup):
+        for _, f in modes:
+            f()
+    torch.cuda.synchronize(dev)
+    sec = {name: [] for name, _ in modes}
+    for _ in range(args.rounds):
+        for name, f in modes:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize(dev)
+            sec[name].append(time.perf_counter() - t0)
+
+    # untimed: the separation, the heights and the statuses over the rollout, one team and scene-batched
+    run()
+    r = roll.results()
+    torch.cuda.synchronize(dev)
+    safety = {"one_team": safety_of(r)}
+    scenes()
+    r = sroll.results()
+    sc = sroll.scene_results()
+    torch.cuda.synchronize(dev)
+    safety["scenes"] = safety_of(r)
+    safety["scenes"]["per_scene"] = {"min_d_agent": hist(sc["min_d_agent"].cpu().numpy()),
+                                     "min_d_obs": hist(sc["min_d_obs"].cpu().numpy()),
+                                     "scenes_with_a_failed_agent": int((sc["n_failed"] > 0).sum().item()),
+                                     "scenes_with_a_non_converged_solve": int((sc["n_not_converged"] > 0).sum().item())}
+
+    cps = {k: {"median": float(np.median(T / np.array(v))), "min": float(np.min(T / np.array(v))),
+               "max": float(np.max(T / np.array(v)))} for k, v in sec.items()}
+    ms = {k: {"median": 1e3 / v["median"], "min": 1e3 / v["max"], "max": 1e3 / v["min"]} for k, v in cps.items()}
+    res = {"tool": "tools/bench_rollout12.py", "agents": A, "horizon": N, "K_obs": Ko, "K_nbr": Kn,
+           "scenes": {"n_scenes": S, "scene_agents": team, "scene_obs": scene_obs},
+           "cycles_per_window": T, "rounds": args.rounds, "n_gpus": 1, "cycles_per_s": cps, "ms_per_cycle": ms,
+           "overhead_ms_over_plain": {"run": ms["run"]["median"] - ms["plain_solve_loop"]["median"],
+                                      "step": ms["step"]["median"] - ms["plain_solve_loop"]["median"]},
+           "note": "run: Rollout12.run(T), the C driver; step: T x Rollout12.step(); plain_solve_loop: T x solve_device on "
+                   "fixed inputs (no advance, metrics or carried state); scenes_run: Rollout12.run(T) of the scene-batched "
+                   "team; *_kernel: T back-to-back calls of one entry point at cycle 1 (ms_per_cycle = ms per call).  A "
+                   "rollout window includes its reset.",
+           "safety": safety}
+    print(json.dumps(res), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    for s in (solver, ssolver, lsolver):
+        s.close()
+
+
+if __name__ == "__main__":
+    main()
