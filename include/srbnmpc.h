@@ -588,8 +588,9 @@ int srb12_ctx_scenes(srb12_ctx *ctx, int *scene_agents, int *scene_obs);
  * n_all = A, agent_offset = 0; the advance reads batch's x, status, iters; the metrics read batch's obstacles /
  * n_obs and sim.last_state.  The members of either struct that this replaces are ignored; batch.n_all /
  * agent_offset must be A / 0 or both 0 (a shard cannot roll out alone: its neighbours move too).  With scenes,
- * A must be a whole number of scenes.  The solve has no nbr_plan input: the inter-agent rows use the
- * constant-velocity guess in every cycle.
+ * A must be a whole number of scenes.  This driver's solve has no nbr_plan input: the inter-agent rows use the
+ * constant-velocity guess in every cycle.  srb12_rollout_plans_device (below) is the driver that feeds last
+ * cycle's plans forward.
  */
 typedef struct srb12_sim {
     int struct_size;         /* sizeof(srb12_sim) (ABI check) */
@@ -616,6 +617,55 @@ int srb12_sim_advance_device(srb12_ctx *ctx, int n_agents, const srb12_sim *dev_
 int srb12_sim_metrics_device(srb12_ctx *ctx, int n_agents, const srb12_sim *dev_io, int cycle, void *stream);
 int srb12_rollout_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim, int cycles,
                          void *stream);
+
+/*
+ * Neighbour plans in the SRB-12 mode: srb_batch.nbr_plan / plan and SRB_OPT_PLAN_SELECTION for the 12-state body.
+ * The layouts of srb12_batch and srb12_sim stay; the plan pointers travel in a struct of their own through entry
+ * points of their own, which otherwise behave as srb12_solve_batch[_device] / srb12_rollout_device do.
+ *   nbr_plan  [n_all][N][2] in: row i, grid k is global agent i's predicted (x, y) at time (k+1) Ts from the
+ *                           snapshot.  The neighbour rows of the NLP stage read it in place of the constant-
+ *                           velocity guess p + v Ts (k+1); read only by the NLP stage and only for the neighbour
+ *                           columns of `sel` (a -1 column keeps the no-neighbour row x0 + 1000 m).  Row
+ *                           agent_offset + a is agent a's own previous plan: the horizon-aware selection reads
+ *                           it, the CBF rows never do.  Needs nbr_state (the selection's snapshot); with scenes
+ *                           the rows are scene-major like the snapshot.  NULL: constant velocity.
+ *   plan      [A][N][2]     out: (X[12k], X[12k+1]) of the returned x for every agent, whatever its status (FATAL,
+ *                           MAXIT and a rejected polish included); with use_nlp = 0 from the QP x.  Must not
+ *                           overlap nbr_plan or plan_table.  NULL: not written.
+ *   plan_selection          0: the neighbour columns are the rows nearest now (the snapshot selection);
+ *                           1: the rows of closest predicted approach over the horizon (srb_knn_plan_kernel, with
+ *                           scenes srb_knn_plan_scene_kernel on the agent's scene); needs nbr_plan.  The static
+ *                           columns are selected as ever.
+ *   plan_table [A][N][2]    srb12_rollout_plans_device only: the table of the next cycle (below).
+ * A srb12_plans whose pointers are all NULL and whose plan_selection is 0 gives the bits of
+ * srb12_solve_batch[_device].  SRB_ERR_ARG, before anything is launched: a wrong struct_size; nbr_plan without
+ * nbr_state; K_nbr > 0 with agent_offset + n_agents > n_all; plan_selection = 1 without nbr_plan; plan == nbr_plan
+ * or plan == plan_table.  host_plans holds host pointers, dev_plans device pointers.
+ *
+ * srb12_shift_plans_device(ctx, A, plan, grids, table, stream): last cycle's plans as this cycle's table, on the
+ * device (srb12_plan_shift_kernel): the new cycle starts `grids` grids later, so table[a][k] = plan[a][k + grids]
+ * for k < N - grids, and past the horizon last + m (last - previous), m = k + grids - N + 1.  grids >= 0, N >= 2;
+ * plan and table [A][N][2] must be different buffers.
+ *
+ * srb12_rollout_plans_device(ctx, A, batch, sim, plans, cycles, stream): srb12_rollout_device with the plans fed
+ * forward.  plans.plan and plans.plan_table are required.  The first solve reads plans.nbr_plan (NULL: constant
+ * velocity); after every solve the shift (grids = 4, one gait domain) writes plan_table from plan, and every later
+ * solve reads plan_table as its nbr_plan.  plan_selection applies to every cycle that has a table.  No host
+ * synchronisation; scenes are honoured; a sharded batch is refused as by srb12_rollout_device.
+ */
+typedef struct srb12_plans {
+    int struct_size;          /* sizeof(srb12_plans) (ABI check) */
+    const double *nbr_plan;   /* [n_all][N][2]: row i, grid k = global agent i's (x, y) at Ts (k+1); NULL = constant velocity */
+    double *plan;             /* [A][N][2] out: (X[12k], X[12k+1]) of the returned x; NULL = not written */
+    int plan_selection;       /* 0: neighbours nearest now (snapshot); 1: closest predicted approach over the horizon */
+    double *plan_table;       /* rollout only: [A][N][2] the table of the next cycle */
+} srb12_plans;
+int srb12_solve_batch_plans(srb12_ctx *ctx, int n_agents, const srb12_batch *host_io, const srb12_plans *host_plans);
+int srb12_solve_batch_plans_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_plans *dev_plans,
+                                   void *stream);
+int srb12_shift_plans_device(srb12_ctx *ctx, int n_agents, const double *plan, int grids, double *table, void *stream);
+int srb12_rollout_plans_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
+                               const srb12_plans *plans, int cycles, void *stream);
 
 const char *srb_last_error(void);
 

@@ -14,9 +14,11 @@
 #include "srb_host.h"
 
 #define SRB12_DBG_LEN (2 * 64 * 8 + 16 + 128)   // trace, stamp sums, state checks (srb12_kernels.hip)
+#define SRB12_SIM_NDOMAIN 4                     // grids a cycle (srb12_sim.hip): the shift of the plans between cycles
 
 typedef void (*srb12_fn)(Srb12KParams, int, const double *, const double *, const double *, const int *,
-                         const double *, const double *, const int *, double *, double *, double *, int *, int *);
+                         const double *, const double *, const int *, double *, double *, double *, int *, int *,
+                         const double *, double *);
 struct srb12_inst { int tl, to, nc, k1; srb12_fn fn; };
 #define ENTRY12(TL, TO, NC, K1) {TL, TO, NC, K1, srb12_kernel_##TL##_##TO##_##NC##_##K1},
 static const srb12_inst g_inst12[] = {SRB12_INSTANCES(ENTRY12)};
@@ -36,6 +38,8 @@ struct srb12_ctx {
     double *x0, *xref, *foot, *obstacles, *nbr, *x_qp, *x, *obj;
     int *contact, *status, *iters;
     size_t cap_obs, cap_nbr;
+    double *nbr_plan, *plan;       // staging of srb12_solve_batch_plans: the table [cap_plan bytes], the plans [max_agents][N][2]
+    size_t cap_plan;
     int dbg_agent;                 // diagnostics: srb12_debug_trace
     double *dbg;
 };
@@ -163,7 +167,7 @@ extern "C" int srb12_ctx_destroy(srb12_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->order.wait_idle();
     void *bufs[] = {c->dbg, c->pos, c->sel, c->x0, c->xref, c->foot, c->contact, c->obstacles, c->nbr, c->x_qp, c->x, c->obj,
-                    c->status, c->iters};
+                    c->status, c->iters, c->nbr_plan, c->plan};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (int i = 0; i < 3; i++)
@@ -192,7 +196,37 @@ static int check_scenes12(const srb12_ctx *c, int n_agents, const srb12_batch *d
     return srb_internal_check_scenes(c->sel_ctx, n_agents, d->n_obs, d->nbr_state != nullptr, d->n_all, d->agent_offset);
 }
 
-static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_t s)
+// The argument errors of srb12_plans that need no context, in a fixed order (struct_size first); `rollout`: the
+// driver's rules (plan and plan_table required, nbr_state is the rollout's own snapshot, and plan_selection waits
+// for the first cycle that has a table)
+static int check_plans12(const srb12_batch *b, const srb12_plans *pl, bool rollout)
+{
+    if (pl && pl->struct_size != (int)sizeof(srb12_plans))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_plans.struct_size != sizeof(srb12_plans): caller built against another ABI");
+    if (!b || !pl) return srb_internal_fail(SRB_ERR_ARG, "null argument");
+    if (pl->plan_selection != 0 && pl->plan_selection != 1)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_plans.plan_selection: 0 (snapshot) or 1 (closest predicted approach)");
+    if (rollout && (!pl->plan || !pl->plan_table))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_rollout_plans_device needs srb12_plans.plan and plan_table");
+    if (!rollout && pl->nbr_plan && !b->nbr_state)
+        return srb_internal_fail(SRB_ERR_ARG, "nbr_plan needs nbr_state (the selection's snapshot)");
+    if (!rollout && pl->plan_selection && !pl->nbr_plan)
+        return srb_internal_fail(SRB_ERR_ARG, "plan_selection = 1 needs nbr_plan (the horizon-aware selection reads the plan table)");
+    if (pl->plan && (const double *)pl->plan == pl->nbr_plan)
+        return srb_internal_fail(SRB_ERR_ARG, "plan overlaps the nbr_plan table (workgroups read the table while others write "
+                                              "their plans: use two buffers)");
+    if (pl->plan && pl->plan == pl->plan_table)
+        return srb_internal_fail(SRB_ERR_ARG, "plan overlaps plan_table (the shift reads one and writes the other: use two buffers)");
+    return SRB_OK;
+}
+
+static bool overlap12(const double *a, size_t na, const double *b, size_t nb)
+{
+    return a && b && a < b + nb && b < a + na;
+}
+
+// pl: the plan members of this launch (NULL: none, the launch of srb12_solve_batch[_device] as ever)
+static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_t s, const srb12_plans *pl = nullptr)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -203,9 +237,19 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         return srb_internal_fail(SRB_ERR_ARG, "obstacles missing");
     if (p->use_nlp && p->K_nbr > 0 && d->nbr_state && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return srb_internal_fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
+    if (pl && pl->nbr_plan && p->K_nbr > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
+        return srb_internal_fail(SRB_ERR_ARG, "nbr_plan: agent_offset + n_agents exceeds n_all (the plan table's rows)");
+    if (pl && pl->plan) {
+        const size_t rows = (size_t)n_agents * 2 * p->N;
+        if (overlap12(pl->plan, rows, pl->nbr_plan, (size_t)(d->n_all > 0 ? d->n_all : 0) * 2 * p->N) ||
+            overlap12(pl->plan, rows, pl->plan_table, rows))
+            return srb_internal_fail(SRB_ERR_ARG, "plan overlaps the nbr_plan table or plan_table (use two buffers)");
+    }
     if (int rc = check_scenes12(c, n_agents, d)) return rc;
     int Ko = 0, Kn = 0;
     clamp_rows(c, d, &Ko, &Kn);
+    // (the table is read by the NLP stage's neighbour rows only: without them it is never touched)
+    const double *nbr_plan = (pl && p->use_nlp && Kn > 0 && d->nbr_state) ? pl->nbr_plan : nullptr;
     Srb12KParams k = make_k12(p, Ko, Kn);
     k.dbg_agent = c->dbg_agent; k.dbg = c->dbg;
     const srb12_inst *in = pick12(p->N, Ko + Kn);
@@ -217,7 +261,8 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         hipLaunchKernelGGL(srb12_pos_kernel, dim3((n_agents + 255) / 256), dim3(256), 0, s, n_agents, d->x0, c->pos);
         HIPCHK(hipGetLastError());
         int rc = srb_internal_select(c->sel_ctx, n_agents, c->pos, d->obstacles, Ko > 0 ? d->n_obs : 0, d->nbr_state,
-                                     Kn > 0 ? d->n_all : 0, d->agent_offset, Ko, Kn, d->obstacles_version, sel, s);
+                                     Kn > 0 ? d->n_all : 0, d->agent_offset, Ko, Kn, d->obstacles_version, sel, s,
+                                     pl && pl->plan_selection ? nbr_plan : nullptr, p->N);
         if (rc) return rc;
         // the selection context's own ordering event: its grid buffers are reallocated only after
         // this launch (grid_reserve waits on it)
@@ -225,24 +270,38 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[1], s));
     hipLaunchKernelGGL(in->fn, dim3(n_agents), dim3(64), lds, s, k, n_agents, d->x0, d->xref, d->foot, d->contact,
-                       d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters);
+                       d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters, nbr_plan,
+                       pl ? pl->plan : nullptr);
     HIPCHK(hipGetLastError());
     if (c->timing) HIPCHK(hipEventRecord(c->ev[2], s));
     c->timed = c->timing != 0;
     return SRB_OK;
 }
 
-extern "C" int srb12_solve_batch_device(srb12_ctx *c, int n_agents, const srb12_batch *d, void *stream)
+static int solve_device12(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl, bool plans, void *stream)
 {
     if (d && d->struct_size != (int)sizeof(srb12_batch))
         return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    if (plans)
+        if (int rc = check_plans12(d, pl, false)) return rc;
     if (!c || !d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     int rc = c->order.order_after_last(s);
-    if (!rc) rc = launch12(c, n_agents, d, s);
+    if (!rc) rc = launch12(c, n_agents, d, s, pl);
     if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
+}
+
+extern "C" int srb12_solve_batch_device(srb12_ctx *c, int n_agents, const srb12_batch *d, void *stream)
+{
+    return solve_device12(c, n_agents, d, nullptr, false, stream);
+}
+
+extern "C" int srb12_solve_batch_plans_device(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl,
+                                              void *stream)
+{
+    return solve_device12(c, n_agents, d, pl, true, stream);
 }
 
 static int reserve(void **buf, size_t *cap, size_t bytes, srb12_ctx *c)
@@ -255,10 +314,13 @@ static int reserve(void **buf, size_t *cap, size_t bytes, srb12_ctx *c)
     return SRB_OK;
 }
 
-extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *h)
+// hp: the host plan members (NULL: srb12_solve_batch); the table and the plans are staged like the other buffers
+static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp, bool plans)
 {
     if (h && h->struct_size != (int)sizeof(srb12_batch))
         return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    if (plans)
+        if (int rc = check_plans12(h, hp, false)) return rc;
     if (!c || !h) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -295,7 +357,27 @@ extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *
         d.nbr_state = c->nbr;
     }
     d.obstacles_version = 0;               // staging copies: no grid reuse across calls
-    int rc = launch12(c, n_agents, &d, s);
+    srb12_plans dp;
+    std::memset(&dp, 0, sizeof dp);
+    dp.struct_size = (int)sizeof dp;
+    if (hp) {
+        dp.plan_selection = hp->plan_selection;
+        if (hp->nbr_plan && d.nbr_state) {
+            if (c->p.K_nbr > 0 && (h->agent_offset < 0 || h->agent_offset + n_agents > h->n_all))
+                return srb_internal_fail(SRB_ERR_ARG, "nbr_plan: agent_offset + n_agents exceeds n_all (the plan table's rows)");
+            const size_t bytes = (size_t)h->n_all * 2 * N * sizeof(double);
+            size_t cap = c->cap_plan;
+            if (int rc = reserve((void **)&c->nbr_plan, &cap, bytes, c)) return rc;
+            c->cap_plan = cap;
+            HIPCHK(hipMemcpyAsync(c->nbr_plan, hp->nbr_plan, bytes, hipMemcpyHostToDevice, s));
+            dp.nbr_plan = c->nbr_plan;
+        }
+        if (hp->plan) {
+            if (!c->plan) HIPCHK(hipMalloc(&c->plan, (size_t)c->max_agents * 2 * N * sizeof(double)));
+            dp.plan = c->plan;
+        }
+    }
+    int rc = launch12(c, n_agents, &d, s, hp ? &dp : nullptr);
     if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->x_qp) HIPCHK(hipMemcpyAsync(h->x_qp, c->x_qp, A * nv * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -303,6 +385,7 @@ extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *
     HIPCHK(hipMemcpyAsync(h->obj, c->obj, A * sizeof(double), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h->status, c->status, A * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(h->iters, c->iters, A * 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (dp.plan) HIPCHK(hipMemcpyAsync(hp->plan, c->plan, A * 2 * N * sizeof(double), hipMemcpyDeviceToHost, s));
     if (h->sel) {
         int Ko = 0, Kn = 0;
         clamp_rows(c, &d, &Ko, &Kn);
@@ -311,6 +394,16 @@ extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *
     }
     HIPCHK(hipStreamSynchronize(s));
     return SRB_OK;
+}
+
+extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *h)
+{
+    return solve_host12(c, n_agents, h, nullptr, false);
+}
+
+extern "C" int srb12_solve_batch_plans(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp)
+{
+    return solve_host12(c, n_agents, h, hp, true);
 }
 
 extern "C" int srb12_ctx_set_timing(srb12_ctx *c, int on)
@@ -417,15 +510,50 @@ extern "C" int srb12_sim_metrics_device(srb12_ctx *c, int n_agents, const srb12_
     return sim12_call(c, n_agents, d, cycle, stream, false);
 }
 
-extern "C" int srb12_rollout_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, int cycles,
-                                    void *stream)
+// the shift of the plans (srb12_plan_shift_kernel): launch only, the caller orders the stream
+static int launch_shift12(srb12_ctx *c, int n_agents, const double *plan, int grids, double *table, hipStream_t s)
+{
+    const int threads = n_agents * c->p.N;                // one per (agent, grid), as the advance
+    hipLaunchKernelGGL(srb12_plan_shift_kernel, dim3((threads + 255) / 256), dim3(256), 0, s, n_agents, c->p.N, grids, plan,
+                       table);
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+extern "C" int srb12_shift_plans_device(srb12_ctx *c, int n_agents, const double *plan, int grids, double *table,
+                                        void *stream)
+{
+    if (grids < 0) return srb_internal_fail(SRB_ERR_ARG, "srb12_shift_plans_device: grids must be >= 0");
+    if (!plan || !table) return srb_internal_fail(SRB_ERR_ARG, "srb12_shift_plans_device: missing buffer (plan, table)");
+    if (plan == table) return srb_internal_fail(SRB_ERR_ARG, "srb12_shift_plans_device: plan and table must be two buffers");
+    if (!c) return srb_internal_fail(SRB_ERR_ARG, "null argument");
+    if (c->p.N < 2) return srb_internal_fail(SRB_ERR_ARG, "srb12_shift_plans_device needs N >= 2 (the last finite difference)");
+    if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
+    if (overlap12(plan, (size_t)n_agents * 2 * c->p.N, table, (size_t)n_agents * 2 * c->p.N))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_shift_plans_device: plan and table overlap");
+    if (n_agents == 0) return SRB_OK;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->order.order_after_last(s);
+    if (!rc) rc = launch_shift12(c, n_agents, plan, grids, table, s);
+    if (!rc) rc = c->order.mark_done(s);
+    return rc;
+}
+
+// pl: the plans fed forward (srb12_rollout_plans_device), or NULL (srb12_rollout_device: today's launches)
+static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, const srb12_plans *pl,
+                     bool plans, int cycles, void *stream)
 {
     if (b && b->struct_size != (int)sizeof(srb12_batch))
         return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    if (plans && pl && pl->struct_size != (int)sizeof(srb12_plans))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_plans.struct_size != sizeof(srb12_plans): caller built against another ABI");
     // (the layout and null checks of check_sim12 only: the driver's first cycle is c_first itself)
     if (int rc = check_sim12(d, d && d->struct_size == (int)sizeof(srb12_sim) ? d->c_first : 0, false)) return rc;
     if (!b) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (!d->goal) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.goal missing");
+    if (plans)
+        if (int rc = check_plans12(b, pl, true)) return rc;
     if (!c) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (cycles < 0) return srb_internal_fail(SRB_ERR_ARG, "negative cycles");
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
@@ -463,10 +591,31 @@ extern "C" int srb12_rollout_device(srb12_ctx *c, int n_agents, const srb12_batc
         rc = launch_advance12(c, n_agents, &sim, cyc, s);
         if (rc || i == cycles) break;
         rc = launch_metrics12(c, n_agents, &sim, cyc, s);
-        if (!rc) rc = launch12(c, n_agents, &bat, s);
+        if (!pl) {
+            if (!rc) rc = launch12(c, n_agents, &bat, s);
+            continue;
+        }
+        // the first solve against the caller's table (or none), every later one against last cycle's shifted plans
+        srb12_plans cur = *pl;
+        if (i > 0) cur.nbr_plan = pl->plan_table;
+        if (!cur.nbr_plan) cur.plan_selection = 0;
+        if (!rc) rc = launch12(c, n_agents, &bat, s, &cur);
+        if (!rc) rc = launch_shift12(c, n_agents, pl->plan, SRB12_SIM_NDOMAIN, pl->plan_table, s);
     }
     const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier cycles run
     return rc ? rc : rc_mark;
+}
+
+extern "C" int srb12_rollout_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, int cycles,
+                                    void *stream)
+{
+    return rollout12(c, n_agents, b, d, nullptr, false, cycles, stream);
+}
+
+extern "C" int srb12_rollout_plans_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d,
+                                          const srb12_plans *pl, int cycles, void *stream)
+{
+    return rollout12(c, n_agents, b, d, pl, true, cycles, stream);
 }
 
 // diagnostics (not in the public header): agent >= 0 records a per-iteration trace on the next

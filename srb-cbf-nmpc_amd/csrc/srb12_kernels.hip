@@ -223,7 +223,8 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
         const double *__restrict__ xrefg, const double *__restrict__ footg, const int *__restrict__ contactg,
         const double *__restrict__ obstacles, const double *__restrict__ nbr_state, const int *__restrict__ sel_g,
         double *__restrict__ x_qp_out, double *__restrict__ x_out, double *__restrict__ obj_out,
-        int *__restrict__ status_out, int *__restrict__ iters_out, double *lds)
+        int *__restrict__ status_out, int *__restrict__ iters_out, const double *__restrict__ nbr_plan,
+        double *__restrict__ plan_out, double *lds)
 {
     const int tid = threadIdx.x, lane = tid;
     const int N = NC > 0 ? NC : prm.N, K = K1 > 0 ? K1 - 1 : prm.K_obs + prm.K_nbr;
@@ -281,7 +282,20 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
                 L.Wl[36 * k + 9 * l + 3 * i + j] = on * (Ts * (Iwi[3 * i] * S[j] + Iwi[3 * i + 1] * S[3 + j] + Iwi[3 * i + 2] * S[6 + j]));
         if (l == 0) { L.cs[2 * k] = c; L.cs[2 * k + 1] = s; }
     }
-    if (prm.use_nlp) {                                   // obstacle rows: the LIP mode's selection and prediction
+    // obstacle rows.  With a plan table (a kernel argument: the branch is wave-uniform) a neighbour column reads
+    // row sel[j], grid k of the table, that agent's (x, y) at Ts (k + 1); obstacles and nbr_plan are both global
+    if (prm.use_nlp && nbr_plan) {
+        for (int e = tid; e < NK; e += 64) {
+            const int k = e / K, j = e - k * K;
+            const bool st = j < prm.K_obs;
+            const int bi = L.sel[j];
+            const size_t bj = (bi >= 0) ? bi : 0;
+            const double *src = st ? obstacles + 2 * bj : nbr_plan + 2 * (bj * N + k);
+            L.obs[2 * e] = (bi >= 0) ? src[0] : x0[0] + 1000.0;
+            L.obs[2 * e + 1] = (bi >= 0) ? src[1] : x0[1];
+        }
+        if (tid < K) L.eps[tid] = (tid < prm.K_obs) ? prm.eps_obs : prm.eps_nbr;
+    } else if (prm.use_nlp) {                            // obstacle rows: the LIP mode's selection and prediction
         for (int e = tid; e < NK; e += 64) {
             const int k = e / K, j = e - k * K;
             const bool st = j < prm.K_obs;
@@ -1400,6 +1414,9 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
         status_out[2 * agent] = qp_flag; status_out[2 * agent + 1] = nlp_flag;
         iters_out[2 * agent] = qp_it; iters_out[2 * agent + 1] = nlp_it;
     }
+    // ---- this agent's plan: (x, y) of X at every grid, a gather of the words stored to x_out, whatever the status
+    if (plan_out)
+        for (int e = tid; e < 2 * N; e += 64) plan_out[(size_t)agent * 2 * N + e] = L.Z[12 * (e >> 1) + (e & 1)];
 }
 
 #define SRB12_KERNEL(TL, TO, NC, K1)                                                                            \
@@ -1408,13 +1425,13 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
         const double *__restrict__ footg, const int *__restrict__ contactg, const double *__restrict__ obstacles, \
         const double *__restrict__ nbr_state, const int *__restrict__ sel_g, double *__restrict__ x_qp_out,      \
         double *__restrict__ x_out, double *__restrict__ obj_out, int *__restrict__ status_out,                \
-        int *__restrict__ iters_out)                                                                          \
+        int *__restrict__ iters_out, const double *__restrict__ nbr_plan, double *__restrict__ plan_out)       \
     {                                                                                                          \
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         srb12_agent<TL, TO, NC, K1>(prm, agent, x0g, xrefg, footg, contactg, obstacles, nbr_state, sel_g, x_qp_out,     \
-                            x_out, obj_out, status_out, iters_out, lds);                                       \
+                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, lds);                   \
     }
 SRB12_INSTANCES(SRB12_KERNEL)
 

@@ -126,3 +126,31 @@ extern "C" __global__ void __launch_bounds__(256) srb12_sim_advance_kernel(
         for (int i = k; i < nv; i += N) xl[i] = xa[i];
     }
 }
+
+// Last cycle's plans as this cycle's table (dist.shift_plans on the device): the new cycle starts `grids` grids
+// later, so its grid k is the old grid k + grids; past the horizon the plan goes on along its last finite
+// difference, last + m (last - previous) with m = k + grids - N + 1 -- the operation order of
+// srb_sim_advance_kernel's shift (srb_sim.hip), contraction off.  One thread per (agent, grid) as the advance
+// above; a kernel of its own, so the advance and the plans-off rollout keep their code.  N >= 2, grids >= 0,
+// plan and table [n_agents][N][2] distinct buffers (checked by the host).
+extern "C" __global__ void __launch_bounds__(256) srb12_plan_shift_kernel(int n_agents, int N, int grids,
+                                                                          const double *__restrict__ plan,
+                                                                          double *__restrict__ table)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int a = idx / N, k = idx - a * N;
+    if (a >= n_agents) return;
+    const double *pa = plan + (size_t)a * 2 * N;
+    double *pt = table + ((size_t)a * N + k) * 2;
+    // (k + grids < N without the sum: grids is any non-negative int)
+    if (grids < N - k) {
+        pt[0] = pa[2 * (k + grids)];
+        pt[1] = pa[2 * (k + grids) + 1];
+    } else {
+        const double lx = pa[2 * (N - 1)], ly = pa[2 * (N - 1) + 1];
+        const double ex = lx - pa[2 * (N - 2)], ey = ly - pa[2 * (N - 2) + 1];
+        const double m = (double)(k + 1) + ((double)grids - (double)N);
+        pt[0] = lx + m * ex;
+        pt[1] = ly + m * ey;
+    }
+}

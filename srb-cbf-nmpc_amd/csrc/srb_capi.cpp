@@ -441,10 +441,10 @@ static int launch_select(srb_ctx *c, int n_agents, const double *x0, const doubl
 
 int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                        int obstacles_version, int *sel, hipStream_t s)
+                        int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan, int N)
 {
     return launch_select(c, n_agents, x0, obstacles, n_obs, nbr_state, n_all, agent_offset, K_obs, K_nbr,
-                         obstacles_version, sel, s);
+                         obstacles_version, sel, s, -1, nbr_plan, N);
 }
 
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s) { return c->order.mark_done(s); }

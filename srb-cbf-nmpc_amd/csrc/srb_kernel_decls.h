@@ -113,7 +113,8 @@ extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDe
     extern "C" __global__ void srb12_kernel_##TL##_##TO##_##NC##_##K1(                                       \
         Srb12KParams prm, int n_agents, const double *x0g, const double *xrefg, const double *footg,           \
         const int *contactg, const double *obstacles, const double *nbr_state, const int *sel_g,              \
-        double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out);
+        double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
+        const double *nbr_plan, double *plan_out);
 SRB12_INSTANCES(SRB_DECL12)
 #undef SRB_DECL12
 extern "C" __global__ void srb12_pos_kernel(int n_agents, const double *x0g, double *pos);
@@ -126,3 +127,5 @@ extern "C" __global__ void srb12_sim_advance_kernel(int n_agents, int N, double 
                                                     double *xref, double *foot, int *contact, double *last_state,
                                                     double *com, double *traj, int *status_log, int *iters_log,
                                                     double *x_log);
+// last cycle's plans as this cycle's table (dist.shift_plans), one thread per (agent, grid)
+extern "C" __global__ void srb12_plan_shift_kernel(int n_agents, int N, int grids, const double *plan, double *table);

@@ -8,15 +8,18 @@ torch solve on a stream).  Problem statement: DESIGN.md section 11; checker: ora
 
 Team features, as the LIP mode's: Solver12.set_scenes partitions a batch into independent teams
 (srb12_ctx_set_scenes; inputs from workload.make_scenes12), and Rollout12 is the closed-loop rollout on the
-device (csrc/srb12_sim.hip, srb12_rollout_device; DESIGN.md sections 9 and 10.4).
+device (csrc/srb12_sim.hip, srb12_rollout_device; DESIGN.md sections 9 and 10.4).  Neighbour plans (Plans12,
+srb12_plans): Solver12.solve / solve_device take nbr_plan and return plan, Solver12.solve_coupled_device is the
+Jacobi driver over the plans, and Rollout12(plans=True) feeds last cycle's plans forward.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import numpy as np
 
-from . import _check, _dp, _ip, _p, lib, workload
+from . import _check, _check_plan_array, _dp, _ip, _p, lib, workload
 
 _p12_fields = [("N", ctypes.c_int), ("K_obs", ctypes.c_int), ("K_nbr", ctypes.c_int),
                ("Ts", ctypes.c_double), ("mass", ctypes.c_double), ("Ib", ctypes.c_double * 9),
@@ -65,7 +68,17 @@ class Sim12(ctypes.Structure):
         super().__init__(ctypes.sizeof(Sim12), *args, **kw)
 
 
+class Plans12(ctypes.Structure):
+    """Mirror of srb12_plans (the neighbour plans of the SRB-12 mode; struct_size filled in)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("nbr_plan", _dp), ("plan", _dp), ("plan_selection", ctypes.c_int),
+                ("plan_table", _dp)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(ctypes.sizeof(Plans12), *args, **kw)
+
+
 GAITS = {"trot": 0, "stand": 1}       # srb12_sim.gait
+SHIFT_GRIDS = 4                       # grids a cycle (one gait domain): the shift of the plans between cycles
 
 _bound = False
 
@@ -89,6 +102,14 @@ def _lib():
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Sim12), ctypes.c_int, ctypes.c_void_p]
         L.srb12_rollout_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12), ctypes.POINTER(Sim12),
                                            ctypes.c_int, ctypes.c_void_p]
+        L.srb12_solve_batch_plans.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12),
+                                              ctypes.POINTER(Plans12)]
+        L.srb12_solve_batch_plans_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12),
+                                                     ctypes.POINTER(Plans12), ctypes.c_void_p]
+        L.srb12_shift_plans_device.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, ctypes.c_int, _dp, ctypes.c_void_p]
+        L.srb12_rollout_plans_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12),
+                                                 ctypes.POINTER(Sim12), ctypes.POINTER(Plans12), ctypes.c_int,
+                                                 ctypes.c_void_p]
         _bound = True
     return L
 
@@ -160,9 +181,13 @@ class Solver12:
         except Exception:
             pass
 
-    def solve(self, x0, xref, foot, contact, obstacles=None, nbr_state=None, agent_offset: int = 0):
+    def solve(self, x0, xref, foot, contact, obstacles=None, nbr_state=None, agent_offset: int = 0, nbr_plan=None,
+              plan_selection: bool = False):
         """Host numpy: x0 [A,12], xref [A,N,12], foot [A,N,4,3], contact [A,N,4] int.  Returns
-        dict x_qp, x [A, 24N+1], obj, status [A,2], iters [A,2], sel [A, Ko+Kn]."""
+        dict x_qp, x [A, 24N+1], obj, status [A,2], iters [A,2], sel [A, Ko+Kn], plan [A,N,2] (the (x, y) of
+        X at every grid).  nbr_plan ([n_all][N][2], float64, C-contiguous) makes the neighbour rows follow the
+        neighbours' plans instead of the constant-velocity guess; plan_selection selects the neighbours by
+        closest predicted approach over the horizon (needs nbr_plan)."""
         p = self.params
         x0 = np.ascontiguousarray(x0, np.float64); A = x0.shape[0]
         xref = np.ascontiguousarray(xref, np.float64); foot = np.ascontiguousarray(foot, np.float64)
@@ -177,13 +202,21 @@ class Solver12:
                     _p(nb) if nb is not None else None, ob.shape[0], nb.shape[0] if nb is not None else 0,
                     int(agent_offset), _p(out["x_qp"]), _p(out["x"]), _p(out["obj"]), _p(out["status"]),
                     _p(out["iters"]), _p(out["sel"]) if out["sel"].size else None, 0)
-        _check(_lib().srb12_solve_batch(self._h, A, ctypes.byref(b)))
+        if nbr_plan is not None:
+            # (without nbr_state the row count is the table's own: the library refuses that call by name)
+            _check_plan_array(nbr_plan, (nb.shape[0] if nb is not None else len(nbr_plan), p.N, 2), "nbr_plan", np.float64)
+        out["plan"] = np.zeros((A, p.N, 2))
+        pl = Plans12(_p(nbr_plan) if nbr_plan is not None else None, _p(out["plan"]), 1 if plan_selection else 0, None)
+        _check(_lib().srb12_solve_batch_plans(self._h, A, ctypes.byref(b), ctypes.byref(pl)))
         return out
 
     def solve_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, agent_offset: int = 0, stream=None,
-                     obstacles_version: int = 0):
+                     obstacles_version: int = 0, nbr_plan=None, plan_selection: bool = False, plan=None):
         """torch tensors on this device (float64 / int32), contiguous; out holds x_qp (or None), x, obj,
-        status, iters and optionally sel [A, Ko+Kn].  Asynchronous on `stream` (default: torch's current)."""
+        status, iters and optionally sel [A, Ko+Kn] and plan [A, N, 2] (written when the key is present; the
+        `plan` argument overrides it).  nbr_plan ([n_all][N][2] float64, contiguous): the neighbours' plans for the
+        inter-agent rows (None: constant velocity), must not overlap plan; plan_selection: the neighbours by
+        closest predicted approach (needs nbr_plan).  Asynchronous on `stream` (default: torch's current)."""
         def dptr(t):
             return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
 
@@ -203,7 +236,71 @@ class Solver12:
                     0 if obstacles is None else obstacles.shape[0], 0 if nbr_state is None else nbr_state.shape[0],
                     int(agent_offset), dptr(out.get("x_qp")), dptr(out["x"]), dptr(out["obj"]), iptr(out["status"]),
                     iptr(out["iters"]), iptr(out.get("sel")), int(obstacles_version))
-        _check(_lib().srb12_solve_batch_device(self._h, A, ctypes.byref(b), self._stream(stream)))
+        if plan is None:
+            plan = out.get("plan")
+        N = self.params.N
+        if nbr_plan is not None:
+            _check_plan_array(nbr_plan, (nbr_plan.shape[0] if nbr_state is None else nbr_state.shape[0], N, 2),
+                              "nbr_plan", torch.float64)
+        if plan is not None:
+            _check_plan_array(plan, (A, N, 2), "plan", torch.float64)
+        if nbr_plan is None and plan is None and not plan_selection:
+            _check(_lib().srb12_solve_batch_device(self._h, A, ctypes.byref(b), self._stream(stream)))
+            return
+        pl = Plans12(dptr(nbr_plan), dptr(plan), 1 if plan_selection else 0, None)
+        _check(_lib().srb12_solve_batch_plans_device(self._h, A, ctypes.byref(b), ctypes.byref(pl), self._stream(stream)))
+
+    def shift_plans_device(self, plan, table, grids: int = SHIFT_GRIDS, stream=None):
+        """dist.shift_plans on the device (srb12_shift_plans_device): table[a][k] = plan[a][k + grids], past the
+        horizon along the last finite difference.  plan, table [A][N][2] float64 on this device, two buffers."""
+        import torch
+        A = plan.shape[0] if hasattr(plan, "shape") and len(plan.shape) == 3 else -1
+        _check_plan_array(plan, (A, self.params.N, 2), "plan", torch.float64)
+        _check_plan_array(table, (A, self.params.N, 2), "table", torch.float64)
+        _check(_lib().srb12_shift_plans_device(self._h, A, ctypes.cast(ctypes.c_void_p(plan.data_ptr()), _dp), int(grids),
+                                               ctypes.cast(ctypes.c_void_p(table.data_ptr()), _dp), self._stream(stream)))
+
+    def solve_coupled_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, outer: int = 2, exchange=None,
+                             nbr_plan=None, agent_offset: int = 0, stream=None, obstacles_version: int = 0,
+                             plan_selection: bool = False):
+        """Jacobi iteration over the agents' plans (BatchSolver.solve_coupled_device for the 12-state body):
+        `outer` solves of the same cycle, each against the plans the agents wrote in the round before.  Round 0
+        solves against nbr_plan (None: the constant-velocity rows); every later round r reads table =
+        exchange(plan of round r - 1), a dist.PlanExchange, or on one GPU (exchange None: the batch is the whole
+        team, agent_offset 0) that plan tensor itself.  The plans ping-pong between out["plan"] ([A][N][2],
+        required) and a second buffer of this solver; the last round's results are in `out`.  Returns
+        plan_change, a device tensor [outer - 1]: max |plan_r - plan_{r-1}| per round (torch reductions; nothing
+        synchronises with the host inside the loop).  plan_selection applies to every round that has a table."""
+        import torch
+        outer = int(outer)
+        if outer < 1:
+            raise ValueError("outer must be >= 1")
+        plan = out.get("plan")
+        if plan is None:
+            raise ValueError("solve_coupled_device needs out['plan'] ([A][N][2] float64)")
+        A, N = x0.shape[0], self.params.N
+        _check_plan_array(plan, (A, N, 2), "out['plan']", torch.float64)
+        if exchange is None and outer > 1 and (nbr_state is None or nbr_state.shape[0] != A or agent_offset != 0):
+            raise ValueError("solve_coupled_device without an exchange iterates over this batch's own plans: "
+                             "nbr_state must hold exactly the batch's agents (agent_offset 0)")
+        other = getattr(self, "_plan_pong", None)
+        if outer > 1 and (other is None or other.shape != plan.shape or other.device != plan.device):
+            other = self._plan_pong = torch.empty_like(plan)
+        ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream)) if stream is not None else contextlib.nullcontext()
+        change = torch.zeros(max(outer - 1, 0), dtype=torch.float64, device=plan.device)
+        with ctx:
+            table, prev = nbr_plan, None
+            for r in range(outer):
+                cur = plan if (outer - 1 - r) % 2 == 0 else other      # the last round writes out["plan"]
+                if r > 0:
+                    table = exchange(prev) if exchange is not None else prev
+                self.solve_device(x0, xref, foot, contact, obstacles, nbr_state, out, agent_offset=agent_offset,
+                                  stream=stream, obstacles_version=obstacles_version, nbr_plan=table,
+                                  plan_selection=plan_selection and table is not None, plan=cur)
+                if r > 0:
+                    change[r - 1] = (cur - prev).abs().max()
+                prev = cur
+        return change
 
     def last_kernel_ms(self):
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -243,11 +340,16 @@ class Rollout12:
     hcom        reference CoM height
     yaw_step, hold_radius   the yaw reference turns towards the goal's bearing by at most yaw_step a cycle and
                 keeps the yaw within hold_radius of the goal
-    A whole team on one GPU (the SRB-12 mode has no sharded stepping and no neighbour plans).  All tensors are
+    plans       True: from the second cycle on, the inter-agent rows follow the neighbours' previous plans shifted
+                by one gait domain (srb12_plans.nbr_plan) instead of the constant-velocity guess; step() shifts
+                with srb12_shift_plans_device, run() is srb12_rollout_plans_device, the same bits
+    plan_selection  with plans: the neighbours by closest predicted approach, in every cycle that has a table
+    A whole team on one GPU (the SRB-12 mode has no sharded stepping).  All tensors are
     float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
 
     def __init__(self, solver, goal, vref: float = 0.27, phase=None, gait: str = "trot", log_x: bool = False,
-                 obstacles=None, hcom: float = workload.HCOM12, yaw_step: float = 0.1, hold_radius: float = 0.05):
+                 obstacles=None, hcom: float = workload.HCOM12, yaw_step: float = 0.1, hold_radius: float = 0.05,
+                 plans: bool = False, plan_selection: bool = False):
         import torch
         from .rollout import _check_tensor
         self.solver = solver
@@ -272,6 +374,9 @@ class Rollout12:
         self.goal, self.phase, self.obstacles = goal, phase, obstacles
         self.vref, self.gait, self.log_x = float(vref), gait, bool(log_x)
         self.hcom = float(hcom)
+        self.plans, self.plan_selection = bool(plans), bool(plan_selection)
+        if self.plan_selection and not self.plans:
+            raise ValueError("plan_selection needs plans=True (the horizon-aware selection reads the plan table)")
         self.yaw_step, self.hold_radius = float(yaw_step), float(hold_radius)
         N, nv = p.N, p.nv
         f8 = dict(dtype=torch.float64, device=self.device)
@@ -283,6 +388,10 @@ class Rollout12:
         self.contact = torch.zeros((A, N, 4), **i4)
         self.out = dict(x=torch.zeros((A, nv), **f8), obj=torch.zeros(A, **f8), status=torch.zeros((A, 2), **i4),
                         iters=torch.zeros((A, 2), **i4))
+        self.plan_table = None
+        if self.plans:
+            self.plan_table = torch.zeros((A, N, 2), **f8)
+            self.out["plan"] = torch.zeros((A, N, 2), **f8)
         self.metrics = dict(d_obs=torch.zeros(A, **f8), d_agent=torch.zeros(A, **f8), min_d_obs=torch.zeros(A, **f8),
                             min_d_agent=torch.zeros(A, **f8), fail_cycle=torch.full((A,), -1, **i4),
                             distance_to_fail=torch.zeros(A, **f8))
@@ -353,8 +462,11 @@ class Rollout12:
         self._reserve(self.c + 1)
         self.advance(stream)
         _check(_lib().srb12_sim_metrics_device(s._h, self.A, ctypes.byref(self._sim()), self.c, s._stream(stream)))
+        table = self.plan_table if self.plans and self.c > 0 else None
         s.solve_device(self.x0, self.xref, self.foot, self.contact, self.obstacles, self.last_state, self.out,
-                       stream=stream)
+                       stream=stream, nbr_plan=table, plan_selection=self.plan_selection and table is not None)
+        if self.plans:
+            s.shift_plans_device(self.out["plan"], self.plan_table, SHIFT_GRIDS, stream=stream)
         self.c += 1
         self.flushed = False
 
@@ -375,7 +487,13 @@ class Rollout12:
         b = Batch12(None, None, None, None, _dptr(self.obstacles), None,
                     0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                     None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]), None, 0)
-        _check(_lib().srb12_rollout_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), T, s._stream(stream)))
+        if self.plans:
+            pl = Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table))
+            _check(_lib().srb12_rollout_plans_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()),
+                                                     ctypes.byref(pl), T, s._stream(stream)))
+        else:
+            _check(_lib().srb12_rollout_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), T,
+                                               s._stream(stream)))
         self.c = T
         self.flushed = True
 

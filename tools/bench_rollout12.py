@@ -12,6 +12,14 @@ a rollout mode starts from the same reset state and runs the same T cycles.  The
 way, a window being T back-to-back calls at cycle 1 (the later-cycle path, with the logs).
 
     python tools/bench_rollout12.py [--cycles 20] [--rounds 7] [--out profiles/bench_rollout12.json]
+
+--plans adds the neighbour plans (srb12_plans) next to the modes above, in the same interleaved
+rounds: Rollout12(plans=True).run(T), T x step() and the scene-batched run, with and without the horizon-aware
+selection; the shift kernel alone; the selection alone, snapshot and horizon-aware (the library's timing events on a
+context of its own); the separation with the plans on beside the plans-off rollout of the same run; and plan_change
+per Jacobi round of Solver12.solve_coupled_device on the 1024-agent batch.
+
+    python tools/bench_rollout12.py --plans --out profiles/bench_rollout12_plans.json
 """
 import argparse
 import ctypes
@@ -55,6 +63,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1, help="untimed windows per mode")
     ap.add_argument("--agents", type=int, default=1024)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--plans", action="store_true", help="add the plans-on modes (see above)")
+    ap.add_argument("--outer", type=int, default=4, help="--plans: Jacobi rounds of the plan_change measurement")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_rollout12.py needs a GPU (no CPU fallback)")
@@ -130,6 +140,31 @@ def main():
 
     modes = [("run", run), ("step", steps), ("plain_solve_loop", plain), ("scenes_run", scenes),
              ("advance12_kernel", advance12), ("metrics12_kernel", metrics12), ("advance_lip_kernel", advance_lip)]
+
+    if args.plans:
+        proll = srb12.Rollout12(solver, goal, vref=workload.VREF, obstacles=t["obstacles"], plans=True)
+        hroll = srb12.Rollout12(solver, goal, vref=workload.VREF, obstacles=t["obstacles"], plans=True, plan_selection=True)
+        sproll = srb12.Rollout12(ssolver, D(sb["goal"]), vref=workload.VREF, phase=D(sb["phase"], torch.int32),
+                                 obstacles=D(sb["obstacles"]), plans=True)
+        shroll = srb12.Rollout12(ssolver, D(sb["goal"]), vref=workload.VREF, phase=D(sb["phase"], torch.int32),
+                                 obstacles=D(sb["obstacles"]), plans=True, plan_selection=True)
+
+        def rolled(r, x0, stepwise=False):
+            def f():
+                r.reset(x0)
+                if stepwise:
+                    for _ in range(T):
+                        r.step()
+                else:
+                    r.run(T)
+            return f
+
+        def shift12():
+            for _ in range(T):
+                solver.shift_plans_device(proll.out["plan"], proll.plan_table)
+        modes += [("run_plans", rolled(proll, t["x0"])), ("step_plans", rolled(proll, t["x0"], True)),
+                  ("run_plans_horizon_selection", rolled(hroll, t["x0"])), ("scenes_run_plans", rolled(sproll, sx0)),
+                  ("scenes_run_plans_horizon_selection", rolled(shroll, sx0)), ("shift12_kernel", shift12)]
     for _ in range(args.warmup):
         for _, f in modes:
             f()
@@ -158,6 +193,50 @@ def main():
                                      "scenes_with_a_failed_agent": int((sc["n_failed"] > 0).sum().item()),
                                      "scenes_with_a_non_converged_solve": int((sc["n_not_converged"] > 0).sum().item())}
 
+    plans = None
+    if args.plans:
+        def per_scene(r):
+            sc = r.scene_results()
+            torch.cuda.synchronize(dev)
+            return {"min_d_agent": hist(sc["min_d_agent"].cpu().numpy()), "min_d_obs": hist(sc["min_d_obs"].cpu().numpy()),
+                    "scenes_with_a_failed_agent": int((sc["n_failed"] > 0).sum().item()),
+                    "scenes_with_a_non_converged_solve": int((sc["n_not_converged"] > 0).sum().item())}
+        for name, r, x0 in (("one_team_plans", proll, t["x0"]), ("one_team_plans_horizon_selection", hroll, t["x0"]),
+                            ("scenes_plans", sproll, sx0), ("scenes_plans_horizon_selection", shroll, sx0)):
+            r.reset(x0)
+            r.run(T)
+            res_ = r.results()
+            torch.cuda.synchronize(dev)
+            safety[name] = safety_of(res_)
+            if name.startswith("scenes"):
+                safety[name]["per_scene"] = per_scene(r)
+        # plan_change per Jacobi round on the batch of the solve benchmark (fixed inputs, one cycle)
+        cout = dict(plain_out, plan=torch.zeros((A, N, 2), dtype=torch.float64, device=dev))
+        change = solver.solve_coupled_device(t["x0"], t["xref"], t["foot"], t["contact"], t["obstacles"], t["nbr_state"],
+                                             cout, outer=args.outer)
+        torch.cuda.synchronize(dev)
+        st = cout["status"].cpu().numpy()
+        # the selection alone: the library's events around the selection launches of T solves, a context of its own
+        tsolver = srb12.Solver12(p, A, 0)
+        table = cout["plan"].clone()
+        tout = dict(plain_out, x=torch.zeros_like(plain_out["x"]), plan=torch.zeros_like(table))
+        sel_ms = {}
+        for name, kw in (("snapshot", dict()), ("snapshot_with_table", dict(nbr_plan=table)),
+                         ("horizon_aware", dict(nbr_plan=table, plan_selection=True))):
+            v = []
+            for i in range(T + 2):
+                tsolver.solve_device(t["x0"], t["xref"], t["foot"], t["contact"], t["obstacles"], t["nbr_state"], tout, **kw)
+                torch.cuda.synchronize(dev)
+                if i >= 2:
+                    v.append(tsolver.last_kernel_ms())
+            v = np.array(v)
+            sel_ms[name] = {"select_ms_median": float(np.median(v[:, 0])), "select_ms_min": float(v[:, 0].min()),
+                            "select_ms_max": float(v[:, 0].max()), "solve_ms_median": float(np.median(v[:, 1]))}
+        tsolver.close()
+        plans = {"plan_change_per_jacobi_round_m": [float(c) for c in change.cpu().numpy()],
+                 "jacobi_last_round_non_optimal_frac": float(1.0 - (np.isin(st[:, 0], (0, 4)) & (st[:, 1] == 0)).mean()),
+                 "selection_alone_ms": sel_ms}
+
     cps = {k: {"median": float(np.median(T / np.array(v))), "min": float(np.min(T / np.array(v))),
                "max": float(np.max(T / np.array(v)))} for k, v in sec.items()}
     ms = {k: {"median": 1e3 / v["median"], "min": 1e3 / v["max"], "max": 1e3 / v["min"]} for k, v in cps.items()}
@@ -171,6 +250,14 @@ def main():
                    "team; *_kernel: T back-to-back calls of one entry point at cycle 1 (ms_per_cycle = ms per call).  A "
                    "rollout window includes its reset.",
            "safety": safety}
+    if plans is not None:
+        res["plans"] = plans
+        res["plans"]["ms_per_cycle_over_plans_off"] = {
+            k: ms[k]["median"] - ms[ref]["median"]
+            for k, ref in (("run_plans", "run"), ("step_plans", "step"), ("run_plans_horizon_selection", "run"),
+                           ("scenes_run_plans", "scenes_run"), ("scenes_run_plans_horizon_selection", "scenes_run"))}
+        res["note"] += ("  *_plans: Rollout12(plans=True), the reference of each is the plans-off row of the same run; "
+                        "shift12_kernel: T back-to-back srb12_shift_plans_device calls.")
     print(json.dumps(res), flush=True)
     if args.out:
         with open(args.out, "w") as f:
