@@ -188,20 +188,46 @@ __device__ __forceinline__ void ul_add(const double *R, const double *W, const d
         for (int e = tid0; e <= np; e += step) {
             if (e == np) { H[0] = H[0] + W[rs]; continue; }  // slack row: Z = e_0
             const int j = e / (c1 * c1), rem = e - j * c1 * c1, a = 1 + j * c1 + rem / c1, b = 1 + j * c1 + rem % c1;
+            // the grid's 2 + C rows (C <= 4): every load issued before the first product (predicated, as zo_sum),
+            // the sum in the rows' order
+            double wv[6], ra[6], rb[6];
+#pragma unroll
+            for (int u = 0; u < 6; u++) {
+                const bool in = u < 2 + F.C;
+                const int r = (u < 2) ? F.rU + 2 * j + u : rl + F.C * j + (in ? u - 2 : 0);
+                wv[u] = in ? W[r] : 0.0; ra[u] = in ? R[r * LDR + a] : 0.0; rb[u] = in ? R[r * LDR + b] : 0.0;
+            }
+            const double h0 = H[a * LDH + b];
+            __builtin_amdgcn_sched_barrier(0);
             double v = 0.0;
-            for (int d = 0; d < 2; d++) { const int r = F.rU + 2 * j + d; v = fma(W[r] * R[r * LDR + a], R[r * LDR + b], v); }
-            for (int i = 0; i < F.C; i++) { const int r = rl + F.C * j + i; v = fma(W[r] * R[r * LDR + a], R[r * LDR + b], v); }
-            H[a * LDH + b] = H[a * LDH + b] + v;
+#pragma unroll
+            for (int u = 0; u < 6; u++) {
+                if (u >= 2 + F.C) break;
+                v = fma(wv[u] * ra[u], rb[u], v);
+            }
+            H[a * LDH + b] = h0 + v;
         }
     }
     if (RHS) {
         for (int a = tid0; a < nz; a += step) {
             if (a == 0) { g[0] += CF[rs]; continue; }
             const int j = (a - 1) / c1;
+            double cv[6], ra[6];
+#pragma unroll
+            for (int u = 0; u < 6; u++) {
+                const bool in = u < 2 + F.C;
+                const int r = (u < 2) ? F.rU + 2 * j + u : rl + F.C * j + (in ? u - 2 : 0);
+                cv[u] = in ? CF[r] : 0.0; ra[u] = in ? R[r * LDR + a] : 0.0;
+            }
+            const double g0 = g[a];
+            __builtin_amdgcn_sched_barrier(0);
             double v = 0.0;
-            for (int d = 0; d < 2; d++) { const int r = F.rU + 2 * j + d; v = fma(CF[r], R[r * LDR + a], v); }
-            for (int i = 0; i < F.C; i++) { const int r = rl + F.C * j + i; v = fma(CF[r], R[r * LDR + a], v); }
-            g[a] += v;
+#pragma unroll
+            for (int u = 0; u < 6; u++) {
+                if (u >= 2 + F.C) break;
+                v = fma(cv[u], ra[u], v);
+            }
+            g[a] = g0 + v;
         }
     }
 }
@@ -634,22 +660,44 @@ __device__ __forceinline__ void obs_relin(double *R, double *OJ, int rO, int o, 
         constexpr int LDR = NZL + 1;
         double *dst = R + (rO + o) * LDR;
         const double *zx = R + i0 * LDR, *zy = R + i1 * LDR;
+        // both source rows first: dst, zx and zy all point into R with run-time rows, so a load written after a
+        // store could not be moved above it (one dependent LDS round trip an element)
+        double vx[NZL], vy[NZL];
 #pragma unroll
-        for (int a = 0; a < NZL; a++) dst[a] = fma(jx, zx[a], fma(jy, zy[a], (a == 0) ? -1.0 : 0.0));
+        for (int a = 0; a < NZL; a++) { vx[a] = zx[a]; vy[a] = zy[a]; }
+#pragma unroll
+        for (int a = 0; a < NZL; a++) dst[a] = fma(jx, vx[a], fma(jy, vy[a], (a == 0) ? -1.0 : 0.0));
     } else {
         OJ[2 * o] = jx; OJ[2 * o + 1] = jy;
     }
 }
 
-// dot of LDS term row (lane-parallel rows) with a wave-uniform vector held in registers
+// dot of LDS term row (lane-parallel rows) with a wave-uniform vector held in registers: the whole row
+// first (row_load: its loads in flight together, one LDS round trip a row -- written element by element into
+// the FMAs, the compiler ran every pair of elements through one shared temporary, a round trip a pair), then
+// the sums in their fixed order (row_sum)
+template <int NZE>
+__device__ __forceinline__ void row_load(const double *row, double (&a)[NZE])
+{
+#pragma unroll
+    for (int j = 0; j < NZE; j++) a[j] = row[j];
+}
 template <int NZL, int NZE = NZL>
-__device__ __forceinline__ double row_dot(const double *row, const double (&v)[NZL])
+__device__ __forceinline__ double row_sum(const double (&a)[NZE], const double (&v)[NZL])
 {
     double s0 = 0.0, s1 = 0.0;
 #pragma unroll
-    for (int j = 0; j + 1 < NZE; j += 2) { s0 = fma(row[j], v[j], s0); s1 = fma(row[j + 1], v[j + 1], s1); }
-    if (NZE & 1) s0 = fma(row[NZE - 1], v[NZE - 1], s0);
+    for (int j = 0; j + 1 < NZE; j += 2) { s0 = fma(a[j], v[j], s0); s1 = fma(a[j + 1], v[j + 1], s1); }
+    if (NZE & 1) s0 = fma(a[NZE - 1], v[NZE - 1], s0);
     return s0 + s1;
+}
+template <int NZL, int NZE = NZL>
+__device__ __forceinline__ double row_dot(const double *row, const double (&v)[NZL])
+{
+    double a[NZE];
+    row_load<NZE>(row, a);
+    __builtin_amdgcn_sched_barrier(0);
+    return row_sum<NZL, NZE>(a, v);
 }
 
 // row of the reduced matrix a lane holds: lane (NZL > 16, readlane Gauss-Jordan) or lane & 15
@@ -690,6 +738,15 @@ __device__ __forceinline__ void la_solve(const double (&M)[NZL], const double *H
         // round trip or barrier
         const int i = lane & 15;
         const double gi = (i < nz) ? g[i] : 0.0;         // g is zero beyond nz
+        // this lane's row of the matrix the refinement multiplies by (independent of y): loaded once, ahead of
+        // the first product, instead of one element per FMA of the residual
+        double hr[NZE];
+#pragma unroll
+        for (int j = 0; j < NZE; j++) hr[j] = Hs[i * LDH + j];
+        if (dl != 0.0) {                     // the NLP's inertia shift, applied on the fly (H stays unshifted)
+#pragma unroll
+            for (int j = 0; j < NZE; j++) hr[j] = fma(dl, Zs[i * LDH + j], hr[j]);
+        }
         double y0 = 0.0;
 #pragma unroll
         for (int j = 0; j < NZE; j++) y0 = fma(M[j], bc16(gi, j), y0);
@@ -700,13 +757,8 @@ __device__ __forceinline__ void la_solve(const double (&M)[NZL], const double *H
         for (int it = 0; it < (KF ? 8 : SRB_REFINE); it++) {
             if (KF && it >= nr) break;
             double rr = gi;
-            if (dl != 0.0) {                 // the NLP's inertia shift, applied on the fly (H stays unshifted)
 #pragma unroll
-                for (int j = 0; j < NZE; j++) rr = fma(-fma(dl, Zs[i * LDH + j], Hs[i * LDH + j]), bc16(y1, j), rr);
-            } else {
-#pragma unroll
-                for (int j = 0; j < NZE; j++) rr = fma(-Hs[i * LDH + j], bc16(y1, j), rr);
-            }
+            for (int j = 0; j < NZE; j++) rr = fma(-hr[j], bc16(y1, j), rr);
             if (i >= nz) rr = 0.0;
 #pragma unroll
             for (int j = 0; j < NZE; j++) y1 = fma(M[j], bc16(rr, j), y1);
@@ -820,12 +872,17 @@ __device__ __forceinline__ int kind_of(const Slot &q)
     return k;
 }
 
-__device__ __forceinline__ double slot_f(const Slot &q, const double *xs, double s_var)
+// (x0, x1: xs[q.i0], xs[q.i1], loaded by the caller -- the residual loop loads every slot's pair before the
+// first slot's arithmetic: the term-row stores of a slot's re-linearisation would hold the next slot's loads back)
+__device__ __forceinline__ double slot_fx(const Slot &q, double x0, double x1, double s_var)
 {
-    const double x0 = xs[q.i0], x1 = xs[q.i1];
     const int k = kind_of(q);
     const double dx = x0 - q.a0, dy = x1 - q.a1;
     return (k == K_OBS) ? -(dx * dx + dy * dy) - s_var : (k == K_COP) ? x0 - x1 : x0;
+}
+__device__ __forceinline__ double slot_f(const Slot &q, const double *xs, double s_var)
+{
+    return slot_fx(q, xs[q.i0], xs[q.i1], s_var);
 }
 
 
@@ -904,8 +961,7 @@ __device__ __forceinline__ double var_weight(const SrbKParams &prm, int v)
 }
 
 // Polish helper: every slot's row function g(x) into q.jd, each obstacle slot's term row M_o
-// re-linearised at x (entry by entry: the polish runs a few times per solve, so the register
-// staging of the interior-point loop is not worth its pressure here) and its multiplier into zo.
+// re-linearised at x (obs_relin: both source rows loaded before the stores) and its multiplier into zo.
 template <int NZL, int TS, int NW>
 __device__ __forceinline__ void polish_rows(Slot (&Q)[TS], int nts, const double *xs, double *OJ, double *zo, int n,
                                             int rO, double *R, int nz)
@@ -1671,12 +1727,18 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
             const double s_var = xs[n - 1];
             double nrx = 0.0, nrz = 0.0, sz = 0.0, gm = 1.0, zmx = 0.0;
             double fv[TS];
+            double xa[TS], xc[TS];                            // xs[i0], xs[i1] of every slot, loaded together
+#pragma unroll
+            for (int t = 0; t < TS; t++) {
+                xa[t] = xc[t] = 0.0;
+                if (t < nts) { xa[t] = xs[Q[t].i0]; xc[t] = xs[Q[t].i1]; }
+            }
 #pragma unroll
             for (int t = 0; t < TS; t++) {
                 fv[t] = 0.0;
                 if (t < nts) {
                     Slot &q = Q[t];
-                    const double f = slot_f(q, xs, s_var);
+                    const double f = slot_fx(q, xa[t], xc[t], s_var);
                     fv[t] = f;
                     if (kind_of(q) == K_VAR) {
                         nrx = fma(q.rx, q.rx, nrx);
@@ -1691,7 +1753,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                         for (int r = 0; r < 2; r++) { q.iz[r] = rcp_d(q.z[r]); q.is[r] = rcp_d(q.s[r]); }
                     if (nl && kind_of(q) == K_OBS) {              // re-linearise: M_o = J_o(x) Z (gram_rhs)
                         const int o = q.r - rO;
-                        obs_relin<NZL>(R, OJ, rO, o, q.i0, q.i1, -2.0 * (xs[q.i0] - q.a0), -2.0 * (xs[q.i1] - q.a1));
+                        obs_relin<NZL>(R, OJ, rO, o, q.i0, q.i1, -2.0 * (xa[t] - q.a0), -2.0 * (xc[t] - q.a1));
                         zo[o] = q.z[0];
                     }
                 }
@@ -1861,6 +1923,11 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                     for (int v = tid; v < n; v += NTH) dxv[v] = row_dot<NZL, NZE>(R + TL.zr(v) * LDR, dxi);
                     SYNC();
                 }
+                // stored-row instances: two row buffers, slot t + 1's term row loaded before slot t's arithmetic,
+                // so a pass waits for one LDS round trip, not one a slot
+                double rw[SRB_OBS_STORED(NZL) ? 2 : 1][NZE];
+                if constexpr (SRB_OBS_STORED(NZL))
+                    if (0 < nts) row_load<NZE>(R + Q[0].r * LDR, rw[0]);
 #pragma unroll
                 for (int t = 0; t < TS; t++)
                     if (t < nts) {
@@ -1868,7 +1935,9 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                         const int kd = kind_of(q);
                         if constexpr (SRB_OBS_STORED(NZL)) {
                             LCK(q.r >= 0 && q.r < RROWS, 1);
-                            q.jd = row_dot<NZL, NZE>(R + q.r * LDR, dxi);
+                            if (t + 1 < TS && t + 1 < nts) row_load<NZE>(R + Q[(t + 1) % TS].r * LDR, rw[(t + 1) & 1]);
+                            __builtin_amdgcn_sched_barrier(0);
+                            q.jd = row_sum<NZL, NZE>(rw[t & 1], dxi);
                         } else if (kd == K_OBS) {                     /* (QP stage: masked rows, 0) */
                             const int o = q.r - rO;
                             q.jd = nl ? fma(OJ[2 * o], dxv[q.i0], fma(OJ[2 * o + 1], dxv[q.i1], -dxv[n - 1])) : 0.0;
