@@ -373,6 +373,65 @@ int srb_rollout_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, cons
                        void *stream);
 
 /*
+ * Moving obstacles (LIP mode; DESIGN.md 3 "Moving obstacles", 10.6): an optional velocity per obstacle row, read by
+ * the selection, the solve and the rollout.  The layouts of srb_batch and srb_sim (and SRB_ABI_VERSION) stay; the new
+ * members travel in a struct of their own through entry points of their own, which otherwise behave as the entry
+ * points they extend.
+ *   obs_vel   [n_obs][2]    in: row i is the velocity (m/s) of obstacles[i]; row order and, with scenes, the
+ *                           scene-major layout of `obstacles` (scene g owns rows [g scene_obs, + scene_obs) of both
+ *                           tables).  The static column j < K_obs of grid k of the NLP stage then reads
+ *                               o = obstacles[sel[j]] + obs_vel[sel[j]] * (Ts * (k + 1))
+ *                           (uncontracted) where it read obstacles[sel[j]]; the table is read only through sel.
+ *                           NULL: static obstacles.
+ *   horizon_selection       0: the K_obs static columns are the rows nearest now (srb_knn_kernel, as ever);
+ *                           1: the rows of closest predicted approach over the horizon
+ *                           (srb_knn_obs_horizon_kernel): the key of row i for an agent is
+ *                           sqrt(min over k = 0 .. N of dx^2 + dy^2), t_k = Ts * (double)k, the agent at
+ *                           (x0[0] + x0[1] t_k, x0[2] + x0[3] t_k) -- constant velocity even when a plan table is
+ *                           present -- and the obstacle at (o_x + w_x t_k, o_y + w_y t_k), squares and sums
+ *                           uncontracted, a NaN pair making the key NaN for good.  Order, lower index on ties,
+ *                           never-selected NaN rows and the static table's 1000 m rule (a slot whose key is >= 1000
+ *                           gets row 0, with scenes the scene's row 0) are those of the snapshot selection.  One
+ *                           workgroup per agent, brute force: no selection grid is built or consulted.  The
+ *                           neighbour columns are selected as ever, by the snapshot or by plans.  Needs obs_vel.
+ *   obstacles [n_obs][2]    srb_rollout_moving_device only: the table the driver moves in place -- the rows
+ *                           batch.obstacles points to, writable.
+ * With mv == NULL or mv->obs_vel == NULL each entry point is the entry point it extends, output bits included.
+ * SRB_ERR_ARG, by name and before anything is launched: a wrong struct_size; obs_vel together with
+ * batch.obstacles_version != 0 (a kept selection grid of a moving table is stale); horizon_selection without obs_vel;
+ * a rollout with obs_vel but without mv->obstacles, or whose mv->obstacles is not batch.obstacles.  Scenes and
+ * agent_offset shards are honoured exactly as by the entry points extended.  host_mv holds host pointers, mv device
+ * pointers.
+ *
+ * srb_select_moving_device: srb_select_device; with horizon_selection = 1, tables & 1 is the horizon-aware obstacle
+ * selection.  The solve entry points run that selection themselves when horizon_selection = 1 (SRB_OPT_SELECTION = 1).
+ *
+ * srb_obstacles_advance_device(ctx, n_obs, obstacles, obs_vel, stream): one control cycle (NDOMAIN = 4 grids) of the
+ * table, one thread per row (srb_obstacles_advance_kernel), uncontracted:
+ *     obstacles[i][d] = obstacles[i][d] + obs_vel[i][d] * (Ts * 4.0)
+ * No bounce and no interaction between obstacles.
+ *
+ * srb_rollout_moving_device: srb_rollout_device with the table moved.  For each cycle c it enqueues the agents'
+ * advance; for c > c_first the obstacle advance; the metrics (unchanged: they read the moved table, so d_obs and
+ * fail_cycle are taken at matching times); select + solve with the table; and after the last cycle the final flushing
+ * advance of the agents.  Plain launches, no host synchronisation; plans on or off exactly as srb_rollout_device.
+ * The SRB-12 mode and the MPC_dist shims have no moving obstacles.
+ */
+typedef struct srb_moving {
+    int struct_size;           /* sizeof(srb_moving) (ABI check) */
+    const double *obs_vel;     /* [n_obs][2]; NULL: static obstacles */
+    int horizon_selection;     /* 0: K_obs nearest now; 1: closest predicted approach over the horizon */
+    double *obstacles;         /* advance / rollout only: the table moved in place (the rows batch.obstacles points to) */
+} srb_moving;
+int srb_solve_batch_moving(srb_ctx *ctx, int n_agents, const srb_batch *host_io, const srb_moving *host_mv);
+int srb_solve_batch_moving_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_moving *mv, void *stream);
+int srb_select_moving_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_moving *mv, int tables,
+                             void *stream);
+int srb_obstacles_advance_device(srb_ctx *ctx, int n_obs, double *obstacles, const double *obs_vel, void *stream);
+int srb_rollout_moving_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_sim *sim,
+                              const srb_moving *mv, int cycles, void *stream);
+
+/*
  * HL reference planner (generateReferenceTrajectory, MPC_dist.cpp:930-1104; SURVEY.md 8(f)
  * row 3) on HIP device `device`, host buffers, synchronous.  NA agents (1..2^20; up to 1024 in
  * one persistent workgroup, more -- one coupled swarm -- as one launch per step) starting at

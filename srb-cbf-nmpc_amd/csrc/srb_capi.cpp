@@ -22,21 +22,30 @@ typedef void (*srb_kernel_fn)(SrbKParams, int, const double *, const double *, c
 typedef void (*srb_polish_fn)(SrbKParams, int, const double *, const double *, const double *, const double *,
                               const double *, double *, double *, int *, const double *, double *, const int *,
                               const float *, int, const double *, double *);
-struct srb_instance { int nzl, ts, nw, nc, cc, kc; srb_kernel_fn fn; srb_polish_fn polish; };
-// solve kernel (INFIX empty, or f32_) and polish kernel of one instance
+// the moving-obstacle instances (srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*): the velocity table as one more argument
+typedef void (*srb_kernel_mv_fn)(SrbKParams, int, const double *, const double *, const double *, const double *, int,
+                                 const double *, int, int, double *, double *, double *, int *, int *, const double *,
+                                 double *, const int *, float *, int, const double *, double *, const double *);
+typedef void (*srb_polish_mv_fn)(SrbKParams, int, const double *, const double *, const double *, const double *,
+                                 const double *, double *, double *, int *, const double *, double *, const int *,
+                                 const float *, int, const double *, double *, const double *);
+struct srb_instance { int nzl, ts, nw, nc, cc, kc; srb_kernel_fn fn; srb_polish_fn polish; srb_kernel_mv_fn fn_mv; srb_polish_mv_fn polish_mv; };
+// solve kernel (INFIX empty, or f32_) and polish kernel of one instance, then their moving-obstacle instances
 #define ENTRY_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC) NZL, TS, NW, NC, CC, KC, srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
 #define ENTRY_POLISH_(NZL, TS, NW, NC, CC, KC) srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
-#define ENTRY_NMPC(...) {ENTRY_NMPC_(, __VA_ARGS__), ENTRY_POLISH_(__VA_ARGS__)},
-#define ENTRY_F32(...) {ENTRY_NMPC_(f32_, __VA_ARGS__), nullptr},
+#define ENTRY_MV_(INFIX, NZL, TS, NW, NC, CC, KC) srb_nmpc_kernel_mv_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
+#define ENTRY_POLISH_MV_(NZL, TS, NW, NC, CC, KC) srb_polish_kernel_mv_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
+#define ENTRY_NMPC(...) {ENTRY_NMPC_(, __VA_ARGS__), ENTRY_POLISH_(__VA_ARGS__), ENTRY_MV_(, __VA_ARGS__), ENTRY_POLISH_MV_(__VA_ARGS__)},
+#define ENTRY_F32(...) {ENTRY_NMPC_(f32_, __VA_ARGS__), nullptr, ENTRY_MV_(f32_, __VA_ARGS__), nullptr},
 static const srb_instance g_instances[] = {SRB_KERNEL_INSTANCES(ENTRY_NMPC)};
 // the fp32-factor variant of an instance (SRB_OPT_KKT_FP32_MU > 0), or null; these entries carry no polish kernel
 static const srb_instance g_instances_f32[] = {SRB_KF32_INSTANCES(ENTRY_F32)};
 #undef ENTRY_NMPC
 #undef ENTRY_F32
-static srb_kernel_fn f32_variant(const srb_instance *in)
+static const srb_instance *f32_variant(const srb_instance *in)
 {
     for (const srb_instance &v : g_instances_f32)
-        if (v.nzl == in->nzl && v.ts == in->ts && v.nw == in->nw && v.nc == in->nc && v.cc == in->cc && v.kc == in->kc) return v.fn;
+        if (v.nzl == in->nzl && v.ts == in->ts && v.nw == in->nw && v.nc == in->nc && v.cc == in->cc && v.kc == in->kc) return &v;
     return nullptr;
 }
 
@@ -98,6 +107,8 @@ struct srb_ctx {
     int *status, *iters;
     int *sel;                      // [max_agents][2 SRB_KNN_MAX] selected obstacle / neighbour rows
     size_t cap_obs, cap_nbr;
+    double *obs_vel;               // staged obstacle velocities [cap_vel][2] (srb_solve_batch_moving)
+    size_t cap_vel;
     float knn_ms, solve_ms;
     bool timed;
     int last_nw;
@@ -312,7 +323,7 @@ extern "C" int srb_ctx_destroy(srb_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->order.wait_idle();                         // the last launch may be on another stream
     void *bufs[] = {c->x0, c->ref, c->foot, c->x_qp, c->x, c->obj, c->status, c->iters, c->obstacles, c->nbr,
-                    c->abuf, c->alpha, c->sel, c->zpol, c->nbr_plan, c->plan};
+                    c->abuf, c->alpha, c->sel, c->zpol, c->nbr_plan, c->plan, c->obs_vel};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (auto &g : c->grid)
@@ -459,6 +470,48 @@ void srb_internal_clamp_K(const srb_ctx *c, int n_obs, bool has_nbr, int n_all, 
     clamp_K(c, n_obs, has_nbr, n_all, Ko, Kn);
 }
 
+// The horizon-aware obstacle selection (srb_moving.horizon_selection; srb_moving.hip) into the static columns
+// 0 .. K_obs - 1 of sel (rows of stride sel_stride): brute force, with scenes over the agent's scene.  K_obs is
+// already clamped to the table (or the scene).
+static int launch_obs_horizon(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
+                              int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride, hipStream_t s)
+{
+    if (c->scene_agents > 0)
+        hipLaunchKernelGGL(srb_knn_obs_horizon_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents,
+                           x0, obstacles, obs_vel, c->p.N, c->p.Ts, agent_offset, c->scene_agents, c->scene_obs, K_obs, sel,
+                           sel_stride);
+    else
+        hipLaunchKernelGGL(srb_knn_obs_horizon_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents, x0,
+                           obstacles, obs_vel, n_obs, c->p.N, c->p.Ts, K_obs, sel, sel_stride);
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+// The argument errors of srb_moving that need no context, before anything is launched (b may be null: the caller
+// reports that).  rollout: the driver moves the table, so it needs the writable pointer to batch.obstacles.
+static int check_moving(const srb_moving *mv, const srb_batch *b, bool rollout)
+{
+    if (!mv) return SRB_OK;
+    if (mv->struct_size != (int)sizeof(srb_moving))
+        return fail(SRB_ERR_ARG, "srb_moving.struct_size != sizeof(srb_moving): caller built against another ABI");
+    if (mv->horizon_selection != 0 && mv->horizon_selection != 1)
+        return fail(SRB_ERR_ARG, "srb_moving.horizon_selection: 0 (nearest now) or 1 (closest predicted approach)");
+    if (mv->horizon_selection && !mv->obs_vel)
+        return fail(SRB_ERR_ARG, "srb_moving.horizon_selection = 1 needs obs_vel (the horizon-aware selection reads the "
+                                 "velocity table)");
+    if (!mv->obs_vel || !b || b->struct_size != (int)sizeof(srb_batch)) return SRB_OK;
+    if (b->obstacles_version != 0)
+        return fail(SRB_ERR_ARG, "srb_moving.obs_vel with obstacles_version != 0: a kept selection grid of a moving table "
+                                 "is stale (pass version 0)");
+    if (rollout && !mv->obstacles)
+        return fail(SRB_ERR_ARG, "srb_rollout_moving_device: srb_moving.obstacles missing (the driver moves the table in "
+                                 "place)");
+    if (rollout && mv->obstacles != b->obstacles)
+        return fail(SRB_ERR_ARG, "srb_rollout_moving_device: srb_moving.obstacles is not srb_batch.obstacles (the solve and "
+                                 "the metrics read the table the driver moves)");
+    return SRB_OK;
+}
+
 // The argument errors of the plan members (srb_batch.nbr_plan / plan), before anything is launched.  select: the
 // call would run the neighbour selection (the horizon-aware one then needs the table).
 static int check_plans(srb_ctx *c, int n_agents, const srb_batch *d, bool select)
@@ -479,7 +532,9 @@ static int check_plans(srb_ctx *c, int n_agents, const srb_batch *d, bool select
     return SRB_OK;
 }
 
-static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, int use_nlp)
+// obs_vel / obs_horizon: the members of srb_moving (null / 0: static obstacles, every launch as before)
+static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, int use_nlp,
+                  const double *obs_vel = nullptr, int obs_horizon = 0)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -520,11 +575,23 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     int *sel = d->sel ? d->sel : c->sel;
     // SRB_OPT_SELECTION 0: the caller filled d->sel by srb_select_device (its two tables may then be selected
     // around a collective, bench.py's multi-GPU step)
-    if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection) {
+    if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection && obs_vel && obs_horizon) {
+        // srb_moving.horizon_selection: the static columns by closest predicted approach, the neighbour columns as ever
+        if (k.K_nbr > 0) {
+            int rc = launch_select(c, n_agents, d->x0, d->obstacles, 0, d->nbr_state, n_all, d->agent_offset, 0, k.K_nbr,
+                                   0, sel + k.K_obs, s, k.K_obs + k.K_nbr, c->plan_selection ? nbr_plan : nullptr, k.N);
+            if (rc) return rc;
+        }
+        if (k.K_obs > 0)
+            if (int rc = launch_obs_horizon(c, n_agents, d->x0, d->obstacles, obs_vel, n_obs, d->agent_offset, k.K_obs, sel,
+                                            k.K_obs + k.K_nbr, s))
+                return rc;
+    } else if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection) {
         int rc = launch_select(c, n_agents, d->x0, d->obstacles, n_obs, d->nbr_state, n_all, d->agent_offset, k.K_obs,
                                k.K_nbr, d->obstacles_version, sel, s, -1, c->plan_selection ? nbr_plan : nullptr, k.N);
         if (rc) return rc;
     }
+    const double *vel = (use_nlp && k.K_obs > 0) ? obs_vel : nullptr;   // read only for the static columns of sel
     if (c->timing) HIPCHK(hipEventRecord(c->ev[2], s));
     // the solve kernel, then (NLP stage) the active-set polish of its result: fused into the solve
     // kernel's end (SRB_OPT_POLISH_FUSED, instances up to SRB_FUSED_POLISH_MAX = NZL 24), else srb_polish_kernel (same instance
@@ -535,15 +602,23 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     c->last_polish = fused ? 2 : polish ? 1 : 0;
     // SRB_OPT_KKT_FP32_MU > 0: the instance's fp32-factor variant where one is compiled (else the fp64 one)
     srb_kernel_fn fn = in->fn;
+    srb_kernel_mv_fn fn_mv = in->fn_mv;
     c->last_f32 = 0;
     if (c->kkt32_mu > 0.0) {
-        srb_kernel_fn f = f32_variant(in);
-        if (f) { fn = f; c->last_f32 = 1; }
+        const srb_instance *f = f32_variant(in);
+        if (f) { fn = f->fn; fn_mv = f->fn_mv; c->last_f32 = 1; }
     }
-    hipLaunchKernelGGL(fn, dim3(n_agents), dim3(64 * in->nw), lds, s, k, n_agents, d->x0, d->ref, d->foot, d->obstacles,
-                       n_obs, d->nbr_state, n_all, d->agent_offset, d->x_qp, d->x, d->obj, d->status, d->iters,
-                       d->alpha ? d->alpha_buf : nullptr, d->alpha_buf ? d->alpha : nullptr, (const int *)sel,
-                       polish ? c->zpol : nullptr, c->zstride, k.K_nbr > 0 ? nbr_plan : nullptr, d->plan);
+    // with a velocity table the instance's moving-obstacle kernels (one more argument); without, the launches as ever
+    if (vel)
+        hipLaunchKernelGGL(fn_mv, dim3(n_agents), dim3(64 * in->nw), lds, s, k, n_agents, d->x0, d->ref, d->foot, d->obstacles,
+                           n_obs, d->nbr_state, n_all, d->agent_offset, d->x_qp, d->x, d->obj, d->status, d->iters,
+                           d->alpha ? d->alpha_buf : nullptr, d->alpha_buf ? d->alpha : nullptr, (const int *)sel,
+                           polish ? c->zpol : nullptr, c->zstride, k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel);
+    else
+        hipLaunchKernelGGL(fn, dim3(n_agents), dim3(64 * in->nw), lds, s, k, n_agents, d->x0, d->ref, d->foot, d->obstacles,
+                           n_obs, d->nbr_state, n_all, d->agent_offset, d->x_qp, d->x, d->obj, d->status, d->iters,
+                           d->alpha ? d->alpha_buf : nullptr, d->alpha_buf ? d->alpha : nullptr, (const int *)sel,
+                           polish ? c->zpol : nullptr, c->zstride, k.K_nbr > 0 ? nbr_plan : nullptr, d->plan);
     HIPCHK(hipGetLastError());
     if (c->timing) HIPCHK(hipEventRecord(c->ev[3], s));
     if (polish) {
@@ -556,10 +631,16 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         const srb_instance *pin = pnw == in->nw ? in : pick_instance(k, pnw);
         if (!pin || pin->nzl != in->nzl) pin = in;
         const size_t plds = (size_t)srb_lds_doubles(k, pin->nzl, pin->nw) * sizeof(double);
-        hipLaunchKernelGGL(pin->polish, dim3(n_agents), dim3(64 * pin->nw), plds, s, k, n_agents, d->x0, d->ref, d->foot,
-                           d->obstacles, d->nbr_state, d->x, d->obj, d->status, d->alpha ? d->alpha_buf : nullptr,
-                           d->alpha_buf ? d->alpha : nullptr, (const int *)sel, (const float *)c->zpol, c->zstride,
-                           k.K_nbr > 0 ? nbr_plan : nullptr, d->plan);
+        if (vel)
+            hipLaunchKernelGGL(pin->polish_mv, dim3(n_agents), dim3(64 * pin->nw), plds, s, k, n_agents, d->x0, d->ref, d->foot,
+                               d->obstacles, d->nbr_state, d->x, d->obj, d->status, d->alpha ? d->alpha_buf : nullptr,
+                               d->alpha_buf ? d->alpha : nullptr, (const int *)sel, (const float *)c->zpol, c->zstride,
+                               k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel);
+        else
+            hipLaunchKernelGGL(pin->polish, dim3(n_agents), dim3(64 * pin->nw), plds, s, k, n_agents, d->x0, d->ref, d->foot,
+                               d->obstacles, d->nbr_state, d->x, d->obj, d->status, d->alpha ? d->alpha_buf : nullptr,
+                               d->alpha_buf ? d->alpha : nullptr, (const int *)sel, (const float *)c->zpol, c->zstride,
+                               k.K_nbr > 0 ? nbr_plan : nullptr, d->plan);
         HIPCHK(hipGetLastError());
     }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[1], s));
@@ -674,18 +755,30 @@ extern "C" int srb_ctx_set_qp_init(srb_ctx *c, int mode)
     return SRB_OK;
 }
 
-extern "C" int srb_solve_batch_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, void *stream)
+static int solve_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv, void *stream)
 {
     // the layout check comes first: it needs no context (tests/test_abi.py runs it without a GPU)
     if (dev_io && dev_io->struct_size != (int)sizeof(srb_batch))
         return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    if (int rc0 = check_moving(mv, dev_io, false)) return rc0;
     if (!c || !dev_io) return fail(SRB_ERR_ARG, "null argument");
     hipStream_t s = (hipStream_t)stream;          // NULL: the HIP null stream (ordered with blocking streams)
     HIPCHK(hipSetDevice(c->device));
     int rc = c->order.order_after_last(s);
-    if (!rc) rc = launch(c, n_agents, dev_io, s, c->p.use_nlp);
+    if (!rc) rc = launch(c, n_agents, dev_io, s, c->p.use_nlp, mv ? mv->obs_vel : nullptr, mv ? mv->horizon_selection : 0);
     if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
+}
+
+extern "C" int srb_solve_batch_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, void *stream)
+{
+    return solve_device(c, n_agents, dev_io, nullptr, stream);
+}
+
+extern "C" int srb_solve_batch_moving_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
+                                             void *stream)
+{
+    return solve_device(c, n_agents, dev_io, mv, stream);
 }
 
 // One or both tables of the selection into dev_io->sel (required; [A][Ko + Kn], the layout the solve reads):
@@ -718,6 +811,53 @@ extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, i
         rc = launch_select(c, n_agents, d->x0, d->obstacles, ko ? d->n_obs : 0, d->nbr_state, kn ? d->n_all : 0,
                            d->agent_offset, ko, kn, d->obstacles_version, d->sel + (ko ? 0 : Ko), s, Ko + Kn, nbr_plan, p->N);
     if (!rc) rc = c->order.mark_done(s);
+    return rc;
+}
+
+// srb_select_device with the static columns by closest predicted approach (srb_moving.horizon_selection = 1); any
+// other srb_moving is srb_select_device itself (the snapshot selection does not read the velocities).
+extern "C" int srb_select_moving_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv, int tables,
+                                        void *stream)
+{
+    if (d && d->struct_size != (int)sizeof(srb_batch))
+        return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    if (int rc0 = check_moving(mv, d, false)) return rc0;
+    if (!mv || !mv->obs_vel || !mv->horizon_selection || !(tables & 1) || tables < 1 || tables > 3 || !c || !d)
+        return srb_select_device(c, n_agents, d, tables, stream);
+    if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
+    if (!d->x0 || !d->sel) return fail(SRB_ERR_ARG, "missing buffer (x0, sel)");
+    if (n_agents == 0) return SRB_OK;
+    int Ko = c->p.K_obs, Kn = c->p.K_nbr;                 // clamped exactly as the solve does
+    clamp_K(c, d->n_obs, d->nbr_state != nullptr, d->n_all, &Ko, &Kn);
+    if (int rc0 = check_scenes(c, n_agents, d->n_obs, d->nbr_state != nullptr, d->n_all, d->agent_offset)) return rc0;
+    if (Ko > 0 && !d->obstacles) return fail(SRB_ERR_ARG, "obstacles missing");
+    if (tables & 2)                                       // the neighbour columns: the pass of srb_select_device
+        if (int rc0 = srb_select_device(c, n_agents, d, 2, stream)) return rc0;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->order.order_after_last(s);
+    if (!rc && Ko > 0)
+        rc = launch_obs_horizon(c, n_agents, d->x0, d->obstacles, mv->obs_vel, d->n_obs, d->agent_offset, Ko, d->sel,
+                                Ko + Kn, s);
+    if (!rc) rc = c->order.mark_done(s);
+    return rc;
+}
+
+extern "C" int srb_obstacles_advance_device(srb_ctx *c, int n_obs, double *obstacles, const double *obs_vel, void *stream)
+{
+    if (!c) return fail(SRB_ERR_ARG, "null ctx");
+    if (n_obs < 0) return fail(SRB_ERR_ARG, "srb_obstacles_advance_device: negative n_obs");
+    if (n_obs == 0) return SRB_OK;
+    if (!obstacles || !obs_vel) return fail(SRB_ERR_ARG, "srb_obstacles_advance_device: obstacles / obs_vel missing");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->order.order_after_last(s);
+    if (!rc) {
+        hipLaunchKernelGGL(srb_obstacles_advance_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, s, n_obs, c->p.Ts,
+                           obstacles, obs_vel);
+        HIPCHK(hipGetLastError());
+        rc = c->order.mark_done(s);
+    }
     return rc;
 }
 
@@ -826,10 +966,12 @@ extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d
     return sim_call(c, n_agents, d, cycle, stream, false);
 }
 
-extern "C" int srb_rollout_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, int cycles, void *stream)
+static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, const srb_moving *mv, int cycles,
+                   void *stream)
 {
     if (b && b->struct_size != (int)sizeof(srb_batch))
         return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    if (int rc0 = check_moving(mv, b, true)) return rc0;
     // (the layout and null checks of check_sim only: the driver's first cycle is c_first itself)
     if (int rc = check_sim(d, d && d->struct_size == (int)sizeof(srb_sim) ? d->c_first : 0, false)) return rc;
     if (!b) return fail(SRB_ERR_ARG, "null argument");
@@ -868,16 +1010,35 @@ extern "C" int srb_rollout_device(srb_ctx *c, int n_agents, const srb_batch *b, 
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
     int rc = c->order.order_after_last(s);
+    // moving obstacles: the table advances one cycle between the agents' advance and the metrics, from the second
+    // cycle on, so d_obs / fail_cycle and the solve see the agents and the obstacles at matching times
+    const double *vel = (mv && b->n_obs > 0) ? mv->obs_vel : nullptr;
     for (int i = 0; i <= cycles && !rc; i++) {
         const int cyc = d->c_first + i;
         rc = launch_advance(c, n_agents, &sim, cyc, s);
         if (rc || i == cycles) break;
+        if (i > 0 && vel) {
+            hipLaunchKernelGGL(srb_obstacles_advance_kernel, dim3((b->n_obs + 255) / 256), dim3(256), 0, s, b->n_obs, c->p.Ts,
+                               mv->obstacles, vel);
+            HIPCHK(hipGetLastError());
+        }
         rc = launch_metrics(c, n_agents, &sim, cyc, s);
         if (i > 0 && d->plan_table) bat.nbr_plan = d->plan_table;
-        if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp);
+        if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp, vel, mv ? mv->horizon_selection : 0);
     }
     if (!rc) rc = c->order.mark_done(s);
     return rc;
+}
+
+extern "C" int srb_rollout_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, int cycles, void *stream)
+{
+    return rollout(c, n_agents, b, d, nullptr, cycles, stream);
+}
+
+extern "C" int srb_rollout_moving_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
+                                         const srb_moving *mv, int cycles, void *stream)
+{
+    return rollout(c, n_agents, b, d, mv, cycles, stream);
 }
 
 // swarms up to this many agents run as one persistent workgroup (srb_hlplan_kernel); larger ones
@@ -977,11 +1138,12 @@ extern "C" int srb_last_polish_ms(srb_ctx *c, float *polish_ms)
     return SRB_OK;
 }
 
-static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp)
+static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp, const srb_moving *mv = nullptr)
 {
     // the layout check comes first: it needs no context (tests/test_abi.py runs it without a GPU)
     if (h && h->struct_size != (int)sizeof(srb_batch))
         return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    if (int rc0 = check_moving(mv, h, false)) return rc0;
     if (!c || !h) return fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -1043,9 +1205,21 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp)
         d.nbr_plan = c->nbr_plan;
     }
     d.plan = h->plan ? c->plan : nullptr;
+    // the velocity table staged like the obstacle table it belongs to (srb_solve_batch_moving)
+    const double *vel = nullptr;
+    if (use_nlp && mv && mv->obs_vel && d.obstacles) {
+        if ((size_t)h->n_obs > c->cap_vel) {
+            if (c->obs_vel) HIPCHK(hipFree(c->obs_vel));
+            c->obs_vel = nullptr; c->cap_vel = 0;
+            HIPCHK(hipMalloc(&c->obs_vel, (size_t)h->n_obs * 2 * sizeof(double)));
+            c->cap_vel = h->n_obs;
+        }
+        HIPCHK(hipMemcpyAsync(c->obs_vel, mv->obs_vel, (size_t)h->n_obs * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+        vel = c->obs_vel;
+    }
     d.sel = nullptr;                       // the context's scratch; copied out below when asked for
     d.obstacles_version = 0;               // staged copy: rebuilt every call
-    int rc = launch(c, n_agents, &d, s, use_nlp);
+    int rc = launch(c, n_agents, &d, s, use_nlp, vel, vel && mv ? mv->horizon_selection : 0);
     if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->sel && use_nlp) {
@@ -1072,6 +1246,11 @@ extern "C" int srb_solve_batch(srb_ctx *c, int n_agents, const srb_batch *host_i
 extern "C" int srb_solve_qp(srb_ctx *c, int n_agents, const srb_batch *host_io)
 {
     return solve_host(c, n_agents, host_io, 0);
+}
+
+extern "C" int srb_solve_batch_moving(srb_ctx *c, int n_agents, const srb_batch *host_io, const srb_moving *host_mv)
+{
+    return solve_host(c, n_agents, host_io, c ? c->p.use_nlp : 0, host_mv);
 }
 
 // fitComTrajectory_eventbase (MPC_dist.cpp:784-855).  With N == NDOMAIN the reference's

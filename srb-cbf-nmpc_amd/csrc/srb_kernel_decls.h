@@ -25,20 +25,32 @@ struct SrbGrid {
     int ok;                        // 0: not built (brute-force scan)
 };
 
-// ---- srb_kernels.hip: the solve kernel (INFIX empty, or f32_ for the fp32-factor instances) and the polish kernel
+// ---- srb_kernels.hip: the solve kernel (INFIX empty, or f32_ for the fp32-factor instances) and the polish kernel;
+// the moving-obstacle instances (mv_: one more argument, the velocity table) of each
 #define SRB_DECL_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC)                                                         \
     extern "C" __global__ void srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(               \
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
         const double *obstacles, int n_obs, const double *nbr_state, int n_all, int agent_offset,              \
         double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
         const double *alpha_buf, double *alpha_out, const int *sel_g, float *zpol_g, int zstride,             \
-        const double *nbr_plan, double *plan_out);
+        const double *nbr_plan, double *plan_out);                                                            \
+    extern "C" __global__ void srb_nmpc_kernel_mv_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(            \
+        SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
+        const double *obstacles, int n_obs, const double *nbr_state, int n_all, int agent_offset,              \
+        double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
+        const double *alpha_buf, double *alpha_out, const int *sel_g, float *zpol_g, int zstride,             \
+        const double *nbr_plan, double *plan_out, const double *obs_vel);
 #define SRB_DECL_POLISH(NZL, TS, NW, NC, CC, KC)                                                              \
     extern "C" __global__ void srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                   \
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
         const double *obstacles, const double *nbr_state, double *x_out, double *obj_out, int *status_out,     \
         const double *alpha_buf, double *alpha_out, const int *sel_g, const float *zpol_g, int zstride,       \
-        const double *nbr_plan, double *plan_out);
+        const double *nbr_plan, double *plan_out);                                                            \
+    extern "C" __global__ void srb_polish_kernel_mv_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                \
+        SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
+        const double *obstacles, const double *nbr_state, double *x_out, double *obj_out, int *status_out,     \
+        const double *alpha_buf, double *alpha_out, const int *sel_g, const float *zpol_g, int zstride,       \
+        const double *nbr_plan, double *plan_out, const double *obs_vel);
 #define SRB_DECL_NMPC(...) SRB_DECL_NMPC_(, __VA_ARGS__) SRB_DECL_POLISH(__VA_ARGS__)
 #define SRB_DECL_NMPC_F32(...) SRB_DECL_NMPC_(f32_, __VA_ARGS__)
 SRB_KERNEL_INSTANCES(SRB_DECL_NMPC)
@@ -104,6 +116,17 @@ extern "C" __global__ void srb_sim_scene_metrics_kernel(int n_agents, int c, int
                                                         int blocks_per_scene, double *d_obs, double *d_agent,
                                                         double *min_d_obs, double *min_d_agent, int *fail_cycle,
                                                         double *distance_to_fail);
+
+// ---- srb_moving.hip (moving obstacles, srb_moving): the horizon-aware obstacle selection (whole table / the
+// agent's scene, global indices out) and one control cycle of the obstacle table
+extern "C" __global__ void srb_knn_obs_horizon_kernel(int n_agents, const double *x0g, const double *obstacles,
+                                                      const double *obs_vel, int n_obs, int N, double Ts, int K_obs,
+                                                      int *sel_out, int sel_stride);
+extern "C" __global__ void srb_knn_obs_horizon_scene_kernel(int n_agents, const double *x0g, const double *obstacles,
+                                                            const double *obs_vel, int N, double Ts, int agent_offset,
+                                                            int scene_agents, int scene_obs, int K_obs, int *sel_out,
+                                                            int sel_stride);
+extern "C" __global__ void srb_obstacles_advance_kernel(int n_obs, double Ts, double *obstacles, const double *obs_vel);
 
 // ---- srb_llctrl.hip
 extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDev io);

@@ -8,6 +8,7 @@
 #define SRB_KNN_WAVES 2   // waves per agent in the selection kernel (srb_knn_kernel; 2: 1 % faster configs[2] step than 4, round 4)
 #endif
 #define SRB_KNN_PLAN_WAVES 4   // waves per agent in the horizon-aware selection kernel (srb_knn_plan_kernel)
+#define SRB_KNN_OBS_WAVES 4    // waves per agent in the horizon-aware obstacle selection (srb_knn_obs_horizon_kernel)
 #define SRB_GRID_CELLS 16384     // cells of the selection grid (LDS counters of srb_grid_build_kernel)
 #define SRB_GRID_MIN_ROWS 8192    // tables this long get a grid (shorter: brute-force scan)
 #define SRB_GRID_MIN_ROWS_STATIC 4096   // versioned static obstacle tables (grid built once, reused):
@@ -132,7 +133,8 @@ struct SrbKParams {
     X(8, 1, 4, 0, 0, 0) X(12, 1, 4, 0, 0, 0) X(16, 1, 4, 0, 0, 0) X(16, 2, 4, 0, 0, 0) X(32, 2, 4, 0, 0, 0) \
     X(12, 2, 2, 0, 0, 0) X(16, 2, 2, 0, 0, 0) X(24, 4, 2, 0, 0, 0) X(24, 2, 4, 0, 0, 0)
 // the same instances in four parts of about equal compile time: the product build compiles
-// srb_kernels.hip once per part (-DSRB_PART=0..3, in parallel)
+// srb_kernels.hip once per part (-DSRB_PART=0..3, in parallel), and once more per part for its moving-obstacle
+// instances (-DSRB_PART=4..7: srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_* of parts 0..3)
 #define SRB_KI_PART0(X) X(12, 4, 1, 10, 2, 11) X(12, 4, 1, 0, 0, 0) X(8, 1, 1, 0, 0, 0) X(16, 1, 1, 0, 0, 0) \
     X(12, 3, 1, 0, 0, 0) X(8, 1, 4, 0, 0, 0)
 #define SRB_KI_PART1(X) SRB_XE(X, 24, 4, 2, SRB_N20_NC, 2, 11) X(24, 4, 2, 0, 0, 0) X(12, 1, 4, 0, 0, 0) X(16, 4, 1, 0, 0, 0) \

@@ -1110,6 +1110,7 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
 //   SRB_AGENT_OBSTACLES  the K selected rows per grid (srb_knn_kernel's sel; MPC_dist.cpp:371-396
 //                        generalised; neighbours at their planned positions nbr_plan[sel][k], or without a plan
 //                        table predicted at constant velocity o_k = p + v Ts (k+1))
+//                        (the moving-obstacle instances, MV = 1: static rows at o + w Ts (k+1), w = obs_vel[sel])
 //   SRB_AGENT_OUTPUTS    x, the agent's plan (the CoM positions of x), objective, alpha_COM
 #define SRB_AGENT_LAYOUT \
     constexpr int NZM = ((NZL + 15) / 16) * 16; \
@@ -1245,6 +1246,17 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
                     /* no selection (-1): a row 1000 m along +x, as the oracle */ \
                     ox_[t] = (bi >= 0) ? srcp[0] + (st ? 0.0 : srcp[2] * tt) : x0[0] + 1000.0; \
                     oy_[t] = (bi >= 0) ? srcp[1] + (st ? 0.0 : srcp[3] * tt) : x0[2]; \
+                } \
+                if (MV && obs_vel) {   /* MV: the moving-obstacle instances only; a kernel argument: wave-uniform */ \
+                    /* moving obstacles: the static row sel[j] at grid k is o + w (Ts (k + 1)), w = obs_vel[sel[j]], */ \
+                    /* uncontracted (the bits srb_knn_obs_horizon_kernel scans); the -1 row and the neighbour rows */ \
+                    /* are those of the arms above, with or without a plan table */ \
+                    _Pragma("clang fp contract(off)") \
+                    if (st && bi >= 0) { \
+                        const double tk = prm.Ts * (k + 1); \
+                        ox_[t] = obstacles[2 * bj] + obs_vel[2 * bj] * tk; \
+                        oy_[t] = obstacles[2 * bj + 1] + obs_vel[2 * bj + 1] * tk; \
+                    } \
                 } \
             } \
         } \
@@ -1451,7 +1463,7 @@ _Pragma("unroll")                                                               
 // the row slots and the term-row passes are split across the waves and combined through LDS;
 // the reduced-system factorisation and solves run redundantly in every wave (identical data,
 // identical results, no communication).
-template <int NZL, int TS, int NW, int NC, int CC, int KC, int KF = 0>
+template <int NZL, int TS, int NW, int NC, int CC, int KC, int KF = 0, int MV = 0>
 __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 const double *__restrict__ x0g, const double *__restrict__ refg, const double *__restrict__ footg,
                 const double *__restrict__ obstacles, int n_obs,
@@ -1460,7 +1472,8 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 double *__restrict__ obj_out, int *__restrict__ status_out, int *__restrict__ iters_out,
                 const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,
                 const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride,
-                const double *__restrict__ nbr_plan, double *__restrict__ plan_out, double *lds)
+                const double *__restrict__ nbr_plan, double *__restrict__ plan_out,
+                const double *__restrict__ obs_vel, double *lds)
 {
     SRB_AGENT_LAYOUT;
 #ifdef SRB_STAMPS
@@ -2125,14 +2138,15 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
 // status (-> OPTIMAL) only when the polish is accepted.  A kernel of its own: inside the solve
 // kernel the polish's registers competed with the interior-point loop's and pushed its spills
 // from 8 to 100-200 (configs[2] 0.40 -> 0.47-0.66 ms); here the loop is untouched.
-template <int NZL, int TS, int NW, int NC, int CC, int KC>
+template <int NZL, int TS, int NW, int NC, int CC, int KC, int MV = 0>
 __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
                 const double *__restrict__ x0g, const double *__restrict__ refg, const double *__restrict__ footg,
                 const double *__restrict__ obstacles, const double *__restrict__ nbr_state,
                 double *__restrict__ x_out, double *__restrict__ obj_out, int *__restrict__ status_out,
                 const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,
                 const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride,
-                const double *__restrict__ nbr_plan, double *__restrict__ plan_out, double *lds)
+                const double *__restrict__ nbr_plan, double *__restrict__ plan_out,
+                const double *__restrict__ obs_vel, double *lds)
 {
     SRB_AGENT_LAYOUT;
 #ifdef SRB_STAMPS
@@ -2231,7 +2245,7 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         if (agent >= n_agents) return;                                                                         \
         nmpc_agent<NZL, TS, NW, NC, CC, KC, KF>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
                                 x_qp_out, x_out, obj_out, status_out, iters_out, alpha_buf, alpha_out, sel_g, \
-                                zpol_g, zstride, nbr_plan, plan_out, lds);                                     \
+                                zpol_g, zstride, nbr_plan, plan_out, nullptr, lds);                            \
     }
 #define SRB_POLISH_ENTRY(NZL, TS, NW, NC, CC, KC)                                                              \
     extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
@@ -2247,10 +2261,53 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         polish_agent<NZL, TS, NW, NC, CC, KC>(prm, agent, x0g, refg, footg, obstacles, nbr_state, x_out, obj_out,          \
-                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, lds); \
+                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, nullptr, lds); \
+    }
+// The moving-obstacle instances (srb_moving.obs_vel; MV = 1): the same kernels with the velocity table as one more
+// argument and the moving arm of SRB_AGENT_OBSTACLES compiled in, named srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*.
+// Instances of their own, as the fp32-factor instances are, and in code objects of their own (SRB_PART 4 .. 7): with
+// the argument on the default instances the default bench step measured 0.5 % and config 5 0.3 % slower than the
+// parent, outside its run-to-run spread, so the default instances keep their code.
+#define SRB_NMPC_ENTRY_MV(INFIX, KF, NZL, TS, NW, NC, CC, KC)                                                  \
+    extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
+    srb_nmpc_kernel_mv_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                                       \
+        SrbKParams prm, int n_agents, const double *__restrict__ x0g, const double *__restrict__ refg,          \
+        const double *__restrict__ footg, const double *__restrict__ obstacles, int n_obs,                       \
+        const double *__restrict__ nbr_state, int n_all, int agent_offset, double *__restrict__ x_qp_out,        \
+        double *__restrict__ x_out, double *__restrict__ obj_out, int *__restrict__ status_out,                 \
+        int *__restrict__ iters_out, const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,       \
+        const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride,                               \
+        const double *__restrict__ nbr_plan, double *__restrict__ plan_out,                                    \
+        const double *__restrict__ obs_vel)                                                                    \
+    {                                                                                                          \
+        extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
+        const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
+        if (agent >= n_agents) return;                                                                         \
+        nmpc_agent<NZL, TS, NW, NC, CC, KC, KF, 1>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
+                                x_qp_out, x_out, obj_out, status_out, iters_out, alpha_buf, alpha_out, sel_g, \
+                                zpol_g, zstride, nbr_plan, plan_out, obs_vel, lds);                            \
+    }
+#define SRB_POLISH_ENTRY_MV(NZL, TS, NW, NC, CC, KC)                                                           \
+    extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
+    srb_polish_kernel_mv_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                                            \
+        SrbKParams prm, int n_agents, const double *__restrict__ x0g, const double *__restrict__ refg,          \
+        const double *__restrict__ footg, const double *__restrict__ obstacles,                                 \
+        const double *__restrict__ nbr_state, double *__restrict__ x_out, double *__restrict__ obj_out,          \
+        int *__restrict__ status_out, const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,     \
+        const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride,                         \
+        const double *__restrict__ nbr_plan, double *__restrict__ plan_out,                                    \
+        const double *__restrict__ obs_vel)                                                                    \
+    {                                                                                                          \
+        extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
+        const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
+        if (agent >= n_agents) return;                                                                         \
+        polish_agent<NZL, TS, NW, NC, CC, KC, 1>(prm, agent, x0g, refg, footg, obstacles, nbr_state, x_out, obj_out,       \
+                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, obs_vel, lds); \
     }
 #define SRB_NMPC_KERNEL(...) SRB_NMPC_ENTRY(, 0, __VA_ARGS__) SRB_POLISH_ENTRY(__VA_ARGS__)
 #define SRB_NMPC_KERNEL_F32(...) SRB_NMPC_ENTRY(f32_, 1, __VA_ARGS__)
+#define SRB_NMPC_KERNEL_MV(...) SRB_NMPC_ENTRY_MV(, 0, __VA_ARGS__) SRB_POLISH_ENTRY_MV(__VA_ARGS__)
+#define SRB_NMPC_KERNEL_MV_F32(...) SRB_NMPC_ENTRY_MV(f32_, 1, __VA_ARGS__)
 
 #if defined(SRB_PART) && !defined(SRB_DEV_INSTANCES)
 #if SRB_PART == 0
@@ -2260,14 +2317,26 @@ SRB_KI_PART1(SRB_NMPC_KERNEL)
 #elif SRB_PART == 2
 SRB_KI_PART2(SRB_NMPC_KERNEL)
 SRB_KF32_PART2(SRB_NMPC_KERNEL_F32)
-#else
+#elif SRB_PART == 3
 SRB_KI_PART3(SRB_NMPC_KERNEL)
 SRB_KF32_PART3(SRB_NMPC_KERNEL_F32)
+#elif SRB_PART == 4     // parts 4 .. 7: the moving-obstacle instances of parts 0 .. 3
+SRB_KI_PART0(SRB_NMPC_KERNEL_MV)
+#elif SRB_PART == 5
+SRB_KI_PART1(SRB_NMPC_KERNEL_MV)
+#elif SRB_PART == 6
+SRB_KI_PART2(SRB_NMPC_KERNEL_MV)
+SRB_KF32_PART2(SRB_NMPC_KERNEL_MV_F32)
+#else
+SRB_KI_PART3(SRB_NMPC_KERNEL_MV)
+SRB_KF32_PART3(SRB_NMPC_KERNEL_MV_F32)
 #endif
 #else
 SRB_KERNEL_INSTANCES(SRB_NMPC_KERNEL)
 #ifndef SRB_DEV_INSTANCES
 SRB_KF32_INSTANCES(SRB_NMPC_KERNEL_F32)
+SRB_KERNEL_INSTANCES(SRB_NMPC_KERNEL_MV)
+SRB_KF32_INSTANCES(SRB_NMPC_KERNEL_MV_F32)
 #endif
 #endif
 

@@ -290,3 +290,38 @@ __device__ __forceinline__ void knn_plan_select(int tid, const double *own, cons
     }
     knn_pop<SRB_KNN_PLAN_WAVES, KM>(tid, bd, bi, K, 0, sel, wd_lds, wi_lds);
 }
+
+// The scan of the horizon-aware obstacle selection (srb_knn_obs_horizon_kernel; its scene form on a scene's rows):
+// the K rows of n_obs of closest predicted approach to the agent whose N + 1 constant-velocity points are own[]
+// (point k at time Ts k).  The key of row i is sqrt(min_k d_k^2), the obstacle of pair k at o + w (Ts k), w its
+// obs_vel row -- for k >= 1 the bits of the rows the solve builds (SRB_AGENT_OBSTACLES).  Every thread of the
+// SRB_KNN_OBS_WAVES waves scans rows tid, tid + 64 KW, .. and keeps a sorted list (knn_insert); knn_pop merges them
+// into sel[0..K) with the static table's 1000 m rule (cap = 1).
+template <int KM>
+__device__ __forceinline__ void knn_obs_horizon_select(int tid, const double *own, const double *__restrict__ obstacles,
+                                                       const double *__restrict__ obs_vel, int n_obs, int N, double Ts,
+                                                       int K, int *sel, double *wd_lds, int *wi_lds)
+{
+#pragma clang fp contract(off)
+    double bd[KM]; int bi[KM];
+#pragma unroll
+    for (int j = 0; j < KM; j++) { bd[j] = __builtin_inf(); bi[j] = 0x7fffffff; }
+    double wq = __builtin_inf();                   // filter bound on the squared key (knn_select_k's)
+    for (int i = tid; i < n_obs; i += 64 * SRB_KNN_OBS_WAVES) {
+        const double ox = obstacles[2 * (size_t)i], oy = obstacles[2 * (size_t)i + 1];
+        const double wx = obs_vel[2 * (size_t)i], wy = obs_vel[2 * (size_t)i + 1];
+        double m = __builtin_inf();
+        for (int k = 0; k <= N; k++) {
+            const double tk = Ts * (double)k;
+            const double dx = own[2 * k] - (ox + wx * tk), dy = own[2 * k + 1] - (oy + wy * tk);
+            const double d2 = dx * dx + dy * dy;
+            m = (d2 < m || d2 != d2) ? d2 : m;       // the minimum; a NaN pair makes the key NaN for good
+        }
+        if (!(m <= wq)) continue;                  // NaN keys fail: such rows are never selected
+        knn_insert<KM>(bd, bi, sqrt(m), i, K);
+#pragma unroll
+        for (int j = 0; j < KM; j++)
+            if (j == K - 1) wq = bd[j] * bd[j] * (1.0 + 1e-14);
+    }
+    knn_pop<SRB_KNN_OBS_WAVES, KM>(tid, bd, bi, K, 1, sel, wd_lds, wi_lds);
+}

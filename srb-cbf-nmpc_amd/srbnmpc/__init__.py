@@ -95,6 +95,14 @@ class Sim(ctypes.Structure):
         super().__init__(ctypes.sizeof(Sim), *args, **kw)
 
 
+class Moving(ctypes.Structure):
+    """Mirror of srb_moving (moving obstacles; struct_size filled in)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("obs_vel", _dp), ("horizon_selection", ctypes.c_int), ("obstacles", _dp)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(ctypes.sizeof(Moving), *args, **kw)
+
+
 _lib = None
 
 
@@ -142,6 +150,14 @@ def lib():
             getattr(L, f).argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Sim), ctypes.c_int, ctypes.c_void_p]
         L.srb_rollout_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim),
                                          ctypes.c_int, ctypes.c_void_p]
+        L.srb_solve_batch_moving.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Moving)]
+        L.srb_solve_batch_moving_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch),
+                                                    ctypes.POINTER(Moving), ctypes.c_void_p]
+        L.srb_select_moving_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Moving),
+                                               ctypes.c_int, ctypes.c_void_p]
+        L.srb_obstacles_advance_device.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, _dp, ctypes.c_void_p]
+        L.srb_rollout_moving_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim),
+                                                ctypes.POINTER(Moving), ctypes.c_int, ctypes.c_void_p]
         L.srb_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.srb_fit_bezier.argtypes = [_dp, _dp, _dp]
         L.srb_last_error.restype = ctypes.c_char_p
@@ -218,13 +234,15 @@ class BatchSolver:
         return min(p.K_obs, max(n_obs, 0)), (min(p.K_nbr, max(n_all - 1, 0)) if n_all > 0 else 0)
 
     def solve(self, x0, ref, foot, obstacles=None, nbr_state=None, agent_offset: int = 0, qp_only: bool = False,
-              alpha_buf=None, nbr_plan=None, plan=None):
+              alpha_buf=None, nbr_plan=None, plan=None, obs_vel=None, obs_horizon: bool = False):
         """Host arrays in, dict of outputs back.  alpha_buf ([A][4], the Bezier buffer state)
         additionally returns alpha ([A][4][5], get_alphaCOM) from the fused fit.  With the NLP
         stage, sel ([A][Ko + Kn]) holds the selected obstacle / neighbour rows.  nbr_plan
         ([n_all][N][2], float64, C-contiguous) makes the neighbour rows follow the neighbours' plans
         instead of the constant-velocity guess; plan ([A][N][2], the same) receives this batch's plans
-        (out["plan"]; allocated here when None)."""
+        (out["plan"]; allocated here when None).  obs_vel ([n_obs][2], float64, C-contiguous): the obstacles move
+        at these velocities over the horizon (srb_solve_batch_moving); obs_horizon=True additionally selects the
+        static columns by closest predicted approach instead of nearest now."""
         p = self.params
         x0 = _f64(x0).reshape(-1, 4)
         A = x0.shape[0]
@@ -252,13 +270,22 @@ class BatchSolver:
                   _p(out["x_qp"]), _p(out["x"]), _p(out["obj"]), _p(out["status"]), _p(out["iters"]),
                   _p(ab) if ab is not None else None, _p(out["alpha"]) if ab is not None else None,
                   _p(out["sel"]) if out["sel"].size and not qp_only else None, 0, _p(nbr_plan), _p(plan))
+        if obs_vel is not None or obs_horizon:
+            if qp_only:
+                raise ValueError("obs_vel / obs_horizon: the QP-only solve has no obstacle rows")
+            if obs_vel is not None:
+                _check_vel_array(obs_vel, ob.shape[0], np.float64)
+            mv = Moving(_p(obs_vel), int(bool(obs_horizon)), None)
+            _check(lib().srb_solve_batch_moving(self._h, A, ctypes.byref(b), ctypes.byref(mv)))
+            return out
         fn = lib().srb_solve_qp if qp_only else lib().srb_solve_batch
         _check(fn(self._h, A, ctypes.byref(b)))
         return out
 
     # --------------------------------------------------------------- device path
     def solve_device(self, x0, ref, foot, obstacles, nbr_state, out, agent_offset: int = 0, stream=None,
-                     alpha_buf=None, obstacles_version: int = 0, nbr_plan=None, plan=None):
+                     alpha_buf=None, obstacles_version: int = 0, nbr_plan=None, plan=None, obs_vel=None,
+                     obs_horizon: bool = False):
         """All arguments torch tensors on this solver's device (float64 / int32), contiguous.
         `out` is a dict with x_qp (or None), x, obj, status, iters and, with alpha_buf [A][4],
         alpha [A][20]; an optional int32 out["sel"] [A][Ko + Kn] receives the selected rows
@@ -267,7 +294,9 @@ class BatchSolver:
         that version (its selection grid is reused; the reference's obstacles are static).
         nbr_plan ([n_all][N][2] float64, contiguous): the neighbours' plans for the inter-agent rows
         (None: constant velocity); plan (or out["plan"], [A][N][2] float64): receives this batch's plans,
-        and must not overlap nbr_plan.
+        and must not overlap nbr_plan.  obs_vel ([n_obs][2] float64, contiguous): the obstacles' velocities
+        (srb_solve_batch_moving_device; needs obstacles_version 0); obs_horizon=True selects the static columns by
+        closest predicted approach over the horizon.
         Asynchronous on `stream` (a hipStream_t handle), by default torch's current stream on
         this device, so the launch is ordered after the torch work that filled the inputs."""
         def dptr(t):
@@ -300,15 +329,23 @@ class BatchSolver:
                   dptr(out.get("alpha") if alpha_buf is not None else None),
                   iptr(out["sel"]) if out.get("sel") is not None else None, int(obstacles_version),
                   dptr(nbr_plan), dptr(plan))
+        if obs_vel is not None or obs_horizon:
+            if obs_vel is not None:
+                _check_vel_array(obs_vel, 0 if obstacles is None else obstacles.shape[0], torch_float64())
+            mv = Moving(dptr(obs_vel), int(bool(obs_horizon)), None)
+            _check(lib().srb_solve_batch_moving_device(self._h, A, ctypes.byref(b), ctypes.byref(mv), self._stream(stream)))
+            return
         _check(lib().srb_solve_batch_device(self._h, A, ctypes.byref(b), self._stream(stream)))
 
     def select_device(self, x0, obstacles, nbr_state, sel, tables: int = 3, agent_offset: int = 0, stream=None,
-                      obstacles_version: int = 0, nbr_plan=None):
+                      obstacles_version: int = 0, nbr_plan=None, obs_vel=None, obs_horizon: bool = False):
         """The obstacle / neighbour selection alone (srb_select_device) into the int32 tensor sel [A][Ko + Kn]:
         tables 1 the static obstacles, 2 the neighbour snapshot, 3 both.  With the option "selection" set
         to 0, solve_device then uses out["sel"] as filled here (bench.py selects the static obstacles while
         the neighbour all-gather is in flight).  With the option "plan_selection" set to 1, tables & 2 is the
-        horizon-aware selection (closest predicted approach) and needs nbr_plan [n_all][N][2].
+        horizon-aware selection (closest predicted approach) and needs nbr_plan [n_all][N][2].  With obs_vel
+        ([n_obs][2]) and obs_horizon=True, tables & 1 is the horizon-aware obstacle selection
+        (srb_select_moving_device).
         Asynchronous on `stream` like solve_device."""
         A = x0.shape[0]
         Ko, Kn = self.n_selected(0 if obstacles is None else obstacles.shape[0],
@@ -325,11 +362,18 @@ class BatchSolver:
                   0 if obstacles is None else obstacles.shape[0], 0 if nbr_state is None else nbr_state.shape[0],
                   int(agent_offset), None, None, None, None, None, None, None,
                   ctypes.cast(ctypes.c_void_p(sel.data_ptr()), _ip), int(obstacles_version), dptr(nbr_plan), None)
+        if obs_vel is not None or obs_horizon:
+            if obs_vel is not None:
+                _check_vel_array(obs_vel, 0 if obstacles is None else obstacles.shape[0], torch_float64())
+            mv = Moving(dptr(obs_vel), int(bool(obs_horizon)), None)
+            _check(lib().srb_select_moving_device(self._h, A, ctypes.byref(b), ctypes.byref(mv), int(tables),
+                                                  self._stream(stream)))
+            return
         _check(lib().srb_select_device(self._h, A, ctypes.byref(b), int(tables), self._stream(stream)))
 
     def solve_coupled_device(self, x0, ref, foot, obstacles, nbr_state, out, outer: int = 2, exchange=None,
                              nbr_plan=None, agent_offset: int = 0, stream=None, alpha_buf=None,
-                             obstacles_version: int = 0):
+                             obstacles_version: int = 0, obs_vel=None, obs_horizon: bool = False):
         """Jacobi iteration over the agents' plans: `outer` solves of the same cycle, each against the plans
         the agents wrote in the round before.  Round 0 solves against nbr_plan (None: the constant-velocity
         rows); every later round r exchanges the plans of round r - 1 -- table = exchange(plan), a
@@ -338,7 +382,8 @@ class BatchSolver:
         a second buffer of this solver, so the table a round reads is never the buffer it writes; the last
         round's results, its plans included, are in `out`.  Returns plan_change, a device tensor [outer - 1]:
         max |plan_r - plan_{r-1}| per round (torch reductions; nothing synchronises with the host inside the
-        loop).  No damping and no convergence test: the plain Jacobi round.  Other arguments as solve_device."""
+        loop).  No damping and no convergence test: the plain Jacobi round.  Other arguments (obs_vel and
+        obs_horizon included: every round solves against the same moving table) as solve_device."""
         import torch
         outer = int(outer)
         if outer < 1:
@@ -363,7 +408,8 @@ class BatchSolver:
                 if r > 0:
                     table = exchange(prev) if exchange is not None else prev
                 self.solve_device(x0, ref, foot, obstacles, nbr_state, out, agent_offset=agent_offset, stream=stream,
-                                  alpha_buf=alpha_buf, obstacles_version=obstacles_version, nbr_plan=table, plan=cur)
+                                  alpha_buf=alpha_buf, obstacles_version=obstacles_version, nbr_plan=table, plan=cur,
+                                  obs_vel=obs_vel, obs_horizon=obs_horizon)
                 if r > 0:
                     change[r - 1] = (cur - prev).abs().max()
                 prev = cur
@@ -393,6 +439,15 @@ class BatchSolver:
                   iptr(gait_domain), iptr(contact), dptr(toe), dptr(start), dptr(q), dptr(dq),
                   dptr(out["x0"]), dptr(out["ref"]), dptr(out["foot"]), dptr(out["last_state"]), iptr(out["status"]))
         _check(lib().srb_prepare_batch_device(self._h, A, ctypes.byref(pr), self._stream(stream)))
+
+    def advance_obstacles_device(self, obstacles, obs_vel, stream=None):
+        """One control cycle (4 grids) of a moving obstacle table, in place (srb_obstacles_advance_device):
+        obstacles[i] += obs_vel[i] * (Ts * 4).  Both [n_obs][2] float64 tensors on this solver's device."""
+        _check_vel_array(obstacles, obstacles.shape[0], torch_float64(), "obstacles")
+        _check_vel_array(obs_vel, obstacles.shape[0], torch_float64())
+        _check(lib().srb_obstacles_advance_device(self._h, obstacles.shape[0],
+                                                  ctypes.cast(ctypes.c_void_p(obstacles.data_ptr()), _dp),
+                                                  ctypes.cast(ctypes.c_void_p(obs_vel.data_ptr()), _dp), self._stream(stream)))
 
     def sync(self):
         _check(lib().srb_sync(self._h))
@@ -467,6 +522,13 @@ def _check_plan_array(a, shape, name, dtype):
     if a.dtype != dtype or tuple(a.shape) != tuple(shape) or not contiguous:
         raise ValueError(f"{name} must be a contiguous float64 array of shape {tuple(shape)}, got "
                          f"{tuple(a.shape)} {a.dtype}")
+
+
+def _check_vel_array(a, n_obs, dtype, name="obs_vel"):
+    """obs_vel (or the table it belongs to): a contiguous float64 [n_obs][2] array, validated as nbr_plan is."""
+    if not hasattr(a, "dtype") or not hasattr(a, "shape"):
+        raise ValueError(f"{name} must be a contiguous float64 array of shape ({n_obs}, 2), got {type(a).__name__}")
+    _check_plan_array(a, (n_obs, 2), name, dtype)
 
 
 def hl_plan(Pstart, Pobs, loop: int = 100000, device: int = 0):

@@ -13,12 +13,16 @@ run(); shards of a team step in lockstep, each with its dist.NeighbourExchange.
 With the solver's scene partition on (BatchSolver.set_scenes(team, n_obs); inputs from workload.make_scenes) the
 batch is many independent teams rolled out by the same launches -- obstacles is then the scene-major table
 [n_scenes * n_obs][2] -- and scene_results() reduces the metrics per scene.
+
+With obs_vel ([n_obs][2], m/s) the obstacles move: every solve reads the velocities (srb_moving), and from the second
+cycle on the table advances one cycle between the agents' advance and the metrics (srb_rollout_moving_device).  The
+rollout then works on its own copy of `obstacles`; results()["obstacles"] is the current table.
 """
 from __future__ import annotations
 
 import ctypes
 
-from . import Batch, Sim, _check, _dp, _ip, lib
+from . import Batch, Moving, Sim, _check, _check_vel_array, _dp, _ip, lib
 
 
 def _dptr(t):
@@ -47,12 +51,15 @@ class Rollout:
               by one gait domain (srb_batch.nbr_plan) instead of the constant-velocity guess
     log_x     True: keep every cycle's decision vectors (results()["x"], [T][A][nv])
     obstacles [n_obs][2] or None: the static obstacles, for the solve and for d_obs / fail_cycle
+    obs_vel   [n_obs][2] or None: the obstacles' velocities (m/s).  The rollout then clones `obstacles` (it moves the
+              table), reset() restores the start table, and every shard moves its own full copy (the same bits)
+    obs_horizon  True: the static columns by closest predicted approach over the horizon (needs obs_vel)
     agent_offset, n_all   a shard of a larger team: this batch is rows agent_offset .. agent_offset + A of the
               n_all-row neighbour table that step(exchange) gathers (default: the whole team)
     All tensors are float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
 
     def __init__(self, solver, goal, vref: float = 0.27, phase=None, plans: bool = False, log_x: bool = False, *,
-                 obstacles=None, agent_offset: int = 0, n_all: int | None = None):
+                 obstacles=None, agent_offset: int = 0, n_all: int | None = None, obs_vel=None, obs_horizon: bool = False):
         import torch
         self.solver = solver
         p = solver.params
@@ -71,6 +78,17 @@ class Rollout:
             _check_tensor(obstacles, (obstacles.shape[0], 2), "obstacles", torch.float64, self.device)
             if obstacles.shape[0] == 0:
                 obstacles = None
+        if obs_vel is not None:
+            if obstacles is None:
+                raise ValueError("obs_vel needs obstacles (one velocity row per obstacle row)")
+            _check_vel_array(obs_vel, obstacles.shape[0], torch.float64)
+            if obs_vel.device != self.device:
+                raise ValueError(f"obs_vel must be on {self.device}, got {obs_vel.device}")
+            self.obstacles0 = obstacles
+            obstacles = obstacles.clone()            # the rollout moves its table; the caller's stays
+        elif obs_horizon:
+            raise ValueError("obs_horizon needs obs_vel (the horizon-aware obstacle selection reads the velocities)")
+        self.obs_vel, self.obs_horizon = obs_vel, bool(obs_horizon)
         self.goal, self.phase, self.obstacles = goal, phase, obstacles
         self.vref, self.plans, self.log_x = float(vref), bool(plans), bool(log_x)
         self.agent_offset = int(agent_offset)
@@ -120,6 +138,9 @@ class Rollout:
             self.x_log = grow(self.x_log, cap, (A, nv), torch.float64)
         self.cap = cap
 
+    def _moving(self) -> Moving:
+        return Moving(_dptr(self.obs_vel), int(self.obs_horizon), _dptr(self.obstacles))
+
     def _sim(self, nbr_state=None) -> Sim:
         nbr = self.last_state if nbr_state is None else nbr_state
         m, o = self.metrics, self.out
@@ -134,10 +155,14 @@ class Rollout:
 
     # ------------------------------------------------------------------ driving
     def reset(self, state):
-        """Start state [A][4] (x, xdot, y, ydot); the cycle count and the logs start over."""
+        """Start state [A][4] (x, xdot, y, ydot); the cycle count and the logs start over; with obs_vel the start
+        table is restored.  Both are torch copies on torch's current stream: a caller who then passes another
+        stream to step() / run() orders that stream after the current one first (nothing here does)."""
         import torch
         _check_tensor(state, (self.A, 4), "state", torch.float64, self.device)
         self.state.copy_(state)
+        if self.obs_vel is not None:
+            self.obstacles.copy_(self.obstacles0)    # the start table
         self.c = 0
         self.flushed = True
         self._ready = True
@@ -165,6 +190,8 @@ class Rollout:
         s = self.solver
         self._reserve(self.c + 1)
         self.advance(stream)
+        if self.obs_vel is not None and self.c > 0:          # the obstacles' cycle: every rank its own full copy
+            s.advance_obstacles_device(self.obstacles, self.obs_vel, stream)
         nbr = self.last_state if exchange is None else exchange(self.last_state)
         import torch
         _check_tensor(nbr, (self.n_all, 4), "the exchanged neighbour table", torch.float64, self.device)
@@ -173,7 +200,8 @@ class Rollout:
         if self.plans and self.c > 0:
             table = self.plan_table if plan_exchange is None else plan_exchange(self.plan_table)
         s.solve_device(self.x0, self.ref, self.foot, self.obstacles, nbr, self.out, agent_offset=self.agent_offset,
-                       stream=stream, alpha_buf=self.alpha_buf, nbr_plan=table)
+                       stream=stream, alpha_buf=self.alpha_buf, nbr_plan=table, obs_vel=self.obs_vel,
+                       obs_horizon=self.obs_horizon)
         self.c += 1
         self.flushed = False
 
@@ -196,7 +224,12 @@ class Rollout:
                   0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                   None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]),
                   None, _dptr(o["alpha"]), None, 0, None, _dptr(o.get("plan")))
-        _check(lib().srb_rollout_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), T, s._stream(stream)))
+        if self.obs_vel is not None:
+            _check(lib().srb_rollout_moving_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()),
+                                                   ctypes.byref(self._moving()), T, s._stream(stream)))
+        else:
+            _check(lib().srb_rollout_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), T,
+                                            s._stream(stream)))
         self.c = T
         self.flushed = True
 
@@ -204,7 +237,8 @@ class Rollout:
         """The logs and metrics so far, as tensors (views of this object's buffers; asynchronous like the
         launches -- synchronise before reading on the host): traj [T+1][A][4], status / iters [T][A][2],
         x [T][A][nv] (log_x), state [A][4] (the end state), cycles, and d_obs, d_agent, min_d_obs,
-        min_d_agent, fail_cycle, distance_to_fail [A]."""
+        min_d_agent, fail_cycle, distance_to_fail [A]; with obs_vel, obstacles [n_obs][2] (the current table: the
+        rows as the last cycle saw them)."""
         if not self._ready:
             raise RuntimeError("Rollout.results before reset(state)")
         T = self.c
@@ -218,6 +252,8 @@ class Rollout:
                    state=self.state, **self.metrics)
         if self.log_x:
             out["x"] = self.x_log[:T]
+        if self.obs_vel is not None:
+            out["obstacles"] = self.obstacles
         return out
 
     def scene_results(self, stream=None):

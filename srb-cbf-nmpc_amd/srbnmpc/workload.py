@@ -83,6 +83,16 @@ def make_batch(n_agents: int, N: int = 10, C: int = 2, seed: int = 0, n_obs: int
     return dict(x0=x0, ref=ref.reshape(A, 4 * N), foot=foot, obstacles=obstacles, nbr_state=nbr_state)
 
 
+def obstacle_velocities(n_obs: int, seed: int, vmax: float = 1.0):
+    """Velocities [n_obs][2] (m/s) for a moving obstacle table (BatchSolver.solve(obs_vel=...), Rollout(obs_vel=...)),
+    deterministic per seed: speeds U[0.25 vmax, vmax] (all speeds are drawn first), headings U[0, 2 pi], from a
+    generator of their own (100 + seed), so make_batch's draws for that seed stay as they are."""
+    g = np.random.default_rng(100 + seed)
+    sp = g.uniform(0.25 * vmax, vmax, n_obs)
+    th = g.uniform(0, 2 * np.pi, n_obs)
+    return np.stack([sp * np.cos(th), sp * np.sin(th)], 1)
+
+
 SCENE_MAX_ATTEMPTS = 1000     # start draws per scene (make_scenes) before the clearance counts as impossible
 
 
