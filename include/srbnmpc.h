@@ -415,7 +415,8 @@ int srb_rollout_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, cons
  * advance; for c > c_first the obstacle advance; the metrics (unchanged: they read the moved table, so d_obs and
  * fail_cycle are taken at matching times); select + solve with the table; and after the last cycle the final flushing
  * advance of the agents.  Plain launches, no host synchronisation; plans on or off exactly as srb_rollout_device.
- * The SRB-12 mode and the MPC_dist shims have no moving obstacles.
+ * The SRB-12 mode takes the same struct through srb12_*_moving* entry points of its own (below, after srb12_plans); the
+ * MPC_dist shims have no moving obstacles.
  */
 typedef struct srb_moving {
     int struct_size;           /* sizeof(srb_moving) (ABI check) */
@@ -725,6 +726,38 @@ int srb12_solve_batch_plans_device(srb12_ctx *ctx, int n_agents, const srb12_bat
 int srb12_shift_plans_device(srb12_ctx *ctx, int n_agents, const double *plan, int grids, double *table, void *stream);
 int srb12_rollout_plans_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
                                const srb12_plans *plans, int cycles, void *stream);
+
+/*
+ * Moving obstacles in the SRB-12 mode (DESIGN.md 3 "Moving obstacles", 10.7): srb_moving (above), its members with the
+ * meaning they have in the LIP mode.  The static column j < K_obs of grid k of the NLP stage reads
+ *     o = obstacles[sel[j]] + obs_vel[sel[j]] * (Ts * (k + 1))      (uncontracted, Ts of srb12_params)
+ * through the srb12_kernel_mv_* instances; the -1 row and the neighbour columns (constant velocity or nbr_plan) are
+ * unchanged, and the table is read only through sel.  horizon_selection = 1 selects the static columns by
+ * srb_knn_obs_horizon_kernel (with srb12_ctx_set_scenes its scene form) over this context's N and Ts, the agent's own
+ * prediction constant velocity from (x0[0], x0[6], x0[1], x0[7]); the neighbour columns by the snapshot or by plans.
+ * `plans` may be NULL in all three: the call then extends srb12_solve_batch[_device] / srb12_rollout_device, else
+ * srb12_solve_batch_plans[_device] / srb12_rollout_plans_device.  With mv == NULL or mv->obs_vel == NULL each is
+ * that entry point, output bits included; a table of zeros gives the same bits as no table.
+ *
+ * srb12_obstacles_advance_device: srb_obstacles_advance_device with this context's Ts,
+ *     obstacles[i][d] = obstacles[i][d] + obs_vel[i][d] * (Ts * 4.0).
+ *
+ * srb12_rollout_moving_device: per cycle c it enqueues the agents' advance; for c > c_first the obstacle advance; the
+ * metrics (unchanged: agents and obstacles are read at matching times); select + solve with the table; with plans,
+ * after the solve, the shift as srb12_rollout_plans_device does it.  Plain launches, no host synchronisation; scenes
+ * are honoured; a sharded batch is refused as by srb12_rollout_device.
+ *
+ * SRB_ERR_ARG, by name and before anything is launched: a wrong srb_moving.struct_size; obs_vel with
+ * batch.obstacles_version != 0; horizon_selection other than 0 or 1, or set without obs_vel; a rollout with obs_vel
+ * whose mv->obstacles is missing or is not batch.obstacles.  host_mv holds host pointers, mv device pointers.
+ */
+int srb12_solve_batch_moving(srb12_ctx *ctx, int n_agents, const srb12_batch *host_io, const srb12_plans *host_plans,
+                             const srb_moving *host_mv);
+int srb12_solve_batch_moving_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_plans *plans,
+                                    const srb_moving *mv, void *stream);
+int srb12_obstacles_advance_device(srb12_ctx *ctx, int n_obs, double *obstacles, const double *obs_vel, void *stream);
+int srb12_rollout_moving_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
+                                const srb12_plans *plans, const srb_moving *mv, int cycles, void *stream);
 
 const char *srb_last_error(void);
 

@@ -19,8 +19,12 @@
 typedef void (*srb12_fn)(Srb12KParams, int, const double *, const double *, const double *, const int *,
                          const double *, const double *, const int *, double *, double *, double *, int *, int *,
                          const double *, double *);
-struct srb12_inst { int tl, to, nc, k1; srb12_fn fn; };
-#define ENTRY12(TL, TO, NC, K1) {TL, TO, NC, K1, srb12_kernel_##TL##_##TO##_##NC##_##K1},
+// the instance's moving-obstacle kernel (srb12_kernel_mv_*): the velocity table as one more argument
+typedef void (*srb12_mv_fn)(Srb12KParams, int, const double *, const double *, const double *, const int *,
+                            const double *, const double *, const int *, double *, double *, double *, int *, int *,
+                            const double *, double *, const double *);
+struct srb12_inst { int tl, to, nc, k1; srb12_fn fn; srb12_mv_fn fn_mv; };
+#define ENTRY12(TL, TO, NC, K1) {TL, TO, NC, K1, srb12_kernel_##TL##_##TO##_##NC##_##K1, srb12_kernel_mv_##TL##_##TO##_##NC##_##K1},
 static const srb12_inst g_inst12[] = {SRB12_INSTANCES(ENTRY12)};
 #undef ENTRY12
 
@@ -40,6 +44,8 @@ struct srb12_ctx {
     size_t cap_obs, cap_nbr;
     double *nbr_plan, *plan;       // staging of srb12_solve_batch_plans: the table [cap_plan bytes], the plans [max_agents][N][2]
     size_t cap_plan;
+    double *obs_vel;               // staged obstacle velocities [cap_vel bytes] (srb12_solve_batch_moving)
+    size_t cap_vel;
     int dbg_agent;                 // diagnostics: srb12_debug_trace
     double *dbg;
 };
@@ -167,7 +173,7 @@ extern "C" int srb12_ctx_destroy(srb12_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->order.wait_idle();
     void *bufs[] = {c->dbg, c->pos, c->sel, c->x0, c->xref, c->foot, c->contact, c->obstacles, c->nbr, c->x_qp, c->x, c->obj,
-                    c->status, c->iters, c->nbr_plan, c->plan};
+                    c->status, c->iters, c->nbr_plan, c->plan, c->obs_vel};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (int i = 0; i < 3; i++)
@@ -225,8 +231,35 @@ static bool overlap12(const double *a, size_t na, const double *b, size_t nb)
     return a && b && a < b + nb && b < a + na;
 }
 
-// pl: the plan members of this launch (NULL: none, the launch of srb12_solve_batch[_device] as ever)
-static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_t s, const srb12_plans *pl = nullptr)
+// The argument errors of srb_moving that need no context, before anything is launched (b may be null: the caller
+// reports that).  rollout: the driver moves the table, so it needs the writable pointer to batch.obstacles.
+static int check_moving12(const srb_moving *mv, const srb12_batch *b, bool rollout)
+{
+    if (!mv) return SRB_OK;
+    if (mv->struct_size != (int)sizeof(srb_moving))
+        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.struct_size != sizeof(srb_moving): caller built against another ABI");
+    if (mv->horizon_selection != 0 && mv->horizon_selection != 1)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.horizon_selection: 0 (nearest now) or 1 (closest predicted approach)");
+    if (mv->horizon_selection && !mv->obs_vel)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.horizon_selection = 1 needs obs_vel (the horizon-aware selection "
+                                              "reads the velocity table)");
+    if (!mv->obs_vel || !b || b->struct_size != (int)sizeof(srb12_batch)) return SRB_OK;
+    if (b->obstacles_version != 0)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.obs_vel with obstacles_version != 0: a kept selection grid of a "
+                                              "moving table is stale (pass version 0)");
+    if (rollout && !mv->obstacles)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_rollout_moving_device: srb_moving.obstacles missing (the driver moves "
+                                              "the table in place)");
+    if (rollout && mv->obstacles != b->obstacles)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_rollout_moving_device: srb_moving.obstacles is not srb12_batch.obstacles "
+                                              "(the solve and the metrics read the table the driver moves)");
+    return SRB_OK;
+}
+
+// pl: the plan members of this launch (NULL: none, the launch of srb12_solve_batch[_device] as ever); obs_vel /
+// obs_horizon: the members of srb_moving (null / 0: static obstacles, every launch as before)
+static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_t s, const srb12_plans *pl = nullptr,
+                    const double *obs_vel = nullptr, int obs_horizon = 0)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -250,6 +283,8 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     clamp_rows(c, d, &Ko, &Kn);
     // (the table is read by the NLP stage's neighbour rows only: without them it is never touched)
     const double *nbr_plan = (pl && p->use_nlp && Kn > 0 && d->nbr_state) ? pl->nbr_plan : nullptr;
+    // (the velocities are read by the NLP stage's static rows only, through sel)
+    const double *vel = (p->use_nlp && Ko > 0) ? obs_vel : nullptr;
     Srb12KParams k = make_k12(p, Ko, Kn);
     k.dbg_agent = c->dbg_agent; k.dbg = c->dbg;
     const srb12_inst *in = pick12(p->N, Ko + Kn);
@@ -262,33 +297,41 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         HIPCHK(hipGetLastError());
         int rc = srb_internal_select(c->sel_ctx, n_agents, c->pos, d->obstacles, Ko > 0 ? d->n_obs : 0, d->nbr_state,
                                      Kn > 0 ? d->n_all : 0, d->agent_offset, Ko, Kn, d->obstacles_version, sel, s,
-                                     pl && pl->plan_selection ? nbr_plan : nullptr, p->N);
+                                     pl && pl->plan_selection ? nbr_plan : nullptr, p->N, vel, vel ? obs_horizon : 0, p->Ts);
         if (rc) return rc;
         // the selection context's own ordering event: its grid buffers are reallocated only after
         // this launch (grid_reserve waits on it)
         if ((rc = srb_internal_mark_done(c->sel_ctx, s))) return rc;
     }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[1], s));
-    hipLaunchKernelGGL(in->fn, dim3(n_agents), dim3(64), lds, s, k, n_agents, d->x0, d->xref, d->foot, d->contact,
-                       d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters, nbr_plan,
-                       pl ? pl->plan : nullptr);
+    // with a velocity table the instance's moving-obstacle kernel (one more argument); without, the launch as ever
+    if (vel)
+        hipLaunchKernelGGL(in->fn_mv, dim3(n_agents), dim3(64), lds, s, k, n_agents, d->x0, d->xref, d->foot, d->contact,
+                           d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters,
+                           nbr_plan, pl ? pl->plan : nullptr, vel);
+    else
+        hipLaunchKernelGGL(in->fn, dim3(n_agents), dim3(64), lds, s, k, n_agents, d->x0, d->xref, d->foot, d->contact,
+                           d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters, nbr_plan,
+                           pl ? pl->plan : nullptr);
     HIPCHK(hipGetLastError());
     if (c->timing) HIPCHK(hipEventRecord(c->ev[2], s));
     c->timed = c->timing != 0;
     return SRB_OK;
 }
 
-static int solve_device12(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl, bool plans, void *stream)
+static int solve_device12(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl, bool plans, void *stream,
+                          const srb_moving *mv = nullptr)
 {
     if (d && d->struct_size != (int)sizeof(srb12_batch))
         return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    if (int rc0 = check_moving12(mv, d, false)) return rc0;
     if (plans)
         if (int rc = check_plans12(d, pl, false)) return rc;
     if (!c || !d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     int rc = c->order.order_after_last(s);
-    if (!rc) rc = launch12(c, n_agents, d, s, pl);
+    if (!rc) rc = launch12(c, n_agents, d, s, pl, mv ? mv->obs_vel : nullptr, mv ? mv->horizon_selection : 0);
     if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
 }
@@ -304,6 +347,13 @@ extern "C" int srb12_solve_batch_plans_device(srb12_ctx *c, int n_agents, const 
     return solve_device12(c, n_agents, d, pl, true, stream);
 }
 
+// pl may be NULL (srb12_solve_batch_device with the table), else srb12_solve_batch_plans_device with it
+extern "C" int srb12_solve_batch_moving_device(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl,
+                                               const srb_moving *mv, void *stream)
+{
+    return solve_device12(c, n_agents, d, pl, pl != nullptr, stream, mv);
+}
+
 static int reserve(void **buf, size_t *cap, size_t bytes, srb12_ctx *c)
 {
     if (bytes <= *cap) return SRB_OK;
@@ -315,10 +365,12 @@ static int reserve(void **buf, size_t *cap, size_t bytes, srb12_ctx *c)
 }
 
 // hp: the host plan members (NULL: srb12_solve_batch); the table and the plans are staged like the other buffers
-static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp, bool plans)
+static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp, bool plans,
+                        const srb_moving *hmv = nullptr)
 {
     if (h && h->struct_size != (int)sizeof(srb12_batch))
         return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    if (int rc0 = check_moving12(hmv, h, false)) return rc0;
     if (plans)
         if (int rc = check_plans12(h, hp, false)) return rc;
     if (!c || !h) return srb_internal_fail(SRB_ERR_ARG, "null argument");
@@ -377,7 +429,17 @@ static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const 
             dp.plan = c->plan;
         }
     }
-    int rc = launch12(c, n_agents, &d, s, hp ? &dp : nullptr);
+    // the velocity table, staged like the obstacle rows it belongs to (none without them)
+    const double *vel = nullptr;
+    if (hmv && hmv->obs_vel && d.obstacles) {
+        const size_t bytes = (size_t)h->n_obs * 2 * sizeof(double);
+        size_t cap = c->cap_vel;
+        if (int rc = reserve((void **)&c->obs_vel, &cap, bytes, c)) return rc;
+        c->cap_vel = cap;
+        HIPCHK(hipMemcpyAsync(c->obs_vel, hmv->obs_vel, bytes, hipMemcpyHostToDevice, s));
+        vel = c->obs_vel;
+    }
+    int rc = launch12(c, n_agents, &d, s, hp ? &dp : nullptr, vel, vel ? hmv->horizon_selection : 0);
     if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->x_qp) HIPCHK(hipMemcpyAsync(h->x_qp, c->x_qp, A * nv * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -404,6 +466,13 @@ extern "C" int srb12_solve_batch(srb12_ctx *c, int n_agents, const srb12_batch *
 extern "C" int srb12_solve_batch_plans(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp)
 {
     return solve_host12(c, n_agents, h, hp, true);
+}
+
+// hp may be NULL (srb12_solve_batch with the table), else srb12_solve_batch_plans with it
+extern "C" int srb12_solve_batch_moving(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp,
+                                        const srb_moving *hmv)
+{
+    return solve_host12(c, n_agents, h, hp, hp != nullptr, hmv);
 }
 
 extern "C" int srb12_ctx_set_timing(srb12_ctx *c, int on)
@@ -540,12 +609,38 @@ extern "C" int srb12_shift_plans_device(srb12_ctx *c, int n_agents, const double
     return rc;
 }
 
-// pl: the plans fed forward (srb12_rollout_plans_device), or NULL (srb12_rollout_device: today's launches)
+// one control cycle of an obstacle table (srb_obstacles_advance_kernel, 4 grids of this context's Ts): launch only
+static int launch_obstacles12(srb12_ctx *c, int n_obs, double *obstacles, const double *obs_vel, hipStream_t s)
+{
+    hipLaunchKernelGGL(srb_obstacles_advance_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, s, n_obs, c->p.Ts, obstacles,
+                       obs_vel);
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+extern "C" int srb12_obstacles_advance_device(srb12_ctx *c, int n_obs, double *obstacles, const double *obs_vel, void *stream)
+{
+    if (!c) return srb_internal_fail(SRB_ERR_ARG, "null ctx");
+    if (n_obs < 0) return srb_internal_fail(SRB_ERR_ARG, "srb12_obstacles_advance_device: negative n_obs");
+    if (n_obs == 0) return SRB_OK;
+    if (!obstacles || !obs_vel)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_obstacles_advance_device: obstacles / obs_vel missing");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = c->order.order_after_last(s);
+    if (!rc) rc = launch_obstacles12(c, n_obs, obstacles, obs_vel, s);
+    if (!rc) rc = c->order.mark_done(s);
+    return rc;
+}
+
+// pl: the plans fed forward (srb12_rollout_plans_device), or NULL (srb12_rollout_device: today's launches); mv: the
+// moving obstacles (srb12_rollout_moving_device), or NULL
 static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, const srb12_plans *pl,
-                     bool plans, int cycles, void *stream)
+                     bool plans, int cycles, void *stream, const srb_moving *mv = nullptr)
 {
     if (b && b->struct_size != (int)sizeof(srb12_batch))
         return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    if (int rc0 = check_moving12(mv, b, true)) return rc0;
     if (plans && pl && pl->struct_size != (int)sizeof(srb12_plans))
         return srb_internal_fail(SRB_ERR_ARG, "srb12_plans.struct_size != sizeof(srb12_plans): caller built against another ABI");
     // (the layout and null checks of check_sim12 only: the driver's first cycle is c_first itself)
@@ -586,20 +681,25 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
     HIPCHK(hipSetDevice(c->device));
     int rc = c->order.order_after_last(s);
     if (rc) return rc;
+    // moving obstacles: the table advances one cycle between the agents' advance and the metrics, from the second
+    // cycle on, so d_obs / fail_cycle and the solve see the agents and the obstacles at matching times
+    const double *vel = (mv && b->n_obs > 0) ? mv->obs_vel : nullptr;
+    const int hsel = mv ? mv->horizon_selection : 0;
     for (int i = 0; i <= cycles && !rc; i++) {
         const int cyc = d->c_first + i;
         rc = launch_advance12(c, n_agents, &sim, cyc, s);
         if (rc || i == cycles) break;
-        rc = launch_metrics12(c, n_agents, &sim, cyc, s);
+        if (i > 0 && vel) rc = launch_obstacles12(c, b->n_obs, mv->obstacles, vel, s);
+        if (!rc) rc = launch_metrics12(c, n_agents, &sim, cyc, s);
         if (!pl) {
-            if (!rc) rc = launch12(c, n_agents, &bat, s);
+            if (!rc) rc = launch12(c, n_agents, &bat, s, nullptr, vel, hsel);
             continue;
         }
         // the first solve against the caller's table (or none), every later one against last cycle's shifted plans
         srb12_plans cur = *pl;
         if (i > 0) cur.nbr_plan = pl->plan_table;
         if (!cur.nbr_plan) cur.plan_selection = 0;
-        if (!rc) rc = launch12(c, n_agents, &bat, s, &cur);
+        if (!rc) rc = launch12(c, n_agents, &bat, s, &cur, vel, hsel);
         if (!rc) rc = launch_shift12(c, n_agents, pl->plan, SRB12_SIM_NDOMAIN, pl->plan_table, s);
     }
     const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier cycles run
@@ -616,6 +716,13 @@ extern "C" int srb12_rollout_plans_device(srb12_ctx *c, int n_agents, const srb1
                                           const srb12_plans *pl, int cycles, void *stream)
 {
     return rollout12(c, n_agents, b, d, pl, true, cycles, stream);
+}
+
+// pl may be NULL (srb12_rollout_device with the table moved), else srb12_rollout_plans_device with it
+extern "C" int srb12_rollout_moving_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d,
+                                           const srb12_plans *pl, const srb_moving *mv, int cycles, void *stream)
+{
+    return rollout12(c, n_agents, b, d, pl, pl != nullptr, cycles, stream, mv);
 }
 
 // diagnostics (not in the public header): agent >= 0 records a per-iteration trace on the next

@@ -218,13 +218,13 @@ __device__ __forceinline__ d4 mfma(double a, double b, d4 c)
 
 } // namespace
 
-template <int TL, int TO, int NC, int K1>
+template <int TL, int TO, int NC, int K1, int MV>
 __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, const double *__restrict__ x0g,
         const double *__restrict__ xrefg, const double *__restrict__ footg, const int *__restrict__ contactg,
         const double *__restrict__ obstacles, const double *__restrict__ nbr_state, const int *__restrict__ sel_g,
         double *__restrict__ x_qp_out, double *__restrict__ x_out, double *__restrict__ obj_out,
         int *__restrict__ status_out, int *__restrict__ iters_out, const double *__restrict__ nbr_plan,
-        double *__restrict__ plan_out, double *lds)
+        double *__restrict__ plan_out, const double *__restrict__ obs_vel, double *lds)
 {
     const int tid = threadIdx.x, lane = tid;
     const int N = NC > 0 ? NC : prm.N, K = K1 > 0 ? K1 - 1 : prm.K_obs + prm.K_nbr;
@@ -307,6 +307,23 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
             L.obs[2 * e + 1] = (bi >= 0) ? src[1] + (st ? 0.0 : src[3] * tt) : x0[1];
         }
         if (tid < K) L.eps[tid] = (tid < prm.K_obs) ? prm.eps_obs : prm.eps_nbr;
+    }
+    // moving obstacles (the srb12_kernel_mv_* instances, MV = 1; obs_vel is a kernel argument: the branch is
+    // wave-uniform): the static entry sel[j] of grid k is o + w (Ts (k + 1)), w = obs_vel[sel[j]], uncontracted (the
+    // bits srb_knn_obs_horizon_kernel scans).  Entry e is rewritten by the lane that wrote it in the arm above (the
+    // same e = tid + 64 t), so no barrier stands between the two; the -1 row and the neighbour columns are that arm's
+    if (MV && obs_vel) {
+        for (int e = tid; e < NK; e += 64) {
+            const int k = e / K, j = e - k * K;
+            const int bi = L.sel[j];
+            if (j < prm.K_obs && bi >= 0) {
+#pragma clang fp contract(off)
+                const double tt = Ts * (k + 1);
+                const size_t bj = bi;
+                L.obs[2 * e] = obstacles[2 * bj] + obs_vel[2 * bj] * tt;
+                L.obs[2 * e + 1] = obstacles[2 * bj + 1] + obs_vel[2 * bj + 1] * tt;
+            }
+        }
     }
     // start: gravity-compensating forces on the stance legs, the dynamics rolled out, s = 0
     for (int e = tid; e < 12 * N; e += 64) {
@@ -1419,6 +1436,10 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
         for (int e = tid; e < 2 * N; e += 64) plan_out[(size_t)agent * 2 * N + e] = L.Z[12 * (e >> 1) + (e & 1)];
 }
 
+// Which instances a compilation emits: by default the ten srb12_kernel_* and srb12_pos_kernel; under -DSRB12_MOVING the
+// srb12_kernel_mv_* instances alone (the product's second code object); under -DSRB12_ALL both sets (the diagnostic
+// builds, which compile this file once)
+#if !defined(SRB12_MOVING) || defined(SRB12_ALL)
 #define SRB12_KERNEL(TL, TO, NC, K1)                                                                            \
     extern "C" __global__ void __launch_bounds__(64) SRB12_WPE srb12_kernel_##TL##_##TO##_##NC##_##K1(          \
         Srb12KParams prm, int n_agents, const double *__restrict__ x0g, const double *__restrict__ xrefg,        \
@@ -1430,11 +1451,35 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
-        srb12_agent<TL, TO, NC, K1>(prm, agent, x0g, xrefg, footg, contactg, obstacles, nbr_state, sel_g, x_qp_out,     \
-                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, lds);                   \
+        srb12_agent<TL, TO, NC, K1, 0>(prm, agent, x0g, xrefg, footg, contactg, obstacles, nbr_state, sel_g, x_qp_out,  \
+                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, nullptr, lds);          \
     }
 SRB12_INSTANCES(SRB12_KERNEL)
+#endif
+#if defined(SRB12_MOVING) || defined(SRB12_ALL)
+// The moving-obstacle instances (srb_moving.obs_vel; MV = 1), srb12_kernel_mv_*: the same kernels with the velocity
+// table as one more argument and the moving arm of the prologue compiled in.  In the product a code object of their own
+// (this file compiled a second time under -DSRB12_MOVING, which emits only them), so the default instances keep their argument
+// list and their code: the LIP mode measured the extra argument alone at +0.5 % of its step.
+#define SRB12_KERNEL_MV(TL, TO, NC, K1)                                                                         \
+    extern "C" __global__ void __launch_bounds__(64) SRB12_WPE srb12_kernel_mv_##TL##_##TO##_##NC##_##K1(       \
+        Srb12KParams prm, int n_agents, const double *__restrict__ x0g, const double *__restrict__ xrefg,        \
+        const double *__restrict__ footg, const int *__restrict__ contactg, const double *__restrict__ obstacles, \
+        const double *__restrict__ nbr_state, const int *__restrict__ sel_g, double *__restrict__ x_qp_out,      \
+        double *__restrict__ x_out, double *__restrict__ obj_out, int *__restrict__ status_out,                \
+        int *__restrict__ iters_out, const double *__restrict__ nbr_plan, double *__restrict__ plan_out,       \
+        const double *__restrict__ obs_vel)                                                                    \
+    {                                                                                                          \
+        extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
+        const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
+        if (agent >= n_agents) return;                                                                         \
+        srb12_agent<TL, TO, NC, K1, 1>(prm, agent, x0g, xrefg, footg, contactg, obstacles, nbr_state, sel_g, x_qp_out,  \
+                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, obs_vel, lds);          \
+    }
+SRB12_INSTANCES(SRB12_KERNEL_MV)
+#endif
 
+#if !defined(SRB12_MOVING) || defined(SRB12_ALL)
 // CoM rows [x, xdot, y, ydot] of a 12-state batch: the layout the shared selection kernel
 // (srb_knn_kernel) reads its query points from
 extern "C" __global__ void srb12_pos_kernel(int n_agents, const double *__restrict__ x0g, double *__restrict__ pos)
@@ -1444,3 +1489,4 @@ extern "C" __global__ void srb12_pos_kernel(int n_agents, const double *__restri
     const double *x = x0g + 12 * (size_t)a;
     pos[4 * (size_t)a] = x[0]; pos[4 * (size_t)a + 1] = x[6]; pos[4 * (size_t)a + 2] = x[1]; pos[4 * (size_t)a + 3] = x[7];
 }
+#endif

@@ -450,10 +450,26 @@ static int launch_select(srb_ctx *c, int n_agents, const double *x0, const doubl
     return SRB_OK;
 }
 
+static int launch_obs_horizon(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
+                              int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride, hipStream_t s, int N,
+                              double Ts);
+
+// The selection of a solve, both modes.  obs_vel with obs_horizon (srb_moving.horizon_selection): the static columns by
+// closest predicted approach over the caller's grid (N, Ts), the neighbour columns as without
 int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                        int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan, int N)
+                        int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan, int N,
+                        const double *obs_vel, int obs_horizon, double Ts)
 {
+    if (obs_vel && obs_horizon) {
+        if (K_nbr > 0)
+            if (int rc = launch_select(c, n_agents, x0, obstacles, 0, nbr_state, n_all, agent_offset, 0, K_nbr, 0,
+                                       sel + K_obs, s, K_obs + K_nbr, nbr_plan, N))
+                return rc;
+        if (K_obs > 0) return launch_obs_horizon(c, n_agents, x0, obstacles, obs_vel, n_obs, agent_offset, K_obs, sel,
+                                                 K_obs + K_nbr, s, N, Ts);
+        return SRB_OK;
+    }
     return launch_select(c, n_agents, x0, obstacles, n_obs, nbr_state, n_all, agent_offset, K_obs, K_nbr,
                          obstacles_version, sel, s, -1, nbr_plan, N);
 }
@@ -472,17 +488,18 @@ void srb_internal_clamp_K(const srb_ctx *c, int n_obs, bool has_nbr, int n_all, 
 
 // The horizon-aware obstacle selection (srb_moving.horizon_selection; srb_moving.hip) into the static columns
 // 0 .. K_obs - 1 of sel (rows of stride sel_stride): brute force, with scenes over the agent's scene.  K_obs is
-// already clamped to the table (or the scene).
+// already clamped to the table (or the scene).  N, Ts: the grid of the horizon (the SRB-12 mode hands over its own).
 static int launch_obs_horizon(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
-                              int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride, hipStream_t s)
+                              int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride, hipStream_t s, int N,
+                              double Ts)
 {
     if (c->scene_agents > 0)
         hipLaunchKernelGGL(srb_knn_obs_horizon_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents,
-                           x0, obstacles, obs_vel, c->p.N, c->p.Ts, agent_offset, c->scene_agents, c->scene_obs, K_obs, sel,
+                           x0, obstacles, obs_vel, N, Ts, agent_offset, c->scene_agents, c->scene_obs, K_obs, sel,
                            sel_stride);
     else
         hipLaunchKernelGGL(srb_knn_obs_horizon_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents, x0,
-                           obstacles, obs_vel, n_obs, c->p.N, c->p.Ts, K_obs, sel, sel_stride);
+                           obstacles, obs_vel, n_obs, N, Ts, K_obs, sel, sel_stride);
     HIPCHK(hipGetLastError());
     return SRB_OK;
 }
@@ -575,20 +592,11 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     int *sel = d->sel ? d->sel : c->sel;
     // SRB_OPT_SELECTION 0: the caller filled d->sel by srb_select_device (its two tables may then be selected
     // around a collective, bench.py's multi-GPU step)
-    if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection && obs_vel && obs_horizon) {
-        // srb_moving.horizon_selection: the static columns by closest predicted approach, the neighbour columns as ever
-        if (k.K_nbr > 0) {
-            int rc = launch_select(c, n_agents, d->x0, d->obstacles, 0, d->nbr_state, n_all, d->agent_offset, 0, k.K_nbr,
-                                   0, sel + k.K_obs, s, k.K_obs + k.K_nbr, c->plan_selection ? nbr_plan : nullptr, k.N);
-            if (rc) return rc;
-        }
-        if (k.K_obs > 0)
-            if (int rc = launch_obs_horizon(c, n_agents, d->x0, d->obstacles, obs_vel, n_obs, d->agent_offset, k.K_obs, sel,
-                                            k.K_obs + k.K_nbr, s))
-                return rc;
-    } else if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection) {
-        int rc = launch_select(c, n_agents, d->x0, d->obstacles, n_obs, d->nbr_state, n_all, d->agent_offset, k.K_obs,
-                               k.K_nbr, d->obstacles_version, sel, s, -1, c->plan_selection ? nbr_plan : nullptr, k.N);
+    // (with srb_moving.horizon_selection the static columns by closest predicted approach: srb_internal_select)
+    if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection) {
+        int rc = srb_internal_select(c, n_agents, d->x0, d->obstacles, n_obs, d->nbr_state, n_all, d->agent_offset, k.K_obs,
+                                     k.K_nbr, d->obstacles_version, sel, s, c->plan_selection ? nbr_plan : nullptr, k.N,
+                                     obs_vel, obs_horizon, p->Ts);
         if (rc) return rc;
     }
     const double *vel = (use_nlp && k.K_obs > 0) ? obs_vel : nullptr;   // read only for the static columns of sel
@@ -838,7 +846,7 @@ extern "C" int srb_select_moving_device(srb_ctx *c, int n_agents, const srb_batc
     int rc = c->order.order_after_last(s);
     if (!rc && Ko > 0)
         rc = launch_obs_horizon(c, n_agents, d->x0, d->obstacles, mv->obs_vel, d->n_obs, d->agent_offset, Ko, d->sel,
-                                Ko + Kn, s);
+                                Ko + Kn, s, c->p.N, c->p.Ts);
     if (!rc) rc = c->order.mark_done(s);
     return rc;
 }

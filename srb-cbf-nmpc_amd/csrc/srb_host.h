@@ -7,11 +7,13 @@
 
 // defined in srb_capi.cpp: the thread's last-error message (srb_last_error), and the LIP-mode context's selection
 // launch and ordering mark, which the SRB-12 mode reuses (nbr_plan [n_all][N][2] != NULL: the neighbour columns by
-// the horizon-aware selection of SRB_OPT_PLAN_SELECTION, whatever that option of the context says)
+// the horizon-aware selection of SRB_OPT_PLAN_SELECTION, whatever that option of the context says; obs_vel
+// [n_obs][2] with obs_horizon != 0: the static columns by srb_moving.horizon_selection over the grid (N, Ts))
 int srb_internal_fail(int code, const char *msg);
 int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                        int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan = nullptr, int N = 0);
+                        int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan = nullptr, int N = 0,
+                        const double *obs_vel = nullptr, int obs_horizon = 0, double Ts = 0.0);
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s);
 // ... and its scene partition (srb_ctx_set_scenes): the per-call refusals, the "up to K nearest" clamp, and the
 // metrics launch (srb_sim_metrics_kernel, or with scenes srb_sim_scene_metrics_kernel) on d->state rows

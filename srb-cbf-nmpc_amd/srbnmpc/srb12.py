@@ -10,7 +10,9 @@ Team features, as the LIP mode's: Solver12.set_scenes partitions a batch into in
 (srb12_ctx_set_scenes; inputs from workload.make_scenes12), and Rollout12 is the closed-loop rollout on the
 device (csrc/srb12_sim.hip, srb12_rollout_device; DESIGN.md sections 9 and 10.4).  Neighbour plans (Plans12,
 srb12_plans): Solver12.solve / solve_device take nbr_plan and return plan, Solver12.solve_coupled_device is the
-Jacobi driver over the plans, and Rollout12(plans=True) feeds last cycle's plans forward.
+Jacobi driver over the plans, and Rollout12(plans=True) feeds last cycle's plans forward.  Moving
+obstacles (srb_moving): obs_vel / obs_horizon on Solver12.solve, solve_device, solve_coupled_device
+and Rollout12, Solver12.advance_obstacles_device; velocities from workload.obstacle_velocities.
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ import ctypes
 
 import numpy as np
 
-from . import _check, _check_plan_array, _dp, _ip, _p, lib, workload
+from . import Moving, _check, _check_plan_array, _check_vel_array, _dp, _ip, _p, lib, workload
 
 _p12_fields = [("N", ctypes.c_int), ("K_obs", ctypes.c_int), ("K_nbr", ctypes.c_int),
                ("Ts", ctypes.c_double), ("mass", ctypes.c_double), ("Ib", ctypes.c_double * 9),
@@ -110,8 +112,25 @@ def _lib():
         L.srb12_rollout_plans_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12),
                                                  ctypes.POINTER(Sim12), ctypes.POINTER(Plans12), ctypes.c_int,
                                                  ctypes.c_void_p]
+        L.srb12_solve_batch_moving.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12),
+                                               ctypes.POINTER(Plans12), ctypes.POINTER(Moving)]
+        L.srb12_solve_batch_moving_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12),
+                                                      ctypes.POINTER(Plans12), ctypes.POINTER(Moving), ctypes.c_void_p]
+        L.srb12_obstacles_advance_device.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, _dp, ctypes.c_void_p]
+        L.srb12_rollout_moving_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12),
+                                                  ctypes.POINTER(Sim12), ctypes.POINTER(Plans12), ctypes.POINTER(Moving),
+                                                  ctypes.c_int, ctypes.c_void_p]
         _bound = True
     return L
+
+
+def _moving_args(obs_vel, n_obs, dtype, use_nlp):
+    """The checks of obs_vel that need no context, by name (BatchSolver's; obs_horizon without obs_vel is the
+    library's refusal)."""
+    if not use_nlp:
+        raise ValueError("obs_vel / obs_horizon: the QP-only solve has no obstacle rows")
+    if obs_vel is not None:
+        _check_vel_array(obs_vel, n_obs, dtype)
 
 
 def default_params(N: int = 10, **overrides) -> Params12:
@@ -182,12 +201,14 @@ class Solver12:
             pass
 
     def solve(self, x0, xref, foot, contact, obstacles=None, nbr_state=None, agent_offset: int = 0, nbr_plan=None,
-              plan_selection: bool = False):
+              plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False):
         """Host numpy: x0 [A,12], xref [A,N,12], foot [A,N,4,3], contact [A,N,4] int.  Returns
         dict x_qp, x [A, 24N+1], obj, status [A,2], iters [A,2], sel [A, Ko+Kn], plan [A,N,2] (the (x, y) of
         X at every grid).  nbr_plan ([n_all][N][2], float64, C-contiguous) makes the neighbour rows follow the
         neighbours' plans instead of the constant-velocity guess; plan_selection selects the neighbours by
-        closest predicted approach over the horizon (needs nbr_plan)."""
+        closest predicted approach over the horizon (needs nbr_plan).  obs_vel ([n_obs][2], float64, C-contiguous): the
+        obstacles move at these velocities over the horizon (srb12_solve_batch_moving); obs_horizon=True additionally
+        selects the static columns by closest predicted approach (needs obs_vel)."""
         p = self.params
         x0 = np.ascontiguousarray(x0, np.float64); A = x0.shape[0]
         xref = np.ascontiguousarray(xref, np.float64); foot = np.ascontiguousarray(foot, np.float64)
@@ -207,16 +228,24 @@ class Solver12:
             _check_plan_array(nbr_plan, (nb.shape[0] if nb is not None else len(nbr_plan), p.N, 2), "nbr_plan", np.float64)
         out["plan"] = np.zeros((A, p.N, 2))
         pl = Plans12(_p(nbr_plan) if nbr_plan is not None else None, _p(out["plan"]), 1 if plan_selection else 0, None)
+        if obs_vel is not None or obs_horizon:
+            _moving_args(obs_vel, ob.shape[0], np.float64, p.use_nlp)
+            mv = Moving(_p(obs_vel) if obs_vel is not None else None, int(bool(obs_horizon)), None)
+            _check(_lib().srb12_solve_batch_moving(self._h, A, ctypes.byref(b), ctypes.byref(pl), ctypes.byref(mv)))
+            return out
         _check(_lib().srb12_solve_batch_plans(self._h, A, ctypes.byref(b), ctypes.byref(pl)))
         return out
 
     def solve_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, agent_offset: int = 0, stream=None,
-                     obstacles_version: int = 0, nbr_plan=None, plan_selection: bool = False, plan=None):
+                     obstacles_version: int = 0, nbr_plan=None, plan_selection: bool = False, plan=None, obs_vel=None,
+                     obs_horizon: bool = False):
         """torch tensors on this device (float64 / int32), contiguous; out holds x_qp (or None), x, obj,
         status, iters and optionally sel [A, Ko+Kn] and plan [A, N, 2] (written when the key is present; the
         `plan` argument overrides it).  nbr_plan ([n_all][N][2] float64, contiguous): the neighbours' plans for the
         inter-agent rows (None: constant velocity), must not overlap plan; plan_selection: the neighbours by
-        closest predicted approach (needs nbr_plan).  Asynchronous on `stream` (default: torch's current)."""
+        closest predicted approach (needs nbr_plan).  obs_vel ([n_obs][2] float64, contiguous): the obstacles'
+        velocities (srb12_solve_batch_moving_device; needs obstacles_version 0); obs_horizon=True selects the static
+        columns by closest predicted approach (needs obs_vel).  Asynchronous on `stream` (default: torch's current)."""
         def dptr(t):
             return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
 
@@ -244,7 +273,16 @@ class Solver12:
                               "nbr_plan", torch.float64)
         if plan is not None:
             _check_plan_array(plan, (A, N, 2), "plan", torch.float64)
-        if nbr_plan is None and plan is None and not plan_selection:
+        no_plans = nbr_plan is None and plan is None and not plan_selection
+        if obs_vel is not None or obs_horizon:
+            _moving_args(obs_vel, 0 if obstacles is None else obstacles.shape[0], torch.float64,
+                         self.params.use_nlp)
+            mv = Moving(dptr(obs_vel), int(bool(obs_horizon)), None)
+            pl = None if no_plans else ctypes.byref(Plans12(dptr(nbr_plan), dptr(plan), 1 if plan_selection else 0, None))
+            _check(_lib().srb12_solve_batch_moving_device(self._h, A, ctypes.byref(b), pl, ctypes.byref(mv),
+                                                          self._stream(stream)))
+            return
+        if no_plans:
             _check(_lib().srb12_solve_batch_device(self._h, A, ctypes.byref(b), self._stream(stream)))
             return
         pl = Plans12(dptr(nbr_plan), dptr(plan), 1 if plan_selection else 0, None)
@@ -260,9 +298,20 @@ class Solver12:
         _check(_lib().srb12_shift_plans_device(self._h, A, ctypes.cast(ctypes.c_void_p(plan.data_ptr()), _dp), int(grids),
                                                ctypes.cast(ctypes.c_void_p(table.data_ptr()), _dp), self._stream(stream)))
 
+    def advance_obstacles_device(self, obstacles, obs_vel, stream=None):
+        """One control cycle (4 grids) of a moving obstacle table, in place (srb12_obstacles_advance_device):
+        obstacles[i] += obs_vel[i] * (Ts * 4).  Both [n_obs][2] float64 tensors on this solver's device."""
+        import torch
+        n = obstacles.shape[0] if hasattr(obstacles, "shape") and len(obstacles.shape) else -1
+        _check_vel_array(obstacles, n, torch.float64, "obstacles")
+        _check_vel_array(obs_vel, n, torch.float64)
+        _check(_lib().srb12_obstacles_advance_device(self._h, n, ctypes.cast(ctypes.c_void_p(obstacles.data_ptr()), _dp),
+                                                     ctypes.cast(ctypes.c_void_p(obs_vel.data_ptr()), _dp),
+                                                     self._stream(stream)))
+
     def solve_coupled_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, outer: int = 2, exchange=None,
                              nbr_plan=None, agent_offset: int = 0, stream=None, obstacles_version: int = 0,
-                             plan_selection: bool = False):
+                             plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False):
         """Jacobi iteration over the agents' plans (BatchSolver.solve_coupled_device for the 12-state body):
         `outer` solves of the same cycle, each against the plans the agents wrote in the round before.  Round 0
         solves against nbr_plan (None: the constant-velocity rows); every later round r reads table =
@@ -270,7 +319,8 @@ class Solver12:
         team, agent_offset 0) that plan tensor itself.  The plans ping-pong between out["plan"] ([A][N][2],
         required) and a second buffer of this solver; the last round's results are in `out`.  Returns
         plan_change, a device tensor [outer - 1]: max |plan_r - plan_{r-1}| per round (torch reductions; nothing
-        synchronises with the host inside the loop).  plan_selection applies to every round that has a table."""
+        synchronises with the host inside the loop).  plan_selection applies to every round that has a table; obs_vel
+        and obs_horizon as solve_device (every round solves against the same moving table)."""
         import torch
         outer = int(outer)
         if outer < 1:
@@ -296,7 +346,8 @@ class Solver12:
                     table = exchange(prev) if exchange is not None else prev
                 self.solve_device(x0, xref, foot, contact, obstacles, nbr_state, out, agent_offset=agent_offset,
                                   stream=stream, obstacles_version=obstacles_version, nbr_plan=table,
-                                  plan_selection=plan_selection and table is not None, plan=cur)
+                                  plan_selection=plan_selection and table is not None, plan=cur, obs_vel=obs_vel,
+                                  obs_horizon=obs_horizon)
                 if r > 0:
                     change[r - 1] = (cur - prev).abs().max()
                 prev = cur
@@ -344,12 +395,16 @@ class Rollout12:
                 by one gait domain (srb12_plans.nbr_plan) instead of the constant-velocity guess; step() shifts
                 with srb12_shift_plans_device, run() is srb12_rollout_plans_device, the same bits
     plan_selection  with plans: the neighbours by closest predicted approach, in every cycle that has a table
+    obs_vel     [n_obs][2] or None: the obstacles' velocities (m/s).  The rollout then clones `obstacles` (it moves the
+                table: from the second cycle on by obs_vel * (Ts * 4) before the metrics), reset() restores the clone,
+                results()["obstacles"] is the current table; run() is srb12_rollout_moving_device
+    obs_horizon True: the static columns by closest predicted approach over the horizon (needs obs_vel)
     A whole team on one GPU (the SRB-12 mode has no sharded stepping).  All tensors are
     float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
 
     def __init__(self, solver, goal, vref: float = 0.27, phase=None, gait: str = "trot", log_x: bool = False,
                  obstacles=None, hcom: float = workload.HCOM12, yaw_step: float = 0.1, hold_radius: float = 0.05,
-                 plans: bool = False, plan_selection: bool = False):
+                 plans: bool = False, plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False):
         import torch
         from .rollout import _check_tensor
         self.solver = solver
@@ -371,6 +426,17 @@ class Rollout12:
             _check_tensor(obstacles, (obstacles.shape[0], 2), "obstacles", torch.float64, self.device)
             if obstacles.shape[0] == 0:
                 obstacles = None
+        if obs_vel is not None:
+            if obstacles is None:
+                raise ValueError("obs_vel needs obstacles (one velocity row per obstacle row)")
+            _check_vel_array(obs_vel, obstacles.shape[0], torch.float64)
+            if obs_vel.device != self.device:
+                raise ValueError(f"obs_vel must be on {self.device}, got {obs_vel.device}")
+            self.obstacles0 = obstacles
+            obstacles = obstacles.clone()            # the rollout moves its table; the caller's stays
+        elif obs_horizon:
+            raise ValueError("obs_horizon needs obs_vel (the horizon-aware obstacle selection reads the velocities)")
+        self.obs_vel, self.obs_horizon = obs_vel, bool(obs_horizon)
         self.goal, self.phase, self.obstacles = goal, phase, obstacles
         self.vref, self.gait, self.log_x = float(vref), gait, bool(log_x)
         self.hcom = float(hcom)
@@ -436,11 +502,14 @@ class Rollout12:
 
     # ------------------------------------------------------------------ driving
     def reset(self, state):
-        """Start state [A][12] (p, roll/pitch/yaw, v, omega); the cycle count and the logs start over."""
+        """Start state [A][12] (p, roll/pitch/yaw, v, omega); the cycle count and the logs start over; with obs_vel
+        the start table is restored (torch copies on torch's current stream)."""
         import torch
         from .rollout import _check_tensor
         _check_tensor(state, (self.A, 12), "state", torch.float64, self.device)
         self.state.copy_(state)
+        if self.obs_vel is not None:
+            self.obstacles.copy_(self.obstacles0)    # the start table
         self.c = 0
         self.flushed = True
         self._ready = True
@@ -461,10 +530,13 @@ class Rollout12:
         s = self.solver
         self._reserve(self.c + 1)
         self.advance(stream)
+        if self.obs_vel is not None and self.c > 0:          # the obstacles' cycle, before the metrics read the table
+            s.advance_obstacles_device(self.obstacles, self.obs_vel, stream)
         _check(_lib().srb12_sim_metrics_device(s._h, self.A, ctypes.byref(self._sim()), self.c, s._stream(stream)))
         table = self.plan_table if self.plans and self.c > 0 else None
         s.solve_device(self.x0, self.xref, self.foot, self.contact, self.obstacles, self.last_state, self.out,
-                       stream=stream, nbr_plan=table, plan_selection=self.plan_selection and table is not None)
+                       stream=stream, nbr_plan=table, plan_selection=self.plan_selection and table is not None,
+                       obs_vel=self.obs_vel, obs_horizon=self.obs_horizon)
         if self.plans:
             s.shift_plans_device(self.out["plan"], self.plan_table, SHIFT_GRIDS, stream=stream)
         self.c += 1
@@ -487,7 +559,14 @@ class Rollout12:
         b = Batch12(None, None, None, None, _dptr(self.obstacles), None,
                     0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                     None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]), None, 0)
-        if self.plans:
+        if self.obs_vel is not None:
+            pl = None
+            if self.plans:
+                pl = ctypes.byref(Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table)))
+            mv = Moving(_dptr(self.obs_vel), int(self.obs_horizon), _dptr(self.obstacles))
+            _check(_lib().srb12_rollout_moving_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl,
+                                                      ctypes.byref(mv), T, s._stream(stream)))
+        elif self.plans:
             pl = Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table))
             _check(_lib().srb12_rollout_plans_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()),
                                                      ctypes.byref(pl), T, s._stream(stream)))
@@ -501,7 +580,8 @@ class Rollout12:
         """The logs and metrics so far, as tensors (views of this object's buffers; asynchronous like the
         launches -- synchronise before reading on the host): traj [T+1][A][12], status / iters [T][A][2],
         x [T][A][24N+1] (log_x), state [A][12] (the end state), cycles, and d_obs, d_agent, min_d_obs,
-        min_d_agent, fail_cycle, distance_to_fail [A]."""
+        min_d_agent, fail_cycle, distance_to_fail [A]; with obs_vel, obstacles [n_obs][2] (the current table: the rows
+        as the last cycle saw them)."""
         if not self._ready:
             raise RuntimeError("Rollout12.results before reset(state)")
         T = self.c
@@ -515,6 +595,8 @@ class Rollout12:
                    state=self.state, **self.metrics)
         if self.log_x:
             out["x"] = self.x_log[:T]
+        if self.obs_vel is not None:
+            out["obstacles"] = self.obstacles
         return out
 
     def scene_results(self, stream=None):

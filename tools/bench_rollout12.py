@@ -20,6 +20,15 @@ context of its own); the separation with the plans on beside the plans-off rollo
 per Jacobi round of Solver12.solve_coupled_device on the 1024-agent batch.
 
     python tools/bench_rollout12.py --plans --out profiles/bench_rollout12_plans.json
+
+--moving measures the moving obstacles instead (srb_moving), by the same method: the rollout cycle
+(Rollout12.run(T), reset included) with the velocity table off / on / on with the horizon-aware obstacle selection,
+for the 1024-agent team and for the 128 x 8 scene batch; and the separation table of 10.6 over T cycles of the moved
+world (velocities workload.obstacle_velocities(n_obs, 1234, --vmax)): the solver aware of the velocities, with and
+without the horizon selection, against obs_vel=None -- a solver that re-reads the moved table every cycle and takes it
+for static.
+
+    python tools/bench_rollout12.py --moving [--vmax 1.0] [--out profiles/bench_rollout12_moving.json]
 """
 import argparse
 import ctypes
@@ -56,6 +65,90 @@ def safety_of(r):
             "non_optimal_frac_per_cycle": [float(1.0 - (np.isin(s[:, 0], (0, 4)) & (s[:, 1] == 0)).mean()) for s in st]}
 
 
+def moving(args):
+    """--moving: see the module docstring."""
+    dev = torch.device("cuda", 0)
+    A, N, Ko, Kn, T = args.agents, 10, 3, 8, args.cycles
+    team, scene_obs = 8, 20
+    S = A // team
+    D = lambda v, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(v), dtype=dt, device=dev)
+    p = srb12.default_params(N, K_obs=Ko, K_nbr=Kn)
+    b = workload.make_batch12(A, N, "trot", seed=1234)
+    sb = workload.make_scenes12(S, team, N, "trot", seed=1234, n_obs=scene_obs)
+    goal = D(np.tile(workload.GOAL * np.array([workload.arena_scale(A), 1.0]), (A, 1)))
+    worlds = {}
+    for name, x0, g, phase, ob, scenes in (("one_team", b["x0"], goal, None, b["obstacles"], (0, 0)),
+                                           ("scenes", sb["x0"], D(sb["goal"]), D(sb["phase"], torch.int32), sb["obstacles"],
+                                            (team, scene_obs))):
+        solver = srb12.Solver12(p, x0.shape[0], 0)
+        solver.set_timing(False)
+        solver.set_scenes(*scenes)
+        ob = D(ob)
+        vel = D(workload.obstacle_velocities(ob.shape[0], 1234, args.vmax))
+        mk = lambda v, h: srb12.Rollout12(solver, g, vref=workload.VREF, phase=phase, obstacles=ob, obs_vel=v, obs_horizon=h)
+        worlds[name] = dict(solver=solver, x0=D(x0), ob=ob, vel=vel, goal=g, phase=phase,
+                            rolls={"off": mk(None, False), "on": mk(vel, False), "on_horizon": mk(vel, True)})
+
+    def cycle(w, r):
+        def f():
+            r.reset(w["x0"])
+            r.run(T)
+        return f
+    modes = [(f"{name}_{k}", cycle(w, r)) for name, w in worlds.items() for k, r in w["rolls"].items()]
+    for _ in range(args.warmup):
+        for _, f in modes:
+            f()
+    torch.cuda.synchronize(dev)
+    ms = {name: [] for name, _ in modes}
+    for _ in range(args.rounds):
+        for name, f in modes:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize(dev)
+            ms[name].append(1e3 * (time.perf_counter() - t0) / T)
+
+    def stats(r):
+        res = r.results()
+        torch.cuda.synchronize(dev)
+        d, fc, st = res["min_d_obs"].cpu().numpy(), res["fail_cycle"].cpu().numpy(), res["status"].cpu().numpy()
+        ok = np.isin(st[..., 0], (0, 4)) & (st[..., 1] == 0)
+        return {"min_d_obs": {"smallest": float(d.min()), "median": float(np.median(d))},
+                "agents_inside_0.5m": {"at_cycle_0": int((fc == 0).sum()), "later": int((fc > 0).sum()),
+                                       "never": int((fc < 0).sum())},
+                "non_converged_solves": int((~ok).sum()), "solves": int(ok.size)}
+    sep = {}
+    for name, w in worlds.items():
+        sep[name] = {}
+        for k, label in (("on", "aware"), ("on_horizon", "aware_horizon_selection")):
+            cycle(w, w["rolls"][k])()
+            sep[name][label] = stats(w["rolls"][k])
+        table = w["ob"].clone()                       # the unaware solver: the table moves, the solver is not told
+        blind = srb12.Rollout12(w["solver"], w["goal"], vref=workload.VREF, phase=w["phase"], obstacles=table)
+        blind.reset(w["x0"])
+        for c in range(T):
+            if c > 0:
+                w["solver"].advance_obstacles_device(table, w["vel"])
+            blind.step()
+        sep[name]["obs_vel_none"] = stats(blind)
+    spread = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+    res = {"tool": "tools/bench_rollout12.py --moving", "agents": A, "horizon": N, "K_obs": Ko, "K_nbr": Kn,
+           "vmax": args.vmax, "scenes": {"n_scenes": S, "scene_agents": team, "scene_obs": scene_obs},
+           "one_team_obstacles": int(worlds["one_team"]["ob"].shape[0]), "cycles_per_window": T, "rounds": args.rounds,
+           "n_gpus": 1, "ms_per_cycle": {k: spread(v) for k, v in ms.items()},
+           "separation_over_cycles": T, "separation": sep,
+           "note": "ms_per_cycle: Rollout12.run(T), reset included, per cycle; *_off no velocity table, *_on the table, "
+                   "*_on_horizon the table with the horizon-aware obstacle selection.  separation: one run each, the same "
+                   "moving world; obs_vel_none re-reads the moved table every cycle and solves it as static."}
+    print(json.dumps(res), flush=True)
+    out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "bench_rollout12_moving.json")
+    if out:
+        with open(out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    for w in worlds.values():
+        w["solver"].close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=20, help="T: cycles per window")
@@ -65,9 +158,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--plans", action="store_true", help="add the plans-on modes (see above)")
     ap.add_argument("--outer", type=int, default=4, help="--plans: Jacobi rounds of the plan_change measurement")
+    ap.add_argument("--moving", action="store_true", help="the moving-obstacle measurement alone (see above)")
+    ap.add_argument("--vmax", type=float, default=1.0, help="--moving: the obstacles' top speed (m/s)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_rollout12.py needs a GPU (no CPU fallback)")
+    if args.moving:
+        return moving(args)
     dev = torch.device("cuda", 0)
     A, N, Ko, Kn, T = args.agents, 10, 3, 8, args.cycles
     team, scene_obs = 8, 20
