@@ -479,6 +479,81 @@ def test_srb12_tables_shorter_than_k_vs_oracle(n_obs, n_all):
     np.testing.assert_allclose(out["x"][:, 12 * N:], r["x"][:, 12 * N:], atol=1e-4)
 
 
+def _grid_tables(b, n_obs, n_all, off, seed):
+    """Tables long enough for the selection grid at the SRB-12 selection context's default thresholds, around the
+    batch b: rows spread at about one per 12 m^2 (a few within reach of every agent, none closer than 2 m to an
+    agent's start), a collinear stretch, a block of NaN rows, and the batch's agents at rows off .. off + A of the
+    snapshot."""
+    rng = np.random.default_rng(seed)
+    A = b["x0"].shape[0]
+    pos = b["x0"][:, :2]
+
+    def spread(n):
+        t = rng.uniform(-160, 170, (n, 2))
+        t[1000:1400, 1] = 6.0                                 # a collinear stretch, 2 m beside the arena (|y| <= 4)
+        near = (np.linalg.norm(t[:, None] - pos[None], axis=2) < 2.0).any(1)
+        t[near, 1] = rng.uniform(6.5, 7.5, near.sum())
+        assert not (np.linalg.norm(t[:, None] - pos[None], axis=2) < 2.0).any()
+        t[2000:2100] = np.nan
+        return t
+    ob = spread(n_obs)
+    nb = np.zeros((n_all, 4))
+    nb[:, :2] = spread(n_all)
+    nb[off:off + A] = b["nbr_state"]
+    return ob, nb
+
+
+def _sel_want(b, ob, nb, off, Ko=3, Kn=8):
+    op = oracle.params(N, 2, K_obs=Ko, K_nbr=Kn)
+    return np.array([oracle.select_idx(op, np.array([x[0], x[6], x[1], x[7]]), ob, nb, off + a)
+                     for a, x in enumerate(b["x0"])], np.int32).reshape(len(b["x0"]), -1)
+
+
+@pytest.mark.gpu
+def test_srb12_selection_grid_default_thresholds():
+    """The SRB-12 solve selects through its own selection context, whose thresholds are the defaults: an obstacle
+    table and a neighbour snapshot of 8192 rows and more go through the selection grid.  The selected rows are
+    oracle.select_idx's for every agent."""
+    _gpu()
+    A, Nh, off = 16, N, 4100
+    b, _ = _batch(A, "trot", 41)
+    ob, nb = _grid_tables(b, 8192, 8300, off, 42)
+    s = srb12.Solver12(srb12.default_params(Nh, K_obs=3, K_nbr=8), A)
+    out = s.solve(b["x0"], b["xref"], b["foot"], b["contact"], ob, nb, agent_offset=off)
+    s.close()
+    np.testing.assert_array_equal(out["sel"], _sel_want(b, ob, nb, off))
+    assert _opt(out["status"]).all(), out["status"]
+
+
+@pytest.mark.gpu
+def test_srb12_selection_grid_versioned_obstacles():
+    """4096 obstacle rows with obstacles_version != 0 (the static threshold): the grid is built, kept for a second
+    call with the same version, and rebuilt for version 2 with the table reversed."""
+    torch = _gpu()
+    A, Nh = 16, N
+    b, _ = _batch(A, "trot", 43)
+    ob, _ = _grid_tables(b, 4096, 4096, 0, 44)
+    prm = srb12.default_params(Nh, K_obs=3, K_nbr=8)
+    s = srb12.Solver12(prm, A)
+    dev = torch.device("cuda:0")
+    T = lambda v, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(v), dtype=dt, device=dev)
+    x0, xref, foot, contact = T(b["x0"]), T(b["xref"]), T(b["foot"]), T(b["contact"], torch.int32)
+    tob, tnb = T(ob), T(b["nbr_state"])
+    for ver, table in ((1, ob), (1, ob), (2, ob[::-1].copy())):
+        tob.copy_(T(table))
+        o = dict(x_qp=torch.zeros((A, prm.nv), dtype=torch.float64, device=dev),
+                 x=torch.zeros((A, prm.nv), dtype=torch.float64, device=dev),
+                 obj=torch.zeros(A, dtype=torch.float64, device=dev),
+                 status=torch.zeros((A, 2), dtype=torch.int32, device=dev),
+                 iters=torch.zeros((A, 2), dtype=torch.int32, device=dev),
+                 sel=torch.full((A, 11), -7, dtype=torch.int32, device=dev))
+        s.solve_device(x0, xref, foot, contact, tob, tnb, o, obstacles_version=ver)
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(o["sel"].cpu().numpy(), _sel_want(b, table, b["nbr_state"], 0), err_msg=f"version {ver}")
+        assert _opt(o["status"].cpu().numpy()).all()
+    s.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("gait,tol_final", [("stand", 1e-8), ("trot", 1e-8), ("stand", 1e-9)])
 def test_srb12_gpu_forces_within_1e4_of_exact_optimum_1024(gait, tol_final):
