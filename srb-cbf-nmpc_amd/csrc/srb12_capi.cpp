@@ -207,8 +207,7 @@ static int check_scenes12(const srb12_ctx *c, int n_agents, const srb12_batch *d
 // for the first cycle that has a table)
 static int check_plans12(const srb12_batch *b, const srb12_plans *pl, bool rollout)
 {
-    if (pl && pl->struct_size != (int)sizeof(srb12_plans))
-        return srb_internal_fail(SRB_ERR_ARG, "srb12_plans.struct_size != sizeof(srb12_plans): caller built against another ABI");
+    if (int rc = srb_check_struct(pl, "srb12_plans")) return rc;
     if (!b || !pl) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (pl->plan_selection != 0 && pl->plan_selection != 1)
         return srb_internal_fail(SRB_ERR_ARG, "srb12_plans.plan_selection: 0 (snapshot) or 1 (closest predicted approach)");
@@ -226,34 +225,10 @@ static int check_plans12(const srb12_batch *b, const srb12_plans *pl, bool rollo
     return SRB_OK;
 }
 
-static bool overlap12(const double *a, size_t na, const double *b, size_t nb)
-{
-    return a && b && a < b + nb && b < a + na;
-}
-
-// The argument errors of srb_moving that need no context, before anything is launched (b may be null: the caller
-// reports that).  rollout: the driver moves the table, so it needs the writable pointer to batch.obstacles.
+// the checks of srb_moving that need no context (srb_host.h), with this mode's names in the messages
 static int check_moving12(const srb_moving *mv, const srb12_batch *b, bool rollout)
 {
-    if (!mv) return SRB_OK;
-    if (mv->struct_size != (int)sizeof(srb_moving))
-        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.struct_size != sizeof(srb_moving): caller built against another ABI");
-    if (mv->horizon_selection != 0 && mv->horizon_selection != 1)
-        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.horizon_selection: 0 (nearest now) or 1 (closest predicted approach)");
-    if (mv->horizon_selection && !mv->obs_vel)
-        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.horizon_selection = 1 needs obs_vel (the horizon-aware selection "
-                                              "reads the velocity table)");
-    if (!mv->obs_vel || !b || b->struct_size != (int)sizeof(srb12_batch)) return SRB_OK;
-    if (b->obstacles_version != 0)
-        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.obs_vel with obstacles_version != 0: a kept selection grid of a "
-                                              "moving table is stale (pass version 0)");
-    if (rollout && !mv->obstacles)
-        return srb_internal_fail(SRB_ERR_ARG, "srb12_rollout_moving_device: srb_moving.obstacles missing (the driver moves "
-                                              "the table in place)");
-    if (rollout && mv->obstacles != b->obstacles)
-        return srb_internal_fail(SRB_ERR_ARG, "srb12_rollout_moving_device: srb_moving.obstacles is not srb12_batch.obstacles "
-                                              "(the solve and the metrics read the table the driver moves)");
-    return SRB_OK;
+    return srb_check_moving(mv, b, rollout, "srb12_rollout_moving_device", "srb12_batch");
 }
 
 // pl: the plan members of this launch (NULL: none, the launch of srb12_solve_batch[_device] as ever); obs_vel /
@@ -274,8 +249,8 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         return srb_internal_fail(SRB_ERR_ARG, "nbr_plan: agent_offset + n_agents exceeds n_all (the plan table's rows)");
     if (pl && pl->plan) {
         const size_t rows = (size_t)n_agents * 2 * p->N;
-        if (overlap12(pl->plan, rows, pl->nbr_plan, (size_t)(d->n_all > 0 ? d->n_all : 0) * 2 * p->N) ||
-            overlap12(pl->plan, rows, pl->plan_table, rows))
+        if (srb_overlap(pl->plan, rows, pl->nbr_plan, (size_t)(d->n_all > 0 ? d->n_all : 0) * 2 * p->N) ||
+            srb_overlap(pl->plan, rows, pl->plan_table, rows))
             return srb_internal_fail(SRB_ERR_ARG, "plan overlaps the nbr_plan table or plan_table (use two buffers)");
     }
     if (int rc = check_scenes12(c, n_agents, d)) return rc;
@@ -322,8 +297,7 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
 static int solve_device12(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl, bool plans, void *stream,
                           const srb_moving *mv = nullptr)
 {
-    if (d && d->struct_size != (int)sizeof(srb12_batch))
-        return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    if (int rc = srb_check_struct(d, "srb12_batch")) return rc;
     if (int rc0 = check_moving12(mv, d, false)) return rc0;
     if (plans)
         if (int rc = check_plans12(d, pl, false)) return rc;
@@ -354,22 +328,11 @@ extern "C" int srb12_solve_batch_moving_device(srb12_ctx *c, int n_agents, const
     return solve_device12(c, n_agents, d, pl, pl != nullptr, stream, mv);
 }
 
-static int reserve(void **buf, size_t *cap, size_t bytes, srb12_ctx *c)
-{
-    if (bytes <= *cap) return SRB_OK;
-    if (int rc = c->order.wait_idle()) return rc;
-    if (*buf) HIPCHK(hipFree(*buf));
-    HIPCHK(hipMalloc(buf, bytes));
-    *cap = bytes;
-    return SRB_OK;
-}
-
 // hp: the host plan members (NULL: srb12_solve_batch); the table and the plans are staged like the other buffers
 static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp, bool plans,
                         const srb_moving *hmv = nullptr)
 {
-    if (h && h->struct_size != (int)sizeof(srb12_batch))
-        return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    if (int rc = srb_check_struct(h, "srb12_batch")) return rc;
     if (int rc0 = check_moving12(hmv, h, false)) return rc0;
     if (plans)
         if (int rc = check_plans12(h, hp, false)) return rc;
@@ -395,16 +358,12 @@ static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const 
     d.sel = h->sel ? c->sel : nullptr;
     d.obstacles = nullptr; d.nbr_state = nullptr;
     if (h->n_obs > 0 && h->obstacles) {
-        size_t cap = c->cap_obs;
-        if (int rc = reserve((void **)&c->obstacles, &cap, (size_t)h->n_obs * 2 * sizeof(double), c)) return rc;
-        c->cap_obs = cap;
+        if (int rc = srb_stage_reserve(c->order, c->obstacles, c->cap_obs, (size_t)h->n_obs * 2 * sizeof(double))) return rc;
         HIPCHK(hipMemcpyAsync(c->obstacles, h->obstacles, (size_t)h->n_obs * 2 * sizeof(double), hipMemcpyHostToDevice, s));
         d.obstacles = c->obstacles;
     }
     if (h->n_all > 0 && h->nbr_state) {
-        size_t cap = c->cap_nbr;
-        if (int rc = reserve((void **)&c->nbr, &cap, (size_t)h->n_all * 4 * sizeof(double), c)) return rc;
-        c->cap_nbr = cap;
+        if (int rc = srb_stage_reserve(c->order, c->nbr, c->cap_nbr, (size_t)h->n_all * 4 * sizeof(double))) return rc;
         HIPCHK(hipMemcpyAsync(c->nbr, h->nbr_state, (size_t)h->n_all * 4 * sizeof(double), hipMemcpyHostToDevice, s));
         d.nbr_state = c->nbr;
     }
@@ -418,9 +377,7 @@ static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const 
             if (c->p.K_nbr > 0 && (h->agent_offset < 0 || h->agent_offset + n_agents > h->n_all))
                 return srb_internal_fail(SRB_ERR_ARG, "nbr_plan: agent_offset + n_agents exceeds n_all (the plan table's rows)");
             const size_t bytes = (size_t)h->n_all * 2 * N * sizeof(double);
-            size_t cap = c->cap_plan;
-            if (int rc = reserve((void **)&c->nbr_plan, &cap, bytes, c)) return rc;
-            c->cap_plan = cap;
+            if (int rc = srb_stage_reserve(c->order, c->nbr_plan, c->cap_plan, bytes)) return rc;
             HIPCHK(hipMemcpyAsync(c->nbr_plan, hp->nbr_plan, bytes, hipMemcpyHostToDevice, s));
             dp.nbr_plan = c->nbr_plan;
         }
@@ -433,9 +390,7 @@ static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const 
     const double *vel = nullptr;
     if (hmv && hmv->obs_vel && d.obstacles) {
         const size_t bytes = (size_t)h->n_obs * 2 * sizeof(double);
-        size_t cap = c->cap_vel;
-        if (int rc = reserve((void **)&c->obs_vel, &cap, bytes, c)) return rc;
-        c->cap_vel = cap;
+        if (int rc = srb_stage_reserve(c->order, c->obs_vel, c->cap_vel, bytes)) return rc;
         HIPCHK(hipMemcpyAsync(c->obs_vel, hmv->obs_vel, bytes, hipMemcpyHostToDevice, s));
         vel = c->obs_vel;
     }
@@ -511,8 +466,7 @@ extern "C" int srb12_ctx_scenes(srb12_ctx *c, int *scene_agents, int *scene_obs)
 // (struct_size, c_first, goal, x), as check_sim of srb_capi.cpp
 static int check_sim12(const srb12_sim *d, int cycle, bool advance)
 {
-    if (d && d->struct_size != (int)sizeof(srb12_sim))
-        return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.struct_size != sizeof(srb12_sim): caller built against another ABI");
+    if (int rc = srb_check_struct(d, "srb12_sim")) return rc;
     if (!d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (cycle < d->c_first) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim: cycle precedes c_first");
     if (!advance) return SRB_OK;
@@ -562,11 +516,9 @@ static int sim12_call(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle,
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->order.order_after_last(s);
-    if (!rc) rc = advance ? launch_advance12(c, n_agents, d, cycle, s) : launch_metrics12(c, n_agents, d, cycle, s);
-    if (!rc) rc = c->order.mark_done(s);
-    return rc;
+    return c->order.run(c->device, s, [&] {
+        return advance ? launch_advance12(c, n_agents, d, cycle, s) : launch_metrics12(c, n_agents, d, cycle, s);
+    });
 }
 
 extern "C" int srb12_sim_advance_device(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream)
@@ -598,24 +550,11 @@ extern "C" int srb12_shift_plans_device(srb12_ctx *c, int n_agents, const double
     if (!c) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (c->p.N < 2) return srb_internal_fail(SRB_ERR_ARG, "srb12_shift_plans_device needs N >= 2 (the last finite difference)");
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
-    if (overlap12(plan, (size_t)n_agents * 2 * c->p.N, table, (size_t)n_agents * 2 * c->p.N))
+    if (srb_overlap(plan, (size_t)n_agents * 2 * c->p.N, table, (size_t)n_agents * 2 * c->p.N))
         return srb_internal_fail(SRB_ERR_ARG, "srb12_shift_plans_device: plan and table overlap");
     if (n_agents == 0) return SRB_OK;
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->order.order_after_last(s);
-    if (!rc) rc = launch_shift12(c, n_agents, plan, grids, table, s);
-    if (!rc) rc = c->order.mark_done(s);
-    return rc;
-}
-
-// one control cycle of an obstacle table (srb_obstacles_advance_kernel, 4 grids of this context's Ts): launch only
-static int launch_obstacles12(srb12_ctx *c, int n_obs, double *obstacles, const double *obs_vel, hipStream_t s)
-{
-    hipLaunchKernelGGL(srb_obstacles_advance_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, s, n_obs, c->p.Ts, obstacles,
-                       obs_vel);
-    HIPCHK(hipGetLastError());
-    return SRB_OK;
+    return c->order.run(c->device, s, [&] { return launch_shift12(c, n_agents, plan, grids, table, s); });
 }
 
 extern "C" int srb12_obstacles_advance_device(srb12_ctx *c, int n_obs, double *obstacles, const double *obs_vel, void *stream)
@@ -626,11 +565,7 @@ extern "C" int srb12_obstacles_advance_device(srb12_ctx *c, int n_obs, double *o
     if (!obstacles || !obs_vel)
         return srb_internal_fail(SRB_ERR_ARG, "srb12_obstacles_advance_device: obstacles / obs_vel missing");
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->order.order_after_last(s);
-    if (!rc) rc = launch_obstacles12(c, n_obs, obstacles, obs_vel, s);
-    if (!rc) rc = c->order.mark_done(s);
-    return rc;
+    return c->order.run(c->device, s, [&] { return srb_launch_obstacles_advance(n_obs, c->p.Ts, obstacles, obs_vel, s); });
 }
 
 // pl: the plans fed forward (srb12_rollout_plans_device), or NULL (srb12_rollout_device: today's launches); mv: the
@@ -638,11 +573,10 @@ extern "C" int srb12_obstacles_advance_device(srb12_ctx *c, int n_obs, double *o
 static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, const srb12_plans *pl,
                      bool plans, int cycles, void *stream, const srb_moving *mv = nullptr)
 {
-    if (b && b->struct_size != (int)sizeof(srb12_batch))
-        return srb_internal_fail(SRB_ERR_ARG, "srb12_batch.struct_size != sizeof(srb12_batch): caller built against another ABI");
+    if (int rc = srb_check_struct(b, "srb12_batch")) return rc;
     if (int rc0 = check_moving12(mv, b, true)) return rc0;
-    if (plans && pl && pl->struct_size != (int)sizeof(srb12_plans))
-        return srb_internal_fail(SRB_ERR_ARG, "srb12_plans.struct_size != sizeof(srb12_plans): caller built against another ABI");
+    if (plans)
+        if (int rc = srb_check_struct(pl, "srb12_plans")) return rc;
     // (the layout and null checks of check_sim12 only: the driver's first cycle is c_first itself)
     if (int rc = check_sim12(d, d && d->struct_size == (int)sizeof(srb12_sim) ? d->c_first : 0, false)) return rc;
     if (!b) return srb_internal_fail(SRB_ERR_ARG, "null argument");
@@ -689,7 +623,7 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
         const int cyc = d->c_first + i;
         rc = launch_advance12(c, n_agents, &sim, cyc, s);
         if (rc || i == cycles) break;
-        if (i > 0 && vel) rc = launch_obstacles12(c, b->n_obs, mv->obstacles, vel, s);
+        if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
         if (!rc) rc = launch_metrics12(c, n_agents, &sim, cyc, s);
         if (!pl) {
             if (!rc) rc = launch12(c, n_agents, &bat, s, nullptr, vel, hsel);

@@ -101,13 +101,13 @@ struct srb_ctx {
     SrbCallOrder order;            // submission-order chaining of the calls on this context
     // device staging
     double *x0, *ref, *foot, *obstacles, *nbr, *x_qp, *x, *obj, *abuf, *alpha;
-    double *nbr_plan, *plan;       // neighbour plan table [cap_plan][N][2], this batch's plans [max_agents][N][2]
-    size_t cap_plan;
+    double *nbr_plan, *plan;       // neighbour plan table (staged), this batch's plans [max_agents][N][2]
+    size_t cap_plan;               // (the cap_* of the staged tables are bytes: srb_stage_reserve)
     int plan_selection;            // SRB_OPT_PLAN_SELECTION: 1 neighbours by closest predicted approach
     int *status, *iters;
     int *sel;                      // [max_agents][2 SRB_KNN_MAX] selected obstacle / neighbour rows
     size_t cap_obs, cap_nbr;
-    double *obs_vel;               // staged obstacle velocities [cap_vel][2] (srb_solve_batch_moving)
+    double *obs_vel;               // staged obstacle velocities (srb_solve_batch_moving)
     size_t cap_vel;
     float knn_ms, solve_ms;
     bool timed;
@@ -504,29 +504,10 @@ static int launch_obs_horizon(srb_ctx *c, int n_agents, const double *x0, const 
     return SRB_OK;
 }
 
-// The argument errors of srb_moving that need no context, before anything is launched (b may be null: the caller
-// reports that).  rollout: the driver moves the table, so it needs the writable pointer to batch.obstacles.
+// the checks of srb_moving that need no context (srb_host.h), with this mode's names in the messages
 static int check_moving(const srb_moving *mv, const srb_batch *b, bool rollout)
 {
-    if (!mv) return SRB_OK;
-    if (mv->struct_size != (int)sizeof(srb_moving))
-        return fail(SRB_ERR_ARG, "srb_moving.struct_size != sizeof(srb_moving): caller built against another ABI");
-    if (mv->horizon_selection != 0 && mv->horizon_selection != 1)
-        return fail(SRB_ERR_ARG, "srb_moving.horizon_selection: 0 (nearest now) or 1 (closest predicted approach)");
-    if (mv->horizon_selection && !mv->obs_vel)
-        return fail(SRB_ERR_ARG, "srb_moving.horizon_selection = 1 needs obs_vel (the horizon-aware selection reads the "
-                                 "velocity table)");
-    if (!mv->obs_vel || !b || b->struct_size != (int)sizeof(srb_batch)) return SRB_OK;
-    if (b->obstacles_version != 0)
-        return fail(SRB_ERR_ARG, "srb_moving.obs_vel with obstacles_version != 0: a kept selection grid of a moving table "
-                                 "is stale (pass version 0)");
-    if (rollout && !mv->obstacles)
-        return fail(SRB_ERR_ARG, "srb_rollout_moving_device: srb_moving.obstacles missing (the driver moves the table in "
-                                 "place)");
-    if (rollout && mv->obstacles != b->obstacles)
-        return fail(SRB_ERR_ARG, "srb_rollout_moving_device: srb_moving.obstacles is not srb_batch.obstacles (the solve and "
-                                 "the metrics read the table the driver moves)");
-    return SRB_OK;
+    return srb_check_moving(mv, b, rollout, "srb_rollout_moving_device", "srb_batch");
 }
 
 // The argument errors of the plan members (srb_batch.nbr_plan / plan), before anything is launched.  select: the
@@ -537,13 +518,9 @@ static int check_plans(srb_ctx *c, int n_agents, const srb_batch *d, bool select
     if (d->nbr_plan && !d->nbr_state) return fail(SRB_ERR_ARG, "nbr_plan needs nbr_state (the selection's snapshot)");
     if (d->nbr_plan && p->K_nbr > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return fail(SRB_ERR_ARG, "nbr_plan: agent_offset + n_agents exceeds n_all (the plan table's rows)");
-    if (d->nbr_plan && d->plan) {
-        const char *t0 = (const char *)d->nbr_plan, *t1 = t0 + (size_t)std::max(d->n_all, 0) * 2 * p->N * sizeof(double);
-        const char *o0 = (const char *)d->plan, *o1 = o0 + (size_t)n_agents * 2 * p->N * sizeof(double);
-        if (o0 < t1 && t0 < o1)
-            return fail(SRB_ERR_ARG, "plan overlaps the nbr_plan table (workgroups read the table while others write their "
-                                     "plans: use two buffers)");
-    }
+    if (srb_overlap(d->plan, (size_t)n_agents * 2 * p->N, d->nbr_plan, (size_t)std::max(d->n_all, 0) * 2 * p->N))
+        return fail(SRB_ERR_ARG, "plan overlaps the nbr_plan table (workgroups read the table while others write their "
+                                 "plans: use two buffers)");
     if (select && c->plan_selection && !d->nbr_plan && d->nbr_state && std::min(p->K_nbr, d->n_all - 1) > 0)
         return fail(SRB_ERR_ARG, "SRB_OPT_PLAN_SELECTION = 1 needs nbr_plan (the horizon-aware selection reads the plan table)");
     return SRB_OK;
@@ -765,9 +742,7 @@ extern "C" int srb_ctx_set_qp_init(srb_ctx *c, int mode)
 
 static int solve_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv, void *stream)
 {
-    // the layout check comes first: it needs no context (tests/test_abi.py runs it without a GPU)
-    if (dev_io && dev_io->struct_size != (int)sizeof(srb_batch))
-        return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    if (int rc0 = srb_check_struct(dev_io, "srb_batch")) return rc0;   // first: it needs no context
     if (int rc0 = check_moving(mv, dev_io, false)) return rc0;
     if (!c || !dev_io) return fail(SRB_ERR_ARG, "null argument");
     hipStream_t s = (hipStream_t)stream;          // NULL: the HIP null stream (ordered with blocking streams)
@@ -795,8 +770,7 @@ extern "C" int srb_solve_batch_moving_device(srb_ctx *c, int n_agents, const srb
 // while the neighbour all-gather is in flight and the neighbours after it (bench.py).
 extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, int tables, void *stream)
 {
-    if (d && d->struct_size != (int)sizeof(srb_batch))
-        return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    if (int rc0 = srb_check_struct(d, "srb_batch")) return rc0;
     if (!c || !d) return fail(SRB_ERR_ARG, "null argument");
     if (tables < 1 || tables > 3) return fail(SRB_ERR_ARG, "tables: 1 (static obstacles), 2 (neighbours) or 3 (both)");
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
@@ -812,14 +786,12 @@ extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, i
     if (int rc0 = check_plans(c, n_agents, d, (tables & 2) != 0)) return rc0;
     const double *nbr_plan = (c->plan_selection && (tables & 2)) ? d->nbr_plan : nullptr;
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->order.order_after_last(s);
     const int ko = (tables & 1) ? Ko : 0, kn = (tables & 2) ? Kn : 0;
-    if (!rc && ko + kn > 0)
-        rc = launch_select(c, n_agents, d->x0, d->obstacles, ko ? d->n_obs : 0, d->nbr_state, kn ? d->n_all : 0,
-                           d->agent_offset, ko, kn, d->obstacles_version, d->sel + (ko ? 0 : Ko), s, Ko + Kn, nbr_plan, p->N);
-    if (!rc) rc = c->order.mark_done(s);
-    return rc;
+    return c->order.run(c->device, s, [&] {
+        if (ko + kn == 0) return (int)SRB_OK;
+        return launch_select(c, n_agents, d->x0, d->obstacles, ko ? d->n_obs : 0, d->nbr_state, kn ? d->n_all : 0,
+                             d->agent_offset, ko, kn, d->obstacles_version, d->sel + (ko ? 0 : Ko), s, Ko + Kn, nbr_plan, p->N);
+    });
 }
 
 // srb_select_device with the static columns by closest predicted approach (srb_moving.horizon_selection = 1); any
@@ -827,8 +799,7 @@ extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, i
 extern "C" int srb_select_moving_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv, int tables,
                                         void *stream)
 {
-    if (d && d->struct_size != (int)sizeof(srb_batch))
-        return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    if (int rc0 = srb_check_struct(d, "srb_batch")) return rc0;
     if (int rc0 = check_moving(mv, d, false)) return rc0;
     if (!mv || !mv->obs_vel || !mv->horizon_selection || !(tables & 1) || tables < 1 || tables > 3 || !c || !d)
         return srb_select_device(c, n_agents, d, tables, stream);
@@ -842,13 +813,11 @@ extern "C" int srb_select_moving_device(srb_ctx *c, int n_agents, const srb_batc
     if (tables & 2)                                       // the neighbour columns: the pass of srb_select_device
         if (int rc0 = srb_select_device(c, n_agents, d, 2, stream)) return rc0;
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->order.order_after_last(s);
-    if (!rc && Ko > 0)
-        rc = launch_obs_horizon(c, n_agents, d->x0, d->obstacles, mv->obs_vel, d->n_obs, d->agent_offset, Ko, d->sel,
-                                Ko + Kn, s, c->p.N, c->p.Ts);
-    if (!rc) rc = c->order.mark_done(s);
-    return rc;
+    return c->order.run(c->device, s, [&] {
+        if (Ko == 0) return (int)SRB_OK;
+        return launch_obs_horizon(c, n_agents, d->x0, d->obstacles, mv->obs_vel, d->n_obs, d->agent_offset, Ko, d->sel,
+                                  Ko + Kn, s, c->p.N, c->p.Ts);
+    });
 }
 
 extern "C" int srb_obstacles_advance_device(srb_ctx *c, int n_obs, double *obstacles, const double *obs_vel, void *stream)
@@ -858,22 +827,12 @@ extern "C" int srb_obstacles_advance_device(srb_ctx *c, int n_obs, double *obsta
     if (n_obs == 0) return SRB_OK;
     if (!obstacles || !obs_vel) return fail(SRB_ERR_ARG, "srb_obstacles_advance_device: obstacles / obs_vel missing");
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->order.order_after_last(s);
-    if (!rc) {
-        hipLaunchKernelGGL(srb_obstacles_advance_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, s, n_obs, c->p.Ts,
-                           obstacles, obs_vel);
-        HIPCHK(hipGetLastError());
-        rc = c->order.mark_done(s);
-    }
-    return rc;
+    return c->order.run(c->device, s, [&] { return srb_launch_obstacles_advance(n_obs, c->p.Ts, obstacles, obs_vel, s); });
 }
 
 extern "C" int srb_prepare_batch_device(srb_ctx *c, int n_agents, const srb_prep *d, void *stream)
 {
-    // the layout check comes first: it needs no context (tests/test_abi.py runs it without a GPU)
-    if (d && d->struct_size != (int)sizeof(srb_prep))
-        return fail(SRB_ERR_ARG, "srb_prep.struct_size != sizeof(srb_prep): caller built against another ABI");
+    if (int rc0 = srb_check_struct(d, "srb_prep")) return rc0;     // first: it needs no context
     if (!c || !d) return fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0) return fail(SRB_ERR_ARG, "negative n_agents");
     if (n_agents == 0) return SRB_OK;
@@ -894,8 +853,7 @@ extern "C" int srb_prepare_batch_device(srb_ctx *c, int n_agents, const srb_prep
 // (struct_size, goal, x), so that tests/test_rollout.py reaches them without a GPU
 static int check_sim(const srb_sim *d, int cycle, bool advance)
 {
-    if (d && d->struct_size != (int)sizeof(srb_sim))
-        return fail(SRB_ERR_ARG, "srb_sim.struct_size != sizeof(srb_sim): caller built against another ABI");
+    if (int rc = srb_check_struct(d, "srb_sim")) return rc;
     if (!d) return fail(SRB_ERR_ARG, "null argument");
     if (cycle < d->c_first) return fail(SRB_ERR_ARG, "srb_sim: cycle precedes c_first");
     if (!advance) return SRB_OK;
@@ -957,11 +915,9 @@ static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void 
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
     hipStream_t s = (hipStream_t)stream;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = c->order.order_after_last(s);
-    if (!rc) rc = advance ? launch_advance(c, n_agents, d, cycle, s) : launch_metrics(c, n_agents, d, cycle, s);
-    if (!rc) rc = c->order.mark_done(s);
-    return rc;
+    return c->order.run(c->device, s, [&] {
+        return advance ? launch_advance(c, n_agents, d, cycle, s) : launch_metrics(c, n_agents, d, cycle, s);
+    });
 }
 
 extern "C" int srb_sim_advance_device(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream)
@@ -977,8 +933,7 @@ extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d
 static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, const srb_moving *mv, int cycles,
                    void *stream)
 {
-    if (b && b->struct_size != (int)sizeof(srb_batch))
-        return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    if (int rc0 = srb_check_struct(b, "srb_batch")) return rc0;
     if (int rc0 = check_moving(mv, b, true)) return rc0;
     // (the layout and null checks of check_sim only: the driver's first cycle is c_first itself)
     if (int rc = check_sim(d, d && d->struct_size == (int)sizeof(srb_sim) ? d->c_first : 0, false)) return rc;
@@ -991,13 +946,9 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
         (d->n_all != 0 && d->n_all != n_agents))
         return fail(SRB_ERR_ARG, "srb_rollout_device rolls out a whole team on one GPU: a sharded batch (agent_offset != 0 "
                                  "or n_all != n_agents) needs the neighbour exchange between advance and metrics");
-    if (d->plan_table && b->plan) {
-        const size_t bytes = (size_t)n_agents * 2 * c->p.N * sizeof(double);
-        const char *t0 = (const char *)d->plan_table, *o0 = (const char *)b->plan;
-        if (o0 < t0 + bytes && t0 < o0 + bytes)
-            return fail(SRB_ERR_ARG, "srb_sim.plan_table overlaps srb_batch.plan (the solve reads the table while it "
-                                     "writes its plans: use two buffers)");
-    }
+    if (srb_overlap(b->plan, (size_t)n_agents * 2 * c->p.N, d->plan_table, (size_t)n_agents * 2 * c->p.N))
+        return fail(SRB_ERR_ARG, "srb_sim.plan_table overlaps srb_batch.plan (the solve reads the table while it writes "
+                                 "its plans: use two buffers)");
     if (c->scene_agents > 0) {
         if (n_agents % c->scene_agents != 0)
             return fail(SRB_ERR_ARG, "scenes: srb_rollout_device rolls out whole scenes, n_agents (" + std::to_string(n_agents) +
@@ -1018,6 +969,7 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
     int rc = c->order.order_after_last(s);
+    if (rc) return rc;
     // moving obstacles: the table advances one cycle between the agents' advance and the metrics, from the second
     // cycle on, so d_obs / fail_cycle and the solve see the agents and the obstacles at matching times
     const double *vel = (mv && b->n_obs > 0) ? mv->obs_vel : nullptr;
@@ -1025,17 +977,13 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
         const int cyc = d->c_first + i;
         rc = launch_advance(c, n_agents, &sim, cyc, s);
         if (rc || i == cycles) break;
-        if (i > 0 && vel) {
-            hipLaunchKernelGGL(srb_obstacles_advance_kernel, dim3((b->n_obs + 255) / 256), dim3(256), 0, s, b->n_obs, c->p.Ts,
-                               mv->obstacles, vel);
-            HIPCHK(hipGetLastError());
-        }
-        rc = launch_metrics(c, n_agents, &sim, cyc, s);
+        if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
+        if (!rc) rc = launch_metrics(c, n_agents, &sim, cyc, s);
         if (i > 0 && d->plan_table) bat.nbr_plan = d->plan_table;
         if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp, vel, mv ? mv->horizon_selection : 0);
     }
-    if (!rc) rc = c->order.mark_done(s);
-    return rc;
+    const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier launches run
+    return rc ? rc : rc_mark;
 }
 
 extern "C" int srb_rollout_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, int cycles, void *stream)
@@ -1148,9 +1096,7 @@ extern "C" int srb_last_polish_ms(srb_ctx *c, float *polish_ms)
 
 static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp, const srb_moving *mv = nullptr)
 {
-    // the layout check comes first: it needs no context (tests/test_abi.py runs it without a GPU)
-    if (h && h->struct_size != (int)sizeof(srb_batch))
-        return fail(SRB_ERR_ARG, "srb_batch.struct_size != sizeof(srb_batch): caller built against another ABI");
+    if (int rc0 = srb_check_struct(h, "srb_batch")) return rc0;   // first: it needs no context
     if (int rc0 = check_moving(mv, h, false)) return rc0;
     if (!c || !h) return fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
@@ -1180,21 +1126,15 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp,
     }
     d.obstacles = nullptr; d.nbr_state = nullptr;
     if (h->n_obs > 0 && h->obstacles) {
-        if ((size_t)h->n_obs > c->cap_obs) {
-            if (c->obstacles) HIPCHK(hipFree(c->obstacles));
-            HIPCHK(hipMalloc(&c->obstacles, (size_t)h->n_obs * 2 * sizeof(double)));
-            c->cap_obs = h->n_obs;
-        }
-        HIPCHK(hipMemcpyAsync(c->obstacles, h->obstacles, (size_t)h->n_obs * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+        const size_t bytes = (size_t)h->n_obs * 2 * sizeof(double);
+        if (int rc0 = srb_stage_reserve(c->order, c->obstacles, c->cap_obs, bytes)) return rc0;
+        HIPCHK(hipMemcpyAsync(c->obstacles, h->obstacles, bytes, hipMemcpyHostToDevice, s));
         d.obstacles = c->obstacles;
     }
     if (h->n_all > 0 && h->nbr_state) {
-        if ((size_t)h->n_all > c->cap_nbr) {
-            if (c->nbr) HIPCHK(hipFree(c->nbr));
-            HIPCHK(hipMalloc(&c->nbr, (size_t)h->n_all * 4 * sizeof(double)));
-            c->cap_nbr = h->n_all;
-        }
-        HIPCHK(hipMemcpyAsync(c->nbr, h->nbr_state, (size_t)h->n_all * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+        const size_t bytes = (size_t)h->n_all * 4 * sizeof(double);
+        if (int rc0 = srb_stage_reserve(c->order, c->nbr, c->cap_nbr, bytes)) return rc0;
+        HIPCHK(hipMemcpyAsync(c->nbr, h->nbr_state, bytes, hipMemcpyHostToDevice, s));
         d.nbr_state = c->nbr;
     }
     // the plan members: the table staged like nbr_state (NLP stage only), the plans like x
@@ -1202,27 +1142,18 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp,
     if (use_nlp)                           // the overlap rule holds for the caller's own (host) buffers
         if (int rc0 = check_plans(c, n_agents, h, false)) return rc0;
     if (use_nlp && h->nbr_plan && d.nbr_state) {
-        const size_t rows = (size_t)h->n_all * 2 * N;
-        if ((size_t)h->n_all > c->cap_plan) {
-            if (c->nbr_plan) HIPCHK(hipFree(c->nbr_plan));
-            c->nbr_plan = nullptr; c->cap_plan = 0;
-            HIPCHK(hipMalloc(&c->nbr_plan, rows * sizeof(double)));
-            c->cap_plan = h->n_all;
-        }
-        HIPCHK(hipMemcpyAsync(c->nbr_plan, h->nbr_plan, rows * sizeof(double), hipMemcpyHostToDevice, s));
+        const size_t bytes = (size_t)h->n_all * 2 * N * sizeof(double);
+        if (int rc0 = srb_stage_reserve(c->order, c->nbr_plan, c->cap_plan, bytes)) return rc0;
+        HIPCHK(hipMemcpyAsync(c->nbr_plan, h->nbr_plan, bytes, hipMemcpyHostToDevice, s));
         d.nbr_plan = c->nbr_plan;
     }
     d.plan = h->plan ? c->plan : nullptr;
     // the velocity table staged like the obstacle table it belongs to (srb_solve_batch_moving)
     const double *vel = nullptr;
     if (use_nlp && mv && mv->obs_vel && d.obstacles) {
-        if ((size_t)h->n_obs > c->cap_vel) {
-            if (c->obs_vel) HIPCHK(hipFree(c->obs_vel));
-            c->obs_vel = nullptr; c->cap_vel = 0;
-            HIPCHK(hipMalloc(&c->obs_vel, (size_t)h->n_obs * 2 * sizeof(double)));
-            c->cap_vel = h->n_obs;
-        }
-        HIPCHK(hipMemcpyAsync(c->obs_vel, mv->obs_vel, (size_t)h->n_obs * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+        const size_t bytes = (size_t)h->n_obs * 2 * sizeof(double);
+        if (int rc0 = srb_stage_reserve(c->order, c->obs_vel, c->cap_vel, bytes)) return rc0;
+        HIPCHK(hipMemcpyAsync(c->obs_vel, mv->obs_vel, bytes, hipMemcpyHostToDevice, s));
         vel = c->obs_vel;
     }
     d.sel = nullptr;                       // the context's scratch; copied out below when asked for

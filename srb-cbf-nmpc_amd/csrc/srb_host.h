@@ -1,9 +1,12 @@
 // Host plumbing shared by the three C-ABI files (srb_capi.cpp, srb12_capi.cpp, srb_ll_capi.cpp): the error
-// channel, the HIP-error macros and the submission-order chaining of a context.  Internal, host only.
+// channel, the HIP-error macros, the submission-order chaining of a context, and what the LIP and the SRB-12 mode
+// check and launch alike (the struct-size refusal, the range-overlap test, the srb_moving checks, the growth of a
+// staging buffer, the obstacle-advance launch).  Internal, host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
 #include "srbnmpc.h"
+#include "srb_kernel_decls.h"
 
 // defined in srb_capi.cpp: the thread's last-error message (srb_last_error), and the LIP-mode context's selection
 // launch and ordering mark, which the SRB-12 mode reuses (nbr_plan [n_all][N][2] != NULL: the neighbour columns by
@@ -60,4 +63,83 @@ struct SrbCallOrder {
         if (any) HIPCHK(hipEventSynchronize(done));
         return SRB_OK;
     }
+    // One whole call: on `device`, `launch()` on s after the context's previous call, then the mark.  (The solves
+    // and the rollout drivers differ -- no mark without agents, a mark after a refusal -- and spell it out.)
+    template <class Launch> int run(int device, hipStream_t s, Launch launch)
+    {
+        HIPCHK(hipSetDevice(device));
+        int rc = order_after_last(s);
+        if (!rc) rc = launch();
+        if (!rc) rc = mark_done(s);
+        return rc;
+    }
 };
+
+// The layout refusal of a struct that carries its size (x null: nothing to refuse here); `name`: the struct's.
+// It needs no context, so every entry point runs it first (tests/test_abi.py reaches it without a GPU).
+template <class T> static inline int srb_check_struct(const T *x, const char *name)
+{
+    if (!x || x->struct_size == (int)sizeof(T)) return SRB_OK;
+    const std::string n(name);
+    return srb_internal_fail(SRB_ERR_ARG,
+                             (n + ".struct_size != sizeof(" + n + "): caller built against another ABI").c_str());
+}
+
+// [a, a + na) and [b, b + nb) share an element (a null range shares none)
+static inline bool srb_overlap(const double *a, size_t na, const double *b, size_t nb)
+{
+    return a && b && a < b + nb && b < a + na;
+}
+
+// The argument errors of srb_moving that need no context, before anything is launched (b may be null: the caller
+// reports that).  rollout: the driver moves the table, so it needs the writable pointer to batch.obstacles.
+// Batch: srb_batch or srb12_batch; `entry`, `batch`: the names of the mode's moving rollout and of its batch struct.
+template <class Batch>
+static int srb_check_moving(const srb_moving *mv, const Batch *b, bool rollout, const char *entry, const char *batch)
+{
+    if (int rc = srb_check_struct(mv, "srb_moving")) return rc;
+    if (!mv) return SRB_OK;
+    if (mv->horizon_selection != 0 && mv->horizon_selection != 1)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.horizon_selection: 0 (nearest now) or 1 (closest predicted "
+                                              "approach)");
+    if (mv->horizon_selection && !mv->obs_vel)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.horizon_selection = 1 needs obs_vel (the horizon-aware selection "
+                                              "reads the velocity table)");
+    if (!mv->obs_vel || !b || b->struct_size != (int)sizeof(Batch)) return SRB_OK;
+    if (b->obstacles_version != 0)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_moving.obs_vel with obstacles_version != 0: a kept selection grid of a "
+                                              "moving table is stale (pass version 0)");
+    if (rollout && !mv->obstacles)
+        return srb_internal_fail(SRB_ERR_ARG, (std::string(entry) + ": srb_moving.obstacles missing (the driver moves the "
+                                               "table in place)").c_str());
+    if (rollout && mv->obstacles != b->obstacles)
+        return srb_internal_fail(SRB_ERR_ARG, (std::string(entry) + ": srb_moving.obstacles is not " + batch + ".obstacles "
+                                               "(the solve and the metrics read the table the driver moves)").c_str());
+    return SRB_OK;
+}
+
+// A staging buffer of the host-buffer entry points grown to `bytes` (contents not kept).  The context's last call
+// may still read the old buffer; and whatever fails, the context is left with no buffer and no capacity, never
+// with a freed pointer that a later, smaller call would copy into and the destroy would free again.
+template <class T> static int srb_stage_reserve(SrbCallOrder &order, T *&buf, size_t &cap, size_t bytes)
+{
+    if (bytes <= cap) return SRB_OK;
+    if (int rc = order.wait_idle()) return rc;
+    T *old = buf;
+    buf = nullptr; cap = 0;
+    if (old) HIPCHK(hipFree(old));
+    void *fresh = nullptr;                 // (a failed hipMalloc is not promised to leave its argument null)
+    HIPCHK(hipMalloc(&fresh, bytes));
+    buf = (T *)fresh; cap = bytes;
+    return SRB_OK;
+}
+
+// one control cycle of an obstacle table (srb_obstacles_advance_kernel: 4 grids of Ts): launch only, the caller
+// orders the stream
+static inline int srb_launch_obstacles_advance(int n_obs, double Ts, double *obstacles, const double *obs_vel, hipStream_t s)
+{
+    hipLaunchKernelGGL(srb_obstacles_advance_kernel, dim3((n_obs + 255) / 256), dim3(256), 0, s, n_obs, Ts, obstacles,
+                       obs_vel);
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}

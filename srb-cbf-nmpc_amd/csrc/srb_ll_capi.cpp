@@ -152,8 +152,7 @@ static int ll_launch(srb_ll_ctx *c, int n_agents, SrbLLDev k, hipStream_t s)
 
 extern "C" int srb_ll_calc_torque_device(srb_ll_ctx *c, int n_agents, const srb_ll_io *d, void *stream)
 {
-    if (d && d->struct_size != (int)sizeof(srb_ll_io))    // layout check first (no context needed)
-        return srb_internal_fail(SRB_ERR_ARG, "srb_ll_io.struct_size != sizeof(srb_ll_io): caller built against another ABI");
+    if (int rc0 = srb_check_struct(d, "srb_ll_io")) return rc0;   // layout check first (no context needed)
     if (!c || !d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -169,8 +168,7 @@ extern "C" int srb_ll_calc_torque_device(srb_ll_ctx *c, int n_agents, const srb_
 
 extern "C" int srb_ll_calc_torque(srb_ll_ctx *c, int n_agents, const srb_ll_io *h)
 {
-    if (h && h->struct_size != (int)sizeof(srb_ll_io))    // layout check first (no context needed)
-        return srb_internal_fail(SRB_ERR_ARG, "srb_ll_io.struct_size != sizeof(srb_ll_io): caller built against another ABI");
+    if (int rc0 = srb_check_struct(h, "srb_ll_io")) return rc0;   // layout check first (no context needed)
     if (!c || !h) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;

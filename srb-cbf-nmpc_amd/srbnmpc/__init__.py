@@ -11,6 +11,9 @@ constructing a solver raises.
     workload      -- synthetic agent batches with the SURVEY.md §8d distributions
     LowLevelCtrl  -- batched low-level CLF-QP (LowLevelCtrl::calcTorque), srbnmpc.lowlevel
     ll_workload   -- synthetic A1-sized low-level controller inputs
+
+What the LIP and the SRB-12 mode (srbnmpc.srb12) do alike is here once: _SolverBase under BatchSolver and
+srb12.Solver12, the pointer casts _p / _dptr / _iptr, _clamp_selected and _moving_args.
 """
 from __future__ import annotations
 
@@ -196,25 +199,56 @@ def _p(a):
     return a.ctypes.data_as(_ip)
 
 
-class BatchSolver:
-    """One HIP context solving batches of up to `max_agents` agents.
+def _dptr(t):
+    """A device tensor's address as double * (None stays None: the C ABI's "absent"); _p for torch tensors."""
+    return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
 
-    solve(...)        host numpy in/out (srb_solve_batch, synchronous)
-    solve_device(...) torch CUDA tensors in/out (srb_solve_batch_device, async on a stream)
-    """
 
-    def __init__(self, params: Params, max_agents: int, device: int = 0):
+def _iptr(t):
+    return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _ip)
+
+
+def _clamp_selected(K_obs: int, K_nbr: int, n_obs: int, n_all: int, scenes):
+    """(Ko, Kn) of "up to K nearest" for tables of these sizes, as the C ABI clamps them: to the tables, or with a
+    scene partition (scene_agents, scene_obs) to the agent's own sub-tables."""
+    rows, others = max(n_obs, 0), max(n_all - 1, 0)
+    if scenes[0] > 0:
+        rows, others = min(rows, scenes[1]), (scenes[0] - 1 if n_all > 0 else 0)
+    return min(K_obs, rows), min(K_nbr, others)
+
+
+def _moving_args(obs_vel, obs_horizon, n_obs, dtype, ptr, obstacle_rows=True) -> Moving:
+    """The srb_moving of a solve / select call, both modes, after the checks of obs_vel that need no context, by name
+    (obs_horizon without obs_vel is the library's refusal).  ptr: _p for host arrays, _dptr for device tensors."""
+    if not obstacle_rows:
+        raise ValueError("obs_vel / obs_horizon: the QP-only solve has no obstacle rows")
+    if obs_vel is not None:
+        _check_vel_array(obs_vel, n_obs, dtype)
+    return Moving(ptr(obs_vel), int(bool(obs_horizon)), None)
+
+
+class _SolverBase:
+    """What BatchSolver and srb12.Solver12 share: the context's life, the stream of a launch, the scene partition
+    and the Jacobi loop of solve_coupled_device.  A mode names the prefix of its entry points (_abi) and, where
+    they are bound on first use, the function that loads the library (_lib)."""
+    _abi = "srb"
+    _lib = staticmethod(lib)
+
+    def __init__(self, params, max_agents: int, device: int = 0):
         self.params = params
         self.max_agents = int(max_agents)
         self.device = int(device)
         h = ctypes.c_void_p()
-        _check(lib().srb_ctx_create(ctypes.byref(params), self.max_agents, self.device, ctypes.byref(h)))
+        _check(self._entry("ctx_create")(ctypes.byref(params), self.max_agents, self.device, ctypes.byref(h)))
         self._h = h
         self._scenes = (0, 0)
 
+    def _entry(self, name: str):
+        return getattr(self._lib(), f"{self._abi}_{name}")
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
-            lib().srb_ctx_destroy(self._h)
+            self._entry("ctx_destroy")(self._h)
             self._h = None
 
     def __del__(self):
@@ -223,15 +257,76 @@ class BatchSolver:
         except Exception:
             pass
 
+    def _stream(self, stream):
+        """hipStream_t for a launch: the caller's, else torch's current stream on this device
+        (the C ABI's NULL would mean the context's own stream, unordered against torch's)."""
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+        return ctypes.c_void_p(stream)
+
+    def set_scenes(self, scene_agents: int = 0, scene_obs: int = 0):
+        """The batch as independent teams (srb_ctx_set_scenes / srb12_ctx_set_scenes): scene_agents agents and
+        scene_obs obstacle rows per scene, tables flat and scene-major; agent g selects and is measured within scene
+        g // scene_agents, sel holds global rows.  (0, 0): off, one team."""
+        _check(self._entry("ctx_set_scenes")(self._h, int(scene_agents), int(scene_obs)))
+        a, o = ctypes.c_int(), ctypes.c_int()
+        _check(self._entry("ctx_scenes")(self._h, ctypes.byref(a), ctypes.byref(o)))
+        self._scenes = (a.value, o.value)
+
+    @property
+    def scenes(self):
+        """(scene_agents, scene_obs) as last set through set_scenes; (0, 0) when off."""
+        return self._scenes
+
+    def _solve_coupled(self, args, outer, exchange, nbr_plan, agent_offset, stream, round_kw, **kw):
+        """The Jacobi loop of solve_coupled_device.  args: the mode's positional arguments of solve_device (x0 first,
+        nbr_state and out last); round_kw(table): the mode's own keywords for the round that solves against `table`;
+        kw: the keywords every round gets."""
+        import torch
+        x0, nbr_state, out = args[0], args[-2], args[-1]
+        outer = int(outer)
+        if outer < 1:
+            raise ValueError("outer must be >= 1")
+        plan = out.get("plan")
+        if plan is None:
+            raise ValueError("solve_coupled_device needs out['plan'] ([A][N][2] float64)")
+        A, N = x0.shape[0], self.params.N
+        _check_plan_array(plan, (A, N, 2), "out['plan']", torch.float64)
+        if exchange is None and outer > 1 and (nbr_state is None or nbr_state.shape[0] != A or agent_offset != 0):
+            raise ValueError("solve_coupled_device without an exchange iterates over this batch's own plans: "
+                             "nbr_state must hold exactly the batch's agents (agent_offset 0)")
+        other = getattr(self, "_plan_pong", None)
+        if outer > 1 and (other is None or other.shape != plan.shape or other.device != plan.device):
+            other = self._plan_pong = torch.empty_like(plan)
+        ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream)) if stream is not None else contextlib.nullcontext()
+        change = torch.zeros(max(outer - 1, 0), dtype=torch.float64, device=plan.device)
+        with ctx:
+            table, prev = nbr_plan, None
+            for r in range(outer):
+                cur = plan if (outer - 1 - r) % 2 == 0 else other      # the last round writes out["plan"]
+                if r > 0:
+                    table = exchange(prev) if exchange is not None else prev
+                self.solve_device(*args, agent_offset=agent_offset, stream=stream, nbr_plan=table, plan=cur,
+                                  **round_kw(table), **kw)
+                if r > 0:
+                    change[r - 1] = (cur - prev).abs().max()
+                prev = cur
+        return change
+
+
+class BatchSolver(_SolverBase):
+    """One HIP context solving batches of up to `max_agents` agents.
+
+    solve(...)        host numpy in/out (srb_solve_batch, synchronous)
+    solve_device(...) torch CUDA tensors in/out (srb_solve_batch_device, async on a stream)
+    """
+
     # --------------------------------------------------------------- host path
     def n_selected(self, n_obs: int, n_all: int):
         """(Ko, Kn): selected static obstacles / neighbours per agent for tables of these sizes
         ("up to K nearest", the clamp the C ABI applies)."""
-        p = self.params
-        sa, so = self.scenes
-        if sa > 0:                                            # per scene: the agent's own sub-tables
-            return min(p.K_obs, max(n_obs, 0), so), (min(p.K_nbr, sa - 1) if n_all > 0 else 0)
-        return min(p.K_obs, max(n_obs, 0)), (min(p.K_nbr, max(n_all - 1, 0)) if n_all > 0 else 0)
+        return _clamp_selected(self.params.K_obs, self.params.K_nbr, n_obs, n_all, self._scenes)
 
     def solve(self, x0, ref, foot, obstacles=None, nbr_state=None, agent_offset: int = 0, qp_only: bool = False,
               alpha_buf=None, nbr_plan=None, plan=None, obs_vel=None, obs_horizon: bool = False):
@@ -271,11 +366,7 @@ class BatchSolver:
                   _p(ab) if ab is not None else None, _p(out["alpha"]) if ab is not None else None,
                   _p(out["sel"]) if out["sel"].size and not qp_only else None, 0, _p(nbr_plan), _p(plan))
         if obs_vel is not None or obs_horizon:
-            if qp_only:
-                raise ValueError("obs_vel / obs_horizon: the QP-only solve has no obstacle rows")
-            if obs_vel is not None:
-                _check_vel_array(obs_vel, ob.shape[0], np.float64)
-            mv = Moving(_p(obs_vel), int(bool(obs_horizon)), None)
+            mv = _moving_args(obs_vel, obs_horizon, ob.shape[0], np.float64, _p, not qp_only)
             _check(lib().srb_solve_batch_moving(self._h, A, ctypes.byref(b), ctypes.byref(mv)))
             return out
         fn = lib().srb_solve_qp if qp_only else lib().srb_solve_batch
@@ -299,11 +390,6 @@ class BatchSolver:
         closest predicted approach over the horizon.
         Asynchronous on `stream` (a hipStream_t handle), by default torch's current stream on
         this device, so the launch is ordered after the torch work that filled the inputs."""
-        def dptr(t):
-            return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
-
-        def iptr(t):
-            return ctypes.cast(ctypes.c_void_p(t.data_ptr()), _ip)
         A = x0.shape[0]
         Ko, Kn = self.n_selected(0 if obstacles is None else obstacles.shape[0],
                                  0 if nbr_state is None else nbr_state.shape[0])
@@ -322,17 +408,14 @@ class BatchSolver:
                               torch_float64())
         if plan is not None:
             _check_plan_array(plan, (A, N, 2), "plan", torch_float64())
-        b = Batch(dptr(x0), dptr(ref), dptr(foot), dptr(obstacles), dptr(nbr_state),
+        b = Batch(_dptr(x0), _dptr(ref), _dptr(foot), _dptr(obstacles), _dptr(nbr_state),
                   0 if obstacles is None else obstacles.shape[0], 0 if nbr_state is None else nbr_state.shape[0],
-                  int(agent_offset), dptr(out.get("x_qp")), dptr(out["x"]), dptr(out["obj"]),
-                  iptr(out["status"]), iptr(out["iters"]), dptr(alpha_buf),
-                  dptr(out.get("alpha") if alpha_buf is not None else None),
-                  iptr(out["sel"]) if out.get("sel") is not None else None, int(obstacles_version),
-                  dptr(nbr_plan), dptr(plan))
+                  int(agent_offset), _dptr(out.get("x_qp")), _dptr(out["x"]), _dptr(out["obj"]),
+                  _iptr(out["status"]), _iptr(out["iters"]), _dptr(alpha_buf),
+                  _dptr(out.get("alpha") if alpha_buf is not None else None), _iptr(sel), int(obstacles_version),
+                  _dptr(nbr_plan), _dptr(plan))
         if obs_vel is not None or obs_horizon:
-            if obs_vel is not None:
-                _check_vel_array(obs_vel, 0 if obstacles is None else obstacles.shape[0], torch_float64())
-            mv = Moving(dptr(obs_vel), int(bool(obs_horizon)), None)
+            mv = _moving_args(obs_vel, obs_horizon, 0 if obstacles is None else obstacles.shape[0], torch_float64(), _dptr)
             _check(lib().srb_solve_batch_moving_device(self._h, A, ctypes.byref(b), ctypes.byref(mv), self._stream(stream)))
             return
         _check(lib().srb_solve_batch_device(self._h, A, ctypes.byref(b), self._stream(stream)))
@@ -355,17 +438,12 @@ class BatchSolver:
         if nbr_plan is not None:
             _check_plan_array(nbr_plan, (nbr_plan.shape[0] if nbr_state is None else nbr_state.shape[0], self.params.N, 2), "nbr_plan",
                               torch_float64())
-
-        def dptr(t):
-            return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
-        b = Batch(dptr(x0), None, None, dptr(obstacles), dptr(nbr_state),
+        b = Batch(_dptr(x0), None, None, _dptr(obstacles), _dptr(nbr_state),
                   0 if obstacles is None else obstacles.shape[0], 0 if nbr_state is None else nbr_state.shape[0],
                   int(agent_offset), None, None, None, None, None, None, None,
-                  ctypes.cast(ctypes.c_void_p(sel.data_ptr()), _ip), int(obstacles_version), dptr(nbr_plan), None)
+                  _iptr(sel), int(obstacles_version), _dptr(nbr_plan), None)
         if obs_vel is not None or obs_horizon:
-            if obs_vel is not None:
-                _check_vel_array(obs_vel, 0 if obstacles is None else obstacles.shape[0], torch_float64())
-            mv = Moving(dptr(obs_vel), int(bool(obs_horizon)), None)
+            mv = _moving_args(obs_vel, obs_horizon, 0 if obstacles is None else obstacles.shape[0], torch_float64(), _dptr)
             _check(lib().srb_select_moving_device(self._h, A, ctypes.byref(b), ctypes.byref(mv), int(tables),
                                                   self._stream(stream)))
             return
@@ -384,44 +462,9 @@ class BatchSolver:
         max |plan_r - plan_{r-1}| per round (torch reductions; nothing synchronises with the host inside the
         loop).  No damping and no convergence test: the plain Jacobi round.  Other arguments (obs_vel and
         obs_horizon included: every round solves against the same moving table) as solve_device."""
-        import torch
-        outer = int(outer)
-        if outer < 1:
-            raise ValueError("outer must be >= 1")
-        plan = out.get("plan")
-        if plan is None:
-            raise ValueError("solve_coupled_device needs out['plan'] ([A][N][2] float64)")
-        A, N = x0.shape[0], self.params.N
-        _check_plan_array(plan, (A, N, 2), "out['plan']", torch.float64)
-        if exchange is None and outer > 1 and (nbr_state is None or nbr_state.shape[0] != A or agent_offset != 0):
-            raise ValueError("solve_coupled_device without an exchange iterates over this batch's own plans: "
-                             "nbr_state must hold exactly the batch's agents (agent_offset 0)")
-        other = getattr(self, "_plan_pong", None)
-        if outer > 1 and (other is None or other.shape != plan.shape or other.device != plan.device):
-            other = self._plan_pong = torch.empty_like(plan)
-        ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream)) if stream is not None else contextlib.nullcontext()
-        change = torch.zeros(max(outer - 1, 0), dtype=torch.float64, device=plan.device)
-        with ctx:
-            table, prev = nbr_plan, None
-            for r in range(outer):
-                cur = plan if (outer - 1 - r) % 2 == 0 else other      # the last round writes out["plan"]
-                if r > 0:
-                    table = exchange(prev) if exchange is not None else prev
-                self.solve_device(x0, ref, foot, obstacles, nbr_state, out, agent_offset=agent_offset, stream=stream,
-                                  alpha_buf=alpha_buf, obstacles_version=obstacles_version, nbr_plan=table, plan=cur,
-                                  obs_vel=obs_vel, obs_horizon=obs_horizon)
-                if r > 0:
-                    change[r - 1] = (cur - prev).abs().max()
-                prev = cur
-        return change
-
-    def _stream(self, stream):
-        """hipStream_t for a launch: the caller's, else torch's current stream on this device
-        (the C ABI's NULL would mean the context's own stream, unordered against torch's)."""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        return ctypes.c_void_p(stream)
+        return self._solve_coupled((x0, ref, foot, obstacles, nbr_state, out), outer, exchange, nbr_plan, agent_offset,
+                                   stream, lambda table: {"alpha_buf": alpha_buf}, obstacles_version=obstacles_version,
+                                   obs_vel=obs_vel, obs_horizon=obs_horizon)
 
     def prepare_device(self, Pr, Prd, gait_domain, contact, toe, start, q, dq, out, agent_id=None,
                        agent_offset: int = 0, stream=None):
@@ -429,15 +472,10 @@ class BatchSolver:
         solver's device.  Pr, Prd: [T, 2*NA] (column-major 2*NA x T); gait_domain [A] int32;
         contact [A,4] int32; toe [A,3,4]; start [A,2]; q, dq [A,18].  `out` holds x0 [A,4],
         ref [A,4N], foot [A,N*2*C], last_state [A,4], status [A] int32.  Asynchronous."""
-        def dptr(t):
-            return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
-
-        def iptr(t):
-            return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _ip)
         A = q.shape[0]
-        pr = Prep(dptr(Pr), dptr(Prd), Pr.shape[1], Pr.shape[0], int(agent_offset), iptr(agent_id),
-                  iptr(gait_domain), iptr(contact), dptr(toe), dptr(start), dptr(q), dptr(dq),
-                  dptr(out["x0"]), dptr(out["ref"]), dptr(out["foot"]), dptr(out["last_state"]), iptr(out["status"]))
+        pr = Prep(_dptr(Pr), _dptr(Prd), Pr.shape[1], Pr.shape[0], int(agent_offset), _iptr(agent_id),
+                  _iptr(gait_domain), _iptr(contact), _dptr(toe), _dptr(start), _dptr(q), _dptr(dq),
+                  _dptr(out["x0"]), _dptr(out["ref"]), _dptr(out["foot"]), _dptr(out["last_state"]), _iptr(out["status"]))
         _check(lib().srb_prepare_batch_device(self._h, A, ctypes.byref(pr), self._stream(stream)))
 
     def advance_obstacles_device(self, obstacles, obs_vel, stream=None):
@@ -445,9 +483,8 @@ class BatchSolver:
         obstacles[i] += obs_vel[i] * (Ts * 4).  Both [n_obs][2] float64 tensors on this solver's device."""
         _check_vel_array(obstacles, obstacles.shape[0], torch_float64(), "obstacles")
         _check_vel_array(obs_vel, obstacles.shape[0], torch_float64())
-        _check(lib().srb_obstacles_advance_device(self._h, obstacles.shape[0],
-                                                  ctypes.cast(ctypes.c_void_p(obstacles.data_ptr()), _dp),
-                                                  ctypes.cast(ctypes.c_void_p(obs_vel.data_ptr()), _dp), self._stream(stream)))
+        _check(lib().srb_obstacles_advance_device(self._h, obstacles.shape[0], _dptr(obstacles), _dptr(obs_vel),
+                                                  self._stream(stream)))
 
     def sync(self):
         _check(lib().srb_sync(self._h))
@@ -455,20 +492,6 @@ class BatchSolver:
     def set_waves(self, nw: int = 0):
         """Waves per agent (0 automatic, 1, 2, 4; srb_ctx_set_waves)."""
         _check(lib().srb_ctx_set_waves(self._h, int(nw)))
-
-    def set_scenes(self, scene_agents: int = 0, scene_obs: int = 0):
-        """The batch as independent teams (srb_ctx_set_scenes): scene_agents agents and scene_obs obstacle rows
-        per scene, tables flat and scene-major; agent g selects and is measured within scene g // scene_agents,
-        sel holds global rows.  (0, 0): off, one team."""
-        _check(lib().srb_ctx_set_scenes(self._h, int(scene_agents), int(scene_obs)))
-        a, o = ctypes.c_int(), ctypes.c_int()
-        _check(lib().srb_ctx_scenes(self._h, ctypes.byref(a), ctypes.byref(o)))
-        self._scenes = (a.value, o.value)
-
-    @property
-    def scenes(self):
-        """(scene_agents, scene_obs) as last set through set_scenes; (0, 0) when off."""
-        return self._scenes
 
     def set_option(self, name: str, value: float):
         """Context option (srb_ctx_set_option): name one of OPTIONS ("polish", "polish_rho",

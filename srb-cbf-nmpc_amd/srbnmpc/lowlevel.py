@@ -14,7 +14,7 @@ import ctypes
 
 import numpy as np
 
-from . import _check, _dp, _ip, _f64, lib
+from . import _check, _dp, _dptr, _ip, _iptr, _f64, lib
 
 IN_KEYS = ("q", "dq", "Dinv", "B", "Hv", "Jc", "dJc", "Js", "Jtoe", "Jhip", "toePos", "hipPos",
            "H0", "dH0", "y", "dy", "hd", "dhd", "fDes")
@@ -134,19 +134,14 @@ class LowLevelCtrl:
         (float64) and status, iters (int32).  Asynchronous on `stream` (a raw hipStream_t
         handle), by default torch's current stream on this device (ordered after the torch
         work that filled the inputs)."""
-        def dptr(t):
-            return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
-
-        def iptr(t):
-            return ctypes.cast(ctypes.c_void_p(t.data_ptr()), _ip)
         A = dev["ind"].shape[0]
-        ptrs = {"ind": iptr(dev["ind"])}
+        ptrs = {"ind": _iptr(dev["ind"])}
         for k in IN_KEYS:
-            ptrs[k] = dptr(dev[k])
+            ptrs[k] = _dptr(dev[k])
         for k in OUT_SIZE:
-            ptrs["out_" + k] = dptr(out.get(k))
-        ptrs["out_status"] = iptr(out["status"])
-        ptrs["out_iters"] = iptr(out["iters"])
+            ptrs["out_" + k] = _dptr(out.get(k))
+        ptrs["out_status"] = _iptr(out["status"])
+        ptrs["out_iters"] = _iptr(out["iters"])
         io = _io_from(ptrs)
         if stream is None:
             import torch

@@ -17,20 +17,17 @@ batch is many independent teams rolled out by the same launches -- obstacles is 
 With obs_vel ([n_obs][2], m/s) the obstacles move: every solve reads the velocities (srb_moving), and from the second
 cycle on the table advances one cycle between the agents' advance and the metrics (srb_rollout_moving_device).  The
 rollout then works on its own copy of `obstacles`; results()["obstacles"] is the current table.
+
+_RolloutBase is what this class and srb12.Rollout12 share: the checks of goal / phase / obstacles / obs_vel, the moving
+table's clone and its restore, the solve, metrics and log buffers, reset / advance / results / scene_results and the
+preconditions of run().  A mode adds its state width, its own buffers, its srb_sim (_sim), step() and the driver
+call of run() (_drive); the entry points are the solver's own (its _entry).
 """
 from __future__ import annotations
 
 import ctypes
 
-from . import Batch, Moving, Sim, _check, _check_vel_array, _dp, _ip, lib
-
-
-def _dptr(t):
-    return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
-
-
-def _iptr(t):
-    return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _ip)
+from . import Batch, Moving, Sim, _check, _check_vel_array, _dptr, _iptr, lib
 
 
 def _check_tensor(t, shape, name, dtype, device):
@@ -42,29 +39,19 @@ def _check_tensor(t, shape, name, dtype, device):
         raise ValueError(f"{name} must be on {device}, got {t.device}")
 
 
-class Rollout:
-    """The closed loop of `solver` (a BatchSolver with N >= 4) for the agents whose goals are `goal` [A][2].
+class _RolloutBase:
+    """The closed loop of one mode's solver, as far as the LIP and the SRB-12 mode agree (the module docstring).
+    Subclasses set the attributes below and define _sim(), step() and _drive()."""
+    _nx = 4                              # state width: the rows of state, x0 and traj
+    _name = "Rollout"                    # the class, in messages
+    sharded = False                      # a shard of a larger team (Rollout only)
 
-    vref      reference speed of the goal-directed line (workload.VREF)
-    phase     [A] int32 or None: added to the cycle index for the trot parity
-    plans     True: from the second cycle on, the inter-agent rows follow the neighbours' previous plans shifted
-              by one gait domain (srb_batch.nbr_plan) instead of the constant-velocity guess
-    log_x     True: keep every cycle's decision vectors (results()["x"], [T][A][nv])
-    obstacles [n_obs][2] or None: the static obstacles, for the solve and for d_obs / fail_cycle
-    obs_vel   [n_obs][2] or None: the obstacles' velocities (m/s).  The rollout then clones `obstacles` (it moves the
-              table), reset() restores the start table, and every shard moves its own full copy (the same bits)
-    obs_horizon  True: the static columns by closest predicted approach over the horizon (needs obs_vel)
-    agent_offset, n_all   a shard of a larger team: this batch is rows agent_offset .. agent_offset + A of the
-              n_all-row neighbour table that step(exchange) gathers (default: the whole team)
-    All tensors are float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
-
-    def __init__(self, solver, goal, vref: float = 0.27, phase=None, plans: bool = False, log_x: bool = False, *,
-                 obstacles=None, agent_offset: int = 0, n_all: int | None = None, obs_vel=None, obs_horizon: bool = False):
+    def __init__(self, solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon):
         import torch
         self.solver = solver
         p = solver.params
         if p.N < 4:
-            raise ValueError("Rollout needs N >= 4 (one cycle is one gait domain of 4 grids)")
+            raise ValueError(f"{self._name} needs N >= 4 (one cycle is one gait domain of 4 grids)")
         self.device = torch.device("cuda", solver.device)
         if not hasattr(goal, "shape") or len(goal.shape) != 2:
             raise ValueError("goal must be a [A][2] tensor")
@@ -91,22 +78,16 @@ class Rollout:
         self.obs_vel, self.obs_horizon = obs_vel, bool(obs_horizon)
         self.goal, self.phase, self.obstacles = goal, phase, obstacles
         self.vref, self.plans, self.log_x = float(vref), bool(plans), bool(log_x)
-        self.agent_offset = int(agent_offset)
-        self.n_all = A if n_all is None else int(n_all)
-        if self.agent_offset < 0 or self.agent_offset + A > self.n_all:
-            raise ValueError("agent_offset + A exceeds n_all")
-        self.sharded = self.agent_offset != 0 or self.n_all != A
-        N, C, nv = p.N, p.C, p.nv
+        N, nx = p.N, self._nx
         f8 = dict(dtype=torch.float64, device=self.device)
         i4 = dict(dtype=torch.int32, device=self.device)
-        self.state = torch.zeros((A, 4), **f8)
-        self.x0, self.last_state, self.alpha_buf = (torch.zeros((A, 4), **f8) for _ in range(3))
-        self.ref = torch.zeros((A, 4 * N), **f8)
-        self.foot = torch.zeros((A, N, 2, C), **f8)
-        self.plan_table = torch.zeros((A, N, 2), **f8) if self.plans else None
-        self.out = dict(x=torch.zeros((A, nv), **f8), obj=torch.zeros(A, **f8), status=torch.zeros((A, 2), **i4),
-                        iters=torch.zeros((A, 2), **i4), alpha=torch.zeros((A, 20), **f8))
+        self.state, self.x0 = torch.zeros((A, nx), **f8), torch.zeros((A, nx), **f8)
+        self.last_state = torch.zeros((A, 4), **f8)
+        self.out = dict(x=torch.zeros((A, p.nv), **f8), obj=torch.zeros(A, **f8), status=torch.zeros((A, 2), **i4),
+                        iters=torch.zeros((A, 2), **i4))
+        self.plan_table = None
         if self.plans:
+            self.plan_table = torch.zeros((A, N, 2), **f8)
             self.out["plan"] = torch.zeros((A, N, 2), **f8)
         self.metrics = dict(d_obs=torch.zeros(A, **f8), d_agent=torch.zeros(A, **f8), min_d_obs=torch.zeros(A, **f8),
                             min_d_agent=torch.zeros(A, **f8), fail_cycle=torch.full((A,), -1, **i4),
@@ -131,7 +112,7 @@ class Rollout:
             if old is not None:
                 new[:old.shape[0]] = old
             return new
-        self.traj = grow(self.traj, cap + 1, (A, 4), torch.float64)
+        self.traj = grow(self.traj, cap + 1, (A, self._nx), torch.float64)
         self.status_log = grow(self.status_log, cap, (A, 2), torch.int32)
         self.iters_log = grow(self.iters_log, cap, (A, 2), torch.int32)
         if self.log_x:
@@ -140,6 +121,119 @@ class Rollout:
 
     def _moving(self) -> Moving:
         return Moving(_dptr(self.obs_vel), int(self.obs_horizon), _dptr(self.obstacles))
+
+    # ------------------------------------------------------------------ driving
+    def reset(self, state):
+        """Start state [A][4] (x, xdot, y, ydot; Rollout12: [A][12] p, roll/pitch/yaw, v, omega); the cycle count and
+        the logs start over; with obs_vel the start table is restored.  Both are torch copies on torch's current
+        stream: a caller who then passes another stream to step() / run() orders that stream after the current one
+        first (nothing here does)."""
+        import torch
+        _check_tensor(state, (self.A, self._nx), "state", torch.float64, self.device)
+        self.state.copy_(state)
+        if self.obs_vel is not None:
+            self.obstacles.copy_(self.obstacles0)    # the start table
+        self.c = 0
+        self.flushed = True
+        self._ready = True
+
+    def advance(self, stream=None):
+        """The advance of the current cycle alone: state, x0, the reference, foot, last_state and the mode's other
+        inputs of the solve (and the previous cycle's logs).  step() runs it itself; calling it first as well changes
+        nothing (it rewrites the same values) and lets shards driven from one process fill their snapshot rows before
+        a stand-in exchange gathers them."""
+        if not self._ready:
+            raise RuntimeError(f"{self._name}.advance before reset(state)")
+        s = self.solver
+        self._reserve(self.c + 1)
+        _check(s._entry("sim_advance_device")(s._h, self.A, ctypes.byref(self._sim()), self.c, s._stream(stream)))
+
+    def run(self, T: int, stream=None):
+        """T cycles by the C driver (srb_rollout_device, srb12_rollout_device or, with plans / obs_vel, their
+        variants), right after reset(): one call, nothing synchronises with the host inside.  A whole team only."""
+        T = int(T)
+        if not self._ready or self.c != 0:
+            raise RuntimeError(f"{self._name}.run starts from reset(state) (use step() to go on)")
+        if T < 0:
+            raise ValueError("T must be >= 0")
+        if self.sharded:
+            raise ValueError("run() rolls out a whole team; a shard steps with its exchange (step)")
+        sa = self.solver.scenes[0]
+        if sa > 0 and self.A % sa != 0:
+            raise ValueError(f"run() rolls out whole scenes: {self.A} agents are not a multiple of scene_agents = {sa}")
+        self._reserve(T)
+        self._drive(T, stream)
+        self.c = T
+        self.flushed = True
+
+    def results(self, stream=None):
+        """The logs and metrics so far, as tensors (views of this object's buffers; asynchronous like the
+        launches -- synchronise before reading on the host): traj [T+1][A][nx] (nx 4, Rollout12: 12), status / iters
+        [T][A][2], x [T][A][nv] (log_x), state [A][nx] (the end state), cycles, and d_obs, d_agent, min_d_obs,
+        min_d_agent, fail_cycle, distance_to_fail [A]; with obs_vel, obstacles [n_obs][2] (the current table: the
+        rows as the last cycle saw them)."""
+        if not self._ready:
+            raise RuntimeError(f"{self._name}.results before reset(state)")
+        T = self.c
+        self._reserve(max(T, 1))
+        if not self.flushed:
+            self.advance(stream)                 # the final advance: the last logs and the end state
+            self.flushed = True
+        elif T == 0:
+            self.advance(stream)
+        out = dict(cycles=T, traj=self.traj[:T + 1], status=self.status_log[:T], iters=self.iters_log[:T],
+                   state=self.state, **self.metrics)
+        if self.log_x:
+            out["x"] = self.x_log[:T]
+        if self.obs_vel is not None:
+            out["obstacles"] = self.obstacles
+        return out
+
+    def scene_results(self, stream=None):
+        """results() reduced per scene of the solver's partition (set_scenes; a whole number of scenes), as device
+        tensors [n_scenes]: min_d_agent and min_d_obs (the smallest over the scene's agents), n_failed (agents with
+        fail_cycle >= 0) and n_not_converged (solves of the logged cycles that did not converge: QP stage neither
+        OPTIMAL nor QP_WARM, or NLP stage not OPTIMAL); plus scene_agents and n_scenes.  Asynchronous like results()."""
+        sa = self.solver.scenes[0]
+        if sa <= 0:
+            raise ValueError(f"scene_results needs the solver's scene partition ({type(self.solver).__name__}.set_scenes)")
+        if self.sharded or self.A % sa != 0:
+            raise ValueError(f"scene_results reduces whole scenes: {self.A} agents (a shard: {self.sharded}) "
+                             f"are not a whole number of scenes of {sa}")
+        return reduce_scenes(self.results(stream), sa)
+
+
+class Rollout(_RolloutBase):
+    """The closed loop of `solver` (a BatchSolver with N >= 4) for the agents whose goals are `goal` [A][2].
+
+    vref      reference speed of the goal-directed line (workload.VREF)
+    phase     [A] int32 or None: added to the cycle index for the trot parity
+    plans     True: from the second cycle on, the inter-agent rows follow the neighbours' previous plans shifted
+              by one gait domain (srb_batch.nbr_plan) instead of the constant-velocity guess
+    log_x     True: keep every cycle's decision vectors (results()["x"], [T][A][nv])
+    obstacles [n_obs][2] or None: the static obstacles, for the solve and for d_obs / fail_cycle
+    obs_vel   [n_obs][2] or None: the obstacles' velocities (m/s).  The rollout then clones `obstacles` (it moves the
+              table), reset() restores the start table, and every shard moves its own full copy (the same bits)
+    obs_horizon  True: the static columns by closest predicted approach over the horizon (needs obs_vel)
+    agent_offset, n_all   a shard of a larger team: this batch is rows agent_offset .. agent_offset + A of the
+              n_all-row neighbour table that step(exchange) gathers (default: the whole team)
+    All tensors are float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
+
+    def __init__(self, solver, goal, vref: float = 0.27, phase=None, plans: bool = False, log_x: bool = False, *,
+                 obstacles=None, agent_offset: int = 0, n_all: int | None = None, obs_vel=None, obs_horizon: bool = False):
+        import torch
+        super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon)
+        A, p = self.A, solver.params
+        self.agent_offset = int(agent_offset)
+        self.n_all = A if n_all is None else int(n_all)
+        if self.agent_offset < 0 or self.agent_offset + A > self.n_all:
+            raise ValueError("agent_offset + A exceeds n_all")
+        self.sharded = self.agent_offset != 0 or self.n_all != A
+        f8 = dict(dtype=torch.float64, device=self.device)
+        self.alpha_buf = torch.zeros((A, 4), **f8)
+        self.ref = torch.zeros((A, 4 * p.N), **f8)
+        self.foot = torch.zeros((A, p.N, 2, p.C), **f8)
+        self.out["alpha"] = torch.zeros((A, 20), **f8)
 
     def _sim(self, nbr_state=None) -> Sim:
         nbr = self.last_state if nbr_state is None else nbr_state
@@ -152,30 +246,6 @@ class Rollout:
                    0 if self.obstacles is None else self.obstacles.shape[0], nbr.shape[0], self.agent_offset,
                    _dptr(m["d_obs"]), _dptr(m["d_agent"]), _dptr(m["min_d_obs"]), _dptr(m["min_d_agent"]),
                    _iptr(m["fail_cycle"]), _dptr(m["distance_to_fail"]))
-
-    # ------------------------------------------------------------------ driving
-    def reset(self, state):
-        """Start state [A][4] (x, xdot, y, ydot); the cycle count and the logs start over; with obs_vel the start
-        table is restored.  Both are torch copies on torch's current stream: a caller who then passes another
-        stream to step() / run() orders that stream after the current one first (nothing here does)."""
-        import torch
-        _check_tensor(state, (self.A, 4), "state", torch.float64, self.device)
-        self.state.copy_(state)
-        if self.obs_vel is not None:
-            self.obstacles.copy_(self.obstacles0)    # the start table
-        self.c = 0
-        self.flushed = True
-        self._ready = True
-
-    def advance(self, stream=None):
-        """The advance of the current cycle alone: state, x0, ref, foot, last_state (and the previous cycle's logs).
-        step() runs it itself; calling it first as well changes nothing (it rewrites the same values) and lets
-        shards driven from one process fill their snapshot rows before a stand-in exchange gathers them."""
-        if not self._ready:
-            raise RuntimeError("Rollout.advance before reset(state)")
-        s = self.solver
-        self._reserve(self.c + 1)
-        _check(lib().srb_sim_advance_device(s._h, self.A, ctypes.byref(self._sim()), self.c, s._stream(stream)))
 
     def step(self, exchange=None, plan_exchange=None, stream=None):
         """One cycle: advance, metrics, solve.  exchange (a dist.NeighbourExchange, or any callable
@@ -205,21 +275,8 @@ class Rollout:
         self.c += 1
         self.flushed = False
 
-    def run(self, T: int, stream=None):
-        """T cycles by the C driver (srb_rollout_device), right after reset(): one call, nothing synchronises
-        with the host inside.  A whole team only."""
-        T = int(T)
-        if not self._ready or self.c != 0:
-            raise RuntimeError("Rollout.run starts from reset(state) (use step() to go on)")
-        if T < 0:
-            raise ValueError("T must be >= 0")
-        if self.sharded:
-            raise ValueError("run() rolls out a whole team; a shard steps with its exchange (step)")
-        sa = self.solver.scenes[0]
-        if sa > 0 and self.A % sa != 0:
-            raise ValueError(f"run() rolls out whole scenes: {self.A} agents are not a multiple of scene_agents = {sa}")
+    def _drive(self, T: int, stream):
         s, o = self.solver, self.out
-        self._reserve(T)
         b = Batch(None, None, None, _dptr(self.obstacles), None,
                   0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                   None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]),
@@ -230,45 +287,6 @@ class Rollout:
         else:
             _check(lib().srb_rollout_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), T,
                                             s._stream(stream)))
-        self.c = T
-        self.flushed = True
-
-    def results(self, stream=None):
-        """The logs and metrics so far, as tensors (views of this object's buffers; asynchronous like the
-        launches -- synchronise before reading on the host): traj [T+1][A][4], status / iters [T][A][2],
-        x [T][A][nv] (log_x), state [A][4] (the end state), cycles, and d_obs, d_agent, min_d_obs,
-        min_d_agent, fail_cycle, distance_to_fail [A]; with obs_vel, obstacles [n_obs][2] (the current table: the
-        rows as the last cycle saw them)."""
-        if not self._ready:
-            raise RuntimeError("Rollout.results before reset(state)")
-        T = self.c
-        self._reserve(max(T, 1))
-        if not self.flushed:
-            self.advance(stream)                 # the final advance: the last logs and the end state
-            self.flushed = True
-        elif T == 0:
-            self.advance(stream)
-        out = dict(cycles=T, traj=self.traj[:T + 1], status=self.status_log[:T], iters=self.iters_log[:T],
-                   state=self.state, **self.metrics)
-        if self.log_x:
-            out["x"] = self.x_log[:T]
-        if self.obs_vel is not None:
-            out["obstacles"] = self.obstacles
-        return out
-
-    def scene_results(self, stream=None):
-        """results() reduced per scene of the solver's partition (BatchSolver.set_scenes; a whole number of scenes),
-        as device tensors [n_scenes]: min_d_agent and min_d_obs (the smallest over the scene's agents), n_failed
-        (agents with fail_cycle >= 0) and n_not_converged (solves of the logged cycles that did not converge: QP
-        stage neither OPTIMAL nor QP_WARM, or NLP stage not OPTIMAL); plus scene_agents and n_scenes.
-        Asynchronous like results()."""
-        sa = self.solver.scenes[0]
-        if sa <= 0:
-            raise ValueError("scene_results needs the solver's scene partition (BatchSolver.set_scenes)")
-        if self.sharded or self.A % sa != 0:
-            raise ValueError(f"scene_results reduces whole scenes: {self.A} agents (a shard: {self.sharded}) "
-                             f"are not a whole number of scenes of {sa}")
-        return reduce_scenes(self.results(stream), sa)
 
 
 def reduce_scenes(res, scene_agents: int):

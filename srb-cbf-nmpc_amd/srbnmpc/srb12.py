@@ -13,15 +13,20 @@ srb12_plans): Solver12.solve / solve_device take nbr_plan and return plan, Solve
 Jacobi driver over the plans, and Rollout12(plans=True) feeds last cycle's plans forward.  Moving
 obstacles (srb_moving): obs_vel / obs_horizon on Solver12.solve, solve_device, solve_coupled_device
 and Rollout12, Solver12.advance_obstacles_device; velocities from workload.obstacle_velocities.
+
+The host layer of these features is written once for both modes: Solver12 is a _SolverBase (srbnmpc/__init__.py: the
+context's life, _stream, set_scenes, the Jacobi loop), Rollout12 a rollout._RolloutBase (the checks, buffers, logs,
+reset / advance / run / results), and the pointer casts, the (Ko, Kn) clamp and the srb_moving checks are the package's.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes
 
 import numpy as np
 
-from . import Moving, _check, _check_plan_array, _check_vel_array, _dp, _ip, _p, lib, workload
+from . import (Moving, _SolverBase, _check, _check_plan_array, _check_vel_array, _clamp_selected, _dp, _dptr, _ip, _iptr,
+               _moving_args, _p, lib, workload)
+from .rollout import _RolloutBase
 
 _p12_fields = [("N", ctypes.c_int), ("K_obs", ctypes.c_int), ("K_nbr", ctypes.c_int),
                ("Ts", ctypes.c_double), ("mass", ctypes.c_double), ("Ib", ctypes.c_double * 9),
@@ -124,15 +129,6 @@ def _lib():
     return L
 
 
-def _moving_args(obs_vel, n_obs, dtype, use_nlp):
-    """The checks of obs_vel that need no context, by name (BatchSolver's; obs_horizon without obs_vel is the
-    library's refusal)."""
-    if not use_nlp:
-        raise ValueError("obs_vel / obs_horizon: the QP-only solve has no obstacle rows")
-    if obs_vel is not None:
-        _check_vel_array(obs_vel, n_obs, dtype)
-
-
 def default_params(N: int = 10, **overrides) -> Params12:
     p = Params12()
     _lib().srb12_params_default(ctypes.byref(p), N)
@@ -148,57 +144,13 @@ def lds_bytes(p: Params12) -> int:
 def n_selected(p: Params12, n_obs: int, n_all: int, scenes=(0, 0)):
     """(Ko, Kn) rows selected per agent for tables of these sizes (clamped as the C ABI does; with a scene
     partition (scene_agents, scene_obs) to the agent's scene)."""
-    rows, others = max(n_obs, 0), max(n_all - 1, 0)
-    if scenes[0] > 0:
-        rows, others = min(rows, scenes[1]), (scenes[0] - 1 if n_all > 0 else 0)
-    Ko = min(p.K_obs, rows) if p.use_nlp else 0
-    Kn = min(p.K_nbr, others) if p.use_nlp else 0
-    return Ko, Kn
+    return _clamp_selected(p.K_obs, p.K_nbr, n_obs, n_all, scenes) if p.use_nlp else (0, 0)
 
 
-class Solver12:
+class Solver12(_SolverBase):
     """One HIP context solving SRB-12 batches of up to `max_agents` agents."""
-
-    def __init__(self, params: Params12, max_agents: int, device: int = 0):
-        self.params = params
-        self.max_agents = int(max_agents)
-        self.device = int(device)
-        h = ctypes.c_void_p()
-        _check(_lib().srb12_ctx_create(ctypes.byref(params), self.max_agents, self.device, ctypes.byref(h)))
-        self._h = h
-        self._scenes = (0, 0)
-
-    def _stream(self, stream):
-        """hipStream_t for a launch: the caller's, else torch's current stream on this device."""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-        return ctypes.c_void_p(stream)
-
-    def set_scenes(self, scene_agents: int = 0, scene_obs: int = 0):
-        """The batch as independent teams (srb12_ctx_set_scenes): scene_agents agents and scene_obs obstacle rows
-        per scene, tables flat and scene-major; agent g selects and is measured within scene g // scene_agents,
-        sel holds global rows.  (0, 0): off, one team."""
-        _check(_lib().srb12_ctx_set_scenes(self._h, int(scene_agents), int(scene_obs)))
-        a, o = ctypes.c_int(), ctypes.c_int()
-        _check(_lib().srb12_ctx_scenes(self._h, ctypes.byref(a), ctypes.byref(o)))
-        self._scenes = (a.value, o.value)
-
-    @property
-    def scenes(self):
-        """(scene_agents, scene_obs) as last set through set_scenes; (0, 0) when off."""
-        return self._scenes
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _lib().srb12_ctx_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _abi = "srb12"
+    _lib = staticmethod(_lib)
 
     def solve(self, x0, xref, foot, contact, obstacles=None, nbr_state=None, agent_offset: int = 0, nbr_plan=None,
               plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False):
@@ -229,8 +181,7 @@ class Solver12:
         out["plan"] = np.zeros((A, p.N, 2))
         pl = Plans12(_p(nbr_plan) if nbr_plan is not None else None, _p(out["plan"]), 1 if plan_selection else 0, None)
         if obs_vel is not None or obs_horizon:
-            _moving_args(obs_vel, ob.shape[0], np.float64, p.use_nlp)
-            mv = Moving(_p(obs_vel) if obs_vel is not None else None, int(bool(obs_horizon)), None)
+            mv = _moving_args(obs_vel, obs_horizon, ob.shape[0], np.float64, _p, p.use_nlp)
             _check(_lib().srb12_solve_batch_moving(self._h, A, ctypes.byref(b), ctypes.byref(pl), ctypes.byref(mv)))
             return out
         _check(_lib().srb12_solve_batch_plans(self._h, A, ctypes.byref(b), ctypes.byref(pl)))
@@ -246,11 +197,6 @@ class Solver12:
         closest predicted approach (needs nbr_plan).  obs_vel ([n_obs][2] float64, contiguous): the obstacles'
         velocities (srb12_solve_batch_moving_device; needs obstacles_version 0); obs_horizon=True selects the static
         columns by closest predicted approach (needs obs_vel).  Asynchronous on `stream` (default: torch's current)."""
-        def dptr(t):
-            return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _dp)
-
-        def iptr(t):
-            return None if t is None else ctypes.cast(ctypes.c_void_p(t.data_ptr()), _ip)
         A = x0.shape[0]
         import torch
         Ko, Kn = n_selected(self.params, 0 if obstacles is None else obstacles.shape[0],
@@ -261,10 +207,10 @@ class Solver12:
         if sel is not None and (sel.dtype != torch.int32 or tuple(sel.shape) != (A, Ko + Kn) or not sel.is_contiguous()):
             raise ValueError(f"out['sel'] must be a contiguous int32 tensor of shape ({A}, {Ko + Kn}) "
                              f"(n_selected(params, n_obs, n_all)), got {tuple(sel.shape)} {sel.dtype}")
-        b = Batch12(dptr(x0), dptr(xref), dptr(foot), iptr(contact), dptr(obstacles), dptr(nbr_state),
+        b = Batch12(_dptr(x0), _dptr(xref), _dptr(foot), _iptr(contact), _dptr(obstacles), _dptr(nbr_state),
                     0 if obstacles is None else obstacles.shape[0], 0 if nbr_state is None else nbr_state.shape[0],
-                    int(agent_offset), dptr(out.get("x_qp")), dptr(out["x"]), dptr(out["obj"]), iptr(out["status"]),
-                    iptr(out["iters"]), iptr(out.get("sel")), int(obstacles_version))
+                    int(agent_offset), _dptr(out.get("x_qp")), _dptr(out["x"]), _dptr(out["obj"]), _iptr(out["status"]),
+                    _iptr(out["iters"]), _iptr(sel), int(obstacles_version))
         if plan is None:
             plan = out.get("plan")
         N = self.params.N
@@ -275,17 +221,16 @@ class Solver12:
             _check_plan_array(plan, (A, N, 2), "plan", torch.float64)
         no_plans = nbr_plan is None and plan is None and not plan_selection
         if obs_vel is not None or obs_horizon:
-            _moving_args(obs_vel, 0 if obstacles is None else obstacles.shape[0], torch.float64,
-                         self.params.use_nlp)
-            mv = Moving(dptr(obs_vel), int(bool(obs_horizon)), None)
-            pl = None if no_plans else ctypes.byref(Plans12(dptr(nbr_plan), dptr(plan), 1 if plan_selection else 0, None))
+            mv = _moving_args(obs_vel, obs_horizon, 0 if obstacles is None else obstacles.shape[0], torch.float64, _dptr,
+                              self.params.use_nlp)
+            pl = None if no_plans else ctypes.byref(Plans12(_dptr(nbr_plan), _dptr(plan), 1 if plan_selection else 0, None))
             _check(_lib().srb12_solve_batch_moving_device(self._h, A, ctypes.byref(b), pl, ctypes.byref(mv),
                                                           self._stream(stream)))
             return
         if no_plans:
             _check(_lib().srb12_solve_batch_device(self._h, A, ctypes.byref(b), self._stream(stream)))
             return
-        pl = Plans12(dptr(nbr_plan), dptr(plan), 1 if plan_selection else 0, None)
+        pl = Plans12(_dptr(nbr_plan), _dptr(plan), 1 if plan_selection else 0, None)
         _check(_lib().srb12_solve_batch_plans_device(self._h, A, ctypes.byref(b), ctypes.byref(pl), self._stream(stream)))
 
     def shift_plans_device(self, plan, table, grids: int = SHIFT_GRIDS, stream=None):
@@ -295,8 +240,7 @@ class Solver12:
         A = plan.shape[0] if hasattr(plan, "shape") and len(plan.shape) == 3 else -1
         _check_plan_array(plan, (A, self.params.N, 2), "plan", torch.float64)
         _check_plan_array(table, (A, self.params.N, 2), "table", torch.float64)
-        _check(_lib().srb12_shift_plans_device(self._h, A, ctypes.cast(ctypes.c_void_p(plan.data_ptr()), _dp), int(grids),
-                                               ctypes.cast(ctypes.c_void_p(table.data_ptr()), _dp), self._stream(stream)))
+        _check(_lib().srb12_shift_plans_device(self._h, A, _dptr(plan), int(grids), _dptr(table), self._stream(stream)))
 
     def advance_obstacles_device(self, obstacles, obs_vel, stream=None):
         """One control cycle (4 grids) of a moving obstacle table, in place (srb12_obstacles_advance_device):
@@ -305,9 +249,7 @@ class Solver12:
         n = obstacles.shape[0] if hasattr(obstacles, "shape") and len(obstacles.shape) else -1
         _check_vel_array(obstacles, n, torch.float64, "obstacles")
         _check_vel_array(obs_vel, n, torch.float64)
-        _check(_lib().srb12_obstacles_advance_device(self._h, n, ctypes.cast(ctypes.c_void_p(obstacles.data_ptr()), _dp),
-                                                     ctypes.cast(ctypes.c_void_p(obs_vel.data_ptr()), _dp),
-                                                     self._stream(stream)))
+        _check(_lib().srb12_obstacles_advance_device(self._h, n, _dptr(obstacles), _dptr(obs_vel), self._stream(stream)))
 
     def solve_coupled_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, outer: int = 2, exchange=None,
                              nbr_plan=None, agent_offset: int = 0, stream=None, obstacles_version: int = 0,
@@ -321,37 +263,10 @@ class Solver12:
         plan_change, a device tensor [outer - 1]: max |plan_r - plan_{r-1}| per round (torch reductions; nothing
         synchronises with the host inside the loop).  plan_selection applies to every round that has a table; obs_vel
         and obs_horizon as solve_device (every round solves against the same moving table)."""
-        import torch
-        outer = int(outer)
-        if outer < 1:
-            raise ValueError("outer must be >= 1")
-        plan = out.get("plan")
-        if plan is None:
-            raise ValueError("solve_coupled_device needs out['plan'] ([A][N][2] float64)")
-        A, N = x0.shape[0], self.params.N
-        _check_plan_array(plan, (A, N, 2), "out['plan']", torch.float64)
-        if exchange is None and outer > 1 and (nbr_state is None or nbr_state.shape[0] != A or agent_offset != 0):
-            raise ValueError("solve_coupled_device without an exchange iterates over this batch's own plans: "
-                             "nbr_state must hold exactly the batch's agents (agent_offset 0)")
-        other = getattr(self, "_plan_pong", None)
-        if outer > 1 and (other is None or other.shape != plan.shape or other.device != plan.device):
-            other = self._plan_pong = torch.empty_like(plan)
-        ctx = torch.cuda.stream(torch.cuda.ExternalStream(stream)) if stream is not None else contextlib.nullcontext()
-        change = torch.zeros(max(outer - 1, 0), dtype=torch.float64, device=plan.device)
-        with ctx:
-            table, prev = nbr_plan, None
-            for r in range(outer):
-                cur = plan if (outer - 1 - r) % 2 == 0 else other      # the last round writes out["plan"]
-                if r > 0:
-                    table = exchange(prev) if exchange is not None else prev
-                self.solve_device(x0, xref, foot, contact, obstacles, nbr_state, out, agent_offset=agent_offset,
-                                  stream=stream, obstacles_version=obstacles_version, nbr_plan=table,
-                                  plan_selection=plan_selection and table is not None, plan=cur, obs_vel=obs_vel,
-                                  obs_horizon=obs_horizon)
-                if r > 0:
-                    change[r - 1] = (cur - prev).abs().max()
-                prev = cur
-        return change
+        return self._solve_coupled((x0, xref, foot, contact, obstacles, nbr_state, out), outer, exchange, nbr_plan,
+                                   agent_offset, stream,
+                                   lambda table: {"plan_selection": plan_selection and table is not None},
+                                   obstacles_version=obstacles_version, obs_vel=obs_vel, obs_horizon=obs_horizon)
 
     def last_kernel_ms(self):
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -370,7 +285,7 @@ def split(p: Params12, x):
             x[..., 24 * N])
 
 
-class Rollout12:
+class Rollout12(_RolloutBase):
     """The closed loop of `solver` (a Solver12 with N >= 4) for the agents whose goals are `goal` [A][2]
     (srb12_sim_advance_device / srb12_sim_metrics_device / srb12_rollout_device): srbnmpc.Rollout for the 12-state
     body, with the nominal plant, the goal-directed reference of workload.make_batch12 re-centred every cycle and
@@ -401,95 +316,29 @@ class Rollout12:
     obs_horizon True: the static columns by closest predicted approach over the horizon (needs obs_vel)
     A whole team on one GPU (the SRB-12 mode has no sharded stepping).  All tensors are
     float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
+    _nx = 12
+    _name = "Rollout12"
 
     def __init__(self, solver, goal, vref: float = 0.27, phase=None, gait: str = "trot", log_x: bool = False,
                  obstacles=None, hcom: float = workload.HCOM12, yaw_step: float = 0.1, hold_radius: float = 0.05,
                  plans: bool = False, plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False):
         import torch
-        from .rollout import _check_tensor
-        self.solver = solver
-        p = solver.params
-        if p.N < 4:
-            raise ValueError("Rollout12 needs N >= 4 (one cycle is one gait domain of 4 grids)")
         if gait not in GAITS:
             raise ValueError(f"gait must be one of {sorted(GAITS)}, got {gait!r}")
-        self.device = torch.device("cuda", solver.device)
-        if not hasattr(goal, "shape") or len(goal.shape) != 2:
-            raise ValueError("goal must be a [A][2] tensor")
-        A = self.A = int(goal.shape[0])
-        if A < 1 or A > solver.max_agents:
-            raise ValueError(f"goal holds {A} agents, the solver takes 1 .. {solver.max_agents}")
-        _check_tensor(goal, (A, 2), "goal", torch.float64, self.device)
-        if phase is not None:
-            _check_tensor(phase, (A,), "phase", torch.int32, self.device)
-        if obstacles is not None:
-            _check_tensor(obstacles, (obstacles.shape[0], 2), "obstacles", torch.float64, self.device)
-            if obstacles.shape[0] == 0:
-                obstacles = None
-        if obs_vel is not None:
-            if obstacles is None:
-                raise ValueError("obs_vel needs obstacles (one velocity row per obstacle row)")
-            _check_vel_array(obs_vel, obstacles.shape[0], torch.float64)
-            if obs_vel.device != self.device:
-                raise ValueError(f"obs_vel must be on {self.device}, got {obs_vel.device}")
-            self.obstacles0 = obstacles
-            obstacles = obstacles.clone()            # the rollout moves its table; the caller's stays
-        elif obs_horizon:
-            raise ValueError("obs_horizon needs obs_vel (the horizon-aware obstacle selection reads the velocities)")
-        self.obs_vel, self.obs_horizon = obs_vel, bool(obs_horizon)
-        self.goal, self.phase, self.obstacles = goal, phase, obstacles
-        self.vref, self.gait, self.log_x = float(vref), gait, bool(log_x)
-        self.hcom = float(hcom)
-        self.plans, self.plan_selection = bool(plans), bool(plan_selection)
+        super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon)
+        self.gait, self.hcom = gait, float(hcom)
+        self.plan_selection = bool(plan_selection)
         if self.plan_selection and not self.plans:
             raise ValueError("plan_selection needs plans=True (the horizon-aware selection reads the plan table)")
         self.yaw_step, self.hold_radius = float(yaw_step), float(hold_radius)
-        N, nv = p.N, p.nv
+        A, N = self.A, solver.params.N
         f8 = dict(dtype=torch.float64, device=self.device)
-        i4 = dict(dtype=torch.int32, device=self.device)
-        self.state, self.x0 = torch.zeros((A, 12), **f8), torch.zeros((A, 12), **f8)
-        self.last_state, self.com = torch.zeros((A, 4), **f8), torch.zeros((A, 4), **f8)
+        self.com = torch.zeros((A, 4), **f8)
         self.xref = torch.zeros((A, N, 12), **f8)
         self.foot = torch.zeros((A, N, 4, 3), **f8)
-        self.contact = torch.zeros((A, N, 4), **i4)
-        self.out = dict(x=torch.zeros((A, nv), **f8), obj=torch.zeros(A, **f8), status=torch.zeros((A, 2), **i4),
-                        iters=torch.zeros((A, 2), **i4))
-        self.plan_table = None
-        if self.plans:
-            self.plan_table = torch.zeros((A, N, 2), **f8)
-            self.out["plan"] = torch.zeros((A, N, 2), **f8)
-        self.metrics = dict(d_obs=torch.zeros(A, **f8), d_agent=torch.zeros(A, **f8), min_d_obs=torch.zeros(A, **f8),
-                            min_d_agent=torch.zeros(A, **f8), fail_cycle=torch.full((A,), -1, **i4),
-                            distance_to_fail=torch.zeros(A, **f8))
-        self.cap = 0
-        self.traj = self.status_log = self.iters_log = self.x_log = None
-        self.c = 0
-        self.flushed = True
-        self._ready = False
-
-    # ------------------------------------------------------------------ buffers
-    def _reserve(self, cycles: int):
-        """Log rows for `cycles` cycles (traj one more); grown by copying, so earlier rows stay."""
-        import torch
-        if cycles <= self.cap:
-            return
-        cap = max(cycles, 2 * self.cap, 8)
-        A, nv = self.A, self.solver.params.nv
-
-        def grow(old, rows, tail, dtype):
-            new = torch.zeros((rows,) + tail, dtype=dtype, device=self.device)
-            if old is not None:
-                new[:old.shape[0]] = old
-            return new
-        self.traj = grow(self.traj, cap + 1, (A, 12), torch.float64)
-        self.status_log = grow(self.status_log, cap, (A, 2), torch.int32)
-        self.iters_log = grow(self.iters_log, cap, (A, 2), torch.int32)
-        if self.log_x:
-            self.x_log = grow(self.x_log, cap, (A, nv), torch.float64)
-        self.cap = cap
+        self.contact = torch.zeros((A, N, 4), dtype=torch.int32, device=self.device)
 
     def _sim(self) -> Sim12:
-        from .rollout import _dptr, _iptr
         m, o = self.metrics, self.out
         return Sim12(_dptr(self.state), _dptr(self.goal), _iptr(self.phase), self.vref, self.hcom, self.yaw_step,
                      self.hold_radius, GAITS[self.gait], 0, _dptr(o["x"]), _iptr(o["status"]), _iptr(o["iters"]),
@@ -499,29 +348,6 @@ class Rollout12:
                      0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                      _dptr(m["d_obs"]), _dptr(m["d_agent"]), _dptr(m["min_d_obs"]), _dptr(m["min_d_agent"]),
                      _iptr(m["fail_cycle"]), _dptr(m["distance_to_fail"]))
-
-    # ------------------------------------------------------------------ driving
-    def reset(self, state):
-        """Start state [A][12] (p, roll/pitch/yaw, v, omega); the cycle count and the logs start over; with obs_vel
-        the start table is restored (torch copies on torch's current stream)."""
-        import torch
-        from .rollout import _check_tensor
-        _check_tensor(state, (self.A, 12), "state", torch.float64, self.device)
-        self.state.copy_(state)
-        if self.obs_vel is not None:
-            self.obstacles.copy_(self.obstacles0)    # the start table
-        self.c = 0
-        self.flushed = True
-        self._ready = True
-
-    def advance(self, stream=None):
-        """The advance of the current cycle alone: state, x0, xref, foot, contact, last_state, com (and the previous
-        cycle's logs).  step() runs it itself; calling it first as well rewrites the same values."""
-        if not self._ready:
-            raise RuntimeError("Rollout12.advance before reset(state)")
-        s = self.solver
-        self._reserve(self.c + 1)
-        _check(_lib().srb12_sim_advance_device(s._h, self.A, ctypes.byref(self._sim()), self.c, s._stream(stream)))
 
     def step(self, stream=None):
         """One cycle: advance, metrics, solve."""
@@ -542,20 +368,8 @@ class Rollout12:
         self.c += 1
         self.flushed = False
 
-    def run(self, T: int, stream=None):
-        """T cycles by the C driver (srb12_rollout_device), right after reset(): one call, nothing synchronises
-        with the host inside."""
-        from .rollout import _dptr, _iptr
-        T = int(T)
-        if not self._ready or self.c != 0:
-            raise RuntimeError("Rollout12.run starts from reset(state) (use step() to go on)")
-        if T < 0:
-            raise ValueError("T must be >= 0")
-        sa = self.solver.scenes[0]
-        if sa > 0 and self.A % sa != 0:
-            raise ValueError(f"run() rolls out whole scenes: {self.A} agents are not a multiple of scene_agents = {sa}")
+    def _drive(self, T: int, stream):
         s, o = self.solver, self.out
-        self._reserve(T)
         b = Batch12(None, None, None, None, _dptr(self.obstacles), None,
                     0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                     None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]), None, 0)
@@ -563,9 +377,8 @@ class Rollout12:
             pl = None
             if self.plans:
                 pl = ctypes.byref(Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table)))
-            mv = Moving(_dptr(self.obs_vel), int(self.obs_horizon), _dptr(self.obstacles))
             _check(_lib().srb12_rollout_moving_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl,
-                                                      ctypes.byref(mv), T, s._stream(stream)))
+                                                      ctypes.byref(self._moving()), T, s._stream(stream)))
         elif self.plans:
             pl = Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table))
             _check(_lib().srb12_rollout_plans_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()),
@@ -573,41 +386,3 @@ class Rollout12:
         else:
             _check(_lib().srb12_rollout_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), T,
                                                s._stream(stream)))
-        self.c = T
-        self.flushed = True
-
-    def results(self, stream=None):
-        """The logs and metrics so far, as tensors (views of this object's buffers; asynchronous like the
-        launches -- synchronise before reading on the host): traj [T+1][A][12], status / iters [T][A][2],
-        x [T][A][24N+1] (log_x), state [A][12] (the end state), cycles, and d_obs, d_agent, min_d_obs,
-        min_d_agent, fail_cycle, distance_to_fail [A]; with obs_vel, obstacles [n_obs][2] (the current table: the rows
-        as the last cycle saw them)."""
-        if not self._ready:
-            raise RuntimeError("Rollout12.results before reset(state)")
-        T = self.c
-        self._reserve(max(T, 1))
-        if not self.flushed:
-            self.advance(stream)                 # the final advance: the last logs and the end state
-            self.flushed = True
-        elif T == 0:
-            self.advance(stream)
-        out = dict(cycles=T, traj=self.traj[:T + 1], status=self.status_log[:T], iters=self.iters_log[:T],
-                   state=self.state, **self.metrics)
-        if self.log_x:
-            out["x"] = self.x_log[:T]
-        if self.obs_vel is not None:
-            out["obstacles"] = self.obstacles
-        return out
-
-    def scene_results(self, stream=None):
-        """results() reduced per scene of the solver's partition (Solver12.set_scenes; a whole number of scenes):
-        rollout.reduce_scenes -- min_d_agent, min_d_obs, n_failed, n_not_converged [n_scenes], scene_agents and
-        n_scenes.  Asynchronous like results()."""
-        from .rollout import reduce_scenes
-        sa = self.solver.scenes[0]
-        if sa <= 0:
-            raise ValueError("scene_results needs the solver's scene partition (Solver12.set_scenes)")
-        if self.A % sa != 0:
-            raise ValueError(f"scene_results reduces whole scenes: {self.A} agents are not a whole number of scenes "
-                             f"of {sa}")
-        return reduce_scenes(self.results(stream), sa)
