@@ -158,6 +158,68 @@ SRB_HD static inline int srb_slots(int N, int C, int K) { return (6 + C) * N + 1
 
 SRB_HD static inline int srb_r4(int x) { return (x + 3) & ~3; }
 
+// ---- slot kinds (srb_kernels.hip `Slot`): the one rule that maps a slot index to its kind, from the slot ranges
+// sE = n, sV = sE + 2(N-1), sO = sV + 2N, S = sO + N K -- slot_init tests a slot against the same range ends
+// (SRB_SLOT_END), and the per-trip tables of the compiled-shape instances below are derived from those ranges
+// (the kernel static_asserts them against the rule, srb_trips_cover)
+enum { SRB_K_NONE = 0, SRB_K_VAR = 1, SRB_K_COP = 2, SRB_K_VEL = 3, SRB_K_OBS = 4 };
+#define SRB_KM(k) (1 << (k))
+#define SRB_KM_ANY (SRB_KM(SRB_K_NONE) | SRB_KM(SRB_K_VAR) | SRB_KM(SRB_K_COP) | SRB_KM(SRB_K_VEL) | SRB_KM(SRB_K_OBS))
+// the slots of kind k end (exclusive) here; the kinds follow one another in the order VAR, COP, VEL, OBS, then NONE.
+// (a macro, so that slot_init's `sl < SRB_SLOT_END(K_VAR, ..)` is the bare comparison to the compiler)
+#define SRB_SLOT_END(k, sE, sV, sO, S) ((k) == SRB_K_VAR ? (sE) : (k) == SRB_K_COP ? (sV) : (k) == SRB_K_VEL ? (sO) : (S))
+SRB_HD constexpr int srb_slot_kind(int sl, int sE, int sV, int sO, int S)
+{
+    return sl < SRB_SLOT_END(SRB_K_VAR, sE, sV, sO, S) ? SRB_K_VAR : sl < SRB_SLOT_END(SRB_K_COP, sE, sV, sO, S) ? SRB_K_COP :
+           sl < SRB_SLOT_END(SRB_K_VEL, sE, sV, sO, S) ? SRB_K_VEL : sl < SRB_SLOT_END(SRB_K_OBS, sE, sV, sO, S) ? SRB_K_OBS : SRB_K_NONE;
+}
+// Trip t of an instance with NTH threads per agent holds the slots [NTH t, NTH (t + 1)).  For a compiled shape
+// (NC, CC, KC > 0) the kinds that can occur there are known when the kernel is compiled; a run-time shape
+// (any of them 0) reports every kind, two rows, for every trip.
+SRB_HD constexpr bool srb_shape_compiled(int NC, int CC, int KC) { return NC > 0 && CC > 0 && KC > 0; }
+// bitmask (SRB_KM) of the kinds that can occur on trip t
+SRB_HD constexpr int srb_trip_kinds(int NC, int CC, int KC, int NTH, int t)
+{
+    if (!srb_shape_compiled(NC, CC, KC)) return SRB_KM_ANY;
+    const int n = (6 + CC) * NC + 1, sE = n, sV = sE + 2 * (NC - 1), sO = sV + 2 * NC, S = sO + NC * KC;
+    const int lo = NTH * t, hi = lo + NTH;                 // the kind of range [a, b) occurs iff lo < b and a < hi
+    return (lo < sE ? SRB_KM(SRB_K_VAR) : 0) | ((lo < sV && sE < hi) ? SRB_KM(SRB_K_COP) : 0) |
+           ((lo < sO && sV < hi) ? SRB_KM(SRB_K_VEL) : 0) | ((lo < S && sO < hi) ? SRB_KM(SRB_K_OBS) : 0) |
+           (S < hi ? SRB_KM(SRB_K_NONE) : 0);
+}
+// rows a slot of trip t can have on: 1 where only single-row kinds occur (OBS, NONE: row 1 is off in every stage)
+SRB_HD constexpr int srb_trip_rows(int NC, int CC, int KC, int NTH, int t)
+{
+    return (srb_trip_kinds(NC, CC, KC, NTH, t) & ~(SRB_KM(SRB_K_OBS) | SRB_KM(SRB_K_NONE))) ? 2 : 1;
+}
+// every slot of trip t is a VAR below n - 1 (X, U, lambda; not the slack): both rows are on in both stages
+SRB_HD constexpr bool srb_trip_all_rows_on(int NC, int CC, int KC, int NTH, int t)
+{
+    return srb_shape_compiled(NC, CC, KC) && NTH * (t + 1) <= (6 + CC) * NC;
+}
+// some slot of trip t is the VAR of a CoM position or velocity (v < 4 N): only those carry an obstacle-dual sum
+SRB_HD constexpr bool srb_trip_has_com(int NC, int CC, int KC, int NTH, int t)
+{
+    return !srb_shape_compiled(NC, CC, KC) || NTH * t < 4 * NC;
+}
+// the tables above against the rule, slot by slot, over TS trips (the kernel's static_assert: a kind missing from
+// a trip's mask would silently drop that slot's constraint rows)
+SRB_HD constexpr bool srb_trips_cover(int NC, int CC, int KC, int NTH, int TS)
+{
+    if (!srb_shape_compiled(NC, CC, KC)) return true;
+    const int n = (6 + CC) * NC + 1, sE = n, sV = sE + 2 * (NC - 1), sO = sV + 2 * NC, S = sO + NC * KC;
+    if (S > NTH * TS) return false;
+    for (int t = 0; t < TS; t++)
+        for (int i = 0; i < NTH; i++) {
+            const int sl = NTH * t + i, kd = srb_slot_kind(sl, sE, sV, sO, S);
+            if (!(srb_trip_kinds(NC, CC, KC, NTH, t) & SRB_KM(kd))) return false;
+            if (srb_trip_rows(NC, CC, KC, NTH, t) == 1 && kd != SRB_K_OBS && kd != SRB_K_NONE) return false;
+            if (srb_trip_all_rows_on(NC, CC, KC, NTH, t) && !(kd == SRB_K_VAR && sl < n - 1)) return false;
+            if (!srb_trip_has_com(NC, CC, KC, NTH, t) && sl < 4 * NC) return false;
+        }
+    return true;
+}
+
 
 // doubles of dynamic LDS one agent needs for instance bound NZL; must match the carve in
 // nmpc_agent (srb_kernels.hip)

@@ -849,7 +849,11 @@ __device__ __forceinline__ int lambda_basis(const double *F, int C, int t, doubl
 //   VEL  [.., + 2N) (NLP):       f = xdot_k / ydot_k, +-vsat; adds into term row v
 //   OBS  [.., + N K) (NLP):      f = -|p_k - o_kj|^2 - s, single row <= -eps_j; term row M_o
 // so residuals, Newton rows, step lengths and updates are one straight-line code path.
-enum { K_NONE = 0, K_VAR = 1, K_COP = 2, K_VEL = 3, K_OBS = 4 };
+// In a compiled-shape instance the kinds of trip t = s / (64 NW) are known when the kernel is compiled
+// (SlotTrips below): e.g. 12_4_1_10_2_11 has trip 0 all VAR, trip 1 mixed, trips 2 and 3 OBS / NONE, and on
+// the last two the row-1 fields of the slot (s[1], z[1], ...) are never touched, so they hold no registers.
+// (the rule slot -> kind: srb_slot_kind, srb_kernel_params.h)
+enum { K_NONE = SRB_K_NONE, K_VAR = SRB_K_VAR, K_COP = SRB_K_COP, K_VEL = SRB_K_VEL, K_OBS = SRB_K_OBS };
 
 struct Slot {
     double s[2], z[2], iz[2], is[2], dz[2], ds[2], dsT[2], r3[2];
@@ -864,7 +868,9 @@ struct Slot {
 };
 
 // kind read through an opaque copy: comparisons on it are recomputed at each use instead
-// of being hoisted into lane masks that stay live across the whole iteration
+// of being hoisted into lane masks that stay live across the whole iteration.  The slot passes
+// reach it through SlotTrips (below), which answers from the compiled shape's trip table where it can
+// and reads the kind only on the trips that mix kinds
 __device__ __forceinline__ int kind_of(const Slot &q)
 {
     int k = q.kind;
@@ -872,17 +878,69 @@ __device__ __forceinline__ int kind_of(const Slot &q)
     return k;
 }
 
+// What the slot passes know at compile time about trip t of an instance (NTH threads per agent, shape NC, CC, KC):
+// the slots tid + NTH t of a compiled shape can only be of the kinds srb_trip_kinds gives (srb_kernel_params.h),
+// so after the passes' `#pragma unroll` over t
+//   - a test for a kind that cannot occur on the trip is false, and a trip of one kind never reads q.kind;
+//   - on a trip of single-row kinds (OBS / NONE) row 1 is neither computed nor kept (two(t) false, m(q, t, 1) = 0);
+//   - where every slot is a VAR below n - 1 the row masks could be the constant 1 (on(t); switched off, see there).
+// A trip of mixed kinds keeps the opaque kind_of() path, and so does every trip of a run-time shape (any kind, two
+// rows, masks from q.m): those instances compile to what they were without the table.
+template <int NTH, int TS, int NC, int CC, int KC>
+struct SlotTrips {
+    static_assert(srb_trips_cover(NC, CC, KC, NTH, TS), "slot-kind tables do not cover the slots of a trip");
+    static constexpr bool compiled = srb_shape_compiled(NC, CC, KC);
+    static __device__ __forceinline__ constexpr int kinds(int t) { return srb_trip_kinds(NC, CC, KC, NTH, t); }
+    static __device__ __forceinline__ constexpr bool can(int t, int k) { return (kinds(t) >> k) & 1; }
+    static __device__ __forceinline__ constexpr bool only(int t, int k) { return kinds(t) == (1 << k); }
+    static __device__ __forceinline__ constexpr bool single(int t) { return (kinds(t) & (kinds(t) - 1)) == 0; }
+    static __device__ __forceinline__ constexpr bool two(int t) { return srb_trip_rows(NC, CC, KC, NTH, t) == 2; }
+    // both rows on in both stages (srb_trip_all_rows_on: the all-VAR trip).  Not used for the masks: with m = 1 folded
+    // into the arithmetic of that trip every product is still exact, but the compiler then pairs some multiply and
+    // add of the iteration into a different fma, and 190 of configs[2]'s 1024 agents ended 5e-12 off the bits they
+    // had (bisected on the GPU, one part of the table at a time).  The masks of that trip stay in q.m.
+    static constexpr bool USE_ALL_ROWS_ON = false;
+    static __device__ __forceinline__ constexpr bool on(int t) { return USE_ALL_ROWS_ON && srb_trip_all_rows_on(NC, CC, KC, NTH, t); }
+    static __device__ __forceinline__ constexpr bool com(int t) { return srb_trip_has_com(NC, CC, KC, NTH, t); }
+    static __device__ __forceinline__ constexpr int the_kind(int t)
+    {
+        return only(t, K_VAR) ? K_VAR : only(t, K_COP) ? K_COP : only(t, K_VEL) ? K_VEL : only(t, K_OBS) ? K_OBS : K_NONE;
+    }
+    // the slot's kind for several tests (eq): the trip's one kind, or the opaque / plain read of q.kind
+    static __device__ __forceinline__ int kind(const Slot &q, int t) { return single(t) ? the_kind(t) : kind_of(q); }
+    static __device__ __forceinline__ constexpr bool eq(int t, int kd, int k) { return can(t, k) && kd == k; }
+    // one test (opaque / plain)
+    static __device__ __forceinline__ bool is(const Slot &q, int t, int k) { return can(t, k) && (only(t, k) || kind_of(q) == k); }
+    static __device__ __forceinline__ bool isp(const Slot &q, int t, int k) { return can(t, k) && (only(t, k) || q.kind == k); }
+    // row mask
+    static __device__ __forceinline__ double m(const Slot &q, int t, int r) { return on(t) ? 1.0 : (r && !two(t)) ? 0.0 : q.m[r]; }
+};
+
+// The slot passes' view of SlotTrips (TK: the pass's instance of it, t: the unrolled trip).  For a run-time shape each
+// of these is the plain expression the pass used before the table existed, chosen while the source is parsed
+// (TK::compiled is a constant there), so those instances compile to the code they had.
+#define SK_IS(q, t, k) (TK::compiled ? TK::is(q, t, k) : kind_of(q) == (k))        /* one kind test, opaque read */
+#define SK_ISP(q, t, k) (TK::compiled ? TK::isp(q, t, k) : (q).kind == (k))        /* ... plain read */
+#define SK_KIND(q, t) (TK::compiled ? TK::kind(q, t) : kind_of(q))                 /* the kind for several SK_EQ tests */
+#define SK_EQ(t, kd, k) (TK::compiled ? TK::eq(t, kd, k) : (kd) == (k))
+#define SK_M(q, t, r) (TK::compiled ? TK::m(q, t, r) : (q).m[r])                   /* row mask */
+#define SK_TWO(t) (!TK::compiled || TK::two(t))                                    /* row 1 exists on the trip */
+#define SK_ON(t) (TK::compiled && TK::on(t))                                       /* both rows on in both stages */
+#define SK_COM(t) (!TK::compiled || TK::com(t))                                    /* CoM VAR slots can occur */
+
 // (x0, x1: xs[q.i0], xs[q.i1], loaded by the caller -- the residual loop loads every slot's pair before the
 // first slot's arithmetic: the term-row stores of a slot's re-linearisation would hold the next slot's loads back)
-__device__ __forceinline__ double slot_fx(const Slot &q, double x0, double x1, double s_var)
+template <class TK>
+__device__ __forceinline__ double slot_fx(const Slot &q, int t, double x0, double x1, double s_var)
 {
-    const int k = kind_of(q);
+    const int k = SK_KIND(q, t);
     const double dx = x0 - q.a0, dy = x1 - q.a1;
-    return (k == K_OBS) ? -(dx * dx + dy * dy) - s_var : (k == K_COP) ? x0 - x1 : x0;
+    return SK_EQ(t, k, K_OBS) ? -(dx * dx + dy * dy) - s_var : SK_EQ(t, k, K_COP) ? x0 - x1 : x0;
 }
-__device__ __forceinline__ double slot_f(const Slot &q, const double *xs, double s_var)
+template <class TK>
+__device__ __forceinline__ double slot_f(const Slot &q, int t, const double *xs, double s_var)
 {
-    return slot_fx(q, xs[q.i0], xs[q.i1], s_var);
+    return slot_fx<TK>(q, t, xs[q.i0], xs[q.i1], s_var);
 }
 
 
@@ -911,22 +969,22 @@ __device__ __forceinline__ void slot_init(Slot &q, int sl, const SrbKParams &prm
     const int N = prm.N, n = prm.n;
     q.kind = K_NONE; q.i0 = q.i1 = 0; q.r = 0; q.h[0] = q.h[1] = 0.0; q.a0 = q.a1 = 0.0; q.rx = 0.0; q.jd = 0.0;
     q.m[0] = q.m[1] = 0.0; q.wr = TT;
-    if (sl < sE) {                                   // VAR
+    if (sl < SRB_SLOT_END(K_VAR, sE, sV, sO, S)) {
         const int v = sl;
         const bool isX = v < 4 * N, isU = !isX && v < 6 * N, isL = !isX && !isU && v < n - 1;
         q.kind = K_VAR; q.i0 = q.i1 = v; q.r = TL.zr(v);
         q.a0 = isX ? ((v >= 4 * (N - 1)) ? prm.Pw : prm.Qw) : isU ? prm.Rw : isL ? 0.0 : prm.Sw;
         q.a1 = isX ? -q.a0 * ref[v] : 0.0;
         q.h[0] = isL ? 1.0 : prm.box; q.h[1] = isL ? 0.0 : prm.box;
-    } else if (sl < sV) {                            // COP
+    } else if (sl < SRB_SLOT_END(K_COP, sE, sV, sO, S)) {
         const int e = sl - sE, i = e >> 1, d = e & 1;
         q.kind = K_COP; q.i0 = 4 * i + 2 * d; q.i1 = 4 * N + 2 * (i + 1) + d; q.r = rC + e;
         q.h[0] = q.h[1] = prm.fr;
-    } else if (sl < sO) {                            // VEL
+    } else if (sl < SRB_SLOT_END(K_VEL, sE, sV, sO, S)) {
         const int tt = sl - sV, comp = (tt < N) ? 1 : 3, k = tt % N;
         q.kind = K_VEL; q.i0 = q.i1 = 4 * k + comp; q.r = 4 * k + comp;
         q.h[0] = q.h[1] = prm.vsat;
-    } else if (sl < S) {                             // OBS (positions filled at the NLP stage)
+    } else if (sl < SRB_SLOT_END(K_OBS, sE, sV, sO, S)) {                        // (positions filled at the NLP stage)
         const int o = sl - sO, k = o / K;
         q.kind = K_OBS; q.i0 = 4 * k; q.i1 = 4 * k + 2; q.r = rO + o;
     }
@@ -936,12 +994,13 @@ __device__ __forceinline__ void slot_init(Slot &q, int sl, const SrbKParams &prm
 
 // the rows of slot q active in the stage (QP: linear rows; NLP: all), and the weight / rhs entry
 // it stores to (VEL adds into its variable's term row instead: the scratch entry TT)
-__device__ __forceinline__ void slot_stage(Slot &q, int n, bool nl, int TT)
+template <class TK>
+__device__ __forceinline__ void slot_stage(Slot &q, int t, int n, bool nl, int TT)
 {
-    const bool lin = (q.kind == K_VAR && q.i0 < n - 1) || q.kind == K_COP;
-    q.m[0] = (lin || (nl && (q.kind == K_VEL || q.kind == K_OBS))) ? 1.0 : 0.0;
-    q.m[1] = (lin || (nl && q.kind == K_VEL)) ? 1.0 : 0.0;
-    q.wr = (q.kind == K_VAR || q.kind == K_COP || q.kind == K_OBS) ? q.r : TT;
+    const bool lin = (SK_ISP(q, t, K_VAR) && (SK_ON(t) || q.i0 < n - 1)) || SK_ISP(q, t, K_COP);
+    q.m[0] = (lin || (nl && (SK_ISP(q, t, K_VEL) || SK_ISP(q, t, K_OBS)))) ? 1.0 : 0.0;
+    q.m[1] = (lin || (nl && SK_ISP(q, t, K_VEL))) ? 1.0 : 0.0;
+    q.wr = (SK_ISP(q, t, K_VAR) || SK_ISP(q, t, K_COP) || SK_ISP(q, t, K_OBS)) ? q.r : TT;
 }
 
 // LDS-bounds diagnostic build: the indices slot q (slot number sl) reads and writes through (LCK above)
@@ -962,7 +1021,7 @@ __device__ __forceinline__ double var_weight(const SrbKParams &prm, int v)
 
 // Polish helper: every slot's row function g(x) into q.jd, each obstacle slot's term row M_o
 // re-linearised at x (obs_relin: both source rows loaded before the stores) and its multiplier into zo.
-template <int NZL, int TS, int NW>
+template <int NZL, int TS, int NW, class TK>
 __device__ __forceinline__ void polish_rows(Slot (&Q)[TS], int nts, const double *xs, double *OJ, double *zo, int n,
                                             int rO, double *R, int nz)
 {
@@ -971,8 +1030,8 @@ __device__ __forceinline__ void polish_rows(Slot (&Q)[TS], int nts, const double
     for (int t = 0; t < TS; t++)
         if (t < nts) {
             Slot &q = Q[t];
-            q.jd = slot_f(q, xs, s_var);
-            if (kind_of(q) == K_OBS) {
+            q.jd = slot_f<TK>(q, t, xs, s_var);
+            if (SK_IS(q, t, K_OBS)) {
                 const int o = q.r - rO;
                 obs_relin<NZL>(R, OJ, rO, o, q.i0, q.i1, -2.0 * (xs[q.i0] - q.a0), -2.0 * (xs[q.i1] - q.a1));
                 zo[o] = q.ds[0] * q.dz[0];
@@ -1033,7 +1092,7 @@ __device__ __forceinline__ double lip_eq_res(const SrbKParams &prm, const double
 // pointer build returned as OPTIMAL although they were not stationary; this one does not.  The
 // term rows are those of the last Newton step (the obstacle rows linearised at its start: O(|dx|) <= 1e-7 off).
 // Uniform over the workgroup (every value reduced).  oracle/nlp_ipm.c `polish`: the same test.
-template <int NZL, int TS, int NW, int NZE>
+template <int NZL, int TS, int NW, int NZE, class TK>
 __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, const SrbKParams &prm, const double *xs,
                                                   const double *ref, double *CF, double *R, double *OJ, double *zo, int rO,
                                                   int cnt, const ObsFold &OF, int nko, double *vg, double *vy, double *vr,
@@ -1043,26 +1102,26 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
     SYNC();                                              // every lane's reads of R / OJ / CF / vg of the last step are done
     // the obstacle rows linearised at the polished point itself (the last Newton step, up to 1e-4 when the
     // active rows then hold to 1e-10, ran on rows taken before it: J'z would be off by 2 |dx| |z| there)
-    polish_rows<NZL, TS, NW>(Q, nts, xs, OJ, zo, n, rO, R, nz);
+    polish_rows<NZL, TS, NW, TK>(Q, nts, xs, OJ, zo, n, rO, R, nz);
     SYNC();
 #pragma unroll
     for (int t = 0; t < TS; t++)
         if (t < nts) {
             const Slot &q = Q[t];
-            const double zj = q.ds[0] * q.dz[0] - q.ds[1] * q.dz[1];
-            const int kd = kind_of(q);
-            if (kd == K_VAR) {
+            const double zj = SK_TWO(t) ? q.ds[0] * q.dz[0] - q.ds[1] * q.dz[1] : q.ds[0] * q.dz[0];
+            const int kd = SK_KIND(q, t);
+            if (SK_EQ(t, kd, K_VAR)) {
                 const int v = q.i0;
                 const double a0 = var_weight(prm, v), gf = fma(a0, xs[v], (v < 4 * N) ? -a0 * ref[v] : 0.0);
                 CF[q.wr] = gf + zj;
-            } else if (kd == K_COP || kd == K_OBS) {
+            } else if (SK_EQ(t, kd, K_COP) || SK_EQ(t, kd, K_OBS)) {
                 CF[q.wr] = zj;
             }
         }
     if (NW > 1) SYNC();                                  // the VAR rows' plain stores land before the VEL adds
 #pragma unroll
     for (int t = 0; t < TS; t++)
-        if (t < nts && kind_of(Q[t]) == K_VEL)
+        if (t < nts && SK_IS(Q[t], t, K_VEL))
             __hip_atomic_fetch_add(&CF[Q[t].r], Q[t].ds[0] * Q[t].dz[0] - Q[t].ds[1] * Q[t].dz[1], __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_WORKGROUP);
     SYNC();
@@ -1082,15 +1141,15 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
     double zmin = 1e300, zmax = 1.0;
 #pragma unroll
     for (int t = 0; t < TS; t++)
-        if (t < nts && (Q[t].ds[0] != 0.0 || Q[t].ds[1] != 0.0)) {
+        if (t < nts && (Q[t].ds[0] != 0.0 || (SK_TWO(t) && Q[t].ds[1] != 0.0))) {
             const Slot &q = Q[t];
-            const double jd = -((!SRB_OBS_STORED(NZL) && kind_of(q) == K_OBS)
+            const double jd = -((!SRB_OBS_STORED(NZL) && SK_IS(q, t, K_OBS))
                 ? fma(OJ[2 * (q.r - rO)], row_dot<NZL, NZE>(R + q.i0 * LDR, dxs),
                       fma(OJ[2 * (q.r - rO) + 1], row_dot<NZL, NZE>(R + q.i1 * LDR, dxs), -row_dot<NZL, NZE>(R + srow * LDR, dxs)))
                 : row_dot<NZL, NZE>(R + q.r * LDR, dxs));
 #pragma unroll
             for (int r = 0; r < 2; r++)
-                if (q.ds[r] != 0.0) {
+                if ((SK_TWO(t) || r == 0) && q.ds[r] != 0.0) {
                     const double zn = fma(prm.polish_rho, q.r3[r] + (r ? -jd : jd), q.dz[r]);
                     zmin = fmin(zmin, zn); zmax = fmax(zmax, fabs(zn));
                 }
@@ -1321,7 +1380,7 @@ _Pragma("clang loop unroll(disable)")                                           
 _Pragma("clang loop unroll(disable)")                                                                                                         \
         for (int pit = 0; pit < SRB_POLISH_IT; pit++) {                                                                                       \
             SYNC(); /* xs of the previous step / pass */                                                                                      \
-            polish_rows<NZL, TS, NW>(PS, nts, xs, OJ, zo, n, rO, R, nz); /* q.jd = g(x), M_o (OJ), zo = z_A */                                \
+            polish_rows<NZL, TS, NW, TK>(PS, nts, xs, OJ, zo, n, rO, R, nz); /* q.jd = g(x), M_o (OJ), zo = z_A */                            \
             SYNC(); /* R rows, zo */                                                                                                          \
             if (pit > 0) { /* converged after a small step (oracle, same rule) */                                                             \
                 double cm = 0.0;                                                                                                              \
@@ -1329,7 +1388,8 @@ _Pragma("unroll")                                                               
                 for (int t = 0; t < TS; t++)                                                                                                  \
                     if (t < nts) {                                                                                                            \
                         const Slot &q = PS[t];                                                                                                \
-                        cm = fmax(cm, fmax(q.ds[0] * fabs(q.jd - q.h[0]), q.ds[1] * fabs(q.jd + q.h[1])));                                    \
+                        if (SK_TWO(t)) cm = fmax(cm, fmax(q.ds[0] * fabs(q.jd - q.h[0]), q.ds[1] * fabs(q.jd + q.h[1])));                    \
+                        else cm = fmax(cm, fmax(q.ds[0] * fabs(q.jd - q.h[0]), 0.0)); /* (single-row trip: row 1 is off) */                   \
                     }                                                                                                                         \
                 double rv[1] = {cm};                                                                                                          \
                 wred_x<1, 1u, NW>(rv, red + 6 * 8 * NW, tid);                                                                                 \
@@ -1339,12 +1399,16 @@ _Pragma("unroll")                                                               
             for (int t = 0; t < TS; t++)                                                                                                      \
                 if (t < nts) {                                                                                                                \
                     Slot &q = PS[t];                                                                                                          \
-                    q.r3[0] = q.jd - q.h[0]; q.r3[1] = -q.jd - q.h[1];                                                                        \
-                    const double cfa = q.ds[0] * fma(prm.polish_rho, q.r3[0], q.dz[0]) - q.ds[1] * fma(prm.polish_rho, q.r3[1], q.dz[1]);     \
-                    const double wa = (q.ds[0] != 0.0 ? prm.polish_rho : q.s[0]) + (q.ds[1] != 0.0 ? prm.polish_rho : q.s[1]);                \
-                    if (kind_of(q) == K_VAR) {                                                                                                \
+                    q.r3[0] = q.jd - q.h[0];                                                                                                  \
+                    if (SK_TWO(t)) q.r3[1] = -q.jd - q.h[1];                                                                                 \
+                    const double cfa = SK_TWO(t)                                                                                              \
+                        ? q.ds[0] * fma(prm.polish_rho, q.r3[0], q.dz[0]) - q.ds[1] * fma(prm.polish_rho, q.r3[1], q.dz[1])                   \
+                        : q.ds[0] * fma(prm.polish_rho, q.r3[0], q.dz[0]);                                                                    \
+                    const double wa = SK_TWO(t) ? (q.ds[0] != 0.0 ? prm.polish_rho : q.s[0]) + (q.ds[1] != 0.0 ? prm.polish_rho : q.s[1])     \
+                                                : (q.ds[0] != 0.0 ? prm.polish_rho : q.s[0]);                                                 \
+                    if (SK_IS(q, t, K_VAR)) {                                                                                             \
                         double hs = 0.0;                                                                                                      \
-                        if (q.i0 < 4 * N && !(q.i0 & 1)) hs = -2.0 * zo_sum(zo, q.i0 >> 2, K);                                                \
+                        if (SK_COM(t) && q.i0 < 4 * N && !(q.i0 & 1)) hs = -2.0 * zo_sum(zo, q.i0 >> 2, K);                                           \
                         W[q.wr] = q.a0 + hs + wa;                                                                                             \
                         CF[q.wr] = -(fma(q.a0, q.jd, q.a1) + cfa);                                                                            \
                     } else {                                                                                                                  \
@@ -1355,7 +1419,7 @@ _Pragma("unroll")                                                               
             if (NW > 1) SYNC(); /* the VAR rows' plain stores land before the VEL adds */                                                     \
 _Pragma("unroll")                                                                                                                             \
             for (int t = 0; t < TS; t++)                                                                                                      \
-                if (t < nts && kind_of(PS[t]) == K_VEL) {                                                                                     \
+                if (t < nts && SK_IS(PS[t], t, K_VEL)) {                                                                                     \
                     const Slot &q = PS[t];                                                                                                    \
                     const double cfa = q.ds[0] * fma(prm.polish_rho, q.r3[0], q.dz[0]) - q.ds[1] * fma(prm.polish_rho, q.r3[1], q.dz[1]);     \
                     __hip_atomic_fetch_add(&W[q.r], (q.ds[0] != 0.0 ? prm.polish_rho : q.s[0]) + (q.ds[1] != 0.0 ? prm.polish_rho : q.s[1]),  \
@@ -1374,13 +1438,13 @@ _Pragma("unroll")                                                               
             for (int t = 0; t < TS; t++)                                                                                                      \
                 if (t < nts) {                                                                                                                \
                     Slot &q = PS[t];                                                                                                          \
-                    const double jd = (!SRB_OBS_STORED(NZL) && kind_of(q) == K_OBS) /* J_o Z dxi, folded instances (OJ) */                \
+                    const double jd = (!SRB_OBS_STORED(NZL) && SK_IS(q, t, K_OBS)) /* J_o Z dxi, folded instances (OJ) */                \
                         ? fma(OJ[2 * (q.r - rO)], row_dot<NZL, NZE>(R + q.i0 * LDR, dxi),                                                          \
                               fma(OJ[2 * (q.r - rO) + 1], row_dot<NZL, NZE>(R + q.i1 * LDR, dxi), -row_dot<NZL, NZE>(R + TL.zr(n - 1) * LDR, dxi)))     \
                         : row_dot<NZL, NZE>(R + q.r * LDR, dxi);                                                                                   \
                     q.dz[0] = fma(q.ds[0] * prm.polish_rho, q.r3[0] + jd, q.dz[0]);                                                           \
-                    q.dz[1] = fma(q.ds[1] * prm.polish_rho, q.r3[1] - jd, q.dz[1]);                                                           \
-                    if (kind_of(q) == K_VAR) {                                                                                                \
+                    if (SK_TWO(t)) q.dz[1] = fma(q.ds[1] * prm.polish_rho, q.r3[1] - jd, q.dz[1]);                                                      \
+                    if (SK_IS(q, t, K_VAR)) {                                                                                                \
                         xs[q.i0] = q.jd + jd; /* every read of xs this step is behind a barrier */                                            \
                         mdx = fmax(mdx, fabs(jd));                                                                                            \
                     }                                                                                                                         \
@@ -1404,15 +1468,16 @@ _Pragma("unroll")                                                               
             for (int t = 0; t < TS; t++)                                                                                                      \
                 if (t < nts) {                                                                                                                \
                     Slot &q = PS[t];                                                                                                          \
-                    const double fq = slot_f(q, xs, s_var);                                                                                   \
+                    const double fq = slot_f<TK>(q, t, xs, s_var);                                                                            \
 _Pragma("unroll")                                                                                                                             \
-                    for (int r = 0; r < 2; r++) {                                                                                             \
-                        const double v = r ? -fq - q.h[1] : fq - q.h[0];                                                                      \
-                        q.r3[r] = v;                                                                                                          \
-                        if (q.m[r] != 0.0) pv = fmax(pv, v);                                                                                  \
-                        if (q.ds[r] != 0.0) { cv = fmax(cv, fabs(v)); nzmin = fmax(nzmin, -q.dz[r]); zm = fmax(zm, fabs(q.dz[r])); }          \
-                        else if (q.m[r] != 0.0) vi = fmax(vi, v);                                                                             \
-                    }                                                                                                                         \
+                    for (int r = 0; r < 2; r++)                                                                                               \
+                        if (SK_TWO(t) || r == 0) {                                                                                           \
+                            const double v = r ? -fq - q.h[1] : fq - q.h[0];                                                                  \
+                            q.r3[r] = v;                                                                                                      \
+                            if (SK_M(q, t, r) != 0.0) pv = fmax(pv, v);                                                                      \
+                            if (q.ds[r] != 0.0) { cv = fmax(cv, fabs(v)); nzmin = fmax(nzmin, -q.dz[r]); zm = fmax(zm, fabs(q.dz[r])); }      \
+                            else if (SK_M(q, t, r) != 0.0) vi = fmax(vi, v);                                                                 \
+                        }                                                                                                                     \
                 }                                                                                                                             \
             double rv[6] = {pv, cv, nzmin, zm, vi, lip_eq_res(prm, x0, xs, foot, N, C, tid, NTH)};                                   \
             wred_x<6, 0x3Fu, NW>(rv, red + 7 * 8 * NW, tid);                                                                                  \
@@ -1422,7 +1487,7 @@ _Pragma("unroll")                                                               
         POLDBG(pass, 5, lastdx); POLDBG(pass, 7, eqr);                                                                                        \
         const bool pcand = pv <= SRB_POLISH_PTOL && cv <= SRB_POLISH_PTOL && nzmin <= 1e-9 * zm && lastdx <= SRB_POLISH_DXTOL &&           \
                            eqr <= SRB_POLISH_EQTOL;                                                                                           \
-        const double sratio = pcand ? polish_stationary<NZL, TS, NW, NZE>(PS, nts, prm, xs, ref, CF, R, OJ, zo, rO, cnt, OF, nko, vg, vy,    \
+        const double sratio = pcand ? polish_stationary<NZL, TS, NW, NZE, TK>(PS, nts, prm, xs, ref, CF, R, OJ, zo, rO, cnt, OF, nko, vg, vy,\
                                                               vr, vd, Mi, H0, nz, tid, part, bmask, red, N, n, TT, TL.zr(n - 1)) : 0.0;       \
         SRB_POLISH_DIAG();                                                                                                                    \
         if (pcand && sratio <= SRB_POLISH_STOL) {                                                                                             \
@@ -1439,18 +1504,19 @@ _Pragma("unroll")                                                               
             if (t < nts)                                                                                                                      \
 _Pragma("unroll")                                                                                                                             \
                 for (int r = 0; r < 2; r++)                                                                                                   \
-                    if (PS[t].ds[r] != 0.0 && PS[t].dz[r] < -1e-9 * zm) lexmin(wd, wk, PS[t].dz[r], 2 * (tid + NTH * t) + r);                 \
+                    if ((SK_TWO(t) || r == 0) && PS[t].ds[r] != 0.0 && PS[t].dz[r] < -1e-9 * zm) lexmin(wd, wk, PS[t].dz[r], 2 * (tid + NTH * t) + r);                 \
         wargmin_x<NW>(wd, wk, red + 9 * 8 * NW, tid);                                                                                         \
         if (wk == 0x7fffffff && !(vi > SRB_POLISH_PTOL)) break; /* nothing to change: rejected */                                             \
 _Pragma("unroll")                                                                                                                             \
         for (int t = 0; t < TS; t++) {                                                                                                        \
             Slot &q = PS[t];                                                                                                                  \
 _Pragma("unroll")                                                                                                                             \
-            for (int r = 0; r < 2; r++) {                                                                                                     \
-                if (2 * (tid + NTH * t) + r == wk) q.ds[r] = 0.0;                                                                             \
-                else if (t < nts && q.ds[r] == 0.0 && q.m[r] != 0.0 && q.r3[r] > SRB_POLISH_PTOL) q.ds[r] = 1.0;                              \
-                q.dz[r] = q.ds[r] * fmax(q.dz[r], 0.0);                                                                                       \
-            }                                                                                                                                 \
+            for (int r = 0; r < 2; r++)                                                                                                       \
+                if (SK_TWO(t) || r == 0) {                                                                                                   \
+                    if (2 * (tid + NTH * t) + r == wk) q.ds[r] = 0.0;                                                                         \
+                    else if (t < nts && q.ds[r] == 0.0 && SK_M(q, t, r) != 0.0 && q.r3[r] > SRB_POLISH_PTOL) q.ds[r] = 1.0;                  \
+                    q.dz[r] = q.ds[r] * fmax(q.dz[r], 0.0);                                                                                   \
+                }                                                                                                                             \
         }                                                                                                                                     \
         SYNC();                                                                                                                               \
         for (int v = tid; v < n; v += NTH) xs[v] = xsv[v]; /* the next pass starts from the interior-point result */                          \
@@ -1481,6 +1547,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
     if (tid < 64) stamp_lds[tid] = 0;
 #endif
     double *Rt = R + rC * LDR;                          // CoM-CoP rows
+    using TK = SlotTrips<NTH, TS, NC, CC, KC>;          // the kinds each slot trip can hold (compiled shapes)
 
     STAMP_BEGIN();
     // ---- inputs (a1/a2/a3: x0, reference window, footholds), null-space basis Z, xbar, term rows
@@ -1530,24 +1597,24 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
 #pragma unroll
         for (int t = 0; t < TS; t++) {
             Slot &q = Q[t];
-            const bool lin = (q.kind == K_VAR && q.i0 < n - 1) || q.kind == K_COP;
-            q.m[0] = (lin || (nl && (q.kind == K_VEL || q.kind == K_OBS))) ? 1.0 : 0.0;
-            q.m[1] = (lin || (nl && q.kind == K_VEL)) ? 1.0 : 0.0;
-            q.wr = (q.kind == K_VAR || q.kind == K_COP || q.kind == K_OBS) ? q.r : TT;
+            const bool lin = (SK_ISP(q, t, K_VAR) && (SK_ON(t) || q.i0 < n - 1)) || SK_ISP(q, t, K_COP);
+            q.m[0] = (lin || (nl && (SK_ISP(q, t, K_VEL) || SK_ISP(q, t, K_OBS)))) ? 1.0 : 0.0;
+            q.m[1] = (lin || (nl && SK_ISP(q, t, K_VEL))) ? 1.0 : 0.0;
+            q.wr = (SK_ISP(q, t, K_VAR) || SK_ISP(q, t, K_COP) || SK_ISP(q, t, K_OBS)) ? q.r : TT;
         }
         if (!nl) {
             // ---------------- QP stage setup: kkt_initialize (Auxilary.c:680-755) ----------------
             // [P A' G'; A 0 0; G 0 -I] [x; y; z] = [-c; b; h]:  (Z'(P + G'G)Z) xi = -Z'(P xbar + c) + Z'G'(h - G xbar)
 #pragma unroll
             for (int t = 0; t < TS; t++)
-                if (t < nts) {
+                if (SK_TWO(t) && t < nts) {                 // (a single-row trip holds no QP row)
                     Slot &q = Q[t];
-                    const double f = slot_f(q, xs, 0.0);
-                    const double w0 = q.m[0] * (q.h[0] - f), w1 = q.m[1] * (q.h[1] + f);
-                    const bool var = q.kind == K_VAR;
-                    const double wgt = (var ? q.a0 : 0.0) + q.m[0] + q.m[1];
+                    const double f = slot_f<TK>(q, t, xs, 0.0);
+                    const double w0 = SK_M(q, t, 0) * (q.h[0] - f), w1 = SK_M(q, t, 1) * (q.h[1] + f);
+                    const bool var = SK_ISP(q, t, K_VAR);
+                    const double wgt = (var ? q.a0 : 0.0) + SK_M(q, t, 0) + SK_M(q, t, 1);
                     const double cfv = (var ? -q.a1 - q.a0 * f : 0.0) + (w0 - w1);
-                    if (q.kind == K_VAR || q.kind == K_COP) { W[q.r] = wgt; CF[q.r] = cfv; }
+                    if (SK_ISP(q, t, K_VAR) || SK_ISP(q, t, K_COP)) { W[q.r] = wgt; CF[q.r] = cfv; }
                 }
             SYNC();
             gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, H0, vg, nz, tid, part, bmask);
@@ -1562,14 +1629,14 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
             double mn = 1e300, mx = -1e300;
 #pragma unroll
             for (int t = 0; t < TS; t++)
-                if (t < nts) {
+                if (SK_TWO(t) && t < nts) {
                     Slot &q = Q[t];
-                    const double f = slot_f(q, xs, 0.0) +
-                        ((!SRB_OBS_STORED(NZL) && q.kind == K_OBS) ? 0.0 : row_dot<NZL, NZE>(R + q.r * LDR, dxi));   /* (OBS: masked here) */
+                    const double f = slot_f<TK>(q, t, xs, 0.0) +
+                        ((!SRB_OBS_STORED(NZL) && SK_ISP(q, t, K_OBS)) ? 0.0 : row_dot<NZL, NZE>(R + q.r * LDR, dxi));   /* (OBS: masked here) */
                     q.jd = f;                                 // f(x) for the shift below
                     const double z0 = q.h[0] - f, z1 = q.h[1] + f;
-                    if (q.m[0] != 0.0) { mn = fmin(mn, z0); mx = fmax(mx, z0); }
-                    if (q.m[1] != 0.0) { mn = fmin(mn, z1); mx = fmax(mx, z1); }
+                    if (SK_M(q, t, 0) != 0.0) { mn = fmin(mn, z0); mx = fmax(mx, z0); }
+                    if (SK_M(q, t, 1) != 0.0) { mn = fmin(mn, z1); mx = fmax(mx, z1); }
                 }
             double rv[2] = {-mn, mx};
             wred_x<2, 3u, NW>(rv, red + 0 * 8 * NW, tid);
@@ -1582,14 +1649,14 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
             const bool scaled = prm.qp_init == 1;
 #pragma unroll
             for (int t = 0; t < TS; t++)
-                if (t < nts) {
+                if (SK_TWO(t) && t < nts) {
                     Slot &q = Q[t];
                     const double f = q.jd, z0 = q.h[0] - f, z1 = q.h[1] + f;
-                    q.s[0] = (q.m[0] != 0.0) ? (scaled ? fmax(z0, 0.1) : z0 + ssh) : 1.0;
-                    q.s[1] = (q.m[1] != 0.0) ? (scaled ? fmax(z1, 0.1) : z1 + ssh) : 1.0;
-                    q.z[0] = (q.m[0] != 0.0) ? (scaled ? rcp_d(q.s[0]) : -z0 + zsh) : 1.0;
-                    q.z[1] = (q.m[1] != 0.0) ? (scaled ? rcp_d(q.s[1]) : -z1 + zsh) : 1.0;
-                    if (q.kind == K_VAR) xs[q.i0] = f;
+                    q.s[0] = (SK_M(q, t, 0) != 0.0) ? (scaled ? fmax(z0, 0.1) : z0 + ssh) : 1.0;
+                    q.s[1] = (SK_M(q, t, 1) != 0.0) ? (scaled ? fmax(z1, 0.1) : z1 + ssh) : 1.0;
+                    q.z[0] = (SK_M(q, t, 0) != 0.0) ? (scaled ? rcp_d(q.s[0]) : -z0 + zsh) : 1.0;
+                    q.z[1] = (SK_M(q, t, 1) != 0.0) ? (scaled ? rcp_d(q.s[1]) : -z1 + zsh) : 1.0;
+                    if (SK_ISP(q, t, K_VAR)) xs[q.i0] = f;
                     // rx = -(P x + c + A'y + G'z) = -G'(z - (G x - h)) at the least-squares start: 0 for
                     // iSWIFT's z (the shift is the same on the two rows of every +- pair), below for the
                     // scaled one (each row's z + (h - Gx) scattered onto its variables)
@@ -1599,14 +1666,14 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 SYNC();
 #pragma unroll
                 for (int t = 0; t < TS; t++)              // the VAR rows' own bounds first (plain stores)
-                    if (t < nts && Q[t].kind == K_VAR) {
+                    if (t < nts && SK_ISP(Q[t], t, K_VAR)) {
                         const Slot &q = Q[t];
-                        CF[q.r] = q.m[0] * (q.z[0] + q.h[0] - q.jd) - q.m[1] * (q.z[1] + q.h[1] + q.jd);
+                        CF[q.r] = SK_M(q, t, 0) * (q.z[0] + q.h[0] - q.jd) - SK_M(q, t, 1) * (q.z[1] + q.h[1] + q.jd);
                     }
                 SYNC();
 #pragma unroll
                 for (int t = 0; t < TS; t++)              // CoM-CoP rows +-(p_i - u_i+1): onto p_i and u_i+1
-                    if (t < nts && Q[t].kind == K_COP) {
+                    if (t < nts && SK_ISP(Q[t], t, K_COP)) {
                         const Slot &q = Q[t];
                         const double g = q.m[0] * (q.z[0] + q.h[0] - q.jd) - q.m[1] * (q.z[1] + q.h[1] + q.jd);
                         __hip_atomic_fetch_add(&CF[TL.zr(q.i0)], g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1615,7 +1682,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 SYNC();
 #pragma unroll
                 for (int t = 0; t < TS; t++)
-                    if (t < nts && Q[t].kind == K_VAR) Q[t].rx = -CF[Q[t].r];
+                    if (t < nts && SK_ISP(Q[t], t, K_VAR)) Q[t].rx = -CF[Q[t].r];
             }
             SYNC();
             STAMP_END(1);
@@ -1636,15 +1703,15 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
             for (int t = 0; t < TS; t++)
                 if (t < nts) {
                     Slot &q = Q[t];
-                    if (q.kind == K_OBS) {
+                    if (SK_ISP(q, t, K_OBS)) {
                         const int o = tid + NTH * t - sO;
                         LCK(o >= 0 && o < NK, 5);
                         q.a0 = obs[2 * o]; q.a1 = obs[2 * o + 1]; q.h[0] = -eps[o % K];
                     }
-                    const double f = slot_f(q, xs, s_var);
+                    const double f = slot_f<TK>(q, t, xs, s_var);
                     q.jd = f;
-                    if (q.m[0] != 0.0) mn = fmin(mn, q.h[0] - f);
-                    if (q.m[1] != 0.0) mn = fmin(mn, q.h[1] + f);
+                    if (SK_M(q, t, 0) != 0.0) mn = fmin(mn, q.h[0] - f);
+                    if (SK_M(q, t, 1) != 0.0) mn = fmin(mn, q.h[1] + f);
                 }
             {
                 double rv[1] = {-mn};
@@ -1657,27 +1724,27 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 if (t < nts) {
                     Slot &q = Q[t];
                     const double f = q.jd;
-                    q.s[0] = (q.m[0] != 0.0) ? q.h[0] - f + ssh : 1.0;
-                    q.s[1] = (q.m[1] != 0.0) ? q.h[1] + f + ssh : 1.0;
+                    q.s[0] = (SK_M(q, t, 0) != 0.0) ? q.h[0] - f + ssh : 1.0;
+                    if (SK_TWO(t)) q.s[1] = (SK_M(q, t, 1) != 0.0) ? q.h[1] + f + ssh : 1.0;
                     // z = Z0 / max(s, 1): rows far from their bound start at complementarity Z0, the
                     // others at Z0 (oracle/nlp_ipm.c, same rule)
                     q.z[0] = SRB_NLP_Z0 * rcp_d(fmax(q.s[0], 1.0));
-                    q.z[1] = SRB_NLP_Z0 * rcp_d(fmax(q.s[1], 1.0));
-                    if (q.kind == K_OBS) {                     // M_o = J_o Z at the current x (gram_rhs)
+                    if (SK_TWO(t)) q.z[1] = SRB_NLP_Z0 * rcp_d(fmax(q.s[1], 1.0));
+                    if (SK_ISP(q, t, K_OBS)) {                     // M_o = J_o Z at the current x (gram_rhs)
                         const int o = q.r - rO;
                         obs_relin<NZL>(R, OJ, rO, o, q.i0, q.i1, -2.0 * (xs[q.i0] - q.a0), -2.0 * (xs[q.i1] - q.a1));
                     }
                     // Z'Z (delta shifts) and rx0 = -Z (Z'Z)^-1 Z'(P x + c + J'z): each row's J'z on its
                     // term row (the velocity rows' below, onto their variables' rows)
-                    const double jz = q.m[0] * q.z[0] - q.m[1] * q.z[1];
-                    if (q.kind == K_VAR) { W[q.r] = 1.0; CF[q.r] = fma(q.a0, f, q.a1) + jz; }
-                    else if (q.kind == K_COP) { W[q.r] = 0.0; CF[q.r] = jz; }
-                    else if (q.kind == K_OBS) { W[q.r] = 0.0; CF[q.r] = q.z[0]; }
+                    const double jz = SK_TWO(t) ? SK_M(q, t, 0) * q.z[0] - SK_M(q, t, 1) * q.z[1] : q.m[0] * q.z[0];
+                    if (SK_ISP(q, t, K_VAR)) { W[q.r] = 1.0; CF[q.r] = fma(q.a0, f, q.a1) + jz; }
+                    else if (SK_ISP(q, t, K_COP)) { W[q.r] = 0.0; CF[q.r] = jz; }
+                    else if (SK_ISP(q, t, K_OBS)) { W[q.r] = 0.0; CF[q.r] = q.z[0]; }
                 }
             if (NW > 1) SYNC();                               // the VAR rows' plain stores land before the VEL adds
 #pragma unroll
             for (int t = 0; t < TS; t++)
-                if (t < nts && Q[t].kind == K_VEL)
+                if (t < nts && SK_ISP(Q[t], t, K_VEL))
                     __hip_atomic_fetch_add(&CF[Q[t].r], Q[t].m[0] * Q[t].z[0] - Q[t].m[1] * Q[t].z[1], __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_WORKGROUP);
             SYNC();
@@ -1693,7 +1760,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
             for (int t = 0; t < TS; t++)
                 if (t < nts) {
                     Slot &q = Q[t];
-                    q.rx = (q.kind == K_VAR) ? -row_dot<NZL, NZE>(R + q.r * LDR, dxi) : 0.0;
+                    q.rx = (SK_ISP(q, t, K_VAR)) ? -row_dot<NZL, NZE>(R + q.r * LDR, dxi) : 0.0;
                 }
             SYNC();
             STAMP_END(2);
@@ -1727,13 +1794,17 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 if (t < nts && tid + NTH * t < S)
 #pragma unroll
                     for (int r = 0; r < 2; r++) {
-                        const float v = Q[t].m[r] == 0.0 ? 0.0f
+                        const float v = SK_M(Q[t], t, r) == 0.0 ? 0.0f
                             : (float)(Q[t].s[r] * SRB_POLISH_KAPPA < Q[t].z[r] ? Q[t].z[r] : -fmin(Q[t].z[r] / Q[t].s[r], SRB_POLISH_OMCAP));
                         if (to_lds) zl[2 * (tid + NTH * t) + r] = v;
                         else zg[2 * (tid + NTH * t) + r] = v;
                     }
         };
         for (int v = tid; v < n; v += NTH) xprev[v] = xs[v];
+        // compiled shapes, NLP: sum_j z_kj of the grid whose CoM position this lane's VAR slot holds, formed once an
+        // iteration -- by the update, from the new duals -- and carried to the next iteration's weights and update
+        // (iteration 0: by the weights phase); only the trips that hold such slots (TK::com) keep a register
+        double hsc[TS] = {};
         for (int iter = 0; iter < maxit; iter++) {
             STAMP_BEGIN();
             // ---- residuals (computeresiduals, Auxilary.c:524-553), norms, reciprocals
@@ -1751,20 +1822,29 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 fv[t] = 0.0;
                 if (t < nts) {
                     Slot &q = Q[t];
-                    const double f = slot_fx(q, xa[t], xc[t], s_var);
+                    const double f = slot_fx<TK>(q, t, xa[t], xc[t], s_var);
                     fv[t] = f;
-                    if (kind_of(q) == K_VAR) {
+                    if (SK_IS(q, t, K_VAR)) {
                         nrx = fma(q.rx, q.rx, nrx);
                         gm = fmax(gm, fabs(fma(q.a0, f, q.a1)));
                     }
-                    const double rz0 = q.h[0] - q.s[0] - f, rz1 = q.h[1] - q.s[1] + f;
-                    nrz = fma(q.m[0] * rz0, rz0, fma(q.m[1] * rz1, rz1, nrz));
-                    sz = fma(q.m[0] * q.s[0], q.z[0], fma(q.m[1] * q.s[1], q.z[1], sz));
-                    zmx = fmax(zmx, fmax(q.m[0] * q.z[0], q.m[1] * q.z[1]));
+                    const double m0 = SK_M(q, t, 0), m1 = SK_M(q, t, 1);
+                    const double rz0 = q.h[0] - q.s[0] - f;
+                    if (SK_TWO(t)) {
+                        const double rz1 = q.h[1] - q.s[1] + f;
+                        nrz = fma(m0 * rz0, rz0, fma(m1 * rz1, rz1, nrz));
+                        sz = fma(m0 * q.s[0], q.z[0], fma(m1 * q.s[1], q.z[1], sz));
+                        zmx = fmax(zmx, fmax(m0 * q.z[0], m1 * q.z[1]));
+                    } else {                                  // single-row trip: the row-1 terms are 0 (m[1] = 0)
+                        nrz = fma(m0 * rz0, rz0, nrz);
+                        sz = fma(m0 * q.s[0], q.z[0], sz);
+                        zmx = fmax(zmx, m0 * q.z[0]);
+                    }
                     if constexpr (!LEAN)
 #pragma unroll
-                        for (int r = 0; r < 2; r++) { q.iz[r] = rcp_d(q.z[r]); q.is[r] = rcp_d(q.s[r]); }
-                    if (nl && kind_of(q) == K_OBS) {              // re-linearise: M_o = J_o(x) Z (gram_rhs)
+                        for (int r = 0; r < 2; r++)
+                            if (SK_TWO(t) || r == 0) { q.iz[r] = rcp_d(q.z[r]); q.is[r] = rcp_d(q.s[r]); }
+                    if (nl && SK_IS(q, t, K_OBS)) {              // re-linearise: M_o = J_o(x) Z (gram_rhs)
                         const int o = q.r - rO;
                         obs_relin<NZL>(R, OJ, rO, o, q.i0, q.i1, -2.0 * (xa[t] - q.a0), -2.0 * (xc[t] - q.a1));
                         zo[o] = q.z[0];
@@ -1837,17 +1917,18 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                     if (t < nts) {
                         Slot &q = Q[t];
                         const double f = fv[t];
-                        double cf = (kind_of(q) == K_VAR) ? q.rx : 0.0;
+                        double cf = (SK_IS(q, t, K_VAR)) ? q.rx : 0.0;
 #pragma unroll
-                        for (int r = 0; r < 2; r++) {
-                            double dsT = -q.s[r] * q.z[r];
-                            if (corr) dsT -= q.ds[r] * q.dz[r];
-                            dsT += smu;
-                            const double rz = r ? (q.h[1] - q.s[1] + f) : (q.h[0] - q.s[0] - f);
-                            const double r3 = fma(-dsT, IZ(q, r), rz);
-                            if constexpr (!LEAN) { q.dsT[r] = dsT; q.r3[r] = r3; }
-                            cf = fma((r ? -q.m[1] : q.m[0]) * q.z[r] * IS(q, r), r3, cf);
-                        }
+                        for (int r = 0; r < 2; r++)
+                            if (SK_TWO(t) || r == 0) {
+                                double dsT = -q.s[r] * q.z[r];
+                                if (corr) dsT -= q.ds[r] * q.dz[r];
+                                dsT += smu;
+                                const double rz = r ? (q.h[1] - q.s[1] + f) : (q.h[0] - q.s[0] - f);
+                                const double r3 = fma(-dsT, IZ(q, r), rz);
+                                if constexpr (!LEAN) { q.dsT[r] = dsT; q.r3[r] = r3; }
+                                cf = fma((r ? -SK_M(q, t, 1) : SK_M(q, t, 0)) * q.z[r] * IS(q, r), r3, cf);
+                            }
                         cfs[t] = cf;
                         CF[q.wr] = cf;
                     }
@@ -1856,7 +1937,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 if (nl)
 #pragma unroll
                     for (int t = 0; t < TS; t++)
-                        if (t < nts && kind_of(Q[t]) == K_VEL)
+                        if (t < nts && SK_IS(Q[t], t, K_VEL))
                             __hip_atomic_fetch_add(&CF[Q[t].r], cfs[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             };
             if (pc) {
@@ -1868,20 +1949,27 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 for (int t = 0; t < TS; t++)
                     if (t < nts) {
                         Slot &q = Q[t];
-                        const double om = fma(q.m[0] * q.z[0], IS(q, 0), q.m[1] * q.z[1] * IS(q, 1));
+                        const double om = SK_TWO(t) ? fma(SK_M(q, t, 0) * q.z[0], IS(q, 0), SK_M(q, t, 1) * q.z[1] * IS(q, 1))
+                                                     : q.m[0] * q.z[0] * IS(q, 0);
                         double hs = 0.0;
-                        if (nl && kind_of(q) == K_VAR && q.i0 < 4 * N && !(q.i0 & 1)) {
+                        if (nl && SK_COM(t) && SK_IS(q, t, K_VAR) && q.i0 < 4 * N && !(q.i0 & 1)) {
                             const int k = q.i0 >> 2;
-                            hs = zo_sum(zo, k, K);
+                            // compiled shapes: the sum is carried from the previous iteration's update (hsc)
+                            if constexpr (TK::compiled) {
+                                if (iter == 0) hsc[t] = zo_sum(zo, k, K);
+                                hs = hsc[t];
+                            } else {
+                                hs = zo_sum(zo, k, K);
+                            }
                             hs *= -2.0;
                         }
-                        W[q.wr] = om + ((kind_of(q) == K_VAR) ? q.a0 + hs : 0.0);
+                        W[q.wr] = om + ((SK_IS(q, t, K_VAR)) ? q.a0 + hs : 0.0);
                     }
                 if (NW > 1) SYNC();
                 if (nl)
 #pragma unroll
                     for (int t = 0; t < TS; t++)
-                        if (t < nts && kind_of(Q[t]) == K_VEL)
+                        if (t < nts && SK_IS(Q[t], t, K_VEL))
                             __hip_atomic_fetch_add(&W[Q[t].r], Q[t].z[0] * IS(Q[t], 0) + Q[t].z[1] * IS(Q[t], 1), __ATOMIC_RELAXED,
                                                    __HIP_MEMORY_SCOPE_WORKGROUP);
                 STAMP_END(16);
@@ -1945,20 +2033,21 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 for (int t = 0; t < TS; t++)
                     if (t < nts) {
                         Slot &q = Q[t];
-                        const int kd = kind_of(q);
+                        const int kd = SK_KIND(q, t);
                         if constexpr (SRB_OBS_STORED(NZL)) {
                             LCK(q.r >= 0 && q.r < RROWS, 1);
                             if (t + 1 < TS && t + 1 < nts) row_load<NZE>(R + Q[(t + 1) % TS].r * LDR, rw[(t + 1) & 1]);
                             __builtin_amdgcn_sched_barrier(0);
                             q.jd = row_sum<NZL, NZE>(rw[t & 1], dxi);
-                        } else if (kd == K_OBS) {                     /* (QP stage: masked rows, 0) */
+                        } else if (SK_EQ(t, kd, K_OBS)) {            /* (QP stage: masked rows, 0) */
                             const int o = q.r - rO;
                             q.jd = nl ? fma(OJ[2 * o], dxv[q.i0], fma(OJ[2 * o + 1], dxv[q.i1], -dxv[n - 1])) : 0.0;
                         } else {
-                            q.jd = (kd == K_COP) ? dxv[q.i0] - dxv[q.i1] : dxv[q.i0];
+                            q.jd = SK_EQ(t, kd, K_COP) ? dxv[q.i0] - dxv[q.i1] : dxv[q.i0];
                         }
 #pragma unroll
-                        for (int r = 0; r < 2; r++) {
+                        for (int r = 0; r < 2; r++)
+                        if (SK_TWO(t) || r == 0) {
                             const double izr = IZ(q, r), isr = IS(q, r);
                             double dsT, r3;
                             if constexpr (LEAN) {                    // set_rhs(pass)'s terms, recomputed
@@ -1970,8 +2059,8 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                             } else {
                                 dsT = q.dsT[r]; r3 = q.r3[r];
                             }
-                            q.dz[r] = q.m[r] * q.z[r] * isr * fma(r ? -1.0 : 1.0, q.jd, -r3);
-                            q.ds[r] = q.m[r] * fma(-q.s[r], q.dz[r], dsT) * izr;
+                            q.dz[r] = SK_M(q, t, r) * q.z[r] * isr * fma(r ? -1.0 : 1.0, q.jd, -r3);
+                            q.ds[r] = SK_M(q, t, r) * fma(-q.s[r], q.dz[r], dsT) * izr;
                             mxs = fmax(mxs, -q.ds[r] * isr); mxz = fmax(mxz, -q.dz[r] * izr);
                         }
                     }
@@ -1992,8 +2081,8 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                     for (int t = 0; t < TS; t++)
                         if (t < nts) {
                             const Slot &q = Q[t];
-                            num = fma(q.m[0] * fma(ap, q.ds[0], q.s[0]), fma(ad, q.dz[0], q.z[0]), num);
-                            num = fma(q.m[1] * fma(ap, q.ds[1], q.s[1]), fma(ad, q.dz[1], q.z[1]), num);
+                            num = fma(SK_M(q, t, 0) * fma(ap, q.ds[0], q.s[0]), fma(ad, q.dz[0], q.z[0]), num);
+                            if (SK_TWO(t)) num = fma(SK_M(q, t, 1) * fma(ap, q.ds[1], q.s[1]), fma(ad, q.dz[1], q.z[1]), num);
                         }
                     {
                         double rv[1] = {num};
@@ -2018,12 +2107,14 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                     hso[t] = 0.0;
                     if (t < nts) {
                         Slot &q = Q[t];
-                        if (nl && kind_of(q) == K_VAR && q.i0 < 4 * N && !(q.i0 & 1)) {
+                        if (nl && SK_COM(t) && SK_IS(q, t, K_VAR) && q.i0 < 4 * N && !(q.i0 & 1)) {
                             const int k = q.i0 >> 2;
-                            hso[t] = zo_sum(zo, k, K);
+                            if constexpr (TK::compiled) hso[t] = hsc[t];     // zo is as the weights phase read it
+                            else hso[t] = zo_sum(zo, k, K);
                         }
 #pragma unroll
-                        for (int r = 0; r < 2; r++) { q.s[r] = fma(ap, q.ds[r], q.s[r]); q.z[r] = fma(ad, q.dz[r], q.z[r]); }
+                        for (int r = 0; r < 2; r++)
+                            if (SK_TWO(t) || r == 0) { q.s[r] = fma(ap, q.ds[r], q.s[r]); q.z[r] = fma(ad, q.dz[r], q.z[r]); }
                     }
                 }
                 SYNC();          // every lane has read the old duals and x
@@ -2032,8 +2123,8 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 for (int t = 0; t < TS; t++)
                     if (t < nts) {
                         Slot &q = Q[t];
-                        if (nl && kind_of(q) == K_OBS) zo[q.r - rO] = q.z[0];
-                        if (kind_of(q) == K_VAR) {
+                        if (nl && SK_IS(q, t, K_OBS)) zo[q.r - rO] = q.z[0];
+                        if (SK_IS(q, t, K_VAR)) {
                             dxl = fmax(dxl, fabs(ap * q.jd));
                             q.rx = (1.0 - ad) * q.rx + ((ad - ap) * q.a0) * q.jd;
                             if (nl) q.rx = fma(ad * (delta - 2.0 * hso[t]), q.jd, q.rx);
@@ -2048,10 +2139,11 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                     for (int t = 0; t < TS; t++)
                         if (t < nts) {
                             Slot &q = Q[t];
-                            if (kind_of(q) == K_VAR && q.i0 < 4 * N && !(q.i0 & 1)) {   // +2 ap dx sum_j z'_kj on (x_k, y_k)
+                            if (SK_COM(t) && SK_IS(q, t, K_VAR) && q.i0 < 4 * N && !(q.i0 & 1)) {   // +2 ap dx sum_j z'_kj on (x_k, y_k)
                                 const int k = q.i0 >> 2;
                                 double hs_new = 0.0;
                                 hs_new = zo_sum(zo, k, K);
+                                if constexpr (TK::compiled) hsc[t] = hs_new;    // the next iteration's sum
                                 q.rx = fma(2.0 * ap * hs_new, q.jd, q.rx);
                             }
                         }
@@ -2089,7 +2181,8 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
         for (int t = 0; t < TS; t++) {
             const int sl = tid + NTH * t;
 #pragma unroll
-            for (int r = 0; r < 2; r++) {
+            for (int r = 0; r < 2; r++)
+            if (SK_TWO(t) || r == 0) {
                 LCK(!(t < nts && sl < S) || 2 * sl + r < 2 * rnd4(S), 6);
                 const double v = (t < nts && sl < S) ? (double)zpl[2 * sl + r] : 0.0;
                 Q[t].ds[r] = (v > 0.0) ? 1.0 : 0.0;
@@ -2153,6 +2246,7 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
     unsigned long long *stamp_lds = nullptr;                // (the stamps build times the solve kernel only)
 #endif
     double *Rt = R + rC * LDR;
+    using TK = SlotTrips<NTH, TS, NC, CC, KC>;
     (void)xb; (void)dxv; (void)th; (void)tol; (void)wv;
     const int st1 = status_out[2 * agent + 1];
     if (!prm.use_nlp || st1 == 1 || st1 == 3) return;          // the whole workgroup: no usable iterate to polish
@@ -2199,10 +2293,11 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
             const int sl = tid + NTH * t;
             slot_init(q, sl, prm, TL, ref, sE, sV, sO, S, rC, rO, K, TT);
             SRB_SLOT_LCK(q, sl);
-            slot_stage(q, n, true, TT);
-            if (q.kind == K_OBS) { const int o = sl - sO; q.a0 = obs[2 * o]; q.a1 = obs[2 * o + 1]; q.h[0] = -eps[o % K]; }
+            slot_stage<TK>(q, t, n, true, TT);
+            if (SK_ISP(q, t, K_OBS)) { const int o = sl - sO; q.a0 = obs[2 * o]; q.a1 = obs[2 * o + 1]; q.h[0] = -eps[o % K]; }
 #pragma unroll
-            for (int r = 0; r < 2; r++) {
+            for (int r = 0; r < 2; r++)
+            if (SK_TWO(t) || r == 0) {
                 const double v = (t < nts && sl < S) ? (double)zv[t][r] : 0.0;
                 q.ds[r] = (v > 0.0) ? 1.0 : 0.0;
                 q.dz[r] = fmax(v, 0.0);
