@@ -177,7 +177,8 @@ struct ObsFold {
 // column 0), so their part of the Gram is block diagonal: H[a][b] += sum_r W_r R[r][a] R[r][b] over the
 // 2 + C rows of grid j for a, b in grid j's columns (and W_s at [0][0]), g[a] += sum_r CF_r R[r][a] --
 // added directly instead of as MFMA batches of single-entry rows (configs[2] Gram 14 -> 11 batches,
-// N = 20 14 + 4 -> 8 + 4).  Lanes tid0, tid0 + step, .. of the caller; after its tile stores.
+// N = 20 14 + 4 -> 8 + 4).  Lanes tid0, tid0 + step, .. of the caller; after its tile stores.  (One wave with one
+// 16 x 16 tile forms the same sums in registers instead, UlLane below.)
 template <int NZL, bool GRAM, bool RHS>
 __device__ __forceinline__ void ul_add(const double *R, const double *W, const double *CF, const ObsFold &F, double *H,
                                        double *g, int nz, int tid0, int step)
@@ -231,6 +232,56 @@ __device__ __forceinline__ void ul_add(const double *R, const double *W, const d
         }
     }
 }
+
+// ul_add's sums formed by the lane that holds the entry in registers (one wave, one 16 x 16 tile: gram_rhs, rhs_only),
+// so that the entry is stored once as `accumulator + v` instead of stored, re-read, added to and stored again.  Lane
+// (kq, li) of the MFMA D layout holds H[kq + 4 q][li], q = 0 .. 3: of the c1 <= 3 consecutive rows of column li's grid
+// block at most one has a & 3 == kq, so a lane forms at most one Gram sum (he; it belongs to register q), the kq = 0
+// lane of column li the right-hand-side sum (ge), lane 0 the slack entries W[rs] / CF[rs] (hs).  The sums depend on
+// R, W, CF alone: gram_rhs issues load() under the last batch's MFMAs and runs sums() in the accumulator drain (the
+// s_nop the hardware wants before the accumulators are read), rhs_only loads ahead of its term rows.  Each sum takes
+// ul_add's operands in ul_add's order; lanes without an entry read grid 0's rows (in range) and discard the result.
+template <int NZL>
+struct UlLane {
+    double wv[6], ra[6], rb[6], cv[6], sw, sc;
+    int q;
+    bool he, ge, hs;
+    template <bool GRAM, bool RHS>
+    __device__ __forceinline__ void load(const double *R, const double *W, const double *CF, const ObsFold &F, int nz, int lane)
+    {
+        constexpr int LDR = NZL + 1;
+        const int li = lane & 15, kq = lane >> 4;
+        const int c1 = F.C - 1, rl = F.rU + 2 * F.N, rs = F.rU + F.n - 1 - 4 * F.N;
+        const bool col = li >= 1 && li < nz;
+        const int j = col ? (li - 1) / c1 : 0, a0 = 1 + j * c1, off = (kq - a0) & 3;
+        he = GRAM && col && off < c1;
+        ge = RHS && col && kq == 0;
+        hs = lane == 0;
+        const int a = he ? a0 + off : 1, b = col ? li : 1;
+        q = a >> 2;
+#pragma unroll
+        for (int u = 0; u < 6; u++) {
+            const bool in = u < 2 + F.C;
+            const int r = (u < 2) ? F.rU + 2 * j + u : rl + F.C * j + (in ? u - 2 : 0);
+            if (GRAM) { wv[u] = W[r]; ra[u] = R[r * LDR + a]; }
+            rb[u] = R[r * LDR + b];
+            if (RHS) cv[u] = CF[r];
+        }
+        if (GRAM) sw = W[rs];
+        if (RHS) sc = CF[rs];
+    }
+    template <bool GRAM, bool RHS>
+    __device__ __forceinline__ void sums(const ObsFold &F, double &vh, double &vg) const
+    {
+        vh = 0.0; vg = 0.0;
+#pragma unroll
+        for (int u = 0; u < 6; u++) {
+            if (u >= 2 + F.C) break;
+            if (GRAM) vh = fma(wv[u] * ra[u], rb[u], vh);
+            if (RHS) vg = fma(cv[u], rb[u], vg);
+        }
+    }
+};
 
 // S_k and c_k (GRAM) or c_k alone into FO: one lane per grid, the K rows in index order
 template <bool GRAM>
@@ -314,7 +365,15 @@ template <int NZL>
 __device__ __forceinline__ double term_elem(const double *R, int r, int col)
 {
     constexpr int LDR = NZL + 1;
-    return (col < NZL) ? R[r * LDR + col] : 0.0;
+    if constexpr (NZL <= 16) {
+        // one column block: the load is unconditional (the column clamped into the row), the padding columns
+        // selected to zero -- a plain ds_read and a v_cndmask instead of an exec-mask block per load
+        const double v = R[r * LDR + min(col, NZL - 1)];
+        return (col < NZL) ? v : 0.0;
+    } else {
+        // two column blocks (N = 20): measured slower with the unconditional form (config 5 +0.5 %), kept predicated
+        return (col < NZL) ? R[r * LDR + col] : 0.0;
+    }
 }
 
 // obstacle grid term t = 3 k + u: A element (column u of V_k) for column col, and the row of S_k / entry of
@@ -334,7 +393,8 @@ __device__ __forceinline__ double obs_term_a(const double *R, const ObsFold &F, 
 //   [0, NOP) (when nko > 0, the NLP stage): v_mfma_f64_16x16x4f64 with A[a][k] = r_{t0+k}[a],
 //   B[k][b] = W_{t0+k} r_{t0+k}[b] (grid terms: B = V_k S_k e_u); lane l supplies term t0 + (l >> 4),
 //   column l & 15; D layout row (l >> 4) + 4 q, column l & 15; NZM = 32: tiles (0,0), (0,1), (1,1).  Four
-//   term groups per batch: every operand load of the batch issues before the first MFMA waits on one.
+//   term groups per batch: every operand load of the batch issues before the first MFMA waits on one; with one
+//   column block (NZM = 16) the loads of batch b + 1 issue before the MFMAs of batch b.
 // RHS: g[a] = sum_t CF_t r_t[a]: the very element lane l forms for the MFMA is the one its (column, term)
 //   pair needs, so the right-hand side costs one FMA per element; the four term chunks combine by permlane
 //   swaps.
@@ -357,6 +417,10 @@ __device__ __forceinline__ void gram_rhs(const double *R, const double *W, const
     }
     d4 acc[NT];
     double ps[NTC];
+    // one wave, one tile: the U / lambda / slack sums join the accumulators in registers (UlLane), no ul_add pass
+    constexpr bool ULF = NZM == 16 && NW == 1;
+    UlLane<NZL> ul;
+    double ulh = 0.0, ulg = 0.0;
 #pragma unroll
     for (int t = 0; t < NT; t++) acc[t] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -423,7 +487,60 @@ __device__ __forceinline__ void gram_rhs(const double *R, const double *W, const
             }
         }
     };
-    {
+    if constexpr (NZM == 16) {
+        // One column block, stored obstacle rows: the wave's batches -- its chunk of the term rows, then (nko > 0)
+        // its chunk of the obstacle rows -- as one sequence, the operand loads of batch i + 1 issued before the
+        // MFMAs of batch i (two operand buffers, the loop unrolled by two with the buffers swapped; the first batch
+        // loaded ahead of the loop, the last one peeled: nothing is read beyond the wave's own ranges, and with
+        // nko = 0 nothing of the obstacle range).  Every accumulator takes the same operands in the same order as
+        // in the one-batch-at-a-time loop below.
+        const int chunk = cnt / NW, tb = wv * chunk, och = nko / NW, ob = F.rO + wv * och;
+        const int nb1 = chunk >> 4, nbt = nb1 + (och >> 4);
+        auto bt0 = [&](int i) { return i < nb1 ? tb + 16 * i : ob + 16 * (i - nb1); };
+        auto loadb = [&](int t0, double (&a)[4], double (&w)[4], double (&c)[4]) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const int r = t0 + 4 * u + kq;
+                a[u] = R[r * (NZL + 1) + min(li, NZL - 1)];      // term_elem's load; its select waits in mmb
+                w[u] = W[r];
+                c[u] = RHS ? CF[r] : 0.0;
+            }
+            __builtin_amdgcn_sched_barrier(0);     // the next batch's loads stay ahead of this batch's MFMAs
+        };
+        auto mmb = [&](const double (&ar)[4], const double (&w)[4], const double (&c)[4]) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const double a = (li < NZL) ? ar[u] : 0.0;
+                if (RHS) ps[0] = fma(c[u], a, ps[0]);
+                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, w[u] * a, acc[0], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        if (nbt > 0) {
+            double a0[4], w0[4], c0[4], a1[4], w1[4], c1[4];
+            loadb(bt0(0), a0, w0, c0);
+            int i = 0;
+#pragma clang loop unroll(disable)
+            for (; i + 2 < nbt; i += 2) {
+                loadb(bt0(i + 1), a1, w1, c1);
+                mmb(a0, w0, c0);
+                loadb(bt0(i + 2), a0, w0, c0);
+                mmb(a1, w1, c1);
+            }
+            if (i + 1 < nbt) {
+                loadb(bt0(i + 1), a1, w1, c1);
+                mmb(a0, w0, c0);
+                if constexpr (ULF) { ul.template load<true, RHS>(R, W, CF, F, nz, lane); __builtin_amdgcn_sched_barrier(0); }
+                mmb(a1, w1, c1);
+            } else {
+                if constexpr (ULF) { ul.template load<true, RHS>(R, W, CF, F, nz, lane); __builtin_amdgcn_sched_barrier(0); }
+                mmb(a0, w0, c0);
+            }
+        } else if constexpr (ULF) {
+            ul.template load<true, RHS>(R, W, CF, F, nz, lane);
+        }
+        if constexpr (ULF) ul.template sums<true, RHS>(F, ulh, ulg);       // in the accumulator drain
+    } else {
         // NZM = 32 with several waves: the batches dealt round-robin over the waves (the full-width ones
         // cluster at high grids, so contiguous halves left one wave with most of them); else contiguous
         constexpr bool ILV = NZM == 32 && NW > 1;
@@ -463,10 +580,18 @@ __device__ __forceinline__ void gram_rhs(const double *R, const double *W, const
                 if (RHS)
 #pragma unroll
                     for (int tc = 0; tc < NTC; tc++)
-                        if (kq == 0 && 16 * tc + li < nz) g[16 * tc + li] = ph ? g[16 * tc + li] + gs[tc] : gs[tc];
+                        if (kq == 0 && 16 * tc + li < nz) {
+                            if constexpr (ULF) g[li] = ul.ge ? gs[0] + ulg : ul.hs ? gs[0] + ul.sc : gs[0];
+                            else g[16 * tc + li] = ph ? g[16 * tc + li] + gs[tc] : gs[tc];
+                        }
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const int r = kq + 4 * q;
+                    if constexpr (ULF) {
+                        const double h = acc[0][q];
+                        put(r, li, (ul.he && q == ul.q) ? h + ulh : (ul.hs && q == 0) ? h + ul.sw : h, false);
+                        continue;
+                    }
                     put(r, li, acc[0][q], ph > 0);
                     if constexpr (NZM == 32) {
                         put(r, 16 + li, acc[1][q], ph > 0);
@@ -474,7 +599,7 @@ __device__ __forceinline__ void gram_rhs(const double *R, const double *W, const
                         put(16 + r, 16 + li, acc[2][q], ph > 0);
                     }
                 }
-                if (ph == NW - 1) ul_add<NZL, true, RHS>(R, W, CF, F, H, g, nz, lane, 64);   /* (same wave, after its stores) */
+                if (ph == NW - 1 && !ULF) ul_add<NZL, true, RHS>(R, W, CF, F, H, g, nz, lane, 64);   /* (same wave, after its stores) */
             }
         }
     } else {
@@ -525,6 +650,9 @@ __device__ __forceinline__ void rhs_only(const double *R, const double *CF, int 
         srb_sync<NW>();
     }
     double ps[2][NTC];
+    constexpr bool ULF = NZM == 16 && NW == 1;     // as gram_rhs: the U / lambda / slack sum joins sv in registers
+    UlLane<NZL> ul;
+    double ulh = 0.0, ulg = 0.0;
 #pragma unroll
     for (int t = 0; t < NTC; t++) { ps[0][t] = 0.0; ps[1][t] = 0.0; }
     auto chunk32 = [&](int t0, auto fullc) {
@@ -595,6 +723,7 @@ __device__ __forceinline__ void rhs_only(const double *R, const double *CF, int 
             for (int tc = 0; tc < NTC; tc++) ps[0][tc] = fma(cc, term_elem<NZL>(R, r, 16 * tc + li), ps[0][tc]);
         }
     };
+    if constexpr (ULF) ul.template load<false, true>(R, nullptr, CF, F, nz, lane);     // ahead of the term rows' loads
     {
         constexpr bool ILV = NZM == 32 && NW > 1;       // batches round-robin over the waves, as gram_rhs
         const int chunk = cnt / NW, tb = wv * chunk;
@@ -620,6 +749,7 @@ __device__ __forceinline__ void rhs_only(const double *R, const double *CF, int 
             }
         }
     }
+    if constexpr (ULF) ul.template sums<false, true>(F, ulh, ulg);
     double sv[NTC];
 #pragma unroll
     for (int tc = 0; tc < NTC; tc++) sv[tc] = chunk_sum16(ps[0][tc] + ps[1][tc]);
@@ -630,8 +760,11 @@ __device__ __forceinline__ void rhs_only(const double *R, const double *CF, int 
             if (wv == ph) {
 #pragma unroll
                 for (int tc = 0; tc < NTC; tc++)
-                    if (kq == 0 && 16 * tc + li < nz) g[16 * tc + li] = ph ? g[16 * tc + li] + sv[tc] : sv[tc];
-                if (ph == NW - 1) ul_add<NZL, false, true>(R, nullptr, CF, F, nullptr, g, nz, lane, 64);
+                    if (kq == 0 && 16 * tc + li < nz) {
+                        if constexpr (ULF) g[li] = ul.ge ? sv[0] + ulg : ul.hs ? sv[0] + ul.sc : sv[0];
+                        else g[16 * tc + li] = ph ? g[16 * tc + li] + sv[tc] : sv[tc];
+                    }
+                if (ph == NW - 1 && !ULF) ul_add<NZL, false, true>(R, nullptr, CF, F, nullptr, g, nz, lane, 64);
             }
         }
     } else {
