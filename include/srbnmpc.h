@@ -433,6 +433,58 @@ int srb_rollout_moving_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_i
                               const srb_moving *mv, int cycles, void *stream);
 
 /*
+ * Obstacle sizes (LIP mode; DESIGN.md 3 "Obstacle sizes", 10.8): an optional CBF level and an optional body radius per
+ * obstacle row.  As with srb_moving, the layouts of srb_batch, srb_sim and srb_moving (and SRB_ABI_VERSION) stay: the
+ * tables travel in a struct of their own through entry points of their own, each of which takes the srb_moving of the
+ * entry point it extends (mv may be NULL) and otherwise behaves as that entry point.
+ *   obs_eps    [n_obs]      in: the CBF level of obstacles[i] in squared metres, the unit of srb_params.eps_obs: the
+ *                           row of static column j at grid k reads  -|p_k - o_kj|^2 - s <= -obs_eps[sel[j]].  Row
+ *                           order and, with scenes, the scene-major layout of `obstacles`.  The table is read only
+ *                           through sel; the neighbour columns and a -1 row keep eps_nbr.  NULL: eps_obs for every row.
+ *   obs_radius [n_obs]      in: the body radius (m) of obstacles[i] for the metrics' fail test: d_obs is then
+ *                           min over i of (dist_i - obs_radius[i]) (one rounded subtract; a NaN term never wins; an
+ *                           empty table gives +inf), fail_cycle the first cycle with d_obs < 0; min_d_obs,
+ *                           distance_to_fail and the agent-to-agent outputs follow the rules of srb_sim.  A uniform
+ *                           0.5 table gives srb_sim's d_obs - 0.5 bit for bit and its fail_cycle.  NULL: the metrics
+ *                           of srb_sim (centre distances, 0.5 m).
+ *   clearance_selection     0: the K_obs static columns as ever (nearest centres now, or with
+ *                           srb_moving.horizon_selection the closest predicted approach);
+ *                           1: by clearance to the level set (srb_knn_obs_clear_kernel): the key of row i for an
+ *                           agent is sqrt(m) - sqrt(obs_eps[i]), uncontracted, m the squared distance now -- or, with
+ *                           horizon_selection = 1, the min over k = 0 .. N of srb_knn_obs_horizon_kernel's squared
+ *                           distances.  Keys may be negative (an agent inside a level set).  Order by key, lower index
+ *                           on ties; a NaN key (a NaN row, a NaN or negative obs_eps) is never selected; a slot whose
+ *                           key is >= 1000, or with no row left, gets row 0 (with scenes the scene's row 0).  One
+ *                           workgroup per agent, brute force: no selection grid is built or consulted.  The neighbour
+ *                           columns are selected as ever.  Needs obs_eps.
+ * With sz == NULL, or every member NULL / 0, each entry point is the _moving entry point it extends, output bits
+ * included.  SRB_ERR_ARG, by name and before anything is launched: a wrong struct_size; clearance_selection other than
+ * 0 or 1; clearance_selection = 1 without obs_eps.  obs_eps goes together with obstacles_version != 0 (sizes do not
+ * stale a grid of centres).  The QP-only solve ignores the tables.  host_sz holds host pointers, sz device pointers.
+ *
+ * srb_select_sized_device: with clearance_selection = 1, tables & 1 is the clearance selection.  The solve entry
+ * points run it themselves (SRB_OPT_SELECTION = 1).  srb_sim_metrics_sized_device: srb_sim_metrics_device with
+ * obs_radius.  srb_rollout_sized_device: srb_rollout_moving_device's sequence per cycle with the sized metrics, select
+ * and solve; the tables do not change over a rollout.  The SRB-12 mode and the MPC_dist shims have no obstacle sizes.
+ */
+typedef struct srb_sizes {
+    int struct_size;            /* sizeof(srb_sizes) (ABI check) */
+    const double *obs_eps;      /* [n_obs]: the CBF level of obstacles[i], squared metres, the unit of eps_obs; NULL: eps_obs for every row */
+    const double *obs_radius;   /* [n_obs]: body radius (m) for the metrics' fail test; NULL: today's metrics */
+    int clearance_selection;    /* 0: the K_obs columns as ever; 1: by clearance to the level set */
+} srb_sizes;
+int srb_solve_batch_sized(srb_ctx *ctx, int n_agents, const srb_batch *host_io, const srb_moving *host_mv,
+                          const srb_sizes *host_sz);
+int srb_solve_batch_sized_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
+                                 const srb_sizes *sz, void *stream);
+int srb_select_sized_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
+                            const srb_sizes *sz, int tables, void *stream);
+int srb_sim_metrics_sized_device(srb_ctx *ctx, int n_agents, const srb_sim *sim, const srb_sizes *sz, int cycle,
+                                 void *stream);
+int srb_rollout_sized_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_sim *sim,
+                             const srb_moving *mv, const srb_sizes *sz, int cycles, void *stream);
+
+/*
  * HL reference planner (generateReferenceTrajectory, MPC_dist.cpp:930-1104; SURVEY.md 8(f)
  * row 3) on HIP device `device`, host buffers, synchronous.  NA agents (1..2^20; up to 1024 in
  * one persistent workgroup, more -- one coupled swarm -- as one launch per step) starting at

@@ -22,13 +22,15 @@ typedef void (*srb_kernel_fn)(SrbKParams, int, const double *, const double *, c
 typedef void (*srb_polish_fn)(SrbKParams, int, const double *, const double *, const double *, const double *,
                               const double *, double *, double *, int *, const double *, double *, const int *,
                               const float *, int, const double *, double *);
-// the moving-obstacle instances (srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*): the velocity table as one more argument
+// the obstacle-table instances (srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*): two more arguments, the velocity table
+// of srb_moving and the level table of srb_sizes (either may be null)
 typedef void (*srb_kernel_mv_fn)(SrbKParams, int, const double *, const double *, const double *, const double *, int,
                                  const double *, int, int, double *, double *, double *, int *, int *, const double *,
-                                 double *, const int *, float *, int, const double *, double *, const double *);
+                                 double *, const int *, float *, int, const double *, double *, const double *,
+                                 const double *);
 typedef void (*srb_polish_mv_fn)(SrbKParams, int, const double *, const double *, const double *, const double *,
                                  const double *, double *, double *, int *, const double *, double *, const int *,
-                                 const float *, int, const double *, double *, const double *);
+                                 const float *, int, const double *, double *, const double *, const double *);
 struct srb_instance { int nzl, ts, nw, nc, cc, kc; srb_kernel_fn fn; srb_polish_fn polish; srb_kernel_mv_fn fn_mv; srb_polish_mv_fn polish_mv; };
 // solve kernel (INFIX empty, or f32_) and polish kernel of one instance, then their moving-obstacle instances
 #define ENTRY_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC) NZL, TS, NW, NC, CC, KC, srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
@@ -109,6 +111,8 @@ struct srb_ctx {
     size_t cap_obs, cap_nbr;
     double *obs_vel;               // staged obstacle velocities (srb_solve_batch_moving)
     size_t cap_vel;
+    double *obs_eps;               // staged obstacle levels (srb_solve_batch_sized)
+    size_t cap_eps;
     float knn_ms, solve_ms;
     bool timed;
     int last_nw;
@@ -323,7 +327,7 @@ extern "C" int srb_ctx_destroy(srb_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->order.wait_idle();                         // the last launch may be on another stream
     void *bufs[] = {c->x0, c->ref, c->foot, c->x_qp, c->x, c->obj, c->status, c->iters, c->obstacles, c->nbr,
-                    c->abuf, c->alpha, c->sel, c->zpol, c->nbr_plan, c->plan, c->obs_vel};
+                    c->abuf, c->alpha, c->sel, c->zpol, c->nbr_plan, c->plan, c->obs_vel, c->obs_eps};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (auto &g : c->grid)
@@ -453,19 +457,28 @@ static int launch_select(srb_ctx *c, int n_agents, const double *x0, const doubl
 static int launch_obs_horizon(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
                               int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride, hipStream_t s, int N,
                               double Ts);
+static int launch_obs_clear(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
+                            const double *obs_eps, int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride,
+                            hipStream_t s, int N, double Ts);
 
 // The selection of a solve, both modes.  obs_vel with obs_horizon (srb_moving.horizon_selection): the static columns by
-// closest predicted approach over the caller's grid (N, Ts), the neighbour columns as without
+// closest predicted approach over the caller's grid (N, Ts), the neighbour columns as without.  obs_eps with
+// obs_clear (srb_sizes.clearance_selection): the static columns by clearance to the level set -- over the horizon
+// when obs_vel and obs_horizon say so, else now -- and the neighbour columns as without
 int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
                         int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan, int N,
-                        const double *obs_vel, int obs_horizon, double Ts)
+                        const double *obs_vel, int obs_horizon, double Ts, const double *obs_eps, int obs_clear)
 {
-    if (obs_vel && obs_horizon) {
+    const bool clear = obs_eps && obs_clear;
+    if (clear || (obs_vel && obs_horizon)) {
         if (K_nbr > 0)
             if (int rc = launch_select(c, n_agents, x0, obstacles, 0, nbr_state, n_all, agent_offset, 0, K_nbr, 0,
                                        sel + K_obs, s, K_obs + K_nbr, nbr_plan, N))
                 return rc;
+        if (K_obs > 0 && clear)
+            return launch_obs_clear(c, n_agents, x0, obstacles, obs_horizon ? obs_vel : nullptr, obs_eps, n_obs,
+                                    agent_offset, K_obs, sel, K_obs + K_nbr, s, N, Ts);
         if (K_obs > 0) return launch_obs_horizon(c, n_agents, x0, obstacles, obs_vel, n_obs, agent_offset, K_obs, sel,
                                                  K_obs + K_nbr, s, N, Ts);
         return SRB_OK;
@@ -504,6 +517,23 @@ static int launch_obs_horizon(srb_ctx *c, int n_agents, const double *x0, const 
     return SRB_OK;
 }
 
+// The clearance selection (srb_sizes.clearance_selection; srb_sizes.hip) into the static columns 0 .. K_obs - 1 of sel:
+// launch_obs_horizon's geometry.  obs_vel null: the key's distance is the one now; else the horizon's minimum.
+static int launch_obs_clear(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
+                            const double *obs_eps, int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride,
+                            hipStream_t s, int N, double Ts)
+{
+    if (c->scene_agents > 0)
+        hipLaunchKernelGGL(srb_knn_obs_clear_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents,
+                           x0, obstacles, obs_vel, obs_eps, N, Ts, agent_offset, c->scene_agents, c->scene_obs, K_obs, sel,
+                           sel_stride);
+    else
+        hipLaunchKernelGGL(srb_knn_obs_clear_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents, x0,
+                           obstacles, obs_vel, obs_eps, n_obs, N, Ts, K_obs, sel, sel_stride);
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
 // the checks of srb_moving that need no context (srb_host.h), with this mode's names in the messages
 static int check_moving(const srb_moving *mv, const srb_batch *b, bool rollout)
 {
@@ -526,9 +556,10 @@ static int check_plans(srb_ctx *c, int n_agents, const srb_batch *d, bool select
     return SRB_OK;
 }
 
-// obs_vel / obs_horizon: the members of srb_moving (null / 0: static obstacles, every launch as before)
+// obs_vel / obs_horizon: the members of srb_moving (null / 0: static obstacles, every launch as before);
+// obs_eps / obs_clear: those of srb_sizes (null / 0: eps_obs for every row, the selection as before)
 static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, int use_nlp,
-                  const double *obs_vel = nullptr, int obs_horizon = 0)
+                  const double *obs_vel = nullptr, int obs_horizon = 0, const double *obs_eps = nullptr, int obs_clear = 0)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -573,10 +604,11 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection) {
         int rc = srb_internal_select(c, n_agents, d->x0, d->obstacles, n_obs, d->nbr_state, n_all, d->agent_offset, k.K_obs,
                                      k.K_nbr, d->obstacles_version, sel, s, c->plan_selection ? nbr_plan : nullptr, k.N,
-                                     obs_vel, obs_horizon, p->Ts);
+                                     obs_vel, obs_horizon, p->Ts, obs_eps, obs_clear);
         if (rc) return rc;
     }
     const double *vel = (use_nlp && k.K_obs > 0) ? obs_vel : nullptr;   // read only for the static columns of sel
+    const double *eps = (use_nlp && k.K_obs > 0) ? obs_eps : nullptr;   // likewise (the QP-only solve ignores both)
     if (c->timing) HIPCHK(hipEventRecord(c->ev[2], s));
     // the solve kernel, then (NLP stage) the active-set polish of its result: fused into the solve
     // kernel's end (SRB_OPT_POLISH_FUSED, instances up to SRB_FUSED_POLISH_MAX = NZL 24), else srb_polish_kernel (same instance
@@ -593,12 +625,13 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         const srb_instance *f = f32_variant(in);
         if (f) { fn = f->fn; fn_mv = f->fn_mv; c->last_f32 = 1; }
     }
-    // with a velocity table the instance's moving-obstacle kernels (one more argument); without, the launches as ever
-    if (vel)
+    // with a velocity or a level table the instance's obstacle-table kernels (two more arguments); without, the
+    // launches as ever
+    if (vel || eps)
         hipLaunchKernelGGL(fn_mv, dim3(n_agents), dim3(64 * in->nw), lds, s, k, n_agents, d->x0, d->ref, d->foot, d->obstacles,
                            n_obs, d->nbr_state, n_all, d->agent_offset, d->x_qp, d->x, d->obj, d->status, d->iters,
                            d->alpha ? d->alpha_buf : nullptr, d->alpha_buf ? d->alpha : nullptr, (const int *)sel,
-                           polish ? c->zpol : nullptr, c->zstride, k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel);
+                           polish ? c->zpol : nullptr, c->zstride, k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel, eps);
     else
         hipLaunchKernelGGL(fn, dim3(n_agents), dim3(64 * in->nw), lds, s, k, n_agents, d->x0, d->ref, d->foot, d->obstacles,
                            n_obs, d->nbr_state, n_all, d->agent_offset, d->x_qp, d->x, d->obj, d->status, d->iters,
@@ -616,11 +649,11 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         const srb_instance *pin = pnw == in->nw ? in : pick_instance(k, pnw);
         if (!pin || pin->nzl != in->nzl) pin = in;
         const size_t plds = (size_t)srb_lds_doubles(k, pin->nzl, pin->nw) * sizeof(double);
-        if (vel)
+        if (vel || eps)
             hipLaunchKernelGGL(pin->polish_mv, dim3(n_agents), dim3(64 * pin->nw), plds, s, k, n_agents, d->x0, d->ref, d->foot,
                                d->obstacles, d->nbr_state, d->x, d->obj, d->status, d->alpha ? d->alpha_buf : nullptr,
                                d->alpha_buf ? d->alpha : nullptr, (const int *)sel, (const float *)c->zpol, c->zstride,
-                               k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel);
+                               k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel, eps);
         else
             hipLaunchKernelGGL(pin->polish, dim3(n_agents), dim3(64 * pin->nw), plds, s, k, n_agents, d->x0, d->ref, d->foot,
                                d->obstacles, d->nbr_state, d->x, d->obj, d->status, d->alpha ? d->alpha_buf : nullptr,
@@ -740,28 +773,38 @@ extern "C" int srb_ctx_set_qp_init(srb_ctx *c, int mode)
     return SRB_OK;
 }
 
-static int solve_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv, void *stream)
+static int solve_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv, const srb_sizes *sz,
+                        void *stream)
 {
     if (int rc0 = srb_check_struct(dev_io, "srb_batch")) return rc0;   // first: it needs no context
     if (int rc0 = check_moving(mv, dev_io, false)) return rc0;
+    if (int rc0 = srb_check_sizes(sz)) return rc0;
     if (!c || !dev_io) return fail(SRB_ERR_ARG, "null argument");
     hipStream_t s = (hipStream_t)stream;          // NULL: the HIP null stream (ordered with blocking streams)
     HIPCHK(hipSetDevice(c->device));
     int rc = c->order.order_after_last(s);
-    if (!rc) rc = launch(c, n_agents, dev_io, s, c->p.use_nlp, mv ? mv->obs_vel : nullptr, mv ? mv->horizon_selection : 0);
+    if (!rc) rc = launch(c, n_agents, dev_io, s, c->p.use_nlp, mv ? mv->obs_vel : nullptr, mv ? mv->horizon_selection : 0,
+                         sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0);
     if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
 }
 
+// (the plain and the _moving entry points are the _sized ones without a table: one path)
+extern "C" int srb_solve_batch_sized_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
+                                            const srb_sizes *sz, void *stream)
+{
+    return solve_device(c, n_agents, dev_io, mv, sz, stream);
+}
+
 extern "C" int srb_solve_batch_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, void *stream)
 {
-    return solve_device(c, n_agents, dev_io, nullptr, stream);
+    return srb_solve_batch_sized_device(c, n_agents, dev_io, nullptr, nullptr, stream);
 }
 
 extern "C" int srb_solve_batch_moving_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
                                              void *stream)
 {
-    return solve_device(c, n_agents, dev_io, mv, stream);
+    return srb_solve_batch_sized_device(c, n_agents, dev_io, mv, nullptr, stream);
 }
 
 // One or both tables of the selection into dev_io->sel (required; [A][Ko + Kn], the layout the solve reads):
@@ -794,14 +837,17 @@ extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, i
     });
 }
 
-// srb_select_device with the static columns by closest predicted approach (srb_moving.horizon_selection = 1); any
-// other srb_moving is srb_select_device itself (the snapshot selection does not read the velocities).
-extern "C" int srb_select_moving_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv, int tables,
-                                        void *stream)
+// srb_select_device with the static columns by closest predicted approach (srb_moving.horizon_selection = 1) or by
+// clearance to the level set (srb_sizes.clearance_selection = 1, over the horizon with both); any other srb_moving
+// and srb_sizes is srb_select_device itself (the snapshot selection reads neither the velocities nor the levels).
+extern "C" int srb_select_sized_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv,
+                                       const srb_sizes *sz, int tables, void *stream)
 {
     if (int rc0 = srb_check_struct(d, "srb_batch")) return rc0;
     if (int rc0 = check_moving(mv, d, false)) return rc0;
-    if (!mv || !mv->obs_vel || !mv->horizon_selection || !(tables & 1) || tables < 1 || tables > 3 || !c || !d)
+    if (int rc0 = srb_check_sizes(sz)) return rc0;
+    const bool horizon = mv && mv->obs_vel && mv->horizon_selection, clear = sz && sz->obs_eps && sz->clearance_selection;
+    if ((!horizon && !clear) || !(tables & 1) || tables < 1 || tables > 3 || !c || !d)
         return srb_select_device(c, n_agents, d, tables, stream);
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (!d->x0 || !d->sel) return fail(SRB_ERR_ARG, "missing buffer (x0, sel)");
@@ -815,9 +861,18 @@ extern "C" int srb_select_moving_device(srb_ctx *c, int n_agents, const srb_batc
     hipStream_t s = (hipStream_t)stream;
     return c->order.run(c->device, s, [&] {
         if (Ko == 0) return (int)SRB_OK;
+        if (clear)
+            return launch_obs_clear(c, n_agents, d->x0, d->obstacles, horizon ? mv->obs_vel : nullptr, sz->obs_eps, d->n_obs,
+                                    d->agent_offset, Ko, d->sel, Ko + Kn, s, c->p.N, c->p.Ts);
         return launch_obs_horizon(c, n_agents, d->x0, d->obstacles, mv->obs_vel, d->n_obs, d->agent_offset, Ko, d->sel,
                                   Ko + Kn, s, c->p.N, c->p.Ts);
     });
+}
+
+extern "C" int srb_select_moving_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv, int tables,
+                                        void *stream)
+{
+    return srb_select_sized_device(c, n_agents, d, mv, nullptr, tables, stream);
 }
 
 extern "C" int srb_obstacles_advance_device(srb_ctx *c, int n_obs, double *obstacles, const double *obs_vel, void *stream)
@@ -877,7 +932,9 @@ static int launch_advance(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
     return SRB_OK;
 }
 
-static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s)
+// radius: srb_sizes.obs_radius (null: the centre distances and the 0.5 m fail test, the kernels as ever)
+static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s,
+                          const double *radius = nullptr)
 {
     if (!d->state) return fail(SRB_ERR_ARG, "srb_sim: missing buffer (state)");
     if (d->n_obs < 0 || d->n_all < 0 || (d->n_obs > 0 && !d->obstacles) || (d->n_all > 0 && !d->nbr_state))
@@ -888,17 +945,31 @@ static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
     if (n_scenes > 0) {
         const int sa = c->scene_agents, bps = (sa + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK;
         const int s0 = d->agent_offset / sa, s1 = (d->agent_offset + n_agents - 1) / sa;
-        hipLaunchKernelGGL(srb_sim_scene_metrics_kernel, dim3((s1 - s0 + 1) * bps), dim3(256), 0, s, n_agents, cycle,
-                           d->c_first, (const double *)d->state, d->obstacles, d->n_obs > 0 ? c->scene_obs : 0, d->nbr_state,
-                           d->n_all > 0 ? sa : 0, sa, d->agent_offset, s0, bps, d->d_obs, d->d_agent, d->min_d_obs,
-                           d->min_d_agent, d->fail_cycle, d->distance_to_fail);
+        if (radius)
+            hipLaunchKernelGGL(srb_sim_scene_metrics_sized_kernel, dim3((s1 - s0 + 1) * bps), dim3(256), 0, s, n_agents,
+                               cycle, d->c_first, (const double *)d->state, d->obstacles, radius,
+                               d->n_obs > 0 ? c->scene_obs : 0, d->nbr_state, d->n_all > 0 ? sa : 0, sa, d->agent_offset, s0,
+                               bps, d->d_obs, d->d_agent, d->min_d_obs, d->min_d_agent, d->fail_cycle, d->distance_to_fail);
+        else
+            hipLaunchKernelGGL(srb_sim_scene_metrics_kernel, dim3((s1 - s0 + 1) * bps), dim3(256), 0, s, n_agents, cycle,
+                               d->c_first, (const double *)d->state, d->obstacles, d->n_obs > 0 ? c->scene_obs : 0,
+                               d->nbr_state, d->n_all > 0 ? sa : 0, sa, d->agent_offset, s0, bps, d->d_obs, d->d_agent,
+                               d->min_d_obs, d->min_d_agent, d->fail_cycle, d->distance_to_fail);
         HIPCHK(hipGetLastError());
         return SRB_OK;
     }
-    hipLaunchKernelGGL(srb_sim_metrics_kernel, dim3((n_agents + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK),
-                       dim3(256), 0, s, n_agents, cycle, d->c_first,
-                       (const double *)d->state, d->obstacles, d->n_obs, d->nbr_state, d->n_all, d->agent_offset, d->d_obs,
-                       d->d_agent, d->min_d_obs, d->min_d_agent, d->fail_cycle, d->distance_to_fail);
+    if (radius)
+        hipLaunchKernelGGL(srb_sim_metrics_sized_kernel,
+                           dim3((n_agents + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK), dim3(256), 0, s,
+                           n_agents, cycle, d->c_first, (const double *)d->state, d->obstacles, radius, d->n_obs,
+                           d->nbr_state, d->n_all, d->agent_offset, d->d_obs, d->d_agent, d->min_d_obs, d->min_d_agent,
+                           d->fail_cycle, d->distance_to_fail);
+    else
+        hipLaunchKernelGGL(srb_sim_metrics_kernel,
+                           dim3((n_agents + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK), dim3(256), 0, s,
+                           n_agents, cycle, d->c_first, (const double *)d->state, d->obstacles, d->n_obs, d->nbr_state,
+                           d->n_all, d->agent_offset, d->d_obs, d->d_agent, d->min_d_obs, d->min_d_agent, d->fail_cycle,
+                           d->distance_to_fail);
     HIPCHK(hipGetLastError());
     return SRB_OK;
 }
@@ -908,15 +979,18 @@ int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cyc
     return launch_metrics(c, n_agents, d, cycle, s);
 }
 
-static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream, bool advance)
+static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream, bool advance,
+                    const srb_sizes *sz = nullptr)
 {
     if (int rc = check_sim(d, cycle, advance)) return rc;
+    if (int rc = srb_check_sizes(sz)) return rc;
     if (!c) return fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
     hipStream_t s = (hipStream_t)stream;
     return c->order.run(c->device, s, [&] {
-        return advance ? launch_advance(c, n_agents, d, cycle, s) : launch_metrics(c, n_agents, d, cycle, s);
+        return advance ? launch_advance(c, n_agents, d, cycle, s)
+                       : launch_metrics(c, n_agents, d, cycle, s, sz ? sz->obs_radius : nullptr);
     });
 }
 
@@ -925,16 +999,23 @@ extern "C" int srb_sim_advance_device(srb_ctx *c, int n_agents, const srb_sim *d
     return sim_call(c, n_agents, d, cycle, stream, true);
 }
 
-extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream)
+extern "C" int srb_sim_metrics_sized_device(srb_ctx *c, int n_agents, const srb_sim *d, const srb_sizes *sz, int cycle,
+                                            void *stream)
 {
-    return sim_call(c, n_agents, d, cycle, stream, false);
+    return sim_call(c, n_agents, d, cycle, stream, false, sz);
 }
 
-static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, const srb_moving *mv, int cycles,
-                   void *stream)
+extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream)
+{
+    return srb_sim_metrics_sized_device(c, n_agents, d, nullptr, cycle, stream);
+}
+
+static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, const srb_moving *mv,
+                   const srb_sizes *sz, int cycles, void *stream)
 {
     if (int rc0 = srb_check_struct(b, "srb_batch")) return rc0;
     if (int rc0 = check_moving(mv, b, true)) return rc0;
+    if (int rc0 = srb_check_sizes(sz)) return rc0;
     // (the layout and null checks of check_sim only: the driver's first cycle is c_first itself)
     if (int rc = check_sim(d, d && d->struct_size == (int)sizeof(srb_sim) ? d->c_first : 0, false)) return rc;
     if (!b) return fail(SRB_ERR_ARG, "null argument");
@@ -978,23 +1059,31 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
         rc = launch_advance(c, n_agents, &sim, cyc, s);
         if (rc || i == cycles) break;
         if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
-        if (!rc) rc = launch_metrics(c, n_agents, &sim, cyc, s);
+        if (!rc) rc = launch_metrics(c, n_agents, &sim, cyc, s, sz ? sz->obs_radius : nullptr);
         if (i > 0 && d->plan_table) bat.nbr_plan = d->plan_table;
-        if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp, vel, mv ? mv->horizon_selection : 0);
+        if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp, vel, mv ? mv->horizon_selection : 0,
+                             sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0);
     }
     const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier launches run
     return rc ? rc : rc_mark;
 }
 
+// the tables of srb_sizes do not change over a rollout: the same pointers serve every cycle
+extern "C" int srb_rollout_sized_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
+                                        const srb_moving *mv, const srb_sizes *sz, int cycles, void *stream)
+{
+    return rollout(c, n_agents, b, d, mv, sz, cycles, stream);
+}
+
 extern "C" int srb_rollout_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, int cycles, void *stream)
 {
-    return rollout(c, n_agents, b, d, nullptr, cycles, stream);
+    return srb_rollout_sized_device(c, n_agents, b, d, nullptr, nullptr, cycles, stream);
 }
 
 extern "C" int srb_rollout_moving_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
                                          const srb_moving *mv, int cycles, void *stream)
 {
-    return rollout(c, n_agents, b, d, mv, cycles, stream);
+    return srb_rollout_sized_device(c, n_agents, b, d, mv, nullptr, cycles, stream);
 }
 
 // swarms up to this many agents run as one persistent workgroup (srb_hlplan_kernel); larger ones
@@ -1094,10 +1183,12 @@ extern "C" int srb_last_polish_ms(srb_ctx *c, float *polish_ms)
     return SRB_OK;
 }
 
-static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp, const srb_moving *mv = nullptr)
+static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp, const srb_moving *mv = nullptr,
+                      const srb_sizes *sz = nullptr)
 {
     if (int rc0 = srb_check_struct(h, "srb_batch")) return rc0;   // first: it needs no context
     if (int rc0 = check_moving(mv, h, false)) return rc0;
+    if (int rc0 = srb_check_sizes(sz)) return rc0;
     if (!c || !h) return fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -1156,9 +1247,18 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp,
         HIPCHK(hipMemcpyAsync(c->obs_vel, mv->obs_vel, bytes, hipMemcpyHostToDevice, s));
         vel = c->obs_vel;
     }
+    // the level table likewise (srb_solve_batch_sized)
+    const double *eps = nullptr;
+    if (use_nlp && sz && sz->obs_eps && d.obstacles) {
+        const size_t bytes = (size_t)h->n_obs * sizeof(double);
+        if (int rc0 = srb_stage_reserve(c->order, c->obs_eps, c->cap_eps, bytes)) return rc0;
+        HIPCHK(hipMemcpyAsync(c->obs_eps, sz->obs_eps, bytes, hipMemcpyHostToDevice, s));
+        eps = c->obs_eps;
+    }
     d.sel = nullptr;                       // the context's scratch; copied out below when asked for
     d.obstacles_version = 0;               // staged copy: rebuilt every call
-    int rc = launch(c, n_agents, &d, s, use_nlp, vel, vel && mv ? mv->horizon_selection : 0);
+    int rc = launch(c, n_agents, &d, s, use_nlp, vel, vel && mv ? mv->horizon_selection : 0, eps,
+                    eps && sz ? sz->clearance_selection : 0);
     if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->sel && use_nlp) {
@@ -1177,9 +1277,15 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp,
     return SRB_OK;
 }
 
+extern "C" int srb_solve_batch_sized(srb_ctx *c, int n_agents, const srb_batch *host_io, const srb_moving *host_mv,
+                                     const srb_sizes *host_sz)
+{
+    return solve_host(c, n_agents, host_io, c ? c->p.use_nlp : 0, host_mv, host_sz);
+}
+
 extern "C" int srb_solve_batch(srb_ctx *c, int n_agents, const srb_batch *host_io)
 {
-    return solve_host(c, n_agents, host_io, c ? c->p.use_nlp : 0);
+    return srb_solve_batch_sized(c, n_agents, host_io, nullptr, nullptr);
 }
 
 extern "C" int srb_solve_qp(srb_ctx *c, int n_agents, const srb_batch *host_io)
@@ -1189,7 +1295,7 @@ extern "C" int srb_solve_qp(srb_ctx *c, int n_agents, const srb_batch *host_io)
 
 extern "C" int srb_solve_batch_moving(srb_ctx *c, int n_agents, const srb_batch *host_io, const srb_moving *host_mv)
 {
-    return solve_host(c, n_agents, host_io, c ? c->p.use_nlp : 0, host_mv);
+    return srb_solve_batch_sized(c, n_agents, host_io, host_mv, nullptr);
 }
 
 // fitComTrajectory_eventbase (MPC_dist.cpp:784-855).  With N == NDOMAIN the reference's

@@ -1,7 +1,7 @@
 // Host plumbing shared by the three C-ABI files (srb_capi.cpp, srb12_capi.cpp, srb_ll_capi.cpp): the error
 // channel, the HIP-error macros, the submission-order chaining of a context, and what the LIP and the SRB-12 mode
-// check and launch alike (the struct-size refusal, the range-overlap test, the srb_moving checks, the growth of a
-// staging buffer, the obstacle-advance launch).  Internal, host only.
+// check and launch alike (the struct-size refusal, the range-overlap test, the srb_moving and srb_sizes checks, the
+// growth of a staging buffer, the obstacle-advance launch).  Internal, host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -11,12 +11,14 @@
 // defined in srb_capi.cpp: the thread's last-error message (srb_last_error), and the LIP-mode context's selection
 // launch and ordering mark, which the SRB-12 mode reuses (nbr_plan [n_all][N][2] != NULL: the neighbour columns by
 // the horizon-aware selection of SRB_OPT_PLAN_SELECTION, whatever that option of the context says; obs_vel
-// [n_obs][2] with obs_horizon != 0: the static columns by srb_moving.horizon_selection over the grid (N, Ts))
+// [n_obs][2] with obs_horizon != 0: the static columns by srb_moving.horizon_selection over the grid (N, Ts);
+// obs_eps [n_obs] with obs_clear != 0: the static columns by srb_sizes.clearance_selection)
 int srb_internal_fail(int code, const char *msg);
 int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
                         int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan = nullptr, int N = 0,
-                        const double *obs_vel = nullptr, int obs_horizon = 0, double Ts = 0.0);
+                        const double *obs_vel = nullptr, int obs_horizon = 0, double Ts = 0.0,
+                        const double *obs_eps = nullptr, int obs_clear = 0);
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s);
 // ... and its scene partition (srb_ctx_set_scenes): the per-call refusals, the "up to K nearest" clamp, and the
 // metrics launch (srb_sim_metrics_kernel, or with scenes srb_sim_scene_metrics_kernel) on d->state rows
@@ -115,6 +117,22 @@ static int srb_check_moving(const srb_moving *mv, const Batch *b, bool rollout, 
     if (rollout && mv->obstacles != b->obstacles)
         return srb_internal_fail(SRB_ERR_ARG, (std::string(entry) + ": srb_moving.obstacles is not " + batch + ".obstacles "
                                                "(the solve and the metrics read the table the driver moves)").c_str());
+    return SRB_OK;
+}
+
+// The argument errors of srb_sizes, none of which needs a context, before anything is launched.  (obs_eps goes
+// together with obstacles_version != 0: sizes do not stale a grid of centres, and the clearance selection consults
+// no grid.)
+static inline int srb_check_sizes(const srb_sizes *sz)
+{
+    if (int rc = srb_check_struct(sz, "srb_sizes")) return rc;
+    if (!sz) return SRB_OK;
+    if (sz->clearance_selection != 0 && sz->clearance_selection != 1)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_sizes.clearance_selection: 0 (the K_obs columns as ever) or 1 (by "
+                                              "clearance to the level set)");
+    if (sz->clearance_selection && !sz->obs_eps)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_sizes.clearance_selection = 1 needs obs_eps (the clearance selection "
+                                              "reads the level table)");
     return SRB_OK;
 }
 

@@ -26,7 +26,8 @@ struct SrbGrid {
 };
 
 // ---- srb_kernels.hip: the solve kernel (INFIX empty, or f32_ for the fp32-factor instances) and the polish kernel;
-// the moving-obstacle instances (mv_: one more argument, the velocity table) of each
+// the instances that take obstacle-table extras (mv_: two more arguments, the velocity table of srb_moving and the
+// level table of srb_sizes, either may be null) of each
 #define SRB_DECL_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC)                                                         \
     extern "C" __global__ void srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(               \
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
@@ -39,7 +40,7 @@ struct SrbGrid {
         const double *obstacles, int n_obs, const double *nbr_state, int n_all, int agent_offset,              \
         double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
         const double *alpha_buf, double *alpha_out, const int *sel_g, float *zpol_g, int zstride,             \
-        const double *nbr_plan, double *plan_out, const double *obs_vel);
+        const double *nbr_plan, double *plan_out, const double *obs_vel, const double *obs_eps);
 #define SRB_DECL_POLISH(NZL, TS, NW, NC, CC, KC)                                                              \
     extern "C" __global__ void srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                   \
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
@@ -50,7 +51,7 @@ struct SrbGrid {
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
         const double *obstacles, const double *nbr_state, double *x_out, double *obj_out, int *status_out,     \
         const double *alpha_buf, double *alpha_out, const int *sel_g, const float *zpol_g, int zstride,       \
-        const double *nbr_plan, double *plan_out, const double *obs_vel);
+        const double *nbr_plan, double *plan_out, const double *obs_vel, const double *obs_eps);
 #define SRB_DECL_NMPC(...) SRB_DECL_NMPC_(, __VA_ARGS__) SRB_DECL_POLISH(__VA_ARGS__)
 #define SRB_DECL_NMPC_F32(...) SRB_DECL_NMPC_(f32_, __VA_ARGS__)
 SRB_KERNEL_INSTANCES(SRB_DECL_NMPC)
@@ -127,6 +128,28 @@ extern "C" __global__ void srb_knn_obs_horizon_scene_kernel(int n_agents, const 
                                                             int scene_agents, int scene_obs, int K_obs, int *sel_out,
                                                             int sel_stride);
 extern "C" __global__ void srb_obstacles_advance_kernel(int n_obs, double Ts, double *obstacles, const double *obs_vel);
+
+// ---- srb_sizes.hip (obstacle sizes, srb_sizes): the clearance selection (whole table / the agent's scene, global
+// indices out; obs_vel null: the distance now) and the metrics with a body radius per obstacle row
+extern "C" __global__ void srb_knn_obs_clear_kernel(int n_agents, const double *x0g, const double *obstacles,
+                                                    const double *obs_vel, const double *obs_eps, int n_obs, int N,
+                                                    double Ts, int K_obs, int *sel_out, int sel_stride);
+extern "C" __global__ void srb_knn_obs_clear_scene_kernel(int n_agents, const double *x0g, const double *obstacles,
+                                                          const double *obs_vel, const double *obs_eps, int N, double Ts,
+                                                          int agent_offset, int scene_agents, int scene_obs, int K_obs,
+                                                          int *sel_out, int sel_stride);
+extern "C" __global__ void srb_sim_metrics_sized_kernel(int n_agents, int c, int c_first, const double *state,
+                                                        const double *obstacles, const double *obs_radius, int n_obs,
+                                                        const double *nbr_state, int n_all, int agent_offset,
+                                                        double *d_obs, double *d_agent, double *min_d_obs,
+                                                        double *min_d_agent, int *fail_cycle, double *distance_to_fail);
+extern "C" __global__ void srb_sim_scene_metrics_sized_kernel(int n_agents, int c, int c_first, const double *state,
+                                                              const double *obstacles, const double *obs_radius,
+                                                              int obs_rows, const double *nbr_state, int nbr_rows,
+                                                              int scene_agents, int agent_offset, int scene0,
+                                                              int blocks_per_scene, double *d_obs, double *d_agent,
+                                                              double *min_d_obs, double *min_d_agent, int *fail_cycle,
+                                                              double *distance_to_fail);
 
 // ---- srb_llctrl.hip
 extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDev io);

@@ -1303,6 +1303,7 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
 //                        generalised; neighbours at their planned positions nbr_plan[sel][k], or without a plan
 //                        table predicted at constant velocity o_k = p + v Ts (k+1))
 //                        (the moving-obstacle instances, MV = 1: static rows at o + w Ts (k+1), w = obs_vel[sel])
+//                        (likewise with srb_sizes.obs_eps: the level of static column j is obs_eps[sel[j]])
 //   SRB_AGENT_OUTPUTS    x, the agent's plan (the CoM positions of x), objective, alpha_COM
 #define SRB_AGENT_LAYOUT \
     constexpr int NZM = ((NZL + 15) / 16) * 16; \
@@ -1457,6 +1458,10 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
             if (e < NK) { obs[2 * e] = ox_[t]; obs[2 * e + 1] = oy_[t]; } \
         } \
         if (tid < K) eps[tid] = (tid < prm.K_obs) ? prm.eps_obs : prm.eps_nbr; \
+        /* obstacle sizes (srb_sizes.obs_eps; the MV instances only, a kernel argument: wave-uniform): the level of */ \
+        /* static column j is the table's row sel[j]; the lane that wrote the entry rewrites it (no barrier added); */ \
+        /* the neighbour columns and a -1 row keep what they have */ \
+        if (MV && obs_eps) { if (tid < prm.K_obs && sel[tid] >= 0) eps[tid] = obs_eps[sel[tid]]; } \
     } \
     do {} while (0)
 
@@ -1672,7 +1677,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,
                 const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride,
                 const double *__restrict__ nbr_plan, double *__restrict__ plan_out,
-                const double *__restrict__ obs_vel, double *lds)
+                const double *__restrict__ obs_vel, const double *__restrict__ obs_eps, double *lds)
 {
     SRB_AGENT_LAYOUT;
 #ifdef SRB_STAMPS
@@ -2372,7 +2377,7 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
                 const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,
                 const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride,
                 const double *__restrict__ nbr_plan, double *__restrict__ plan_out,
-                const double *__restrict__ obs_vel, double *lds)
+                const double *__restrict__ obs_vel, const double *__restrict__ obs_eps, double *lds)
 {
     SRB_AGENT_LAYOUT;
 #ifdef SRB_STAMPS
@@ -2473,7 +2478,7 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         if (agent >= n_agents) return;                                                                         \
         nmpc_agent<NZL, TS, NW, NC, CC, KC, KF>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
                                 x_qp_out, x_out, obj_out, status_out, iters_out, alpha_buf, alpha_out, sel_g, \
-                                zpol_g, zstride, nbr_plan, plan_out, nullptr, lds);                            \
+                                zpol_g, zstride, nbr_plan, plan_out, nullptr, nullptr, lds);                            \
     }
 #define SRB_POLISH_ENTRY(NZL, TS, NW, NC, CC, KC)                                                              \
     extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
@@ -2489,10 +2494,11 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         polish_agent<NZL, TS, NW, NC, CC, KC>(prm, agent, x0g, refg, footg, obstacles, nbr_state, x_out, obj_out,          \
-                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, nullptr, lds); \
+                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, nullptr, nullptr, lds); \
     }
-// The moving-obstacle instances (srb_moving.obs_vel; MV = 1): the same kernels with the velocity table as one more
-// argument and the moving arm of SRB_AGENT_OBSTACLES compiled in, named srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*.
+// The obstacle-table instances (srb_moving.obs_vel, srb_sizes.obs_eps; MV = 1): the same kernels with the velocity
+// table and the level table as two more arguments (either may be null) and the arms of SRB_AGENT_OBSTACLES that read
+// them compiled in, named srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*.
 // Instances of their own, as the fp32-factor instances are, and in code objects of their own (SRB_PART 4 .. 7): with
 // the argument on the default instances the default bench step measured 0.5 % and config 5 0.3 % slower than the
 // parent, outside its run-to-run spread, so the default instances keep their code.
@@ -2506,14 +2512,14 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         int *__restrict__ iters_out, const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,       \
         const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride,                               \
         const double *__restrict__ nbr_plan, double *__restrict__ plan_out,                                    \
-        const double *__restrict__ obs_vel)                                                                    \
+        const double *__restrict__ obs_vel, const double *__restrict__ obs_eps)                                \
     {                                                                                                          \
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         nmpc_agent<NZL, TS, NW, NC, CC, KC, KF, 1>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
                                 x_qp_out, x_out, obj_out, status_out, iters_out, alpha_buf, alpha_out, sel_g, \
-                                zpol_g, zstride, nbr_plan, plan_out, obs_vel, lds);                            \
+                                zpol_g, zstride, nbr_plan, plan_out, obs_vel, obs_eps, lds);                            \
     }
 #define SRB_POLISH_ENTRY_MV(NZL, TS, NW, NC, CC, KC)                                                           \
     extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
@@ -2524,13 +2530,13 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         int *__restrict__ status_out, const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,     \
         const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride,                         \
         const double *__restrict__ nbr_plan, double *__restrict__ plan_out,                                    \
-        const double *__restrict__ obs_vel)                                                                    \
+        const double *__restrict__ obs_vel, const double *__restrict__ obs_eps)                                \
     {                                                                                                          \
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         polish_agent<NZL, TS, NW, NC, CC, KC, 1>(prm, agent, x0g, refg, footg, obstacles, nbr_state, x_out, obj_out,       \
-                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, obs_vel, lds); \
+                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, obs_vel, obs_eps, lds); \
     }
 #define SRB_NMPC_KERNEL(...) SRB_NMPC_ENTRY(, 0, __VA_ARGS__) SRB_POLISH_ENTRY(__VA_ARGS__)
 #define SRB_NMPC_KERNEL_F32(...) SRB_NMPC_ENTRY(f32_, 1, __VA_ARGS__)

@@ -106,6 +106,14 @@ class Moving(ctypes.Structure):
         super().__init__(ctypes.sizeof(Moving), *args, **kw)
 
 
+class Sizes(ctypes.Structure):
+    """Mirror of srb_sizes (obstacle sizes; struct_size filled in)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("obs_eps", _dp), ("obs_radius", _dp), ("clearance_selection", ctypes.c_int)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(ctypes.sizeof(Sizes), *args, **kw)
+
+
 _lib = None
 
 
@@ -161,6 +169,15 @@ def lib():
         L.srb_obstacles_advance_device.argtypes = [ctypes.c_void_p, ctypes.c_int, _dp, _dp, ctypes.c_void_p]
         L.srb_rollout_moving_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim),
                                                 ctypes.POINTER(Moving), ctypes.c_int, ctypes.c_void_p]
+        MV, SZ = ctypes.POINTER(Moving), ctypes.POINTER(Sizes)
+        L.srb_solve_batch_sized.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), MV, SZ]
+        L.srb_solve_batch_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), MV, SZ, ctypes.c_void_p]
+        L.srb_select_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), MV, SZ, ctypes.c_int,
+                                              ctypes.c_void_p]
+        L.srb_sim_metrics_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Sim), SZ, ctypes.c_int,
+                                                   ctypes.c_void_p]
+        L.srb_rollout_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim), MV,
+                                               SZ, ctypes.c_int, ctypes.c_void_p]
         L.srb_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.srb_fit_bezier.argtypes = [_dp, _dp, _dp]
         L.srb_last_error.restype = ctypes.c_char_p
@@ -225,6 +242,18 @@ def _moving_args(obs_vel, obs_horizon, n_obs, dtype, ptr, obstacle_rows=True) ->
     if obs_vel is not None:
         _check_vel_array(obs_vel, n_obs, dtype)
     return Moving(ptr(obs_vel), int(bool(obs_horizon)), None)
+
+
+def _sizes_args(obs_eps, obs_radius, obs_clearance, n_obs, dtype, ptr, obstacle_rows=True, device=None) -> Sizes:
+    """The srb_sizes of a call after the checks of the tables that need no context, by name (obs_clearance without
+    obs_eps is the library's refusal).  ptr: _p for host arrays, _dptr for device tensors."""
+    if not obstacle_rows:
+        raise ValueError("obs_eps / obs_clearance: the QP-only solve has no obstacle rows")
+    if obs_eps is not None:
+        _check_size_array(obs_eps, n_obs, dtype, "obs_eps", device)
+    if obs_radius is not None:
+        _check_size_array(obs_radius, n_obs, dtype, "obs_radius", device)
+    return Sizes(ptr(obs_eps), ptr(obs_radius), int(bool(obs_clearance)))
 
 
 class _SolverBase:
@@ -329,7 +358,8 @@ class BatchSolver(_SolverBase):
         return _clamp_selected(self.params.K_obs, self.params.K_nbr, n_obs, n_all, self._scenes)
 
     def solve(self, x0, ref, foot, obstacles=None, nbr_state=None, agent_offset: int = 0, qp_only: bool = False,
-              alpha_buf=None, nbr_plan=None, plan=None, obs_vel=None, obs_horizon: bool = False):
+              alpha_buf=None, nbr_plan=None, plan=None, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
+              obs_clearance: bool = False):
         """Host arrays in, dict of outputs back.  alpha_buf ([A][4], the Bezier buffer state)
         additionally returns alpha ([A][4][5], get_alphaCOM) from the fused fit.  With the NLP
         stage, sel ([A][Ko + Kn]) holds the selected obstacle / neighbour rows.  nbr_plan
@@ -337,7 +367,9 @@ class BatchSolver(_SolverBase):
         instead of the constant-velocity guess; plan ([A][N][2], the same) receives this batch's plans
         (out["plan"]; allocated here when None).  obs_vel ([n_obs][2], float64, C-contiguous): the obstacles move
         at these velocities over the horizon (srb_solve_batch_moving); obs_horizon=True additionally selects the
-        static columns by closest predicted approach instead of nearest now."""
+        static columns by closest predicted approach instead of nearest now.  obs_eps ([n_obs], float64, C-contiguous):
+        the CBF level of each obstacle row in squared metres, the unit of eps_obs (srb_solve_batch_sized);
+        obs_clearance=True additionally selects the static columns by clearance to the level set."""
         p = self.params
         x0 = _f64(x0).reshape(-1, 4)
         A = x0.shape[0]
@@ -365,8 +397,14 @@ class BatchSolver(_SolverBase):
                   _p(out["x_qp"]), _p(out["x"]), _p(out["obj"]), _p(out["status"]), _p(out["iters"]),
                   _p(ab) if ab is not None else None, _p(out["alpha"]) if ab is not None else None,
                   _p(out["sel"]) if out["sel"].size and not qp_only else None, 0, _p(nbr_plan), _p(plan))
-        if obs_vel is not None or obs_horizon:
-            mv = _moving_args(obs_vel, obs_horizon, ob.shape[0], np.float64, _p, not qp_only)
+        moving = obs_vel is not None or obs_horizon
+        mv = _moving_args(obs_vel, obs_horizon, ob.shape[0], np.float64, _p, not qp_only) if moving else None
+        if obs_eps is not None or obs_clearance:
+            sz = _sizes_args(obs_eps, None, obs_clearance, ob.shape[0], np.float64, _p, not qp_only)
+            _check(lib().srb_solve_batch_sized(self._h, A, ctypes.byref(b), ctypes.byref(mv) if moving else None,
+                                               ctypes.byref(sz)))
+            return out
+        if moving:
             _check(lib().srb_solve_batch_moving(self._h, A, ctypes.byref(b), ctypes.byref(mv)))
             return out
         fn = lib().srb_solve_qp if qp_only else lib().srb_solve_batch
@@ -376,7 +414,7 @@ class BatchSolver(_SolverBase):
     # --------------------------------------------------------------- device path
     def solve_device(self, x0, ref, foot, obstacles, nbr_state, out, agent_offset: int = 0, stream=None,
                      alpha_buf=None, obstacles_version: int = 0, nbr_plan=None, plan=None, obs_vel=None,
-                     obs_horizon: bool = False):
+                     obs_horizon: bool = False, obs_eps=None, obs_clearance: bool = False):
         """All arguments torch tensors on this solver's device (float64 / int32), contiguous.
         `out` is a dict with x_qp (or None), x, obj, status, iters and, with alpha_buf [A][4],
         alpha [A][20]; an optional int32 out["sel"] [A][Ko + Kn] receives the selected rows
@@ -387,7 +425,9 @@ class BatchSolver(_SolverBase):
         (None: constant velocity); plan (or out["plan"], [A][N][2] float64): receives this batch's plans,
         and must not overlap nbr_plan.  obs_vel ([n_obs][2] float64, contiguous): the obstacles' velocities
         (srb_solve_batch_moving_device; needs obstacles_version 0); obs_horizon=True selects the static columns by
-        closest predicted approach over the horizon.
+        closest predicted approach over the horizon.  obs_eps ([n_obs] float64, contiguous): the CBF level of each
+        obstacle row (srb_solve_batch_sized_device; goes together with obstacles_version); obs_clearance=True selects
+        the static columns by clearance to the level set.
         Asynchronous on `stream` (a hipStream_t handle), by default torch's current stream on
         this device, so the launch is ordered after the torch work that filled the inputs."""
         A = x0.shape[0]
@@ -414,21 +454,30 @@ class BatchSolver(_SolverBase):
                   _iptr(out["status"]), _iptr(out["iters"]), _dptr(alpha_buf),
                   _dptr(out.get("alpha") if alpha_buf is not None else None), _iptr(sel), int(obstacles_version),
                   _dptr(nbr_plan), _dptr(plan))
-        if obs_vel is not None or obs_horizon:
-            mv = _moving_args(obs_vel, obs_horizon, 0 if obstacles is None else obstacles.shape[0], torch_float64(), _dptr)
+        n_obs = 0 if obstacles is None else obstacles.shape[0]
+        moving = obs_vel is not None or obs_horizon
+        mv = _moving_args(obs_vel, obs_horizon, n_obs, torch_float64(), _dptr) if moving else None
+        if obs_eps is not None or obs_clearance:
+            sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch_float64(), _dptr, device=x0.device)
+            _check(lib().srb_solve_batch_sized_device(self._h, A, ctypes.byref(b), ctypes.byref(mv) if moving else None,
+                                                      ctypes.byref(sz), self._stream(stream)))
+            return
+        if moving:
             _check(lib().srb_solve_batch_moving_device(self._h, A, ctypes.byref(b), ctypes.byref(mv), self._stream(stream)))
             return
         _check(lib().srb_solve_batch_device(self._h, A, ctypes.byref(b), self._stream(stream)))
 
     def select_device(self, x0, obstacles, nbr_state, sel, tables: int = 3, agent_offset: int = 0, stream=None,
-                      obstacles_version: int = 0, nbr_plan=None, obs_vel=None, obs_horizon: bool = False):
+                      obstacles_version: int = 0, nbr_plan=None, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
+                      obs_clearance: bool = False):
         """The obstacle / neighbour selection alone (srb_select_device) into the int32 tensor sel [A][Ko + Kn]:
         tables 1 the static obstacles, 2 the neighbour snapshot, 3 both.  With the option "selection" set
         to 0, solve_device then uses out["sel"] as filled here (bench.py selects the static obstacles while
         the neighbour all-gather is in flight).  With the option "plan_selection" set to 1, tables & 2 is the
         horizon-aware selection (closest predicted approach) and needs nbr_plan [n_all][N][2].  With obs_vel
         ([n_obs][2]) and obs_horizon=True, tables & 1 is the horizon-aware obstacle selection
-        (srb_select_moving_device).
+        (srb_select_moving_device).  With obs_eps ([n_obs]) and obs_clearance=True, tables & 1 is the selection by
+        clearance to the level set (srb_select_sized_device), over the horizon when obs_horizon is on as well.
         Asynchronous on `stream` like solve_device."""
         A = x0.shape[0]
         Ko, Kn = self.n_selected(0 if obstacles is None else obstacles.shape[0],
@@ -442,8 +491,15 @@ class BatchSolver(_SolverBase):
                   0 if obstacles is None else obstacles.shape[0], 0 if nbr_state is None else nbr_state.shape[0],
                   int(agent_offset), None, None, None, None, None, None, None,
                   _iptr(sel), int(obstacles_version), _dptr(nbr_plan), None)
-        if obs_vel is not None or obs_horizon:
-            mv = _moving_args(obs_vel, obs_horizon, 0 if obstacles is None else obstacles.shape[0], torch_float64(), _dptr)
+        n_obs = 0 if obstacles is None else obstacles.shape[0]
+        moving = obs_vel is not None or obs_horizon
+        mv = _moving_args(obs_vel, obs_horizon, n_obs, torch_float64(), _dptr) if moving else None
+        if obs_eps is not None or obs_clearance:
+            sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch_float64(), _dptr, device=x0.device)
+            _check(lib().srb_select_sized_device(self._h, A, ctypes.byref(b), ctypes.byref(mv) if moving else None,
+                                                 ctypes.byref(sz), int(tables), self._stream(stream)))
+            return
+        if moving:
             _check(lib().srb_select_moving_device(self._h, A, ctypes.byref(b), ctypes.byref(mv), int(tables),
                                                   self._stream(stream)))
             return
@@ -451,7 +507,8 @@ class BatchSolver(_SolverBase):
 
     def solve_coupled_device(self, x0, ref, foot, obstacles, nbr_state, out, outer: int = 2, exchange=None,
                              nbr_plan=None, agent_offset: int = 0, stream=None, alpha_buf=None,
-                             obstacles_version: int = 0, obs_vel=None, obs_horizon: bool = False):
+                             obstacles_version: int = 0, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
+                             obs_clearance: bool = False):
         """Jacobi iteration over the agents' plans: `outer` solves of the same cycle, each against the plans
         the agents wrote in the round before.  Round 0 solves against nbr_plan (None: the constant-velocity
         rows); every later round r exchanges the plans of round r - 1 -- table = exchange(plan), a
@@ -460,11 +517,12 @@ class BatchSolver(_SolverBase):
         a second buffer of this solver, so the table a round reads is never the buffer it writes; the last
         round's results, its plans included, are in `out`.  Returns plan_change, a device tensor [outer - 1]:
         max |plan_r - plan_{r-1}| per round (torch reductions; nothing synchronises with the host inside the
-        loop).  No damping and no convergence test: the plain Jacobi round.  Other arguments (obs_vel and
-        obs_horizon included: every round solves against the same moving table) as solve_device."""
+        loop).  No damping and no convergence test: the plain Jacobi round.  Other arguments (obs_vel,
+        obs_horizon, obs_eps and obs_clearance included: every round solves against the same obstacle tables) as
+        solve_device."""
         return self._solve_coupled((x0, ref, foot, obstacles, nbr_state, out), outer, exchange, nbr_plan, agent_offset,
                                    stream, lambda table: {"alpha_buf": alpha_buf}, obstacles_version=obstacles_version,
-                                   obs_vel=obs_vel, obs_horizon=obs_horizon)
+                                   obs_vel=obs_vel, obs_horizon=obs_horizon, obs_eps=obs_eps, obs_clearance=obs_clearance)
 
     def prepare_device(self, Pr, Prd, gait_domain, contact, toe, start, q, dq, out, agent_id=None,
                        agent_offset: int = 0, stream=None):
@@ -552,6 +610,15 @@ def _check_vel_array(a, n_obs, dtype, name="obs_vel"):
     if not hasattr(a, "dtype") or not hasattr(a, "shape"):
         raise ValueError(f"{name} must be a contiguous float64 array of shape ({n_obs}, 2), got {type(a).__name__}")
     _check_plan_array(a, (n_obs, 2), name, dtype)
+
+
+def _check_size_array(a, n_obs, dtype, name, device=None):
+    """obs_eps / obs_radius: a contiguous float64 [n_obs] array (on `device` when one is given), by name."""
+    if not hasattr(a, "dtype") or not hasattr(a, "shape"):
+        raise ValueError(f"{name} must be a contiguous float64 array of shape ({n_obs},), got {type(a).__name__}")
+    _check_plan_array(a, (n_obs,), name, dtype)
+    if device is not None and getattr(a, "device", device) != device:
+        raise ValueError(f"{name} must be on {device}, got {a.device}")
 
 
 def hl_plan(Pstart, Pobs, loop: int = 100000, device: int = 0):

@@ -18,6 +18,11 @@ With obs_vel ([n_obs][2], m/s) the obstacles move: every solve reads the velocit
 cycle on the table advances one cycle between the agents' advance and the metrics (srb_rollout_moving_device).  The
 rollout then works on its own copy of `obstacles`; results()["obstacles"] is the current table.
 
+With obs_eps ([n_obs], squared metres) every obstacle row has its own CBF level in the solve, with obs_clearance the
+static columns are selected by clearance to the level set, and with obs_radius ([n_obs], m) d_obs is the clearance to
+the obstacle bodies, min_i (dist_i - obs_radius[i]), and fail_cycle the first cycle with d_obs < 0 (srb_sizes,
+srb_rollout_sized_device).  The tables do not change over a rollout.  LIP mode only.
+
 _RolloutBase is what this class and srb12.Rollout12 share: the checks of goal / phase / obstacles / obs_vel, the moving
 table's clone and its restore, the solve, metrics and log buffers, reset / advance / results / scene_results and the
 preconditions of run().  A mode adds its state width, its own buffers, its srb_sim (_sim), step() and the driver
@@ -27,7 +32,7 @@ from __future__ import annotations
 
 import ctypes
 
-from . import Batch, Moving, Sim, _check, _check_vel_array, _dptr, _iptr, lib
+from . import Batch, Moving, Sim, Sizes, _check, _check_size_array, _check_vel_array, _dptr, _iptr, lib
 
 
 def _check_tensor(t, shape, name, dtype, device):
@@ -215,15 +220,29 @@ class Rollout(_RolloutBase):
     obs_vel   [n_obs][2] or None: the obstacles' velocities (m/s).  The rollout then clones `obstacles` (it moves the
               table), reset() restores the start table, and every shard moves its own full copy (the same bits)
     obs_horizon  True: the static columns by closest predicted approach over the horizon (needs obs_vel)
+    obs_eps   [n_obs] or None: the CBF level of each obstacle row, squared metres (None: eps_obs for every row)
+    obs_radius  [n_obs] or None: the body radius (m) of each obstacle row: d_obs is then min_i (dist_i - obs_radius[i])
+              and fail_cycle the first cycle with d_obs < 0 (None: centre distances and the 0.5 m test)
+    obs_clearance  True: the static columns by clearance to the level set (needs obs_eps)
     agent_offset, n_all   a shard of a larger team: this batch is rows agent_offset .. agent_offset + A of the
               n_all-row neighbour table that step(exchange) gathers (default: the whole team)
     All tensors are float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
 
     def __init__(self, solver, goal, vref: float = 0.27, phase=None, plans: bool = False, log_x: bool = False, *,
-                 obstacles=None, agent_offset: int = 0, n_all: int | None = None, obs_vel=None, obs_horizon: bool = False):
+                 obstacles=None, agent_offset: int = 0, n_all: int | None = None, obs_vel=None, obs_horizon: bool = False,
+                 obs_eps=None, obs_radius=None, obs_clearance: bool = False):
         import torch
         super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon)
         A, p = self.A, solver.params
+        for name, tab in (("obs_eps", obs_eps), ("obs_radius", obs_radius)):
+            if tab is not None:
+                if self.obstacles is None:
+                    raise ValueError(f"{name} needs obstacles (one entry per obstacle row)")
+                _check_size_array(tab, self.obstacles.shape[0], torch.float64, name, self.device)
+        if obs_clearance and obs_eps is None:
+            raise ValueError("obs_clearance needs obs_eps (the clearance selection reads the level table)")
+        self.obs_eps, self.obs_radius, self.obs_clearance = obs_eps, obs_radius, bool(obs_clearance)
+        self.sized = obs_eps is not None or obs_radius is not None
         self.agent_offset = int(agent_offset)
         self.n_all = A if n_all is None else int(n_all)
         if self.agent_offset < 0 or self.agent_offset + A > self.n_all:
@@ -247,6 +266,9 @@ class Rollout(_RolloutBase):
                    _dptr(m["d_obs"]), _dptr(m["d_agent"]), _dptr(m["min_d_obs"]), _dptr(m["min_d_agent"]),
                    _iptr(m["fail_cycle"]), _dptr(m["distance_to_fail"]))
 
+    def _sizes(self) -> Sizes:
+        return Sizes(_dptr(self.obs_eps), _dptr(self.obs_radius), int(self.obs_clearance))
+
     def step(self, exchange=None, plan_exchange=None, stream=None):
         """One cycle: advance, metrics, solve.  exchange (a dist.NeighbourExchange, or any callable
         [A][4] -> [n_all][4]): the all-gather of the snapshot rows between advance and metrics, for a shard;
@@ -265,13 +287,17 @@ class Rollout(_RolloutBase):
         nbr = self.last_state if exchange is None else exchange(self.last_state)
         import torch
         _check_tensor(nbr, (self.n_all, 4), "the exchanged neighbour table", torch.float64, self.device)
-        _check(lib().srb_sim_metrics_device(s._h, self.A, ctypes.byref(self._sim(nbr)), self.c, s._stream(stream)))
+        if self.obs_radius is not None:
+            _check(lib().srb_sim_metrics_sized_device(s._h, self.A, ctypes.byref(self._sim(nbr)), ctypes.byref(self._sizes()),
+                                                      self.c, s._stream(stream)))
+        else:
+            _check(lib().srb_sim_metrics_device(s._h, self.A, ctypes.byref(self._sim(nbr)), self.c, s._stream(stream)))
         table = None
         if self.plans and self.c > 0:
             table = self.plan_table if plan_exchange is None else plan_exchange(self.plan_table)
         s.solve_device(self.x0, self.ref, self.foot, self.obstacles, nbr, self.out, agent_offset=self.agent_offset,
                        stream=stream, alpha_buf=self.alpha_buf, nbr_plan=table, obs_vel=self.obs_vel,
-                       obs_horizon=self.obs_horizon)
+                       obs_horizon=self.obs_horizon, obs_eps=self.obs_eps, obs_clearance=self.obs_clearance)
         self.c += 1
         self.flushed = False
 
@@ -281,7 +307,11 @@ class Rollout(_RolloutBase):
                   0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                   None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]),
                   None, _dptr(o["alpha"]), None, 0, None, _dptr(o.get("plan")))
-        if self.obs_vel is not None:
+        if self.sized:
+            mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
+            _check(lib().srb_rollout_sized_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), mv,
+                                                  ctypes.byref(self._sizes()), T, s._stream(stream)))
+        elif self.obs_vel is not None:
             _check(lib().srb_rollout_moving_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()),
                                                    ctypes.byref(self._moving()), T, s._stream(stream)))
         else:

@@ -93,6 +93,19 @@ def obstacle_velocities(n_obs: int, seed: int, vmax: float = 1.0):
     return np.stack([sp * np.cos(th), sp * np.sin(th)], 1)
 
 
+EPS_OBS = float(np.float32(1.9))      # srb_params.eps_obs, (double)1.9f: the reference's one obstacle level
+FAIL_RADIUS = 0.5                     # ... and its fail radius (updateDistance_to_fail)
+
+
+def obstacle_sizes(n_obs: int, seed: int):
+    """(eps, radius), each [n_obs], for a table of obstacles of different sizes (BatchSolver.solve(obs_eps=...),
+    Rollout(obs_eps=..., obs_radius=...)), deterministic per seed: the CBF levels eps ~ U[0.6, 3.6] (squared metres)
+    and the body radii 0.5 sqrt(eps / eps_obs), the reference's ratio of fail radius to safety radius.  From a
+    generator of their own (200 + seed), so make_batch, make_scenes and obstacle_velocities draw what they drew."""
+    eps = np.random.default_rng(200 + seed).uniform(0.6, 3.6, n_obs)
+    return eps, FAIL_RADIUS * np.sqrt(eps / EPS_OBS)
+
+
 SCENE_MAX_ATTEMPTS = 1000     # start draws per scene (make_scenes) before the clearance counts as impossible
 
 
