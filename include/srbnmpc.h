@@ -465,7 +465,8 @@ int srb_rollout_moving_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_i
  * srb_select_sized_device: with clearance_selection = 1, tables & 1 is the clearance selection.  The solve entry
  * points run it themselves (SRB_OPT_SELECTION = 1).  srb_sim_metrics_sized_device: srb_sim_metrics_device with
  * obs_radius.  srb_rollout_sized_device: srb_rollout_moving_device's sequence per cycle with the sized metrics, select
- * and solve; the tables do not change over a rollout.  The SRB-12 mode and the MPC_dist shims have no obstacle sizes.
+ * and solve; the tables do not change over a rollout.  The SRB-12 mode takes the same struct through srb12_*_sized*
+ * entry points of its own (below, after the srb12_*_moving block); the MPC_dist shims have no obstacle sizes.
  */
 typedef struct srb_sizes {
     int struct_size;            /* sizeof(srb_sizes) (ABI check) */
@@ -810,6 +811,34 @@ int srb12_solve_batch_moving_device(srb12_ctx *ctx, int n_agents, const srb12_ba
 int srb12_obstacles_advance_device(srb12_ctx *ctx, int n_obs, double *obstacles, const double *obs_vel, void *stream);
 int srb12_rollout_moving_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
                                 const srb12_plans *plans, const srb_moving *mv, int cycles, void *stream);
+
+/*
+ * Obstacle sizes in the SRB-12 mode (DESIGN.md 3 "Obstacle sizes", 10.9): srb_sizes (above), its members with the
+ * meaning they have in the LIP mode.  Each entry point takes what the srb12_*_moving entry point it extends takes
+ * (`plans` and `mv` may be NULL, as there) plus the srb_sizes.  What differs from the LIP block:
+ *   obs_eps     the level of static column j < K_obs of the NLP stage is obs_eps[sel[j]], gathered by the
+ *               srb12_kernel_mv_* instances, which a level table selects even without obs_vel; a column without a row
+ *               keeps eps_obs, the neighbour columns (constant velocity or nbr_plan) keep eps_nbr.
+ *   obs_radius  the metrics are those of srb_sim_metrics_sized_device on the srb12_sim.com rows.
+ *   clearance_selection = 1  srb_knn_obs_clear_kernel (with srb12_ctx_set_scenes its scene form) on the agent's CoM
+ *               row (x0[0], x0[6], x0[1], x0[7]); with mv->horizon_selection = 1 the key's distance is the horizon's
+ *               minimum over this context's N and Ts.  The neighbour columns by the snapshot or by plans, as without.
+ * There is no srb12 select entry point: the solve runs the selection itself.  With sz == NULL, or every member NULL / 0,
+ * each call is the srb12_*_moving entry point it extends (srb12_sim_metrics_sized_device: srb12_sim_metrics_device),
+ * output bits included.  SRB_ERR_ARG, by name and before anything is launched: the refusals of srb_sizes (LIP block),
+ * which need no context, and everything the extended entry point refuses.  srb12_rollout_sized_device: the sequence of
+ * srb12_rollout_moving_device per cycle with the sized metrics, selection and solve; the tables do not change over a
+ * rollout.  host_sz holds host pointers, sz device pointers.
+ */
+int srb12_solve_batch_sized(srb12_ctx *ctx, int n_agents, const srb12_batch *host_io, const srb12_plans *host_plans,
+                            const srb_moving *host_mv, const srb_sizes *host_sz);
+int srb12_solve_batch_sized_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_plans *plans,
+                                   const srb_moving *mv, const srb_sizes *sz, void *stream);
+int srb12_sim_metrics_sized_device(srb12_ctx *ctx, int n_agents, const srb12_sim *sim, const srb_sizes *sz, int cycle,
+                                   void *stream);
+int srb12_rollout_sized_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
+                               const srb12_plans *plans, const srb_moving *mv, const srb_sizes *sz, int cycles,
+                               void *stream);
 
 const char *srb_last_error(void);
 

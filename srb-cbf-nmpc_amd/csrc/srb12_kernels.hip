@@ -224,7 +224,8 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
         const double *__restrict__ obstacles, const double *__restrict__ nbr_state, const int *__restrict__ sel_g,
         double *__restrict__ x_qp_out, double *__restrict__ x_out, double *__restrict__ obj_out,
         int *__restrict__ status_out, int *__restrict__ iters_out, const double *__restrict__ nbr_plan,
-        double *__restrict__ plan_out, const double *__restrict__ obs_vel, double *lds)
+        double *__restrict__ plan_out, const double *__restrict__ obs_vel, const double *__restrict__ obs_eps,
+        double *lds)
 {
     const int tid = threadIdx.x, lane = tid;
     const int N = NC > 0 ? NC : prm.N, K = K1 > 0 ? K1 - 1 : prm.K_obs + prm.K_nbr;
@@ -324,6 +325,14 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
                 L.obs[2 * e + 1] = obstacles[2 * bj + 1] + obs_vel[2 * bj + 1] * tt;
             }
         }
+    }
+    // obstacle sizes (srb_sizes.obs_eps; the srb12_kernel_mv_* instances only, a kernel argument: the branch is
+    // wave-uniform, and obs_vel may be null beside it: sizes on static obstacles): the level of static column j is the
+    // table's row sel[j], a plain load.  L.eps[tid] is rewritten by the lane that wrote it in the arm above, and L.sel is
+    // behind the prologue's barrier, so no barrier stands between the two; a column without a row (-1) keeps eps_obs,
+    // the neighbour columns keep eps_nbr.  With scenes sel holds global rows.  The QP-only solve never reads the table.
+    if (MV && obs_eps && prm.use_nlp) {
+        if (tid < prm.K_obs && L.sel[tid] >= 0) L.eps[tid] = obs_eps[L.sel[tid]];
     }
     // start: gravity-compensating forces on the stance legs, the dynamics rolled out, s = 0
     for (int e = tid; e < 12 * N; e += 64) {
@@ -1452,13 +1461,14 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         srb12_agent<TL, TO, NC, K1, 0>(prm, agent, x0g, xrefg, footg, contactg, obstacles, nbr_state, sel_g, x_qp_out,  \
-                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, nullptr, lds);          \
+                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, nullptr, nullptr, lds); \
     }
 SRB12_INSTANCES(SRB12_KERNEL)
 #endif
 #if defined(SRB12_MOVING) || defined(SRB12_ALL)
-// The moving-obstacle instances (srb_moving.obs_vel; MV = 1), srb12_kernel_mv_*: the same kernels with the velocity
-// table as one more argument and the moving arm of the prologue compiled in.  In the product a code object of their own
+// The obstacle-table instances (srb_moving.obs_vel, srb_sizes.obs_eps; MV = 1), srb12_kernel_mv_*: the same kernels with
+// the velocity table and the level table as two more arguments (either may be null) and the arms of the prologue that
+// read them compiled in.  In the product a code object of their own
 // (this file compiled a second time under -DSRB12_MOVING, which emits only them), so the default instances keep their argument
 // list and their code: the LIP mode measured the extra argument alone at +0.5 % of its step.
 #define SRB12_KERNEL_MV(TL, TO, NC, K1)                                                                         \
@@ -1468,13 +1478,13 @@ SRB12_INSTANCES(SRB12_KERNEL)
         const double *__restrict__ nbr_state, const int *__restrict__ sel_g, double *__restrict__ x_qp_out,      \
         double *__restrict__ x_out, double *__restrict__ obj_out, int *__restrict__ status_out,                \
         int *__restrict__ iters_out, const double *__restrict__ nbr_plan, double *__restrict__ plan_out,       \
-        const double *__restrict__ obs_vel)                                                                    \
+        const double *__restrict__ obs_vel, const double *__restrict__ obs_eps)                                \
     {                                                                                                          \
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         srb12_agent<TL, TO, NC, K1, 1>(prm, agent, x0g, xrefg, footg, contactg, obstacles, nbr_state, sel_g, x_qp_out,  \
-                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, obs_vel, lds);          \
+                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, obs_vel, obs_eps, lds); \
     }
 SRB12_INSTANCES(SRB12_KERNEL_MV)
 #endif

@@ -974,9 +974,9 @@ static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
     return SRB_OK;
 }
 
-int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s)
+int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s, const double *radius)
 {
-    return launch_metrics(c, n_agents, d, cycle, s);
+    return launch_metrics(c, n_agents, d, cycle, s, radius);
 }
 
 static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream, bool advance,

@@ -22,10 +22,12 @@ int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s);
 // ... and its scene partition (srb_ctx_set_scenes): the per-call refusals, the "up to K nearest" clamp, and the
 // metrics launch (srb_sim_metrics_kernel, or with scenes srb_sim_scene_metrics_kernel) on d->state rows
-// [x, xdot, y, ydot] -- launches only, the caller orders the stream
+// [x, xdot, y, ydot] -- launches only, the caller orders the stream.  radius [n_obs] != NULL: srb_sizes.obs_radius, the
+// sized kernels of srb_sizes.hip
 int srb_internal_check_scenes(const srb_ctx *c, int n_agents, int n_obs, bool has_nbr, int n_all, int agent_offset);
 void srb_internal_clamp_K(const srb_ctx *c, int n_obs, bool has_nbr, int n_all, int *Ko, int *Kn);
-int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s);
+int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s,
+                             const double *radius = nullptr);
 
 // a failed HIP call returns SRB_ERR_HIP with "<expression>: <HIP's message>"; HIPCHK_UNWIND_ first runs `cleanup`
 // (a create function's local CREATE_CHK names its destroy there once).  `text`: the expression stringified by the

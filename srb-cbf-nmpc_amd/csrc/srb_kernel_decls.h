@@ -163,13 +163,14 @@ extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDe
         const double *nbr_plan, double *plan_out);
 SRB12_INSTANCES(SRB_DECL12)
 #undef SRB_DECL12
-// the moving-obstacle instances (srb12_kernels.hip under -DSRB12_MOVING): the velocity table as one more argument
+// the obstacle-table instances (srb12_kernels.hip under -DSRB12_MOVING): two more arguments, the velocity table of
+// srb_moving and the level table of srb_sizes (either may be null)
 #define SRB_DECL12_MV(TL, TO, NC, K1)                                                                          \
     extern "C" __global__ void srb12_kernel_mv_##TL##_##TO##_##NC##_##K1(                                    \
         Srb12KParams prm, int n_agents, const double *x0g, const double *xrefg, const double *footg,           \
         const int *contactg, const double *obstacles, const double *nbr_state, const int *sel_g,              \
         double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
-        const double *nbr_plan, double *plan_out, const double *obs_vel);
+        const double *nbr_plan, double *plan_out, const double *obs_vel, const double *obs_eps);
 SRB12_INSTANCES(SRB_DECL12_MV)
 #undef SRB_DECL12_MV
 extern "C" __global__ void srb12_pos_kernel(int n_agents, const double *x0g, double *pos);

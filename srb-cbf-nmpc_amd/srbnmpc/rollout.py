@@ -21,12 +21,14 @@ rollout then works on its own copy of `obstacles`; results()["obstacles"] is the
 With obs_eps ([n_obs], squared metres) every obstacle row has its own CBF level in the solve, with obs_clearance the
 static columns are selected by clearance to the level set, and with obs_radius ([n_obs], m) d_obs is the clearance to
 the obstacle bodies, min_i (dist_i - obs_radius[i]), and fail_cycle the first cycle with d_obs < 0 (srb_sizes,
-srb_rollout_sized_device).  The tables do not change over a rollout.  LIP mode only.
+srb_rollout_sized_device; srb12.Rollout12 likewise, srb12_rollout_sized_device).  The tables do not change over a
+rollout.
 
-_RolloutBase is what this class and srb12.Rollout12 share: the checks of goal / phase / obstacles / obs_vel, the moving
-table's clone and its restore, the solve, metrics and log buffers, reset / advance / results / scene_results and the
-preconditions of run().  A mode adds its state width, its own buffers, its srb_sim (_sim), step() and the driver
-call of run() (_drive); the entry points are the solver's own (its _entry).
+_RolloutBase is what this class and srb12.Rollout12 share: the checks of goal / phase / obstacles / obs_vel and of the
+size tables, the moving table's clone and its restore, the srb_moving and srb_sizes of a call, the metrics call, the
+solve, metrics and log buffers, reset / advance / results / scene_results and the preconditions of run().  A mode
+adds its state width, its own buffers, its srb_sim (_sim), step() and the driver call of run() (_drive); the entry
+points are the solver's own (its _entry).
 """
 from __future__ import annotations
 
@@ -51,7 +53,8 @@ class _RolloutBase:
     _name = "Rollout"                    # the class, in messages
     sharded = False                      # a shard of a larger team (Rollout only)
 
-    def __init__(self, solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon):
+    def __init__(self, solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps=None,
+                 obs_radius=None, obs_clearance=False):
         import torch
         self.solver = solver
         p = solver.params
@@ -81,6 +84,15 @@ class _RolloutBase:
         elif obs_horizon:
             raise ValueError("obs_horizon needs obs_vel (the horizon-aware obstacle selection reads the velocities)")
         self.obs_vel, self.obs_horizon = obs_vel, bool(obs_horizon)
+        for name, tab in (("obs_eps", obs_eps), ("obs_radius", obs_radius)):
+            if tab is not None:
+                if obstacles is None:
+                    raise ValueError(f"{name} needs obstacles (one entry per obstacle row)")
+                _check_size_array(tab, obstacles.shape[0], torch.float64, name, self.device)
+        if obs_clearance and obs_eps is None:
+            raise ValueError("obs_clearance needs obs_eps (the clearance selection reads the level table)")
+        self.obs_eps, self.obs_radius, self.obs_clearance = obs_eps, obs_radius, bool(obs_clearance)
+        self.sized = obs_eps is not None or obs_radius is not None     # run(): the _sized driver
         self.goal, self.phase, self.obstacles = goal, phase, obstacles
         self.vref, self.plans, self.log_x = float(vref), bool(plans), bool(log_x)
         N, nx = p.N, self._nx
@@ -126,6 +138,18 @@ class _RolloutBase:
 
     def _moving(self) -> Moving:
         return Moving(_dptr(self.obs_vel), int(self.obs_horizon), _dptr(self.obstacles))
+
+    def _sizes(self) -> Sizes:
+        return Sizes(_dptr(self.obs_eps), _dptr(self.obs_radius), int(self.obs_clearance))
+
+    def _metrics(self, sim, stream):
+        """The metrics of the current cycle on `sim` (the mode's srb_sim): with obs_radius the sized entry point."""
+        s = self.solver
+        if self.obs_radius is not None:
+            _check(s._entry("sim_metrics_sized_device")(s._h, self.A, ctypes.byref(sim), ctypes.byref(self._sizes()),
+                                                        self.c, s._stream(stream)))
+        else:
+            _check(s._entry("sim_metrics_device")(s._h, self.A, ctypes.byref(sim), self.c, s._stream(stream)))
 
     # ------------------------------------------------------------------ driving
     def reset(self, state):
@@ -232,17 +256,9 @@ class Rollout(_RolloutBase):
                  obstacles=None, agent_offset: int = 0, n_all: int | None = None, obs_vel=None, obs_horizon: bool = False,
                  obs_eps=None, obs_radius=None, obs_clearance: bool = False):
         import torch
-        super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon)
+        super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps, obs_radius,
+                         obs_clearance)
         A, p = self.A, solver.params
-        for name, tab in (("obs_eps", obs_eps), ("obs_radius", obs_radius)):
-            if tab is not None:
-                if self.obstacles is None:
-                    raise ValueError(f"{name} needs obstacles (one entry per obstacle row)")
-                _check_size_array(tab, self.obstacles.shape[0], torch.float64, name, self.device)
-        if obs_clearance and obs_eps is None:
-            raise ValueError("obs_clearance needs obs_eps (the clearance selection reads the level table)")
-        self.obs_eps, self.obs_radius, self.obs_clearance = obs_eps, obs_radius, bool(obs_clearance)
-        self.sized = obs_eps is not None or obs_radius is not None
         self.agent_offset = int(agent_offset)
         self.n_all = A if n_all is None else int(n_all)
         if self.agent_offset < 0 or self.agent_offset + A > self.n_all:
@@ -266,9 +282,6 @@ class Rollout(_RolloutBase):
                    _dptr(m["d_obs"]), _dptr(m["d_agent"]), _dptr(m["min_d_obs"]), _dptr(m["min_d_agent"]),
                    _iptr(m["fail_cycle"]), _dptr(m["distance_to_fail"]))
 
-    def _sizes(self) -> Sizes:
-        return Sizes(_dptr(self.obs_eps), _dptr(self.obs_radius), int(self.obs_clearance))
-
     def step(self, exchange=None, plan_exchange=None, stream=None):
         """One cycle: advance, metrics, solve.  exchange (a dist.NeighbourExchange, or any callable
         [A][4] -> [n_all][4]): the all-gather of the snapshot rows between advance and metrics, for a shard;
@@ -287,11 +300,7 @@ class Rollout(_RolloutBase):
         nbr = self.last_state if exchange is None else exchange(self.last_state)
         import torch
         _check_tensor(nbr, (self.n_all, 4), "the exchanged neighbour table", torch.float64, self.device)
-        if self.obs_radius is not None:
-            _check(lib().srb_sim_metrics_sized_device(s._h, self.A, ctypes.byref(self._sim(nbr)), ctypes.byref(self._sizes()),
-                                                      self.c, s._stream(stream)))
-        else:
-            _check(lib().srb_sim_metrics_device(s._h, self.A, ctypes.byref(self._sim(nbr)), self.c, s._stream(stream)))
+        self._metrics(self._sim(nbr), stream)
         table = None
         if self.plans and self.c > 0:
             table = self.plan_table if plan_exchange is None else plan_exchange(self.plan_table)

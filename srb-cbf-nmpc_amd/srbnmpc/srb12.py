@@ -12,11 +12,14 @@ device (csrc/srb12_sim.hip, srb12_rollout_device; DESIGN.md sections 9 and 10.4)
 srb12_plans): Solver12.solve / solve_device take nbr_plan and return plan, Solver12.solve_coupled_device is the
 Jacobi driver over the plans, and Rollout12(plans=True) feeds last cycle's plans forward.  Moving
 obstacles (srb_moving): obs_vel / obs_horizon on Solver12.solve, solve_device, solve_coupled_device
-and Rollout12, Solver12.advance_obstacles_device; velocities from workload.obstacle_velocities.
+and Rollout12, Solver12.advance_obstacles_device; velocities from workload.obstacle_velocities.  Obstacle sizes
+(srb_sizes): obs_eps / obs_clearance on the same three solver calls, obs_eps / obs_radius /
+obs_clearance on Rollout12; tables from workload.obstacle_sizes.
 
 The host layer of these features is written once for both modes: Solver12 is a _SolverBase (srbnmpc/__init__.py: the
 context's life, _stream, set_scenes, the Jacobi loop), Rollout12 a rollout._RolloutBase (the checks, buffers, logs,
-reset / advance / run / results), and the pointer casts, the (Ko, Kn) clamp and the srb_moving checks are the package's.
+reset / advance / run / results, the size tables' checks and the metrics call), and the pointer casts, the (Ko, Kn)
+clamp and the srb_moving / srb_sizes checks are the package's.
 """
 from __future__ import annotations
 
@@ -24,8 +27,8 @@ import ctypes
 
 import numpy as np
 
-from . import (Moving, _SolverBase, _check, _check_plan_array, _check_vel_array, _clamp_selected, _dp, _dptr, _ip, _iptr,
-               _moving_args, _p, lib, workload)
+from . import (Moving, Sizes, _SolverBase, _check, _check_plan_array, _check_vel_array, _clamp_selected, _dp, _dptr, _ip,
+               _iptr, _moving_args, _p, _sizes_args, lib, workload)
 from .rollout import _RolloutBase
 
 _p12_fields = [("N", ctypes.c_int), ("K_obs", ctypes.c_int), ("K_nbr", ctypes.c_int),
@@ -125,6 +128,12 @@ def _lib():
         L.srb12_rollout_moving_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch12),
                                                   ctypes.POINTER(Sim12), ctypes.POINTER(Plans12), ctypes.POINTER(Moving),
                                                   ctypes.c_int, ctypes.c_void_p]
+        B, S, PL, MV, SZ = (ctypes.POINTER(t) for t in (Batch12, Sim12, Plans12, Moving, Sizes))
+        L.srb12_solve_batch_sized.argtypes = [ctypes.c_void_p, ctypes.c_int, B, PL, MV, SZ]
+        L.srb12_solve_batch_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, PL, MV, SZ, ctypes.c_void_p]
+        L.srb12_sim_metrics_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, S, SZ, ctypes.c_int, ctypes.c_void_p]
+        L.srb12_rollout_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, S, PL, MV, SZ, ctypes.c_int,
+                                                 ctypes.c_void_p]
         _bound = True
     return L
 
@@ -153,14 +162,18 @@ class Solver12(_SolverBase):
     _lib = staticmethod(_lib)
 
     def solve(self, x0, xref, foot, contact, obstacles=None, nbr_state=None, agent_offset: int = 0, nbr_plan=None,
-              plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False):
+              plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
+              obs_clearance: bool = False):
         """Host numpy: x0 [A,12], xref [A,N,12], foot [A,N,4,3], contact [A,N,4] int.  Returns
         dict x_qp, x [A, 24N+1], obj, status [A,2], iters [A,2], sel [A, Ko+Kn], plan [A,N,2] (the (x, y) of
         X at every grid).  nbr_plan ([n_all][N][2], float64, C-contiguous) makes the neighbour rows follow the
         neighbours' plans instead of the constant-velocity guess; plan_selection selects the neighbours by
         closest predicted approach over the horizon (needs nbr_plan).  obs_vel ([n_obs][2], float64, C-contiguous): the
         obstacles move at these velocities over the horizon (srb12_solve_batch_moving); obs_horizon=True additionally
-        selects the static columns by closest predicted approach (needs obs_vel)."""
+        selects the static columns by closest predicted approach (needs obs_vel).  obs_eps ([n_obs], float64,
+        C-contiguous): the CBF level of each obstacle row in squared metres, the unit of eps_obs
+        (srb12_solve_batch_sized); obs_clearance=True additionally selects the static columns by clearance to the level
+        set (needs obs_eps)."""
         p = self.params
         x0 = np.ascontiguousarray(x0, np.float64); A = x0.shape[0]
         xref = np.ascontiguousarray(xref, np.float64); foot = np.ascontiguousarray(foot, np.float64)
@@ -180,8 +193,14 @@ class Solver12(_SolverBase):
             _check_plan_array(nbr_plan, (nb.shape[0] if nb is not None else len(nbr_plan), p.N, 2), "nbr_plan", np.float64)
         out["plan"] = np.zeros((A, p.N, 2))
         pl = Plans12(_p(nbr_plan) if nbr_plan is not None else None, _p(out["plan"]), 1 if plan_selection else 0, None)
-        if obs_vel is not None or obs_horizon:
-            mv = _moving_args(obs_vel, obs_horizon, ob.shape[0], np.float64, _p, p.use_nlp)
+        moving = obs_vel is not None or obs_horizon
+        mv = _moving_args(obs_vel, obs_horizon, ob.shape[0], np.float64, _p, p.use_nlp) if moving else None
+        if obs_eps is not None or obs_clearance:
+            sz = _sizes_args(obs_eps, None, obs_clearance, ob.shape[0], np.float64, _p, p.use_nlp)
+            _check(_lib().srb12_solve_batch_sized(self._h, A, ctypes.byref(b), ctypes.byref(pl),
+                                                  ctypes.byref(mv) if moving else None, ctypes.byref(sz)))
+            return out
+        if moving:
             _check(_lib().srb12_solve_batch_moving(self._h, A, ctypes.byref(b), ctypes.byref(pl), ctypes.byref(mv)))
             return out
         _check(_lib().srb12_solve_batch_plans(self._h, A, ctypes.byref(b), ctypes.byref(pl)))
@@ -189,14 +208,17 @@ class Solver12(_SolverBase):
 
     def solve_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, agent_offset: int = 0, stream=None,
                      obstacles_version: int = 0, nbr_plan=None, plan_selection: bool = False, plan=None, obs_vel=None,
-                     obs_horizon: bool = False):
+                     obs_horizon: bool = False, obs_eps=None, obs_clearance: bool = False):
         """torch tensors on this device (float64 / int32), contiguous; out holds x_qp (or None), x, obj,
         status, iters and optionally sel [A, Ko+Kn] and plan [A, N, 2] (written when the key is present; the
         `plan` argument overrides it).  nbr_plan ([n_all][N][2] float64, contiguous): the neighbours' plans for the
         inter-agent rows (None: constant velocity), must not overlap plan; plan_selection: the neighbours by
         closest predicted approach (needs nbr_plan).  obs_vel ([n_obs][2] float64, contiguous): the obstacles'
         velocities (srb12_solve_batch_moving_device; needs obstacles_version 0); obs_horizon=True selects the static
-        columns by closest predicted approach (needs obs_vel).  Asynchronous on `stream` (default: torch's current)."""
+        columns by closest predicted approach (needs obs_vel).  obs_eps ([n_obs] float64, contiguous): the CBF level of
+        each obstacle row (srb12_solve_batch_sized_device; goes together with obstacles_version); obs_clearance=True
+        selects the static columns by clearance to the level set (needs obs_eps).  Asynchronous on `stream` (default:
+        torch's current)."""
         A = x0.shape[0]
         import torch
         Ko, Kn = n_selected(self.params, 0 if obstacles is None else obstacles.shape[0],
@@ -220,9 +242,17 @@ class Solver12(_SolverBase):
         if plan is not None:
             _check_plan_array(plan, (A, N, 2), "plan", torch.float64)
         no_plans = nbr_plan is None and plan is None and not plan_selection
-        if obs_vel is not None or obs_horizon:
-            mv = _moving_args(obs_vel, obs_horizon, 0 if obstacles is None else obstacles.shape[0], torch.float64, _dptr,
-                              self.params.use_nlp)
+        n_obs = 0 if obstacles is None else obstacles.shape[0]
+        moving = obs_vel is not None or obs_horizon
+        mv = _moving_args(obs_vel, obs_horizon, n_obs, torch.float64, _dptr, self.params.use_nlp) if moving else None
+        if obs_eps is not None or obs_clearance:
+            sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch.float64, _dptr, self.params.use_nlp, device=x0.device)
+            pl = None if no_plans else ctypes.byref(Plans12(_dptr(nbr_plan), _dptr(plan), 1 if plan_selection else 0, None))
+            _check(_lib().srb12_solve_batch_sized_device(self._h, A, ctypes.byref(b), pl,
+                                                         ctypes.byref(mv) if moving else None, ctypes.byref(sz),
+                                                         self._stream(stream)))
+            return
+        if moving:
             pl = None if no_plans else ctypes.byref(Plans12(_dptr(nbr_plan), _dptr(plan), 1 if plan_selection else 0, None))
             _check(_lib().srb12_solve_batch_moving_device(self._h, A, ctypes.byref(b), pl, ctypes.byref(mv),
                                                           self._stream(stream)))
@@ -253,7 +283,8 @@ class Solver12(_SolverBase):
 
     def solve_coupled_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, outer: int = 2, exchange=None,
                              nbr_plan=None, agent_offset: int = 0, stream=None, obstacles_version: int = 0,
-                             plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False):
+                             plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
+                             obs_clearance: bool = False):
         """Jacobi iteration over the agents' plans (BatchSolver.solve_coupled_device for the 12-state body):
         `outer` solves of the same cycle, each against the plans the agents wrote in the round before.  Round 0
         solves against nbr_plan (None: the constant-velocity rows); every later round r reads table =
@@ -261,12 +292,13 @@ class Solver12(_SolverBase):
         team, agent_offset 0) that plan tensor itself.  The plans ping-pong between out["plan"] ([A][N][2],
         required) and a second buffer of this solver; the last round's results are in `out`.  Returns
         plan_change, a device tensor [outer - 1]: max |plan_r - plan_{r-1}| per round (torch reductions; nothing
-        synchronises with the host inside the loop).  plan_selection applies to every round that has a table; obs_vel
-        and obs_horizon as solve_device (every round solves against the same moving table)."""
+        synchronises with the host inside the loop).  plan_selection applies to every round that has a table; obs_vel,
+        obs_horizon, obs_eps and obs_clearance as solve_device (every round solves against the same obstacle tables)."""
         return self._solve_coupled((x0, xref, foot, contact, obstacles, nbr_state, out), outer, exchange, nbr_plan,
                                    agent_offset, stream,
                                    lambda table: {"plan_selection": plan_selection and table is not None},
-                                   obstacles_version=obstacles_version, obs_vel=obs_vel, obs_horizon=obs_horizon)
+                                   obstacles_version=obstacles_version, obs_vel=obs_vel, obs_horizon=obs_horizon,
+                                   obs_eps=obs_eps, obs_clearance=obs_clearance)
 
     def last_kernel_ms(self):
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -314,6 +346,11 @@ class Rollout12(_RolloutBase):
                 table: from the second cycle on by obs_vel * (Ts * 4) before the metrics), reset() restores the clone,
                 results()["obstacles"] is the current table; run() is srb12_rollout_moving_device
     obs_horizon True: the static columns by closest predicted approach over the horizon (needs obs_vel)
+    obs_eps     [n_obs] or None: the CBF level of each obstacle row, squared metres (None: eps_obs for every row)
+    obs_radius  [n_obs] or None: the body radius (m) of each obstacle row: d_obs is then min_i (dist_i - obs_radius[i])
+                on the CoM rows and fail_cycle the first cycle with d_obs < 0 (None: centre distances and the 0.5 m test)
+    obs_clearance  True: the static columns by clearance to the level set (needs obs_eps).  With any of the three run()
+                is srb12_rollout_sized_device; the tables do not change over a rollout
     A whole team on one GPU (the SRB-12 mode has no sharded stepping).  All tensors are
     float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
     _nx = 12
@@ -321,11 +358,13 @@ class Rollout12(_RolloutBase):
 
     def __init__(self, solver, goal, vref: float = 0.27, phase=None, gait: str = "trot", log_x: bool = False,
                  obstacles=None, hcom: float = workload.HCOM12, yaw_step: float = 0.1, hold_radius: float = 0.05,
-                 plans: bool = False, plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False):
+                 plans: bool = False, plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False,
+                 obs_eps=None, obs_radius=None, obs_clearance: bool = False):
         import torch
         if gait not in GAITS:
             raise ValueError(f"gait must be one of {sorted(GAITS)}, got {gait!r}")
-        super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon)
+        super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps, obs_radius,
+                         obs_clearance)
         self.gait, self.hcom = gait, float(hcom)
         self.plan_selection = bool(plan_selection)
         if self.plan_selection and not self.plans:
@@ -358,11 +397,12 @@ class Rollout12(_RolloutBase):
         self.advance(stream)
         if self.obs_vel is not None and self.c > 0:          # the obstacles' cycle, before the metrics read the table
             s.advance_obstacles_device(self.obstacles, self.obs_vel, stream)
-        _check(_lib().srb12_sim_metrics_device(s._h, self.A, ctypes.byref(self._sim()), self.c, s._stream(stream)))
+        self._metrics(self._sim(), stream)
         table = self.plan_table if self.plans and self.c > 0 else None
         s.solve_device(self.x0, self.xref, self.foot, self.contact, self.obstacles, self.last_state, self.out,
                        stream=stream, nbr_plan=table, plan_selection=self.plan_selection and table is not None,
-                       obs_vel=self.obs_vel, obs_horizon=self.obs_horizon)
+                       obs_vel=self.obs_vel, obs_horizon=self.obs_horizon, obs_eps=self.obs_eps,
+                       obs_clearance=self.obs_clearance)
         if self.plans:
             s.shift_plans_device(self.out["plan"], self.plan_table, SHIFT_GRIDS, stream=stream)
         self.c += 1
@@ -373,16 +413,19 @@ class Rollout12(_RolloutBase):
         b = Batch12(None, None, None, None, _dptr(self.obstacles), None,
                     0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                     None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]), None, 0)
-        if self.obs_vel is not None:
-            pl = None
-            if self.plans:
-                pl = ctypes.byref(Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table)))
+        pl = None
+        if self.plans:
+            pl = ctypes.byref(Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table)))
+        if self.sized:
+            mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
+            _check(_lib().srb12_rollout_sized_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl, mv,
+                                                     ctypes.byref(self._sizes()), T, s._stream(stream)))
+        elif self.obs_vel is not None:
             _check(_lib().srb12_rollout_moving_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl,
                                                       ctypes.byref(self._moving()), T, s._stream(stream)))
         elif self.plans:
-            pl = Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table))
-            _check(_lib().srb12_rollout_plans_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()),
-                                                     ctypes.byref(pl), T, s._stream(stream)))
+            _check(_lib().srb12_rollout_plans_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl, T,
+                                                     s._stream(stream)))
         else:
             _check(_lib().srb12_rollout_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), T,
                                                s._stream(stream)))
