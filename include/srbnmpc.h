@@ -486,6 +486,68 @@ int srb_rollout_sized_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io
                              const srb_moving *mv, const srb_sizes *sz, int cycles, void *stream);
 
 /*
+ * Agent sizes (LIP mode; DESIGN.md 3 "Agent sizes", 10.10): an optional safety radius, pad and body radius per agent,
+ * so that a mixed team (large carriers among small scouts) need not inflate every pair to the largest.  As with
+ * srb_sizes, SRB_ABI_VERSION and the layouts of srb_batch, srb_sim, srb_moving and srb_sizes stay: the tables travel
+ * in a struct of their own through entry points of their own, each of which takes the srb_moving and srb_sizes of
+ * the _sized entry point it extends (both may be NULL) and otherwise behaves as that entry point.  Every table has
+ * n_all rows in the row order of nbr_state (scene-major with scenes); global agent g = agent_offset + a owns row g.
+ * The tables are read through sel and at row g only.  All arithmetic is fp64, uncontracted.
+ *   agent_rad  [n_all]      in: safety radius (m).  The level of neighbour column j (K_obs <= j < K, sel[j] >= 0) is
+ *                           s * s with s = agent_rad[g] + agent_rad[sel[j]] (one rounded add, one rounded multiply);
+ *                           a -1 column keeps eps_nbr.  NULL: eps_nbr for every neighbour column.
+ *   agent_pad  [n_all]      in: metres added to the safety radius of every static column of agent g: the level of
+ *                           column j < K_obs becomes t * t with t = sqrt(e_j) + agent_pad[g], e_j the level the column
+ *                           has after the obs_eps gather (eps_obs, or obs_eps[sel[j]]); sqrt correctly rounded.
+ *                           May be negative.  NULL: the levels as they are.
+ *   agent_body [n_all]      in: body radius (m), metrics only: d_agent is then
+ *                           min over i != g of (sqrt(d2_i) - (agent_body[g] + agent_body[i])), d2_i the squared centre
+ *                           distance of the metrics, the sum of the radii one rounded add; a NaN term never wins; a
+ *                           table without another row gives +inf.  min_d_agent follows as ever.  A uniform table b
+ *                           gives srb_sim's d_agent - (b + b) bit for bit.  The obstacle half (d_obs, fail_cycle,
+ *                           distance_to_fail) is srb_sizes.obs_radius's when that table is given, else srb_sim's, and
+ *                           does not look at agent bodies.  NULL: the metrics of the _sized call.
+ *   clearance_selection     0: the K_nbr neighbour columns as ever (nearest centres now, or with
+ *                           SRB_OPT_PLAN_SELECTION = 1 the closest predicted approach);
+ *                           1: by clearance (srb_knn_nbr_clear_kernel): the key of row i is dist_i - agent_rad[i]
+ *                           (the agent's own radius shifts every key alike and is left out), dist_i the snapshot
+ *                           distance sqrt(dx*dx + dy*dy) -- or, with SRB_OPT_PLAN_SELECTION = 1 and a plan table,
+ *                           sqrt(m), m the horizon-aware selection's minimum over the N + 1 pairs.  Keys may be
+ *                           negative.  Order by key, lower index on ties; a NaN key is never selected; row g is left
+ *                           out; a slot with no row left gets -1 (no 1000 m rule).  One workgroup per agent, brute
+ *                           force: no selection grid is built or consulted.  The static columns are selected as
+ *                           ever (centres, horizon or obstacle clearance).  Needs agent_rad.
+ *   collide_cycle [A]       out, optional: the first cycle with d_agent < 0, else -1; set by the call with
+ *                           cycle == c_first and never overwritten once set (fail_cycle's rules).  Needs agent_body.
+ * With ag == NULL, or every member NULL / 0, each entry point is the _sized entry point it extends, output bits
+ * included.  SRB_ERR_ARG, by name and before anything is launched: a wrong struct_size; clearance_selection other than
+ * 0 or 1; clearance_selection = 1 without agent_rad; agent_rad or agent_body with a batch that has no neighbour table;
+ * collide_cycle without agent_body.  The QP-only solve ignores the tables.  host_ag holds host pointers (agent_rad and
+ * agent_pad are staged; agent_body and collide_cycle are not read by a solve), ag device pointers.
+ * srb_rollout_agents_device refuses a shard, as srb_rollout_device does; the tables do not change over a rollout.
+ * The SRB-12 mode and the MPC_dist shims have no agent sizes.
+ */
+typedef struct srb_agent_sizes {
+    int struct_size;            /* sizeof(srb_agent_sizes) (ABI check) */
+    const double *agent_rad;    /* [n_all] safety radius (m) of table row i (the row order of nbr_state) */
+    const double *agent_pad;    /* [n_all] metres added to the safety radius of every static column of agent i */
+    const double *agent_body;   /* [n_all] body radius (m), metrics only */
+    int clearance_selection;    /* 0: neighbour columns as ever; 1: by clearance (needs agent_rad) */
+    int *collide_cycle;         /* [A] out, optional, metrics / rollout only */
+} srb_agent_sizes;
+int srb_solve_batch_agents(srb_ctx *ctx, int n_agents, const srb_batch *host_io, const srb_moving *host_mv,
+                           const srb_sizes *host_sz, const srb_agent_sizes *host_ag);
+int srb_solve_batch_agents_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
+                                  const srb_sizes *sz, const srb_agent_sizes *ag, void *stream);
+int srb_select_agents_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
+                             const srb_sizes *sz, const srb_agent_sizes *ag, int tables, void *stream);
+int srb_sim_metrics_agents_device(srb_ctx *ctx, int n_agents, const srb_sim *sim, const srb_sizes *sz,
+                                  const srb_agent_sizes *ag, int cycle, void *stream);
+int srb_rollout_agents_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_sim *sim,
+                              const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag, int cycles,
+                              void *stream);
+
+/*
  * HL reference planner (generateReferenceTrajectory, MPC_dist.cpp:930-1104; SURVEY.md 8(f)
  * row 3) on HIP device `device`, host buffers, synchronous.  NA agents (1..2^20; up to 1024 in
  * one persistent workgroup, more -- one coupled swarm -- as one launch per step) starting at

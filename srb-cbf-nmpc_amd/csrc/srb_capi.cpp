@@ -22,15 +22,17 @@ typedef void (*srb_kernel_fn)(SrbKParams, int, const double *, const double *, c
 typedef void (*srb_polish_fn)(SrbKParams, int, const double *, const double *, const double *, const double *,
                               const double *, double *, double *, int *, const double *, double *, const int *,
                               const float *, int, const double *, double *);
-// the obstacle-table instances (srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*): two more arguments, the velocity table
-// of srb_moving and the level table of srb_sizes (either may be null)
+// the table instances (srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*): further arguments, the velocity table of
+// srb_moving, the level table of srb_sizes and the radius and pad tables of srb_agent_sizes (each may be null); the
+// polish kernel also the agent_offset of the agent tables' own row
 typedef void (*srb_kernel_mv_fn)(SrbKParams, int, const double *, const double *, const double *, const double *, int,
                                  const double *, int, int, double *, double *, double *, int *, int *, const double *,
                                  double *, const int *, float *, int, const double *, double *, const double *,
-                                 const double *);
+                                 const double *, const double *, const double *);
 typedef void (*srb_polish_mv_fn)(SrbKParams, int, const double *, const double *, const double *, const double *,
                                  const double *, double *, double *, int *, const double *, double *, const int *,
-                                 const float *, int, const double *, double *, const double *, const double *);
+                                 const float *, int, const double *, double *, const double *, const double *,
+                                 const double *, const double *, int);
 struct srb_instance { int nzl, ts, nw, nc, cc, kc; srb_kernel_fn fn; srb_polish_fn polish; srb_kernel_mv_fn fn_mv; srb_polish_mv_fn polish_mv; };
 // solve kernel (INFIX empty, or f32_) and polish kernel of one instance, then their moving-obstacle instances
 #define ENTRY_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC) NZL, TS, NW, NC, CC, KC, srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
@@ -113,6 +115,8 @@ struct srb_ctx {
     size_t cap_vel;
     double *obs_eps;               // staged obstacle levels (srb_solve_batch_sized)
     size_t cap_eps;
+    double *agent_rad, *agent_pad; // staged agent tables (srb_solve_batch_agents)
+    size_t cap_rad, cap_pad;
     float knn_ms, solve_ms;
     bool timed;
     int last_nw;
@@ -327,7 +331,8 @@ extern "C" int srb_ctx_destroy(srb_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->order.wait_idle();                         // the last launch may be on another stream
     void *bufs[] = {c->x0, c->ref, c->foot, c->x_qp, c->x, c->obj, c->status, c->iters, c->obstacles, c->nbr,
-                    c->abuf, c->alpha, c->sel, c->zpol, c->nbr_plan, c->plan, c->obs_vel, c->obs_eps};
+                    c->abuf, c->alpha, c->sel, c->zpol, c->nbr_plan, c->plan, c->obs_vel, c->obs_eps,
+                    c->agent_rad, c->agent_pad};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (auto &g : c->grid)
@@ -460,27 +465,40 @@ static int launch_obs_horizon(srb_ctx *c, int n_agents, const double *x0, const 
 static int launch_obs_clear(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
                             const double *obs_eps, int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride,
                             hipStream_t s, int N, double Ts);
+static int launch_nbr_clear(srb_ctx *c, int n_agents, const double *x0, const double *nbr_state, const double *nbr_plan,
+                            const double *agent_rad, int n_all, int agent_offset, int K_nbr, int *sel, int sel_stride,
+                            hipStream_t s, int N);
 
 // The selection of a solve, both modes.  obs_vel with obs_horizon (srb_moving.horizon_selection): the static columns by
 // closest predicted approach over the caller's grid (N, Ts), the neighbour columns as without.  obs_eps with
 // obs_clear (srb_sizes.clearance_selection): the static columns by clearance to the level set -- over the horizon
-// when obs_vel and obs_horizon say so, else now -- and the neighbour columns as without
+// when obs_vel and obs_horizon say so, else now -- and the neighbour columns as without.  agent_rad with nbr_clear
+// (srb_agent_sizes.clearance_selection): the neighbour columns by clearance -- over the horizon when the caller hands
+// over nbr_plan, else now -- and the static columns as without
 int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
                         int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan, int N,
-                        const double *obs_vel, int obs_horizon, double Ts, const double *obs_eps, int obs_clear)
+                        const double *obs_vel, int obs_horizon, double Ts, const double *obs_eps, int obs_clear,
+                        const double *agent_rad, int nbr_clear)
 {
-    const bool clear = obs_eps && obs_clear;
-    if (clear || (obs_vel && obs_horizon)) {
-        if (K_nbr > 0)
-            if (int rc = launch_select(c, n_agents, x0, obstacles, 0, nbr_state, n_all, agent_offset, 0, K_nbr, 0,
-                                       sel + K_obs, s, K_obs + K_nbr, nbr_plan, N))
-                return rc;
+    const bool clear = obs_eps && obs_clear, horizon = obs_vel && obs_horizon, nclear = agent_rad && nbr_clear;
+    if (clear || horizon || nclear) {
+        if (K_nbr > 0) {
+            const int rc = nclear ? launch_nbr_clear(c, n_agents, x0, nbr_state, nbr_plan, agent_rad, n_all, agent_offset,
+                                                     K_nbr, sel + K_obs, K_obs + K_nbr, s, N)
+                                  : launch_select(c, n_agents, x0, obstacles, 0, nbr_state, n_all, agent_offset, 0, K_nbr,
+                                                  0, sel + K_obs, s, K_obs + K_nbr, nbr_plan, N);
+            if (rc) return rc;
+        }
         if (K_obs > 0 && clear)
             return launch_obs_clear(c, n_agents, x0, obstacles, obs_horizon ? obs_vel : nullptr, obs_eps, n_obs,
                                     agent_offset, K_obs, sel, K_obs + K_nbr, s, N, Ts);
-        if (K_obs > 0) return launch_obs_horizon(c, n_agents, x0, obstacles, obs_vel, n_obs, agent_offset, K_obs, sel,
-                                                 K_obs + K_nbr, s, N, Ts);
+        if (K_obs > 0 && horizon)
+            return launch_obs_horizon(c, n_agents, x0, obstacles, obs_vel, n_obs, agent_offset, K_obs, sel, K_obs + K_nbr,
+                                      s, N, Ts);
+        if (K_obs > 0)                        // the static columns alone, by centres (the pass of the plan selection)
+            return launch_select(c, n_agents, x0, obstacles, n_obs, nullptr, 0, agent_offset, K_obs, 0, obstacles_version,
+                                 sel, s, K_obs + K_nbr);
         return SRB_OK;
     }
     return launch_select(c, n_agents, x0, obstacles, n_obs, nbr_state, n_all, agent_offset, K_obs, K_nbr,
@@ -534,6 +552,23 @@ static int launch_obs_clear(srb_ctx *c, int n_agents, const double *x0, const do
     return SRB_OK;
 }
 
+// The neighbour clearance selection (srb_agent_sizes.clearance_selection; srb_agents.hip) into sel (which points at
+// the neighbour columns; rows of stride sel_stride): brute force, with scenes over the agent's scene.  nbr_plan null:
+// the key's distance is the snapshot's; else the horizon's minimum.  K_nbr is already clamped to the table.
+static int launch_nbr_clear(srb_ctx *c, int n_agents, const double *x0, const double *nbr_state, const double *nbr_plan,
+                            const double *agent_rad, int n_all, int agent_offset, int K_nbr, int *sel, int sel_stride,
+                            hipStream_t s, int N)
+{
+    if (c->scene_agents > 0)
+        hipLaunchKernelGGL(srb_knn_nbr_clear_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents,
+                           x0, nbr_state, nbr_plan, agent_rad, N, agent_offset, c->scene_agents, K_nbr, sel, sel_stride);
+    else
+        hipLaunchKernelGGL(srb_knn_nbr_clear_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents, x0,
+                           nbr_state, nbr_plan, agent_rad, n_all, N, agent_offset, K_nbr, sel, sel_stride);
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
 // the checks of srb_moving that need no context (srb_host.h), with this mode's names in the messages
 static int check_moving(const srb_moving *mv, const srb_batch *b, bool rollout)
 {
@@ -557,9 +592,12 @@ static int check_plans(srb_ctx *c, int n_agents, const srb_batch *d, bool select
 }
 
 // obs_vel / obs_horizon: the members of srb_moving (null / 0: static obstacles, every launch as before);
-// obs_eps / obs_clear: those of srb_sizes (null / 0: eps_obs for every row, the selection as before)
+// obs_eps / obs_clear: those of srb_sizes (null / 0: eps_obs for every row, the selection as before);
+// agent_rad / agent_pad / nbr_clear: those of srb_agent_sizes (null / 0: eps_nbr and the levels as they are, the
+// selection as before)
 static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, int use_nlp,
-                  const double *obs_vel = nullptr, int obs_horizon = 0, const double *obs_eps = nullptr, int obs_clear = 0)
+                  const double *obs_vel = nullptr, int obs_horizon = 0, const double *obs_eps = nullptr, int obs_clear = 0,
+                  const double *agent_rad = nullptr, const double *agent_pad = nullptr, int nbr_clear = 0)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -574,6 +612,8 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         return fail(SRB_ERR_ARG, "obstacles missing");
     if (use_nlp && p->K_nbr > 0 && d->nbr_state && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
+    if (use_nlp && (agent_rad || agent_pad) && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
+        return fail(SRB_ERR_ARG, "srb_agent_sizes: agent_offset + n_agents exceeds n_all (the agent tables' rows)");
     // (the QP-only solve ignores nbr_plan: it has no obstacle rows)
     if (use_nlp)
         if (int rc = check_plans(c, n_agents, d, c->selection != 0)) return rc;
@@ -604,11 +644,14 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection) {
         int rc = srb_internal_select(c, n_agents, d->x0, d->obstacles, n_obs, d->nbr_state, n_all, d->agent_offset, k.K_obs,
                                      k.K_nbr, d->obstacles_version, sel, s, c->plan_selection ? nbr_plan : nullptr, k.N,
-                                     obs_vel, obs_horizon, p->Ts, obs_eps, obs_clear);
+                                     obs_vel, obs_horizon, p->Ts, obs_eps, obs_clear, agent_rad, nbr_clear);
         if (rc) return rc;
     }
     const double *vel = (use_nlp && k.K_obs > 0) ? obs_vel : nullptr;   // read only for the static columns of sel
     const double *eps = (use_nlp && k.K_obs > 0) ? obs_eps : nullptr;   // likewise (the QP-only solve ignores both)
+    const double *pad = (use_nlp && k.K_obs > 0) ? agent_pad : nullptr; // likewise
+    const double *rad = (use_nlp && k.K_nbr > 0) ? agent_rad : nullptr; // read only for the neighbour columns of sel
+    const bool tabled = vel || eps || rad || pad;
     if (c->timing) HIPCHK(hipEventRecord(c->ev[2], s));
     // the solve kernel, then (NLP stage) the active-set polish of its result: fused into the solve
     // kernel's end (SRB_OPT_POLISH_FUSED, instances up to SRB_FUSED_POLISH_MAX = NZL 24), else srb_polish_kernel (same instance
@@ -625,13 +668,13 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         const srb_instance *f = f32_variant(in);
         if (f) { fn = f->fn; fn_mv = f->fn_mv; c->last_f32 = 1; }
     }
-    // with a velocity or a level table the instance's obstacle-table kernels (two more arguments); without, the
-    // launches as ever
-    if (vel || eps)
+    // with any of the four tables the instance's table kernels (further arguments); without, the launches as ever
+    if (tabled)
         hipLaunchKernelGGL(fn_mv, dim3(n_agents), dim3(64 * in->nw), lds, s, k, n_agents, d->x0, d->ref, d->foot, d->obstacles,
                            n_obs, d->nbr_state, n_all, d->agent_offset, d->x_qp, d->x, d->obj, d->status, d->iters,
                            d->alpha ? d->alpha_buf : nullptr, d->alpha_buf ? d->alpha : nullptr, (const int *)sel,
-                           polish ? c->zpol : nullptr, c->zstride, k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel, eps);
+                           polish ? c->zpol : nullptr, c->zstride, k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel, eps,
+                           rad, pad);
     else
         hipLaunchKernelGGL(fn, dim3(n_agents), dim3(64 * in->nw), lds, s, k, n_agents, d->x0, d->ref, d->foot, d->obstacles,
                            n_obs, d->nbr_state, n_all, d->agent_offset, d->x_qp, d->x, d->obj, d->status, d->iters,
@@ -649,11 +692,11 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         const srb_instance *pin = pnw == in->nw ? in : pick_instance(k, pnw);
         if (!pin || pin->nzl != in->nzl) pin = in;
         const size_t plds = (size_t)srb_lds_doubles(k, pin->nzl, pin->nw) * sizeof(double);
-        if (vel || eps)
+        if (tabled)
             hipLaunchKernelGGL(pin->polish_mv, dim3(n_agents), dim3(64 * pin->nw), plds, s, k, n_agents, d->x0, d->ref, d->foot,
                                d->obstacles, d->nbr_state, d->x, d->obj, d->status, d->alpha ? d->alpha_buf : nullptr,
                                d->alpha_buf ? d->alpha : nullptr, (const int *)sel, (const float *)c->zpol, c->zstride,
-                               k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel, eps);
+                               k.K_nbr > 0 ? nbr_plan : nullptr, d->plan, vel, eps, rad, pad, d->agent_offset);
         else
             hipLaunchKernelGGL(pin->polish, dim3(n_agents), dim3(64 * pin->nw), plds, s, k, n_agents, d->x0, d->ref, d->foot,
                                d->obstacles, d->nbr_state, d->x, d->obj, d->status, d->alpha ? d->alpha_buf : nullptr,
@@ -773,27 +816,38 @@ extern "C" int srb_ctx_set_qp_init(srb_ctx *c, int mode)
     return SRB_OK;
 }
 
+// the batch has a neighbour table (what srb_agent_sizes.agent_rad / agent_body need)
+static bool has_nbr(const srb_batch *b) { return b && b->struct_size == (int)sizeof(srb_batch) && b->nbr_state && b->n_all > 0; }
+
 static int solve_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv, const srb_sizes *sz,
-                        void *stream)
+                        const srb_agent_sizes *ag, void *stream)
 {
     if (int rc0 = srb_check_struct(dev_io, "srb_batch")) return rc0;   // first: it needs no context
     if (int rc0 = check_moving(mv, dev_io, false)) return rc0;
     if (int rc0 = srb_check_sizes(sz)) return rc0;
+    if (int rc0 = srb_check_agent_sizes(ag, has_nbr(dev_io))) return rc0;
     if (!c || !dev_io) return fail(SRB_ERR_ARG, "null argument");
     hipStream_t s = (hipStream_t)stream;          // NULL: the HIP null stream (ordered with blocking streams)
     HIPCHK(hipSetDevice(c->device));
     int rc = c->order.order_after_last(s);
     if (!rc) rc = launch(c, n_agents, dev_io, s, c->p.use_nlp, mv ? mv->obs_vel : nullptr, mv ? mv->horizon_selection : 0,
-                         sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0);
+                         sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0, ag ? ag->agent_rad : nullptr,
+                         ag ? ag->agent_pad : nullptr, ag ? ag->clearance_selection : 0);
     if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
 }
 
-// (the plain and the _moving entry points are the _sized ones without a table: one path)
+// (the plain, the _moving and the _sized entry points are the _agents ones without a table: one path)
+extern "C" int srb_solve_batch_agents_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
+                                             const srb_sizes *sz, const srb_agent_sizes *ag, void *stream)
+{
+    return solve_device(c, n_agents, dev_io, mv, sz, ag, stream);
+}
+
 extern "C" int srb_solve_batch_sized_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
                                             const srb_sizes *sz, void *stream)
 {
-    return solve_device(c, n_agents, dev_io, mv, sz, stream);
+    return srb_solve_batch_agents_device(c, n_agents, dev_io, mv, sz, nullptr, stream);
 }
 
 extern "C" int srb_solve_batch_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, void *stream)
@@ -840,8 +894,42 @@ extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, i
 // srb_select_device with the static columns by closest predicted approach (srb_moving.horizon_selection = 1) or by
 // clearance to the level set (srb_sizes.clearance_selection = 1, over the horizon with both); any other srb_moving
 // and srb_sizes is srb_select_device itself (the snapshot selection reads neither the velocities nor the levels).
-extern "C" int srb_select_sized_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv,
-                                       const srb_sizes *sz, int tables, void *stream)
+static int select_sized(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv, const srb_sizes *sz,
+                        int tables, void *stream);
+
+// With srb_agent_sizes.clearance_selection = 1, tables & 2 is the neighbour clearance selection (over the horizon
+// with SRB_OPT_PLAN_SELECTION = 1 and a plan table); the static columns as the _sized call selects them.
+extern "C" int srb_select_agents_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv,
+                                        const srb_sizes *sz, const srb_agent_sizes *ag, int tables, void *stream)
+{
+    if (int rc0 = srb_check_struct(d, "srb_batch")) return rc0;
+    if (int rc0 = check_moving(mv, d, false)) return rc0;
+    if (int rc0 = srb_check_sizes(sz)) return rc0;
+    if (int rc0 = srb_check_agent_sizes(ag, has_nbr(d))) return rc0;
+    const bool nclear = ag && ag->agent_rad && ag->clearance_selection;
+    if (!nclear || !(tables & 2) || tables < 1 || tables > 3 || !c || !d)
+        return select_sized(c, n_agents, d, mv, sz, tables, stream);
+    if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
+    if (!d->x0 || !d->sel) return fail(SRB_ERR_ARG, "missing buffer (x0, sel)");
+    if (n_agents == 0) return SRB_OK;
+    int Ko = c->p.K_obs, Kn = c->p.K_nbr;                 // clamped exactly as the solve does
+    clamp_K(c, d->n_obs, d->nbr_state != nullptr, d->n_all, &Ko, &Kn);
+    if (int rc0 = check_scenes(c, n_agents, d->n_obs, d->nbr_state != nullptr, d->n_all, d->agent_offset)) return rc0;
+    if (Kn > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
+        return fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
+    if (int rc0 = check_plans(c, n_agents, d, true)) return rc0;
+    if (tables & 1)                                       // the static columns: the pass of the _sized call
+        if (int rc0 = select_sized(c, n_agents, d, mv, sz, 1, stream)) return rc0;
+    hipStream_t s = (hipStream_t)stream;
+    return c->order.run(c->device, s, [&] {
+        if (Kn == 0) return (int)SRB_OK;
+        return launch_nbr_clear(c, n_agents, d->x0, d->nbr_state, c->plan_selection ? d->nbr_plan : nullptr, ag->agent_rad,
+                                d->n_all, d->agent_offset, Kn, d->sel + Ko, Ko + Kn, s, c->p.N);
+    });
+}
+
+static int select_sized(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv, const srb_sizes *sz,
+                        int tables, void *stream)
 {
     if (int rc0 = srb_check_struct(d, "srb_batch")) return rc0;
     if (int rc0 = check_moving(mv, d, false)) return rc0;
@@ -867,6 +955,13 @@ extern "C" int srb_select_sized_device(srb_ctx *c, int n_agents, const srb_batch
         return launch_obs_horizon(c, n_agents, d->x0, d->obstacles, mv->obs_vel, d->n_obs, d->agent_offset, Ko, d->sel,
                                   Ko + Kn, s, c->p.N, c->p.Ts);
     });
+}
+
+// (the _sized and the _moving entry points are the _agents one without a table: one path)
+extern "C" int srb_select_sized_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv,
+                                       const srb_sizes *sz, int tables, void *stream)
+{
+    return srb_select_agents_device(c, n_agents, d, mv, sz, nullptr, tables, stream);
 }
 
 extern "C" int srb_select_moving_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv, int tables,
@@ -932,20 +1027,30 @@ static int launch_advance(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
     return SRB_OK;
 }
 
-// radius: srb_sizes.obs_radius (null: the centre distances and the 0.5 m fail test, the kernels as ever)
+// radius: srb_sizes.obs_radius (null: the centre distances and the 0.5 m fail test, the kernels as ever);
+// body / collide: srb_agent_sizes.agent_body and collide_cycle (body null: d_agent by centres, the kernels as ever;
+// else the kernels of srb_agents.hip, which take radius null or not)
 static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s,
-                          const double *radius = nullptr)
+                          const double *radius = nullptr, const double *body = nullptr, int *collide = nullptr)
 {
     if (!d->state) return fail(SRB_ERR_ARG, "srb_sim: missing buffer (state)");
     if (d->n_obs < 0 || d->n_all < 0 || (d->n_obs > 0 && !d->obstacles) || (d->n_all > 0 && !d->nbr_state))
         return fail(SRB_ERR_ARG, "srb_sim: obstacles / nbr_state missing for n_obs / n_all rows");
     // scenes: blocks of one scene each, from the scene of the batch's first agent to that of its last
+    if (body && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
+        return fail(SRB_ERR_ARG, "srb_agent_sizes.agent_body: agent_offset + n_agents exceeds n_all (the table's rows)");
     int n_scenes = 0;
     if (int rc = check_scenes(c, n_agents, d->n_obs, d->n_all > 0, d->n_all, d->agent_offset, &n_scenes)) return rc;
     if (n_scenes > 0) {
         const int sa = c->scene_agents, bps = (sa + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK;
         const int s0 = d->agent_offset / sa, s1 = (d->agent_offset + n_agents - 1) / sa;
-        if (radius)
+        if (body)
+            hipLaunchKernelGGL(srb_sim_scene_metrics_agents_kernel, dim3((s1 - s0 + 1) * bps), dim3(256), 0, s, n_agents,
+                               cycle, d->c_first, (const double *)d->state, d->obstacles, radius,
+                               d->n_obs > 0 ? c->scene_obs : 0, d->nbr_state, body, d->n_all > 0 ? sa : 0, sa,
+                               d->agent_offset, s0, bps, d->d_obs, d->d_agent, d->min_d_obs, d->min_d_agent, d->fail_cycle,
+                               d->distance_to_fail, collide);
+        else if (radius)
             hipLaunchKernelGGL(srb_sim_scene_metrics_sized_kernel, dim3((s1 - s0 + 1) * bps), dim3(256), 0, s, n_agents,
                                cycle, d->c_first, (const double *)d->state, d->obstacles, radius,
                                d->n_obs > 0 ? c->scene_obs : 0, d->nbr_state, d->n_all > 0 ? sa : 0, sa, d->agent_offset, s0,
@@ -958,7 +1063,13 @@ static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
         HIPCHK(hipGetLastError());
         return SRB_OK;
     }
-    if (radius)
+    if (body)
+        hipLaunchKernelGGL(srb_sim_metrics_agents_kernel,
+                           dim3((n_agents + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK), dim3(256), 0, s,
+                           n_agents, cycle, d->c_first, (const double *)d->state, d->obstacles, radius, d->n_obs,
+                           d->nbr_state, body, d->n_all, d->agent_offset, d->d_obs, d->d_agent, d->min_d_obs,
+                           d->min_d_agent, d->fail_cycle, d->distance_to_fail, collide);
+    else if (radius)
         hipLaunchKernelGGL(srb_sim_metrics_sized_kernel,
                            dim3((n_agents + SRB_SIM_AGENTS_PER_BLOCK - 1) / SRB_SIM_AGENTS_PER_BLOCK), dim3(256), 0, s,
                            n_agents, cycle, d->c_first, (const double *)d->state, d->obstacles, radius, d->n_obs,
@@ -974,23 +1085,26 @@ static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
     return SRB_OK;
 }
 
-int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s, const double *radius)
+int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s, const double *radius,
+                             const double *agent_body, int *collide_cycle)
 {
-    return launch_metrics(c, n_agents, d, cycle, s, radius);
+    return launch_metrics(c, n_agents, d, cycle, s, radius, agent_body, collide_cycle);
 }
 
 static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream, bool advance,
-                    const srb_sizes *sz = nullptr)
+                    const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr)
 {
     if (int rc = check_sim(d, cycle, advance)) return rc;
     if (int rc = srb_check_sizes(sz)) return rc;
+    if (int rc = srb_check_agent_sizes(ag, d->nbr_state && d->n_all > 0)) return rc;
     if (!c) return fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
     hipStream_t s = (hipStream_t)stream;
     return c->order.run(c->device, s, [&] {
         return advance ? launch_advance(c, n_agents, d, cycle, s)
-                       : launch_metrics(c, n_agents, d, cycle, s, sz ? sz->obs_radius : nullptr);
+                       : launch_metrics(c, n_agents, d, cycle, s, sz ? sz->obs_radius : nullptr,
+                                        ag ? ag->agent_body : nullptr, ag ? ag->collide_cycle : nullptr);
     });
 }
 
@@ -999,10 +1113,16 @@ extern "C" int srb_sim_advance_device(srb_ctx *c, int n_agents, const srb_sim *d
     return sim_call(c, n_agents, d, cycle, stream, true);
 }
 
+extern "C" int srb_sim_metrics_agents_device(srb_ctx *c, int n_agents, const srb_sim *d, const srb_sizes *sz,
+                                             const srb_agent_sizes *ag, int cycle, void *stream)
+{
+    return sim_call(c, n_agents, d, cycle, stream, false, sz, ag);
+}
+
 extern "C" int srb_sim_metrics_sized_device(srb_ctx *c, int n_agents, const srb_sim *d, const srb_sizes *sz, int cycle,
                                             void *stream)
 {
-    return sim_call(c, n_agents, d, cycle, stream, false, sz);
+    return srb_sim_metrics_agents_device(c, n_agents, d, sz, nullptr, cycle, stream);
 }
 
 extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream)
@@ -1011,11 +1131,12 @@ extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d
 }
 
 static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, const srb_moving *mv,
-                   const srb_sizes *sz, int cycles, void *stream)
+                   const srb_sizes *sz, const srb_agent_sizes *ag, int cycles, void *stream)
 {
     if (int rc0 = srb_check_struct(b, "srb_batch")) return rc0;
     if (int rc0 = check_moving(mv, b, true)) return rc0;
     if (int rc0 = srb_check_sizes(sz)) return rc0;
+    if (int rc0 = srb_check_agent_sizes(ag, true)) return rc0;    // (the driver's neighbour table is the team itself)
     // (the layout and null checks of check_sim only: the driver's first cycle is c_first itself)
     if (int rc = check_sim(d, d && d->struct_size == (int)sizeof(srb_sim) ? d->c_first : 0, false)) return rc;
     if (!b) return fail(SRB_ERR_ARG, "null argument");
@@ -1059,20 +1180,29 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
         rc = launch_advance(c, n_agents, &sim, cyc, s);
         if (rc || i == cycles) break;
         if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
-        if (!rc) rc = launch_metrics(c, n_agents, &sim, cyc, s, sz ? sz->obs_radius : nullptr);
+        if (!rc) rc = launch_metrics(c, n_agents, &sim, cyc, s, sz ? sz->obs_radius : nullptr,
+                                     ag ? ag->agent_body : nullptr, ag ? ag->collide_cycle : nullptr);
         if (i > 0 && d->plan_table) bat.nbr_plan = d->plan_table;
         if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp, vel, mv ? mv->horizon_selection : 0,
-                             sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0);
+                             sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0, ag ? ag->agent_rad : nullptr,
+                             ag ? ag->agent_pad : nullptr, ag ? ag->clearance_selection : 0);
     }
     const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier launches run
     return rc ? rc : rc_mark;
 }
 
-// the tables of srb_sizes do not change over a rollout: the same pointers serve every cycle
+// the tables of srb_sizes and srb_agent_sizes do not change over a rollout: the same pointers serve every cycle
+extern "C" int srb_rollout_agents_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
+                                         const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag, int cycles,
+                                         void *stream)
+{
+    return rollout(c, n_agents, b, d, mv, sz, ag, cycles, stream);
+}
+
 extern "C" int srb_rollout_sized_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
                                         const srb_moving *mv, const srb_sizes *sz, int cycles, void *stream)
 {
-    return rollout(c, n_agents, b, d, mv, sz, cycles, stream);
+    return srb_rollout_agents_device(c, n_agents, b, d, mv, sz, nullptr, cycles, stream);
 }
 
 extern "C" int srb_rollout_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, int cycles, void *stream)
@@ -1184,11 +1314,12 @@ extern "C" int srb_last_polish_ms(srb_ctx *c, float *polish_ms)
 }
 
 static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp, const srb_moving *mv = nullptr,
-                      const srb_sizes *sz = nullptr)
+                      const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr)
 {
     if (int rc0 = srb_check_struct(h, "srb_batch")) return rc0;   // first: it needs no context
     if (int rc0 = check_moving(mv, h, false)) return rc0;
     if (int rc0 = srb_check_sizes(sz)) return rc0;
+    if (int rc0 = srb_check_agent_sizes(ag, has_nbr(h))) return rc0;
     if (!c || !h) return fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -1255,10 +1386,27 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp,
         HIPCHK(hipMemcpyAsync(c->obs_eps, sz->obs_eps, bytes, hipMemcpyHostToDevice, s));
         eps = c->obs_eps;
     }
+    // the agent tables likewise, n_all rows each (srb_solve_batch_agents); the QP-only solve reads neither
+    const double *rad = nullptr, *pad = nullptr;
+    if (use_nlp && ag && (ag->agent_rad || ag->agent_pad)) {
+        if (h->agent_offset < 0 || h->agent_offset + n_agents > h->n_all)    // launch()'s refusal, before the copies
+            return fail(SRB_ERR_ARG, "srb_agent_sizes: agent_offset + n_agents exceeds n_all (the agent tables' rows)");
+        const size_t bytes = (size_t)h->n_all * sizeof(double);
+        if (ag->agent_rad) {
+            if (int rc0 = srb_stage_reserve(c->order, c->agent_rad, c->cap_rad, bytes)) return rc0;
+            HIPCHK(hipMemcpyAsync(c->agent_rad, ag->agent_rad, bytes, hipMemcpyHostToDevice, s));
+            rad = c->agent_rad;
+        }
+        if (ag->agent_pad) {
+            if (int rc0 = srb_stage_reserve(c->order, c->agent_pad, c->cap_pad, bytes)) return rc0;
+            HIPCHK(hipMemcpyAsync(c->agent_pad, ag->agent_pad, bytes, hipMemcpyHostToDevice, s));
+            pad = c->agent_pad;
+        }
+    }
     d.sel = nullptr;                       // the context's scratch; copied out below when asked for
     d.obstacles_version = 0;               // staged copy: rebuilt every call
     int rc = launch(c, n_agents, &d, s, use_nlp, vel, vel && mv ? mv->horizon_selection : 0, eps,
-                    eps && sz ? sz->clearance_selection : 0);
+                    eps && sz ? sz->clearance_selection : 0, rad, pad, rad && ag ? ag->clearance_selection : 0);
     if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->sel && use_nlp) {
@@ -1277,10 +1425,16 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp,
     return SRB_OK;
 }
 
+extern "C" int srb_solve_batch_agents(srb_ctx *c, int n_agents, const srb_batch *host_io, const srb_moving *host_mv,
+                                      const srb_sizes *host_sz, const srb_agent_sizes *host_ag)
+{
+    return solve_host(c, n_agents, host_io, c ? c->p.use_nlp : 0, host_mv, host_sz, host_ag);
+}
+
 extern "C" int srb_solve_batch_sized(srb_ctx *c, int n_agents, const srb_batch *host_io, const srb_moving *host_mv,
                                      const srb_sizes *host_sz)
 {
-    return solve_host(c, n_agents, host_io, c ? c->p.use_nlp : 0, host_mv, host_sz);
+    return srb_solve_batch_agents(c, n_agents, host_io, host_mv, host_sz, nullptr);
 }
 
 extern "C" int srb_solve_batch(srb_ctx *c, int n_agents, const srb_batch *host_io)

@@ -1,7 +1,7 @@
 // Host plumbing shared by the three C-ABI files (srb_capi.cpp, srb12_capi.cpp, srb_ll_capi.cpp): the error
 // channel, the HIP-error macros, the submission-order chaining of a context, and what the LIP and the SRB-12 mode
-// check and launch alike (the struct-size refusal, the range-overlap test, the srb_moving and srb_sizes checks, the
-// growth of a staging buffer, the obstacle-advance launch).  Internal, host only.
+// check and launch alike (the struct-size refusal, the range-overlap test, the srb_moving, srb_sizes and srb_agent_sizes checks,
+// the growth of a staging buffer, the obstacle-advance launch).  Internal, host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -12,22 +12,26 @@
 // launch and ordering mark, which the SRB-12 mode reuses (nbr_plan [n_all][N][2] != NULL: the neighbour columns by
 // the horizon-aware selection of SRB_OPT_PLAN_SELECTION, whatever that option of the context says; obs_vel
 // [n_obs][2] with obs_horizon != 0: the static columns by srb_moving.horizon_selection over the grid (N, Ts);
-// obs_eps [n_obs] with obs_clear != 0: the static columns by srb_sizes.clearance_selection)
+// obs_eps [n_obs] with obs_clear != 0: the static columns by srb_sizes.clearance_selection; agent_rad [n_all] with
+// nbr_clear != 0: the neighbour columns by srb_agent_sizes.clearance_selection, over the horizon with nbr_plan)
 int srb_internal_fail(int code, const char *msg);
 int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
                         int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan = nullptr, int N = 0,
                         const double *obs_vel = nullptr, int obs_horizon = 0, double Ts = 0.0,
-                        const double *obs_eps = nullptr, int obs_clear = 0);
+                        const double *obs_eps = nullptr, int obs_clear = 0, const double *agent_rad = nullptr,
+                        int nbr_clear = 0);
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s);
 // ... and its scene partition (srb_ctx_set_scenes): the per-call refusals, the "up to K nearest" clamp, and the
 // metrics launch (srb_sim_metrics_kernel, or with scenes srb_sim_scene_metrics_kernel) on d->state rows
 // [x, xdot, y, ydot] -- launches only, the caller orders the stream.  radius [n_obs] != NULL: srb_sizes.obs_radius, the
-// sized kernels of srb_sizes.hip
+// sized kernels of srb_sizes.hip; agent_body [n_all] != NULL: srb_agent_sizes.agent_body (and its collide_cycle), the
+// kernels of srb_agents.hip
 int srb_internal_check_scenes(const srb_ctx *c, int n_agents, int n_obs, bool has_nbr, int n_all, int agent_offset);
 void srb_internal_clamp_K(const srb_ctx *c, int n_obs, bool has_nbr, int n_all, int *Ko, int *Kn);
 int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s,
-                             const double *radius = nullptr);
+                             const double *radius = nullptr, const double *agent_body = nullptr,
+                             int *collide_cycle = nullptr);
 
 // a failed HIP call returns SRB_ERR_HIP with "<expression>: <HIP's message>"; HIPCHK_UNWIND_ first runs `cleanup`
 // (a create function's local CREATE_CHK names its destroy there once).  `text`: the expression stringified by the
@@ -135,6 +139,30 @@ static inline int srb_check_sizes(const srb_sizes *sz)
     if (sz->clearance_selection && !sz->obs_eps)
         return srb_internal_fail(SRB_ERR_ARG, "srb_sizes.clearance_selection = 1 needs obs_eps (the clearance selection "
                                               "reads the level table)");
+    return SRB_OK;
+}
+
+// The argument errors of srb_agent_sizes, none of which needs a context, before anything is launched.  has_nbr: the
+// call's batch (srb_batch, or srb_sim for the metrics) has a neighbour table, whose rows the tables follow.
+static inline int srb_check_agent_sizes(const srb_agent_sizes *ag, bool has_nbr)
+{
+    if (int rc = srb_check_struct(ag, "srb_agent_sizes")) return rc;
+    if (!ag) return SRB_OK;
+    if (ag->clearance_selection != 0 && ag->clearance_selection != 1)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes.clearance_selection: 0 (the K_nbr columns as ever) or 1 "
+                                              "(by clearance dist - agent_rad)");
+    if (ag->clearance_selection && !ag->agent_rad)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes.clearance_selection = 1 needs agent_rad (the clearance "
+                                              "selection reads the radius table)");
+    if (ag->agent_rad && !has_nbr)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes.agent_rad needs a neighbour table (nbr_state, n_all > 0): "
+                                              "its rows are the table's");
+    if (ag->agent_body && !has_nbr)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes.agent_body needs a neighbour table (nbr_state, n_all > 0): "
+                                              "its rows are the table's");
+    if (ag->collide_cycle && !ag->agent_body)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes.collide_cycle needs agent_body (a collision is two bodies "
+                                              "overlapping)");
     return SRB_OK;
 }
 

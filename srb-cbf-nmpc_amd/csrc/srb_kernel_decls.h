@@ -26,8 +26,9 @@ struct SrbGrid {
 };
 
 // ---- srb_kernels.hip: the solve kernel (INFIX empty, or f32_ for the fp32-factor instances) and the polish kernel;
-// the instances that take obstacle-table extras (mv_: two more arguments, the velocity table of srb_moving and the
-// level table of srb_sizes, either may be null) of each
+// the instances that take table extras (mv_: further arguments, the velocity table of srb_moving, the level table
+// of srb_sizes and the safety-radius and pad tables of srb_agent_sizes, each may be null; the polish kernel also the
+// agent_offset that the agent tables' own row needs) of each
 #define SRB_DECL_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC)                                                         \
     extern "C" __global__ void srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(               \
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
@@ -40,7 +41,8 @@ struct SrbGrid {
         const double *obstacles, int n_obs, const double *nbr_state, int n_all, int agent_offset,              \
         double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
         const double *alpha_buf, double *alpha_out, const int *sel_g, float *zpol_g, int zstride,             \
-        const double *nbr_plan, double *plan_out, const double *obs_vel, const double *obs_eps);
+        const double *nbr_plan, double *plan_out, const double *obs_vel, const double *obs_eps,               \
+        const double *agent_rad, const double *agent_pad);
 #define SRB_DECL_POLISH(NZL, TS, NW, NC, CC, KC)                                                              \
     extern "C" __global__ void srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC(                   \
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
@@ -51,7 +53,8 @@ struct SrbGrid {
         SrbKParams prm, int n_agents, const double *x0g, const double *refg, const double *footg,              \
         const double *obstacles, const double *nbr_state, double *x_out, double *obj_out, int *status_out,     \
         const double *alpha_buf, double *alpha_out, const int *sel_g, const float *zpol_g, int zstride,       \
-        const double *nbr_plan, double *plan_out, const double *obs_vel, const double *obs_eps);
+        const double *nbr_plan, double *plan_out, const double *obs_vel, const double *obs_eps,               \
+        const double *agent_rad, const double *agent_pad, int agent_offset);
 #define SRB_DECL_NMPC(...) SRB_DECL_NMPC_(, __VA_ARGS__) SRB_DECL_POLISH(__VA_ARGS__)
 #define SRB_DECL_NMPC_F32(...) SRB_DECL_NMPC_(f32_, __VA_ARGS__)
 SRB_KERNEL_INSTANCES(SRB_DECL_NMPC)
@@ -150,6 +153,32 @@ extern "C" __global__ void srb_sim_scene_metrics_sized_kernel(int n_agents, int 
                                                               int blocks_per_scene, double *d_obs, double *d_agent,
                                                               double *min_d_obs, double *min_d_agent, int *fail_cycle,
                                                               double *distance_to_fail);
+
+// ---- srb_agents.hip (agent sizes, srb_agent_sizes): the neighbour columns by clearance dist_i - agent_rad[i] (whole
+// table / the agent's scene, global indices out; nbr_plan null: the snapshot distance, else knn_plan_select's
+// minimum over the horizon) and the metrics with a body radius per agent row (obs_radius may be null: srb_sim's
+// obstacle half; collide_cycle may be null)
+extern "C" __global__ void srb_knn_nbr_clear_kernel(int n_agents, const double *x0g, const double *nbr_state,
+                                                    const double *nbr_plan, const double *agent_rad, int n_all, int N,
+                                                    int agent_offset, int K_nbr, int *sel_out, int sel_stride);
+extern "C" __global__ void srb_knn_nbr_clear_scene_kernel(int n_agents, const double *x0g, const double *nbr_state,
+                                                          const double *nbr_plan, const double *agent_rad, int N,
+                                                          int agent_offset, int scene_agents, int K_nbr, int *sel_out,
+                                                          int sel_stride);
+extern "C" __global__ void srb_sim_metrics_agents_kernel(int n_agents, int c, int c_first, const double *state,
+                                                         const double *obstacles, const double *obs_radius, int n_obs,
+                                                         const double *nbr_state, const double *agent_body, int n_all,
+                                                         int agent_offset, double *d_obs, double *d_agent,
+                                                         double *min_d_obs, double *min_d_agent, int *fail_cycle,
+                                                         double *distance_to_fail, int *collide_cycle);
+extern "C" __global__ void srb_sim_scene_metrics_agents_kernel(int n_agents, int c, int c_first, const double *state,
+                                                               const double *obstacles, const double *obs_radius,
+                                                               int obs_rows, const double *nbr_state,
+                                                               const double *agent_body, int nbr_rows, int scene_agents,
+                                                               int agent_offset, int scene0, int blocks_per_scene,
+                                                               double *d_obs, double *d_agent, double *min_d_obs,
+                                                               double *min_d_agent, int *fail_cycle,
+                                                               double *distance_to_fail, int *collide_cycle);
 
 // ---- srb_llctrl.hip
 extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDev io);

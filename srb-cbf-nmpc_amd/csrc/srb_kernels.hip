@@ -1304,6 +1304,8 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
 //                        table predicted at constant velocity o_k = p + v Ts (k+1))
 //                        (the moving-obstacle instances, MV = 1: static rows at o + w Ts (k+1), w = obs_vel[sel])
 //                        (likewise with srb_sizes.obs_eps: the level of static column j is obs_eps[sel[j]])
+//                        (and with srb_agent_sizes: neighbour column j at (agent_rad[g] + agent_rad[sel[j]])^2,
+//                        every static column at (sqrt(level) + agent_pad[g])^2, g = agent_offset + agent)
 //   SRB_AGENT_OUTPUTS    x, the agent's plan (the CoM positions of x), objective, alpha_COM
 #define SRB_AGENT_LAYOUT \
     constexpr int NZM = ((NZL + 15) / 16) * 16; \
@@ -1462,6 +1464,25 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
         /* static column j is the table's row sel[j]; the lane that wrote the entry rewrites it (no barrier added); */ \
         /* the neighbour columns and a -1 row keep what they have */ \
         if (MV && obs_eps) { if (tid < prm.K_obs && sel[tid] >= 0) eps[tid] = obs_eps[sel[tid]]; } \
+        /* agent sizes (srb_agent_sizes; the MV instances only, kernel arguments: wave-uniform), rad then pad, each */ \
+        /* lane again on the entry it wrote itself.  rad: the level of neighbour column j is the squared sum of the */ \
+        /* agent's own safety radius (table row agent_offset + agent) and the neighbour's (row sel[j]), a -1 row */ \
+        /* keeps eps_nbr.  pad: every static column's safety radius sqrt(level) grows by the agent's own pad. */ \
+        /* One rounded operation each: uncontracted, the bits of the host restatement */ \
+        if (MV && agent_rad) { \
+            _Pragma("clang fp contract(off)") \
+            if (tid >= prm.K_obs && tid < K && sel[tid] >= 0) { \
+                const double s_ = agent_rad[(size_t)agent_offset + agent] + agent_rad[sel[tid]]; \
+                eps[tid] = s_ * s_; \
+            } \
+        } \
+        if (MV && agent_pad) { \
+            _Pragma("clang fp contract(off)") \
+            if (tid < prm.K_obs) { \
+                const double t_ = sqrt(eps[tid]) + agent_pad[(size_t)agent_offset + agent]; \
+                eps[tid] = t_ * t_; \
+            } \
+        } \
     } \
     do {} while (0)
 
@@ -1677,7 +1698,8 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,
                 const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride,
                 const double *__restrict__ nbr_plan, double *__restrict__ plan_out,
-                const double *__restrict__ obs_vel, const double *__restrict__ obs_eps, double *lds)
+                const double *__restrict__ obs_vel, const double *__restrict__ obs_eps,
+                const double *__restrict__ agent_rad, const double *__restrict__ agent_pad, double *lds)
 {
     SRB_AGENT_LAYOUT;
 #ifdef SRB_STAMPS
@@ -2377,7 +2399,9 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
                 const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,
                 const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride,
                 const double *__restrict__ nbr_plan, double *__restrict__ plan_out,
-                const double *__restrict__ obs_vel, const double *__restrict__ obs_eps, double *lds)
+                const double *__restrict__ obs_vel, const double *__restrict__ obs_eps,
+                const double *__restrict__ agent_rad, const double *__restrict__ agent_pad, int agent_offset,
+                double *lds)
 {
     SRB_AGENT_LAYOUT;
 #ifdef SRB_STAMPS
@@ -2478,7 +2502,7 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         if (agent >= n_agents) return;                                                                         \
         nmpc_agent<NZL, TS, NW, NC, CC, KC, KF>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
                                 x_qp_out, x_out, obj_out, status_out, iters_out, alpha_buf, alpha_out, sel_g, \
-                                zpol_g, zstride, nbr_plan, plan_out, nullptr, nullptr, lds);                            \
+                                zpol_g, zstride, nbr_plan, plan_out, nullptr, nullptr, nullptr, nullptr, lds);          \
     }
 #define SRB_POLISH_ENTRY(NZL, TS, NW, NC, CC, KC)                                                              \
     extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
@@ -2494,11 +2518,12 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         polish_agent<NZL, TS, NW, NC, CC, KC>(prm, agent, x0g, refg, footg, obstacles, nbr_state, x_out, obj_out,          \
-                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, nullptr, nullptr, lds); \
+                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, nullptr, nullptr, nullptr, nullptr, 0, lds); \
     }
-// The obstacle-table instances (srb_moving.obs_vel, srb_sizes.obs_eps; MV = 1): the same kernels with the velocity
-// table and the level table as two more arguments (either may be null) and the arms of SRB_AGENT_OBSTACLES that read
-// them compiled in, named srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*.
+// The table instances (srb_moving.obs_vel, srb_sizes.obs_eps, srb_agent_sizes.agent_rad / agent_pad; MV = 1): the
+// same kernels with the four tables as further arguments (each may be null; the polish kernel, which has no
+// agent_offset of its own, takes that too: the agent's own row) and the arms of SRB_AGENT_OBSTACLES that read them
+// compiled in, named srb_nmpc_kernel_mv_* / srb_polish_kernel_mv_*.
 // Instances of their own, as the fp32-factor instances are, and in code objects of their own (SRB_PART 4 .. 7): with
 // the argument on the default instances the default bench step measured 0.5 % and config 5 0.3 % slower than the
 // parent, outside its run-to-run spread, so the default instances keep their code.
@@ -2512,14 +2537,15 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         int *__restrict__ iters_out, const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,       \
         const int *__restrict__ sel_g, float *__restrict__ zpol_g, int zstride,                               \
         const double *__restrict__ nbr_plan, double *__restrict__ plan_out,                                    \
-        const double *__restrict__ obs_vel, const double *__restrict__ obs_eps)                                \
+        const double *__restrict__ obs_vel, const double *__restrict__ obs_eps,                                \
+        const double *__restrict__ agent_rad, const double *__restrict__ agent_pad)                            \
     {                                                                                                          \
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         nmpc_agent<NZL, TS, NW, NC, CC, KC, KF, 1>(prm, agent, x0g, refg, footg, obstacles, n_obs, nbr_state, n_all, agent_offset, \
                                 x_qp_out, x_out, obj_out, status_out, iters_out, alpha_buf, alpha_out, sel_g, \
-                                zpol_g, zstride, nbr_plan, plan_out, obs_vel, obs_eps, lds);                            \
+                                zpol_g, zstride, nbr_plan, plan_out, obs_vel, obs_eps, agent_rad, agent_pad, lds);      \
     }
 #define SRB_POLISH_ENTRY_MV(NZL, TS, NW, NC, CC, KC)                                                           \
     extern "C" __global__ void __launch_bounds__(64 * NW) SRB_WPE                                              \
@@ -2530,13 +2556,14 @@ __device__ __forceinline__ void polish_agent(const SrbKParams &prm, int agent,
         int *__restrict__ status_out, const double *__restrict__ alpha_buf, double *__restrict__ alpha_out,     \
         const int *__restrict__ sel_g, const float *__restrict__ zpol_g, int zstride,                         \
         const double *__restrict__ nbr_plan, double *__restrict__ plan_out,                                    \
-        const double *__restrict__ obs_vel, const double *__restrict__ obs_eps)                                \
+        const double *__restrict__ obs_vel, const double *__restrict__ obs_eps,                                \
+        const double *__restrict__ agent_rad, const double *__restrict__ agent_pad, int agent_offset)          \
     {                                                                                                          \
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         polish_agent<NZL, TS, NW, NC, CC, KC, 1>(prm, agent, x0g, refg, footg, obstacles, nbr_state, x_out, obj_out,       \
-                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, obs_vel, obs_eps, lds); \
+                                  status_out, alpha_buf, alpha_out, sel_g, zpol_g, zstride, nbr_plan, plan_out, obs_vel, obs_eps, agent_rad, agent_pad, agent_offset, lds); \
     }
 #define SRB_NMPC_KERNEL(...) SRB_NMPC_ENTRY(, 0, __VA_ARGS__) SRB_POLISH_ENTRY(__VA_ARGS__)
 #define SRB_NMPC_KERNEL_F32(...) SRB_NMPC_ENTRY(f32_, 1, __VA_ARGS__)

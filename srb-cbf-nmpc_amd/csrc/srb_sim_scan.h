@@ -1,5 +1,6 @@
 // The tiled nearest-row scan of the rollout's safety metrics, shared by srb_sim_metrics_kernel (srb_sim.hip) and its
-// per-scene form (srb_scenes.hip).  Header-only, device code; fp64 with contraction off.
+// per-scene form (srb_scenes.hip), and the clearance scan of the sized metrics (srb_sizes.hip, srb_agents.hip).
+// Header-only, device code; fp64 with contraction off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "srb_kernel_decls.h"
@@ -28,6 +29,34 @@ __device__ static __forceinline__ double sim_nearest2(const double *__restrict__
             const double dx = px - tile[i].x, dy = py - tile[i].y;
             const double d2 = dx * dx + dy * dy;
             if (t0 + i != skip && d2 < best) best = d2;
+        }
+    }
+    return best;
+}
+
+// this thread's share of the smallest clearance sqrt(d2_i) - rad[i] from (px, py) to the n obstacle rows, every d2
+// formed as sim_nearest2 forms it and staged through LDS in its tiles (every thread of the block calls this).  A
+// clearance that is NaN never compares smaller; without a row the result is +inf.
+__device__ static __forceinline__ double sim_clearance(const double *__restrict__ tab, const double *__restrict__ rad,
+                                                       int n, double px, double py, double2 *tile, double *rtile)
+{
+#pragma clang fp contract(off)
+    const int slice = (int)threadIdx.x / SIM_AG;
+    double best = INFINITY;
+    for (int t0 = 0; t0 < n; t0 += SIM_TILE) {
+        const int row = t0 + (int)threadIdx.x;
+        __syncthreads();                                  // the previous tile has been read
+        if (row < n) {
+            tile[threadIdx.x] = make_double2(tab[(size_t)row * 2], tab[(size_t)row * 2 + 1]);
+            rtile[threadIdx.x] = rad[row];
+        }
+        __syncthreads();
+        const int m = n - t0 < SIM_TILE ? n - t0 : SIM_TILE;
+        for (int i = slice; i < m; i += SIM_SL) {
+            const double dx = px - tile[i].x, dy = py - tile[i].y;
+            const double d2 = dx * dx + dy * dy;
+            const double cl = sqrt(d2) - rtile[i];
+            if (cl < best) best = cl;
         }
     }
     return best;

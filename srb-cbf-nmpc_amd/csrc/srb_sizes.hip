@@ -128,33 +128,7 @@ extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_OBS_WAVES) srb_knn_obs
 }
 
 // ---------------------------------------------------------------------------------------------- metrics
-// this thread's share of the smallest clearance sqrt(d2_i) - rad[i] from (px, py) to the n obstacle rows, every d2
-// formed as sim_nearest2 forms it and staged through LDS in its tiles (every thread of the block calls this).  A
-// clearance that is NaN never compares smaller; without a row the result is +inf.
-__device__ static __forceinline__ double sim_clearance(const double *__restrict__ tab, const double *__restrict__ rad,
-                                                       int n, double px, double py, double2 *tile, double *rtile)
-{
-#pragma clang fp contract(off)
-    const int slice = (int)threadIdx.x / SIM_AG;
-    double best = INFINITY;
-    for (int t0 = 0; t0 < n; t0 += SIM_TILE) {
-        const int row = t0 + (int)threadIdx.x;
-        __syncthreads();                                  // the previous tile has been read
-        if (row < n) {
-            tile[threadIdx.x] = make_double2(tab[(size_t)row * 2], tab[(size_t)row * 2 + 1]);
-            rtile[threadIdx.x] = rad[row];
-        }
-        __syncthreads();
-        const int m = n - t0 < SIM_TILE ? n - t0 : SIM_TILE;
-        for (int i = slice; i < m; i += SIM_SL) {
-            const double dx = px - tile[i].x, dy = py - tile[i].y;
-            const double d2 = dx * dx + dy * dy;
-            const double cl = sqrt(d2) - rtile[i];
-            if (cl < best) best = cl;
-        }
-    }
-    return best;
-}
+// (the clearance scan sim_clearance is in srb_sim_scan.h, shared with srb_agents.hip)
 
 // agent a's metrics of cycle c from its smallest clearance to an obstacle body (cl_ob) and its smallest squared
 // distance to another agent (b_ag): sim_metrics_store's rules with d_obs = cl_ob and the fail test d_obs < 0

@@ -114,6 +114,15 @@ class Sizes(ctypes.Structure):
         super().__init__(ctypes.sizeof(Sizes), *args, **kw)
 
 
+class AgentSizes(ctypes.Structure):
+    """Mirror of srb_agent_sizes (agent sizes; struct_size filled in)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("agent_rad", _dp), ("agent_pad", _dp), ("agent_body", _dp),
+                ("clearance_selection", ctypes.c_int), ("collide_cycle", _ip)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(ctypes.sizeof(AgentSizes), *args, **kw)
+
+
 _lib = None
 
 
@@ -178,6 +187,16 @@ def lib():
                                                    ctypes.c_void_p]
         L.srb_rollout_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim), MV,
                                                SZ, ctypes.c_int, ctypes.c_void_p]
+        AG = ctypes.POINTER(AgentSizes)
+        L.srb_solve_batch_agents.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), MV, SZ, AG]
+        L.srb_solve_batch_agents_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), MV, SZ, AG,
+                                                    ctypes.c_void_p]
+        L.srb_select_agents_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), MV, SZ, AG, ctypes.c_int,
+                                               ctypes.c_void_p]
+        L.srb_sim_metrics_agents_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Sim), SZ, AG, ctypes.c_int,
+                                                    ctypes.c_void_p]
+        L.srb_rollout_agents_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim), MV,
+                                                SZ, AG, ctypes.c_int, ctypes.c_void_p]
         L.srb_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.srb_fit_bezier.argtypes = [_dp, _dp, _dp]
         L.srb_last_error.restype = ctypes.c_char_p
@@ -254,6 +273,19 @@ def _sizes_args(obs_eps, obs_radius, obs_clearance, n_obs, dtype, ptr, obstacle_
     if obs_radius is not None:
         _check_size_array(obs_radius, n_obs, dtype, "obs_radius", device)
     return Sizes(ptr(obs_eps), ptr(obs_radius), int(bool(obs_clearance)))
+
+
+def _agent_args(agent_rad, agent_pad, agent_body, nbr_clearance, n_all, dtype, ptr, obstacle_rows=True, device=None,
+                checked=None) -> AgentSizes:
+    """The srb_agent_sizes of a call after the checks of the tables that need no context, by name (nbr_clearance
+    without agent_rad is the library's refusal).  ptr: _p for host arrays, _dptr for device tensors; checked: a
+    solver's record of the device tensors whose values it has looked at (_check_agent_array)."""
+    if not obstacle_rows:
+        raise ValueError("agent_rad / agent_pad / nbr_clearance: the QP-only solve has no obstacle rows")
+    for name, tab in (("agent_rad", agent_rad), ("agent_pad", agent_pad), ("agent_body", agent_body)):
+        if tab is not None:
+            _check_agent_array(tab, n_all, dtype, name, device, checked)
+    return AgentSizes(ptr(agent_rad), ptr(agent_pad), ptr(agent_body), int(bool(nbr_clearance)), None)
 
 
 class _SolverBase:
@@ -359,7 +391,7 @@ class BatchSolver(_SolverBase):
 
     def solve(self, x0, ref, foot, obstacles=None, nbr_state=None, agent_offset: int = 0, qp_only: bool = False,
               alpha_buf=None, nbr_plan=None, plan=None, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
-              obs_clearance: bool = False):
+              obs_clearance: bool = False, agent_rad=None, agent_pad=None, nbr_clearance: bool = False):
         """Host arrays in, dict of outputs back.  alpha_buf ([A][4], the Bezier buffer state)
         additionally returns alpha ([A][4][5], get_alphaCOM) from the fused fit.  With the NLP
         stage, sel ([A][Ko + Kn]) holds the selected obstacle / neighbour rows.  nbr_plan
@@ -369,7 +401,11 @@ class BatchSolver(_SolverBase):
         at these velocities over the horizon (srb_solve_batch_moving); obs_horizon=True additionally selects the
         static columns by closest predicted approach instead of nearest now.  obs_eps ([n_obs], float64, C-contiguous):
         the CBF level of each obstacle row in squared metres, the unit of eps_obs (srb_solve_batch_sized);
-        obs_clearance=True additionally selects the static columns by clearance to the level set."""
+        obs_clearance=True additionally selects the static columns by clearance to the level set.  agent_rad, agent_pad
+        ([n_all], float64, C-contiguous, finite; agent_rad >= 0): a safety radius and a pad per row of nbr_state
+        (srb_solve_batch_agents): neighbour column j at the level (agent_rad[g] + agent_rad[sel[j]])^2, every static
+        column of agent g at (sqrt(level) + agent_pad[g])^2; nbr_clearance=True additionally selects the neighbour
+        columns by clearance dist - agent_rad."""
         p = self.params
         x0 = _f64(x0).reshape(-1, 4)
         A = x0.shape[0]
@@ -399,6 +435,14 @@ class BatchSolver(_SolverBase):
                   _p(out["sel"]) if out["sel"].size and not qp_only else None, 0, _p(nbr_plan), _p(plan))
         moving = obs_vel is not None or obs_horizon
         mv = _moving_args(obs_vel, obs_horizon, ob.shape[0], np.float64, _p, not qp_only) if moving else None
+        if agent_rad is not None or agent_pad is not None or nbr_clearance:
+            sized = obs_eps is not None or obs_clearance
+            sz = _sizes_args(obs_eps, None, obs_clearance, ob.shape[0], np.float64, _p, not qp_only) if sized else None
+            ag = _agent_args(agent_rad, agent_pad, None, nbr_clearance, nb.shape[0] if nb is not None else 0, np.float64, _p,
+                             not qp_only)
+            _check(lib().srb_solve_batch_agents(self._h, A, ctypes.byref(b), ctypes.byref(mv) if moving else None,
+                                                ctypes.byref(sz) if sized else None, ctypes.byref(ag)))
+            return out
         if obs_eps is not None or obs_clearance:
             sz = _sizes_args(obs_eps, None, obs_clearance, ob.shape[0], np.float64, _p, not qp_only)
             _check(lib().srb_solve_batch_sized(self._h, A, ctypes.byref(b), ctypes.byref(mv) if moving else None,
@@ -414,7 +458,8 @@ class BatchSolver(_SolverBase):
     # --------------------------------------------------------------- device path
     def solve_device(self, x0, ref, foot, obstacles, nbr_state, out, agent_offset: int = 0, stream=None,
                      alpha_buf=None, obstacles_version: int = 0, nbr_plan=None, plan=None, obs_vel=None,
-                     obs_horizon: bool = False, obs_eps=None, obs_clearance: bool = False):
+                     obs_horizon: bool = False, obs_eps=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
+                     nbr_clearance: bool = False):
         """All arguments torch tensors on this solver's device (float64 / int32), contiguous.
         `out` is a dict with x_qp (or None), x, obj, status, iters and, with alpha_buf [A][4],
         alpha [A][20]; an optional int32 out["sel"] [A][Ko + Kn] receives the selected rows
@@ -427,7 +472,10 @@ class BatchSolver(_SolverBase):
         (srb_solve_batch_moving_device; needs obstacles_version 0); obs_horizon=True selects the static columns by
         closest predicted approach over the horizon.  obs_eps ([n_obs] float64, contiguous): the CBF level of each
         obstacle row (srb_solve_batch_sized_device; goes together with obstacles_version); obs_clearance=True selects
-        the static columns by clearance to the level set.
+        the static columns by clearance to the level set.  agent_rad, agent_pad ([n_all] float64, contiguous, finite;
+        agent_rad >= 0): a safety radius and a pad per row of nbr_state (srb_solve_batch_agents_device; the values of
+        a tensor are looked at once, on its first use with this solver); nbr_clearance=True selects the neighbour
+        columns by clearance dist - agent_rad.
         Asynchronous on `stream` (a hipStream_t handle), by default torch's current stream on
         this device, so the launch is ordered after the torch work that filled the inputs."""
         A = x0.shape[0]
@@ -457,6 +505,15 @@ class BatchSolver(_SolverBase):
         n_obs = 0 if obstacles is None else obstacles.shape[0]
         moving = obs_vel is not None or obs_horizon
         mv = _moving_args(obs_vel, obs_horizon, n_obs, torch_float64(), _dptr) if moving else None
+        if agent_rad is not None or agent_pad is not None or nbr_clearance:
+            sized = obs_eps is not None or obs_clearance
+            sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch_float64(), _dptr, device=x0.device) if sized else None
+            ag = _agent_args(agent_rad, agent_pad, None, nbr_clearance, 0 if nbr_state is None else nbr_state.shape[0],
+                             torch_float64(), _dptr, device=x0.device, checked=self._agent_checked())
+            _check(lib().srb_solve_batch_agents_device(self._h, A, ctypes.byref(b), ctypes.byref(mv) if moving else None,
+                                                       ctypes.byref(sz) if sized else None, ctypes.byref(ag),
+                                                       self._stream(stream)))
+            return
         if obs_eps is not None or obs_clearance:
             sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch_float64(), _dptr, device=x0.device)
             _check(lib().srb_solve_batch_sized_device(self._h, A, ctypes.byref(b), ctypes.byref(mv) if moving else None,
@@ -469,7 +526,7 @@ class BatchSolver(_SolverBase):
 
     def select_device(self, x0, obstacles, nbr_state, sel, tables: int = 3, agent_offset: int = 0, stream=None,
                       obstacles_version: int = 0, nbr_plan=None, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
-                      obs_clearance: bool = False):
+                      obs_clearance: bool = False, agent_rad=None, agent_pad=None, nbr_clearance: bool = False):
         """The obstacle / neighbour selection alone (srb_select_device) into the int32 tensor sel [A][Ko + Kn]:
         tables 1 the static obstacles, 2 the neighbour snapshot, 3 both.  With the option "selection" set
         to 0, solve_device then uses out["sel"] as filled here (bench.py selects the static obstacles while
@@ -478,6 +535,9 @@ class BatchSolver(_SolverBase):
         ([n_obs][2]) and obs_horizon=True, tables & 1 is the horizon-aware obstacle selection
         (srb_select_moving_device).  With obs_eps ([n_obs]) and obs_clearance=True, tables & 1 is the selection by
         clearance to the level set (srb_select_sized_device), over the horizon when obs_horizon is on as well.
+        With agent_rad ([n_all]) and nbr_clearance=True, tables & 2 is the neighbour selection by clearance
+        dist - agent_rad (srb_select_agents_device), over the horizon with "plan_selection" and nbr_plan; agent_pad
+        is validated and otherwise not read by a selection.
         Asynchronous on `stream` like solve_device."""
         A = x0.shape[0]
         Ko, Kn = self.n_selected(0 if obstacles is None else obstacles.shape[0],
@@ -494,6 +554,15 @@ class BatchSolver(_SolverBase):
         n_obs = 0 if obstacles is None else obstacles.shape[0]
         moving = obs_vel is not None or obs_horizon
         mv = _moving_args(obs_vel, obs_horizon, n_obs, torch_float64(), _dptr) if moving else None
+        if agent_rad is not None or agent_pad is not None or nbr_clearance:
+            sized = obs_eps is not None or obs_clearance
+            sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch_float64(), _dptr, device=x0.device) if sized else None
+            ag = _agent_args(agent_rad, agent_pad, None, nbr_clearance, 0 if nbr_state is None else nbr_state.shape[0],
+                             torch_float64(), _dptr, device=x0.device, checked=self._agent_checked())
+            _check(lib().srb_select_agents_device(self._h, A, ctypes.byref(b), ctypes.byref(mv) if moving else None,
+                                                  ctypes.byref(sz) if sized else None, ctypes.byref(ag), int(tables),
+                                                  self._stream(stream)))
+            return
         if obs_eps is not None or obs_clearance:
             sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch_float64(), _dptr, device=x0.device)
             _check(lib().srb_select_sized_device(self._h, A, ctypes.byref(b), ctypes.byref(mv) if moving else None,
@@ -508,7 +577,7 @@ class BatchSolver(_SolverBase):
     def solve_coupled_device(self, x0, ref, foot, obstacles, nbr_state, out, outer: int = 2, exchange=None,
                              nbr_plan=None, agent_offset: int = 0, stream=None, alpha_buf=None,
                              obstacles_version: int = 0, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
-                             obs_clearance: bool = False):
+                             obs_clearance: bool = False, agent_rad=None, agent_pad=None, nbr_clearance: bool = False):
         """Jacobi iteration over the agents' plans: `outer` solves of the same cycle, each against the plans
         the agents wrote in the round before.  Round 0 solves against nbr_plan (None: the constant-velocity
         rows); every later round r exchanges the plans of round r - 1 -- table = exchange(plan), a
@@ -518,11 +587,19 @@ class BatchSolver(_SolverBase):
         round's results, its plans included, are in `out`.  Returns plan_change, a device tensor [outer - 1]:
         max |plan_r - plan_{r-1}| per round (torch reductions; nothing synchronises with the host inside the
         loop).  No damping and no convergence test: the plain Jacobi round.  Other arguments (obs_vel,
-        obs_horizon, obs_eps and obs_clearance included: every round solves against the same obstacle tables) as
-        solve_device."""
+        obs_horizon, obs_eps, obs_clearance, agent_rad, agent_pad and nbr_clearance included: every round solves
+        against the same obstacle and agent tables) as solve_device."""
         return self._solve_coupled((x0, ref, foot, obstacles, nbr_state, out), outer, exchange, nbr_plan, agent_offset,
                                    stream, lambda table: {"alpha_buf": alpha_buf}, obstacles_version=obstacles_version,
-                                   obs_vel=obs_vel, obs_horizon=obs_horizon, obs_eps=obs_eps, obs_clearance=obs_clearance)
+                                   obs_vel=obs_vel, obs_horizon=obs_horizon, obs_eps=obs_eps, obs_clearance=obs_clearance,
+                                   agent_rad=agent_rad, agent_pad=agent_pad, nbr_clearance=nbr_clearance)
+
+    def _agent_checked(self) -> set:
+        """The agent-size tensors whose values this solver has validated (looking at a device tensor's values
+        synchronises with the host: once per tensor and version, not once per solve)."""
+        if not hasattr(self, "_agent_ok"):
+            self._agent_ok = set()
+        return self._agent_ok
 
     def prepare_device(self, Pr, Prd, gait_domain, contact, toe, start, q, dq, out, agent_id=None,
                        agent_offset: int = 0, stream=None):
@@ -619,6 +696,26 @@ def _check_size_array(a, n_obs, dtype, name, device=None):
     _check_plan_array(a, (n_obs,), name, dtype)
     if device is not None and getattr(a, "device", device) != device:
         raise ValueError(f"{name} must be on {device}, got {a.device}")
+
+
+def _check_agent_array(a, n_all, dtype, name, device=None, checked=None):
+    """agent_rad / agent_pad / agent_body: a contiguous float64 [n_all] array (on `device` when one is given) of
+    finite values, agent_rad and agent_body not negative, by name.  checked: a set of the device tensors already
+    looked at (data pointer, version, name), so a tensor used every cycle costs one host synchronisation."""
+    _check_size_array(a, n_all, dtype, name, device)
+    key = (a.data_ptr(), a._version, name, n_all) if hasattr(a, "data_ptr") and hasattr(a, "_version") else None
+    if key is not None and checked is not None and key in checked:
+        return
+    if hasattr(a, "isfinite"):
+        finite, neg = bool(a.isfinite().all()), bool((a < 0).any())
+    else:
+        finite, neg = bool(np.isfinite(a).all()), bool((a < 0).any())
+    if not finite:
+        raise ValueError(f"{name} must be finite (a NaN or infinite radius)")
+    if name != "agent_pad" and neg:
+        raise ValueError(f"{name} must be >= 0 (a radius in metres)")
+    if key is not None and checked is not None:
+        checked.add(key)
 
 
 def hl_plan(Pstart, Pobs, loop: int = 100000, device: int = 0):

@@ -24,6 +24,12 @@ the obstacle bodies, min_i (dist_i - obs_radius[i]), and fail_cycle the first cy
 srb_rollout_sized_device; srb12.Rollout12 likewise, srb12_rollout_sized_device).  The tables do not change over a
 rollout.
 
+With agent_rad / agent_pad ([n_all], m) every agent has its own safety radius towards its neighbours and its own pad on
+the static obstacles' safety radii in the solve, with nbr_clearance the neighbour columns are selected by clearance
+dist - agent_rad, and with agent_body ([n_all], m) d_agent is the clearance between bodies and collide_cycle the first
+cycle with d_agent < 0 (srb_agent_sizes, srb_rollout_agents_device).  The tables do not change over a rollout and every
+shard holds them whole.  LIP mode only.
+
 _RolloutBase is what this class and srb12.Rollout12 share: the checks of goal / phase / obstacles / obs_vel and of the
 size tables, the moving table's clone and its restore, the srb_moving and srb_sizes of a call, the metrics call, the
 solve, metrics and log buffers, reset / advance / results / scene_results and the preconditions of run().  A mode
@@ -34,7 +40,8 @@ from __future__ import annotations
 
 import ctypes
 
-from . import Batch, Moving, Sim, Sizes, _check, _check_size_array, _check_vel_array, _dptr, _iptr, lib
+from . import (AgentSizes, Batch, Moving, Sim, Sizes, _check, _check_agent_array, _check_size_array, _check_vel_array,
+               _dptr, _iptr, lib)
 
 
 def _check_tensor(t, shape, name, dtype, device):
@@ -199,7 +206,7 @@ class _RolloutBase:
         """The logs and metrics so far, as tensors (views of this object's buffers; asynchronous like the
         launches -- synchronise before reading on the host): traj [T+1][A][nx] (nx 4, Rollout12: 12), status / iters
         [T][A][2], x [T][A][nv] (log_x), state [A][nx] (the end state), cycles, and d_obs, d_agent, min_d_obs,
-        min_d_agent, fail_cycle, distance_to_fail [A]; with obs_vel, obstacles [n_obs][2] (the current table: the
+        min_d_agent, fail_cycle, distance_to_fail [A] (with agent_body also collide_cycle [A]); with obs_vel, obstacles [n_obs][2] (the current table: the
         rows as the last cycle saw them)."""
         if not self._ready:
             raise RuntimeError(f"{self._name}.results before reset(state)")
@@ -222,7 +229,8 @@ class _RolloutBase:
         """results() reduced per scene of the solver's partition (set_scenes; a whole number of scenes), as device
         tensors [n_scenes]: min_d_agent and min_d_obs (the smallest over the scene's agents), n_failed (agents with
         fail_cycle >= 0) and n_not_converged (solves of the logged cycles that did not converge: QP stage neither
-        OPTIMAL nor QP_WARM, or NLP stage not OPTIMAL); plus scene_agents and n_scenes.  Asynchronous like results()."""
+        OPTIMAL nor QP_WARM, or NLP stage not OPTIMAL), with agent_body n_collided (agents with collide_cycle >= 0); plus
+        scene_agents and n_scenes.  Asynchronous like results()."""
         sa = self.solver.scenes[0]
         if sa <= 0:
             raise ValueError(f"scene_results needs the solver's scene partition ({type(self.solver).__name__}.set_scenes)")
@@ -248,13 +256,23 @@ class Rollout(_RolloutBase):
     obs_radius  [n_obs] or None: the body radius (m) of each obstacle row: d_obs is then min_i (dist_i - obs_radius[i])
               and fail_cycle the first cycle with d_obs < 0 (None: centre distances and the 0.5 m test)
     obs_clearance  True: the static columns by clearance to the level set (needs obs_eps)
+    agent_rad  [n_all] or None: the safety radius (m) of each agent: neighbour column j of agent g at the level
+              (agent_rad[g] + agent_rad[sel[j]])^2 (None: eps_nbr for every pair)
+    agent_pad  [n_all] or None: metres added to the safety radius of every static column of each agent
+    agent_body  [n_all] or None: the body radius (m) of each agent: d_agent is then
+              min_i (dist_i - (agent_body[g] + agent_body[i])), results() gains collide_cycle (the first cycle with
+              d_agent < 0, else -1) and scene_results() n_collided (None: centre distances)
+    nbr_clearance  True: the neighbour columns by clearance dist - agent_rad (needs agent_rad)
+              The agent tables (srb_agent_sizes) are finite, agent_rad and agent_body not negative, and do not change
+              over a rollout; every shard holds the whole tables.  LIP mode only.
     agent_offset, n_all   a shard of a larger team: this batch is rows agent_offset .. agent_offset + A of the
               n_all-row neighbour table that step(exchange) gathers (default: the whole team)
     All tensors are float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
 
     def __init__(self, solver, goal, vref: float = 0.27, phase=None, plans: bool = False, log_x: bool = False, *,
                  obstacles=None, agent_offset: int = 0, n_all: int | None = None, obs_vel=None, obs_horizon: bool = False,
-                 obs_eps=None, obs_radius=None, obs_clearance: bool = False):
+                 obs_eps=None, obs_radius=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
+                 agent_body=None, nbr_clearance: bool = False):
         import torch
         super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps, obs_radius,
                          obs_clearance)
@@ -263,6 +281,16 @@ class Rollout(_RolloutBase):
         self.n_all = A if n_all is None else int(n_all)
         if self.agent_offset < 0 or self.agent_offset + A > self.n_all:
             raise ValueError("agent_offset + A exceeds n_all")
+        for name, tab in (("agent_rad", agent_rad), ("agent_pad", agent_pad), ("agent_body", agent_body)):
+            if tab is not None:
+                _check_agent_array(tab, self.n_all, torch.float64, name, self.device, solver._agent_checked())
+        if nbr_clearance and agent_rad is None:
+            raise ValueError("nbr_clearance needs agent_rad (the clearance selection reads the radius table)")
+        self.agent_rad, self.agent_pad, self.agent_body = agent_rad, agent_pad, agent_body
+        self.nbr_clearance = bool(nbr_clearance)
+        self.agents = agent_rad is not None or agent_pad is not None or agent_body is not None   # run(): the _agents driver
+        if agent_body is not None:
+            self.metrics["collide_cycle"] = torch.full((A,), -1, dtype=torch.int32, device=self.device)
         self.sharded = self.agent_offset != 0 or self.n_all != A
         f8 = dict(dtype=torch.float64, device=self.device)
         self.alpha_buf = torch.zeros((A, 4), **f8)
@@ -281,6 +309,19 @@ class Rollout(_RolloutBase):
                    0 if self.obstacles is None else self.obstacles.shape[0], nbr.shape[0], self.agent_offset,
                    _dptr(m["d_obs"]), _dptr(m["d_agent"]), _dptr(m["min_d_obs"]), _dptr(m["min_d_agent"]),
                    _iptr(m["fail_cycle"]), _dptr(m["distance_to_fail"]))
+
+    def _agent_sizes(self) -> AgentSizes:
+        return AgentSizes(_dptr(self.agent_rad), _dptr(self.agent_pad), _dptr(self.agent_body), int(self.nbr_clearance),
+                          _iptr(self.metrics.get("collide_cycle")))
+
+    def _metrics(self, sim, stream):
+        """With agent_body the metrics of srb_sim_metrics_agents_device (obs_radius may be absent); else as ever."""
+        if self.agent_body is None:
+            return super()._metrics(sim, stream)
+        s = self.solver
+        sz = ctypes.byref(self._sizes()) if self.obs_radius is not None else None
+        _check(lib().srb_sim_metrics_agents_device(s._h, self.A, ctypes.byref(sim), sz, ctypes.byref(self._agent_sizes()),
+                                                   self.c, s._stream(stream)))
 
     def step(self, exchange=None, plan_exchange=None, stream=None):
         """One cycle: advance, metrics, solve.  exchange (a dist.NeighbourExchange, or any callable
@@ -306,7 +347,8 @@ class Rollout(_RolloutBase):
             table = self.plan_table if plan_exchange is None else plan_exchange(self.plan_table)
         s.solve_device(self.x0, self.ref, self.foot, self.obstacles, nbr, self.out, agent_offset=self.agent_offset,
                        stream=stream, alpha_buf=self.alpha_buf, nbr_plan=table, obs_vel=self.obs_vel,
-                       obs_horizon=self.obs_horizon, obs_eps=self.obs_eps, obs_clearance=self.obs_clearance)
+                       obs_horizon=self.obs_horizon, obs_eps=self.obs_eps, obs_clearance=self.obs_clearance,
+                       agent_rad=self.agent_rad, agent_pad=self.agent_pad, nbr_clearance=self.nbr_clearance)
         self.c += 1
         self.flushed = False
 
@@ -316,7 +358,12 @@ class Rollout(_RolloutBase):
                   0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                   None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]),
                   None, _dptr(o["alpha"]), None, 0, None, _dptr(o.get("plan")))
-        if self.sized:
+        if self.agents:
+            mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
+            sz = ctypes.byref(self._sizes()) if self.sized else None
+            _check(lib().srb_rollout_agents_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), mv, sz,
+                                                   ctypes.byref(self._agent_sizes()), T, s._stream(stream)))
+        elif self.sized:
             mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
             _check(lib().srb_rollout_sized_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), mv,
                                                   ctypes.byref(self._sizes()), T, s._stream(stream)))
@@ -338,7 +385,10 @@ def reduce_scenes(res, scene_agents: int):
     S = A // sa
     st = res["status"]                                       # [T][A][2]
     ok = ((st[..., 0] == 0) | (st[..., 0] == 4)) & (st[..., 1] == 0)
-    return dict(n_scenes=S, scene_agents=sa,
-                min_d_agent=res["min_d_agent"].view(S, sa).amin(1), min_d_obs=res["min_d_obs"].view(S, sa).amin(1),
-                n_failed=(res["fail_cycle"].view(S, sa) >= 0).sum(1),
-                n_not_converged=(~ok).view(st.shape[0], S, sa).sum((0, 2)))
+    out = dict(n_scenes=S, scene_agents=sa,
+               min_d_agent=res["min_d_agent"].view(S, sa).amin(1), min_d_obs=res["min_d_obs"].view(S, sa).amin(1),
+               n_failed=(res["fail_cycle"].view(S, sa) >= 0).sum(1),
+               n_not_converged=(~ok).view(st.shape[0], S, sa).sum((0, 2)))
+    if "collide_cycle" in res:                               # agent bodies (Rollout(agent_body=...))
+        out["n_collided"] = (res["collide_cycle"].view(S, sa) >= 0).sum(1)
+    return out

@@ -106,6 +106,20 @@ def obstacle_sizes(n_obs: int, seed: int):
     return eps, FAIL_RADIUS * np.sqrt(eps / EPS_OBS)
 
 
+EPS_NBR = float(np.float32(2.2))      # srb_params.eps_nbr, (double)2.2f: the reference's one inter-agent level
+
+
+def agent_sizes(n_all: int, seed: int):
+    """(rad, pad, body), each [n_all], for a team of agents of different sizes (BatchSolver.solve(agent_rad=...,
+    agent_pad=...), Rollout(agent_rad=..., agent_pad=..., agent_body=...)), deterministic per seed: the safety radii
+    rad ~ U[0.39, 0.94] m (pair levels (rad_a + rad_b)^2 between about 0.61 and 3.5, the range of obstacle_sizes),
+    the pads rad - sqrt(eps_nbr) / 2 (what the agent's radius differs by from the reference's uniform one) and the
+    body radii 0.5 rad / sqrt(eps_obs), the reference's ratio of fail radius to safety radius.  From a generator of
+    their own (300 + seed), so every other draw of this module is what it was."""
+    rad = np.random.default_rng(300 + seed).uniform(0.39, 0.94, n_all)
+    return rad, rad - np.sqrt(EPS_NBR) / 2, FAIL_RADIUS * rad / np.sqrt(EPS_OBS)
+
+
 SCENE_MAX_ATTEMPTS = 1000     # start draws per scene (make_scenes) before the clearance counts as impossible
 
 
