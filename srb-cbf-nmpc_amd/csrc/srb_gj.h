@@ -13,9 +13,11 @@
 // Rows may be replicated: with NZL <= 16 (and SRB_USE_DPP) every 16-lane row of the wave holds
 // the whole matrix (lane l: matrix row l & 15) for the DPP solves that follow (la_solve); the
 // broadcasts read the first copy, and each copy applies the same operations (bit-identical).
-// A DPP row_newbcast form of this elimination (gj_invert_dpp) measured slower on MI355X: 3546
-// against 3062 cycles for NZL = 12 (tools/ubench/gj_bench.hip), since readlane broadcasts land
-// in SGPRs that the row updates read for free while the DPP copies cost a VALU move each.
+// The solve kernels call gj_factor (below), which takes the DPP row_newbcast form of this elimination
+// (gj_invert_dpp) where the rows are replicated: 2642 against 3062 cycles for NZL = 12 on MI355X
+// (tools/ubench/gj_bench.hip; 3546 while the broadcast still zeroed its destination first).  A step here is
+// 22 v_readlane_b32 and 11 FMAs plus the pivot chain; the chain's dependent FMAs issue at the full 4-cycle
+// rate, so interleaving them with the step's bulk gains nothing (profiles/factor_chain_ubench.txt).
 __device__ __forceinline__ float readlane_f(float v, int lane)
 {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
@@ -91,24 +93,27 @@ __device__ __forceinline__ int gj_invert(double (&A)[NZL], int nz, int lane, int
 // entry that the row update consumes directly, so a step's critical path is the pivot's
 // broadcast, reciprocal and multiplier, not the v_readlane -> SGPR -> VALU latency.  Same
 // arithmetic as the readlane form above (bit-identical results).
-template <int NZL>
+// NZE as in gj_invert.  The pivots are per-lane values here (the same in every lane: each 16-lane row holds the
+// same matrix), so the failure test is kept as a lane mask in SGPRs and the result is wave-uniform.
+template <int NZL, int NZE = NZL>
 __device__ __forceinline__ int gj_invert_dpp(double (&A)[NZL], int lane, int regularise)
 {
     static_assert(NZL <= 16, "row_newbcast reaches within 16 lanes");
+    static_assert(NZE <= NZL, "NZE");
     const int r = lane & 15;
-    int fail = 0;
+    unsigned long long fail = 0;
     double cs = 1.0;
 #pragma unroll
-    for (int k = 0; k < NZL; k++) {
+    for (int k = 0; k < NZE; k++) {
         double piv = bc16(A[k], k);
         if (regularise && piv <= 1e-14 && piv == piv) piv = 1e-7;
-        fail |= !(piv > 0.0);
+        fail |= __ballot(!(piv > 0.0));
         const double inv = rcp_d(piv);
         const bool me = r == k;
         const double f = me ? 0.0 : A[k] * inv;
 #pragma unroll
-        for (int jj = 0; jj < NZL; jj++) {
-            const int j = (k + 1 + jj) % NZL;           // next pivot row's entries first
+        for (int jj = 0; jj < NZE; jj++) {
+            const int j = (k + 1 + jj) % NZE;           // next pivot row's entries first
             if (j != k) A[j] = fma(-f, bc16(A[j], k), A[j]);
         }
         A[k] = me ? 1.0 : -f;
@@ -116,5 +121,16 @@ __device__ __forceinline__ int gj_invert_dpp(double (&A)[NZL], int lane, int reg
     }
 #pragma unroll
     for (int j = 0; j < NZL; j++) A[j] *= cs;
-    return fail;
+    return fail != 0;
+}
+
+// The inverse of the solve kernels' reduced Newton matrix: the DPP form where the rows are replicated in every
+// 16-lane row of the wave (NZL <= 16 under SRB_USE_DPP, gj_load / mrow), else the readlane form.  With
+// row_newbcast as one v_mov_b64_dpp (bc16) the DPP form is the faster one: 2638 against 3062 cycles for
+// NZL = 12 (tools/ubench/gj_bench.hip, profiles/factor_chain_ubench.txt), and it holds no pivot row in SGPRs.
+template <int NZL, int NZE = NZL>
+__device__ __forceinline__ int gj_factor(double (&A)[NZL], int nz, int lane, int regularise)
+{
+    if constexpr (NZL <= 16 && SRB_USE_DPP) return gj_invert_dpp<NZL, NZE>(A, lane, regularise);
+    else return gj_invert<NZL, NZE>(A, nz, lane, regularise);
 }

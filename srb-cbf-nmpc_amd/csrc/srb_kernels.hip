@@ -1590,7 +1590,7 @@ _Pragma("unroll")                                                               
             SYNC();                                                                                                                           \
             if (pass == 0 && pit == 0) POLDBG_MAT(H0, LDH, vg, nz);                                                                           \
             gj_load<NZL, NZE>(Mi, H0, ZZ, 0.0, nz, lane);                                                                                          \
-            if (gj_invert<NZL, NZE>(Mi, nz, lane, 0) != 0) { bad = true; break; } /* not PD: reject */                                            \
+            if (gj_factor<NZL, NZE>(Mi, nz, lane, 0) != 0) { bad = true; break; } /* not PD: reject */                                            \
             la_solve<NZL, NW, NZE>(Mi, H0, ZZ, 0.0, vg, vy, vr, vd, dxi, nz, lane);                                                                    \
             double mdx = 0.0;                                                                                                                 \
 _Pragma("unroll")                                                                                                                             \
@@ -1780,7 +1780,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
             gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, H0, vg, nz, tid, part, bmask);
             SYNC();
             gj_load<NZL, NZE>(Mi, H0, ZZ, 0.0, nz, lane);
-            if (gj_invert<NZL, NZE>(Mi, nz, lane, 1) != 0) {
+            if (gj_factor<NZL, NZE>(Mi, nz, lane, 1) != 0) {
                 qp_flag = 1;                                  // x stays xbar (last iterate is returned)
                 continue;
             }
@@ -1914,7 +1914,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
             gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, ZZ, vg, nz, tid, part, bmask);
             SYNC();
             gj_load<NZL, NZE>(Mi, ZZ, ZZ, 0.0, nz, lane);
-            gj_invert<NZL, NZE>(Mi, nz, lane, 0);
+            gj_factor<NZL, NZE>(Mi, nz, lane, 0);
             la_solve<NZL, NW, NZE>(Mi, ZZ, ZZ, 0.0, vg, vy, vr, vd, dxi, nz, lane);
 #pragma unroll
             for (int t = 0; t < TS; t++)
@@ -2139,20 +2139,31 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                 gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, H0, vg, nz, tid, part, bmask);
                 SYNC();
                 STAMP_END(4);
-                double dstart = 0.0;
                 int ok = 0;
-                for (int tries = 0; tries < (nl ? 14 : 1); tries++) {
-                    if (tries == 0) {       // scale-aware first shift: 1e-10 * max(1, max diag of Z'HZ)
-                        const double dm = (lane < nz) ? H0[lane * LDH + lane] : 1.0;
-                        dstart = 1e-10 * fmax(1.0, wmax(dm));
-                    }
+                const int ntries = nl ? 14 : 1;
+                for (int tries = 0; tries < ntries; tries++) {
                     // the QP stage never shifts: ZZ may still hold the obstacle positions there (SRB_OBS_IN_ZZ)
                     LCK(nl || delta == 0.0, 7);
                     gj_load<NZL, NZE>(Mi, H0, ZZ, delta, nz, lane);    // H0 + delta Z'Z (the solves shift on the fly too)
                     // KF instances: the inverse in fp32 while mu > kkt32_mu (then nref fp64 refinement steps per solve)
-                    const int cf = (KF && f32) ? gj_invert_f32<NZL>(Mi, mrow<NZL>(lane), !nl) : gj_invert<NZL, NZE>(Mi, nz, lane, !nl);
+                    int cf = (KF && f32) ? gj_invert_f32<NZL>(Mi, mrow<NZL>(lane), !nl) : gj_factor<NZL, NZE>(Mi, nz, lane, !nl);
+#ifdef SRB_DIAG_FORCE_SHIFT        // diagnostic builds only: every NLP iteration's first factorisation counts as failed,
+#ifndef SRB_DIAG_BUILD             // so the shift path runs (no batch found so far reaches it; profiles/factor_chain_ab.txt)
+#error "SRB_DIAG_FORCE_SHIFT is a diagnostic-build option"
+#endif
+                    if (nl && tries == 0) cf = 1;
+#endif
                     if (cf == 0) { ok = 1; break; }
-                    delta = (delta == 0.0) ? dstart : delta * 10.0;
+                    if (tries + 1 == ntries) break;             // no factorisation follows: no shift to form
+                    if (delta == 0.0) {
+                        // scale-aware first shift: 1e-10 * max(1, max diag of Z'HZ), formed only here, at the first
+                        // failure (a wave reduction; the branch is uniform: cf comes from broadcast pivots, and with
+                        // NW > 1 every wave factors the same H0, which nothing has written since the Gram)
+                        const double dm = (lane < nz) ? H0[lane * LDH + lane] : 1.0;
+                        delta = 1e-10 * fmax(1.0, wmax(dm));
+                    } else {
+                        delta *= 10.0;
+                    }
                 }
                 STAMP_END(5);
                 if (!ok) { flag = 1; break; }
