@@ -525,7 +525,8 @@ int srb_rollout_sized_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io
  * collide_cycle without agent_body.  The QP-only solve ignores the tables.  host_ag holds host pointers (agent_rad and
  * agent_pad are staged; agent_body and collide_cycle are not read by a solve), ag device pointers.
  * srb_rollout_agents_device refuses a shard, as srb_rollout_device does; the tables do not change over a rollout.
- * The SRB-12 mode and the MPC_dist shims have no agent sizes.
+ * The SRB-12 mode takes the same struct through srb12_*_agents* entry points of its own (below, after the
+ * srb12_*_sized block); the MPC_dist shims have no agent sizes.
  */
 typedef struct srb_agent_sizes {
     int struct_size;            /* sizeof(srb_agent_sizes) (ABI check) */
@@ -901,6 +902,42 @@ int srb12_sim_metrics_sized_device(srb12_ctx *ctx, int n_agents, const srb12_sim
 int srb12_rollout_sized_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
                                const srb12_plans *plans, const srb_moving *mv, const srb_sizes *sz, int cycles,
                                void *stream);
+
+/*
+ * Agent sizes in the SRB-12 mode (DESIGN.md 3 "Agent sizes", 10.11): srb_agent_sizes (above), its members with the
+ * meaning they have in the LIP mode.  Each entry point takes what the srb12_*_sized entry point it extends takes
+ * (`plans`, `mv` and `sz` may be NULL, as there) plus the srb_agent_sizes.  Every table has n_all rows in the row order
+ * of nbr_state (scene-major with scenes); global agent g = agent_offset + a owns row g.  What differs from the LIP block:
+ *   agent_rad   the level of neighbour column j (K_obs <= j < K, sel[j] >= 0) of the NLP stage is
+ *               (agent_rad[g] + agent_rad[sel[j]])^2, set by the srb12_kernel_mv_* instances, which any of the four
+ *               tables selects; a -1 column keeps eps_nbr.  The column's positions are the snapshot's or nbr_plan's,
+ *               as without.
+ *   agent_pad   the level of static column j < K_obs becomes (sqrt(e_j) + agent_pad[g])^2, e_j the level after the
+ *               obs_eps gather (eps_obs, or obs_eps[sel[j]]); a -1 column is included.
+ *   agent_body, collide_cycle  the metrics are those of srb_sim_metrics_agents_device on the srb12_sim.com rows.
+ *   clearance_selection = 1  srb_knn_nbr_clear_kernel (with srb12_ctx_set_scenes its scene form) on the agent's CoM
+ *               row (x0[0], x0[6], x0[1], x0[7]); with plans->plan_selection = 1 and a plan table the key's distance is
+ *               the horizon's minimum.  The static columns as the _sized call selects them.
+ * There is no srb12 select entry point: the solve runs the selection itself.  With ag == NULL, or every member NULL / 0,
+ * each call is the srb12_*_sized entry point it extends, output bits included.  SRB_ERR_ARG, by name and before
+ * anything is launched: the refusals of srb_agent_sizes (LIP block), which need no context -- "has a neighbour table"
+ * is the srb12_batch's nbr_state and n_all > 0, for the metrics the srb12_sim's --; with agent_rad or agent_pad,
+ * agent_offset < 0 or agent_offset + n_agents > n_all (the kernel reads row agent_offset + a of both unchecked); and
+ * everything the extended entry point refuses.  The QP-only solve ignores the tables.  srb12_rollout_agents_device:
+ * the sequence of srb12_rollout_sized_device per cycle with the agents metrics, selection and solve; it refuses a
+ * shard, as srb12_rollout_device does; the tables do not change over a rollout.  host_ag holds host pointers
+ * (agent_rad and agent_pad are staged, n_all rows each; agent_body and collide_cycle are not read by a solve), ag
+ * device pointers.
+ */
+int srb12_solve_batch_agents(srb12_ctx *ctx, int n_agents, const srb12_batch *host_io, const srb12_plans *host_plans,
+                             const srb_moving *host_mv, const srb_sizes *host_sz, const srb_agent_sizes *host_ag);
+int srb12_solve_batch_agents_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_plans *plans,
+                                    const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag, void *stream);
+int srb12_sim_metrics_agents_device(srb12_ctx *ctx, int n_agents, const srb12_sim *sim, const srb_sizes *sz,
+                                    const srb_agent_sizes *ag, int cycle, void *stream);
+int srb12_rollout_agents_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
+                                const srb12_plans *plans, const srb_moving *mv, const srb_sizes *sz,
+                                const srb_agent_sizes *ag, int cycles, void *stream);
 
 const char *srb_last_error(void);
 

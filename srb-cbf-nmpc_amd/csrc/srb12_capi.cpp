@@ -19,11 +19,13 @@
 typedef void (*srb12_fn)(Srb12KParams, int, const double *, const double *, const double *, const int *,
                          const double *, const double *, const int *, double *, double *, double *, int *, int *,
                          const double *, double *);
-// the instance's obstacle-table kernel (srb12_kernel_mv_*): two more arguments, the velocity table of srb_moving and the
-// level table of srb_sizes (either may be null)
+// the instance's table kernel (srb12_kernel_mv_*): five more arguments, the velocity table of srb_moving, the level
+// table of srb_sizes, the radius and pad tables of srb_agent_sizes (each may be null) and the agent_offset of the agent
+// tables' own row
 typedef void (*srb12_mv_fn)(Srb12KParams, int, const double *, const double *, const double *, const int *,
                             const double *, const double *, const int *, double *, double *, double *, int *, int *,
-                            const double *, double *, const double *, const double *);
+                            const double *, double *, const double *, const double *, const double *, const double *,
+                            int);
 struct srb12_inst { int tl, to, nc, k1; srb12_fn fn; srb12_mv_fn fn_mv; };
 #define ENTRY12(TL, TO, NC, K1) {TL, TO, NC, K1, srb12_kernel_##TL##_##TO##_##NC##_##K1, srb12_kernel_mv_##TL##_##TO##_##NC##_##K1},
 static const srb12_inst g_inst12[] = {SRB12_INSTANCES(ENTRY12)};
@@ -49,6 +51,8 @@ struct srb12_ctx {
     size_t cap_vel;
     double *obs_eps;               // staged obstacle levels [cap_eps bytes] (srb12_solve_batch_sized)
     size_t cap_eps;
+    double *agent_rad, *agent_pad; // staged agent tables [cap_rad / cap_pad bytes] (srb12_solve_batch_agents)
+    size_t cap_rad, cap_pad;
     int dbg_agent;                 // diagnostics: srb12_debug_trace
     double *dbg;
 };
@@ -176,7 +180,7 @@ extern "C" int srb12_ctx_destroy(srb12_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     (void)c->order.wait_idle();
     void *bufs[] = {c->dbg, c->pos, c->sel, c->x0, c->xref, c->foot, c->contact, c->obstacles, c->nbr, c->x_qp, c->x, c->obj,
-                    c->status, c->iters, c->nbr_plan, c->plan, c->obs_vel, c->obs_eps};
+                    c->status, c->iters, c->nbr_plan, c->plan, c->obs_vel, c->obs_eps, c->agent_rad, c->agent_pad};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (int i = 0; i < 3; i++)
@@ -236,10 +240,12 @@ static int check_moving12(const srb_moving *mv, const srb12_batch *b, bool rollo
 
 // pl: the plan members of this launch (NULL: none, the launch of srb12_solve_batch[_device] as ever); obs_vel /
 // obs_horizon: the members of srb_moving (null / 0: static obstacles, every launch as before); obs_eps / obs_clear:
-// those of srb_sizes (null / 0: eps_obs for every row, the selection as before)
+// those of srb_sizes (null / 0: eps_obs for every row, the selection as before); agent_rad / agent_pad / nbr_clear:
+// those of srb_agent_sizes (null / 0: eps_nbr and the levels as they are, the selection as before)
 static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_t s, const srb12_plans *pl = nullptr,
                     const double *obs_vel = nullptr, int obs_horizon = 0, const double *obs_eps = nullptr,
-                    int obs_clear = 0)
+                    int obs_clear = 0, const double *agent_rad = nullptr, const double *agent_pad = nullptr,
+                    int nbr_clear = 0)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -252,6 +258,9 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         return srb_internal_fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
     if (pl && pl->nbr_plan && p->K_nbr > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return srb_internal_fail(SRB_ERR_ARG, "nbr_plan: agent_offset + n_agents exceeds n_all (the plan table's rows)");
+    // (the kernel reads row agent_offset + agent of the agent tables unchecked)
+    if (p->use_nlp && (agent_rad || agent_pad) && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
+        return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes: agent_offset + n_agents exceeds n_all (the agent tables' rows)");
     if (pl && pl->plan) {
         const size_t rows = (size_t)n_agents * 2 * p->N;
         if (srb_overlap(pl->plan, rows, pl->nbr_plan, (size_t)(d->n_all > 0 ? d->n_all : 0) * 2 * p->N) ||
@@ -266,6 +275,9 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     // (the velocities are read by the NLP stage's static rows only, through sel)
     const double *vel = (p->use_nlp && Ko > 0) ? obs_vel : nullptr;
     const double *eps = (p->use_nlp && Ko > 0) ? obs_eps : nullptr;   // likewise (the QP-only solve ignores both)
+    const double *pad = (p->use_nlp && Ko > 0) ? agent_pad : nullptr; // likewise
+    // (the radii are read by the NLP stage's neighbour columns only, through sel and at the agent's own row)
+    const double *rad = (p->use_nlp && Kn > 0) ? agent_rad : nullptr;
     Srb12KParams k = make_k12(p, Ko, Kn);
     k.dbg_agent = c->dbg_agent; k.dbg = c->dbg;
     const srb12_inst *in = pick12(p->N, Ko + Kn);
@@ -279,19 +291,18 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         int rc = srb_internal_select(c->sel_ctx, n_agents, c->pos, d->obstacles, Ko > 0 ? d->n_obs : 0, d->nbr_state,
                                      Kn > 0 ? d->n_all : 0, d->agent_offset, Ko, Kn, d->obstacles_version, sel, s,
                                      pl && pl->plan_selection ? nbr_plan : nullptr, p->N, vel, vel ? obs_horizon : 0, p->Ts,
-                                     eps, eps ? obs_clear : 0);
+                                     eps, eps ? obs_clear : 0, rad, rad ? nbr_clear : 0);
         if (rc) return rc;
         // the selection context's own ordering event: its grid buffers are reallocated only after
         // this launch (grid_reserve waits on it)
         if ((rc = srb_internal_mark_done(c->sel_ctx, s))) return rc;
     }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[1], s));
-    // with a velocity or a level table the instance's obstacle-table kernel (two more arguments); without, the launch
-    // as ever
-    if (vel || eps)
+    // with any of the four tables the instance's table kernel (five more arguments); without, the launch as ever
+    if (vel || eps || rad || pad)
         hipLaunchKernelGGL(in->fn_mv, dim3(n_agents), dim3(64), lds, s, k, n_agents, d->x0, d->xref, d->foot, d->contact,
                            d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters,
-                           nbr_plan, pl ? pl->plan : nullptr, vel, eps);
+                           nbr_plan, pl ? pl->plan : nullptr, vel, eps, rad, pad, d->agent_offset);
     else
         hipLaunchKernelGGL(in->fn, dim3(n_agents), dim3(64), lds, s, k, n_agents, d->x0, d->xref, d->foot, d->contact,
                            d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters, nbr_plan,
@@ -302,12 +313,20 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     return SRB_OK;
 }
 
+// the batch has a neighbour table (what srb_agent_sizes.agent_rad / agent_body need)
+static bool has_nbr12(const srb12_batch *b)
+{
+    return b && b->struct_size == (int)sizeof(srb12_batch) && b->nbr_state && b->n_all > 0;
+}
+
 static int solve_device12(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl, bool plans, void *stream,
-                          const srb_moving *mv = nullptr, const srb_sizes *sz = nullptr)
+                          const srb_moving *mv = nullptr, const srb_sizes *sz = nullptr,
+                          const srb_agent_sizes *ag = nullptr)
 {
     if (int rc = srb_check_struct(d, "srb12_batch")) return rc;
     if (int rc0 = check_moving12(mv, d, false)) return rc0;
     if (int rc0 = srb_check_sizes(sz)) return rc0;
+    if (int rc0 = srb_check_agent_sizes(ag, has_nbr12(d))) return rc0;
     if (plans)
         if (int rc = check_plans12(d, pl, false)) return rc;
     if (!c || !d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
@@ -315,17 +334,25 @@ static int solve_device12(srb12_ctx *c, int n_agents, const srb12_batch *d, cons
     hipStream_t s = (hipStream_t)stream;
     int rc = c->order.order_after_last(s);
     if (!rc) rc = launch12(c, n_agents, d, s, pl, mv ? mv->obs_vel : nullptr, mv ? mv->horizon_selection : 0,
-                           sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0);
+                           sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0, ag ? ag->agent_rad : nullptr,
+                           ag ? ag->agent_pad : nullptr, ag ? ag->clearance_selection : 0);
     if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
 }
 
-// pl and mv may be NULL, as in srb12_solve_batch_moving_device; sz NULL (or without a table): that entry point itself.
-// (The _moving entry points are the _sized ones without a table: one path.)
+// pl, mv and sz may be NULL, as in srb12_solve_batch_sized_device; ag NULL (or without a table): that entry point itself.
+// (The _sized and the _moving entry points are the _agents ones without a table: one path.)
+extern "C" int srb12_solve_batch_agents_device(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl,
+                                               const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
+                                               void *stream)
+{
+    return solve_device12(c, n_agents, d, pl, pl != nullptr, stream, mv, sz, ag);
+}
+
 extern "C" int srb12_solve_batch_sized_device(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl,
                                               const srb_moving *mv, const srb_sizes *sz, void *stream)
 {
-    return solve_device12(c, n_agents, d, pl, pl != nullptr, stream, mv, sz);
+    return srb12_solve_batch_agents_device(c, n_agents, d, pl, mv, sz, nullptr, stream);
 }
 
 extern "C" int srb12_solve_batch_device(srb12_ctx *c, int n_agents, const srb12_batch *d, void *stream)
@@ -348,11 +375,13 @@ extern "C" int srb12_solve_batch_moving_device(srb12_ctx *c, int n_agents, const
 
 // hp: the host plan members (NULL: srb12_solve_batch); the table and the plans are staged like the other buffers
 static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp, bool plans,
-                        const srb_moving *hmv = nullptr, const srb_sizes *hsz = nullptr)
+                        const srb_moving *hmv = nullptr, const srb_sizes *hsz = nullptr,
+                        const srb_agent_sizes *hag = nullptr)
 {
     if (int rc = srb_check_struct(h, "srb12_batch")) return rc;
     if (int rc0 = check_moving12(hmv, h, false)) return rc0;
     if (int rc0 = srb_check_sizes(hsz)) return rc0;
+    if (int rc0 = srb_check_agent_sizes(hag, has_nbr12(h))) return rc0;
     if (plans)
         if (int rc = check_plans12(h, hp, false)) return rc;
     if (!c || !h) return srb_internal_fail(SRB_ERR_ARG, "null argument");
@@ -421,8 +450,25 @@ static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const 
         HIPCHK(hipMemcpyAsync(c->obs_eps, hsz->obs_eps, bytes, hipMemcpyHostToDevice, s));
         eps = c->obs_eps;
     }
+    // the agent tables likewise, n_all rows each (srb12_solve_batch_agents); the QP-only solve reads neither
+    const double *rad = nullptr, *pad = nullptr;
+    if (c->p.use_nlp && hag && (hag->agent_rad || hag->agent_pad)) {
+        if (h->agent_offset < 0 || h->agent_offset + n_agents > h->n_all)    // launch12's refusal, before the copies
+            return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes: agent_offset + n_agents exceeds n_all (the agent tables' rows)");
+        const size_t bytes = (size_t)h->n_all * sizeof(double);
+        if (hag->agent_rad) {
+            if (int rc = srb_stage_reserve(c->order, c->agent_rad, c->cap_rad, bytes)) return rc;
+            HIPCHK(hipMemcpyAsync(c->agent_rad, hag->agent_rad, bytes, hipMemcpyHostToDevice, s));
+            rad = c->agent_rad;
+        }
+        if (hag->agent_pad) {
+            if (int rc = srb_stage_reserve(c->order, c->agent_pad, c->cap_pad, bytes)) return rc;
+            HIPCHK(hipMemcpyAsync(c->agent_pad, hag->agent_pad, bytes, hipMemcpyHostToDevice, s));
+            pad = c->agent_pad;
+        }
+    }
     int rc = launch12(c, n_agents, &d, s, hp ? &dp : nullptr, vel, vel ? hmv->horizon_selection : 0, eps,
-                      eps ? hsz->clearance_selection : 0);
+                      eps ? hsz->clearance_selection : 0, rad, pad, rad ? hag->clearance_selection : 0);
     if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->x_qp) HIPCHK(hipMemcpyAsync(h->x_qp, c->x_qp, A * nv * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -462,7 +508,14 @@ extern "C" int srb12_solve_batch_moving(srb12_ctx *c, int n_agents, const srb12_
 extern "C" int srb12_solve_batch_sized(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp,
                                        const srb_moving *hmv, const srb_sizes *hsz)
 {
-    return solve_host12(c, n_agents, h, hp, hp != nullptr, hmv, hsz);
+    return srb12_solve_batch_agents(c, n_agents, h, hp, hmv, hsz, nullptr);
+}
+
+// hp, hmv and hsz may be NULL, as in srb12_solve_batch_sized; hag NULL (or without a table): that entry point itself
+extern "C" int srb12_solve_batch_agents(srb12_ctx *c, int n_agents, const srb12_batch *h, const srb12_plans *hp,
+                                        const srb_moving *hmv, const srb_sizes *hsz, const srb_agent_sizes *hag)
+{
+    return solve_host12(c, n_agents, h, hp, hp != nullptr, hmv, hsz, hag);
 }
 
 extern "C" int srb12_ctx_set_timing(srb12_ctx *c, int on)
@@ -528,9 +581,10 @@ static int launch_advance12(srb12_ctx *c, int n_agents, const srb12_sim *d, int 
 }
 
 // the metrics of the LIP rollout (srb_sim_metrics_kernel, with scenes srb_sim_scene_metrics_kernel) on the com rows;
-// radius: srb_sizes.obs_radius (null: the centre distances and the 0.5 m fail test, the kernels as ever)
+// radius: srb_sizes.obs_radius (null: the centre distances and the 0.5 m fail test, the kernels as ever); body /
+// collide: srb_agent_sizes.agent_body and collide_cycle (body null: d_agent by centres, the kernels as ever)
 static int launch_metrics12(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, hipStream_t s,
-                            const double *radius = nullptr)
+                            const double *radius = nullptr, const double *body = nullptr, int *collide = nullptr)
 {
     if (!d->com) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim: missing buffer (com)");
     if (d->n_obs < 0 || d->n_all < 0 || (d->n_obs > 0 && !d->obstacles) || (d->n_all > 0 && !d->nbr_state))
@@ -543,21 +597,23 @@ static int launch_metrics12(srb12_ctx *c, int n_agents, const srb12_sim *d, int 
     m.n_obs = d->n_obs; m.n_all = d->n_all; m.agent_offset = d->agent_offset;
     m.d_obs = d->d_obs; m.d_agent = d->d_agent; m.min_d_obs = d->min_d_obs; m.min_d_agent = d->min_d_agent;
     m.fail_cycle = d->fail_cycle; m.distance_to_fail = d->distance_to_fail;
-    return srb_internal_sim_metrics(c->sel_ctx, n_agents, &m, cycle, s, radius);
+    return srb_internal_sim_metrics(c->sel_ctx, n_agents, &m, cycle, s, radius, body, collide);
 }
 
 static int sim12_call(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream, bool advance,
-                      const srb_sizes *sz = nullptr)
+                      const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr)
 {
     if (int rc = check_sim12(d, cycle, advance)) return rc;
     if (int rc = srb_check_sizes(sz)) return rc;
+    if (int rc = srb_check_agent_sizes(ag, d->nbr_state && d->n_all > 0)) return rc;
     if (!c) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
     hipStream_t s = (hipStream_t)stream;
     return c->order.run(c->device, s, [&] {
         return advance ? launch_advance12(c, n_agents, d, cycle, s)
-                       : launch_metrics12(c, n_agents, d, cycle, s, sz ? sz->obs_radius : nullptr);
+                       : launch_metrics12(c, n_agents, d, cycle, s, sz ? sz->obs_radius : nullptr,
+                                          ag ? ag->agent_body : nullptr, ag ? ag->collide_cycle : nullptr);
     });
 }
 
@@ -566,10 +622,16 @@ extern "C" int srb12_sim_advance_device(srb12_ctx *c, int n_agents, const srb12_
     return sim12_call(c, n_agents, d, cycle, stream, true);
 }
 
+extern "C" int srb12_sim_metrics_agents_device(srb12_ctx *c, int n_agents, const srb12_sim *d, const srb_sizes *sz,
+                                               const srb_agent_sizes *ag, int cycle, void *stream)
+{
+    return sim12_call(c, n_agents, d, cycle, stream, false, sz, ag);
+}
+
 extern "C" int srb12_sim_metrics_sized_device(srb12_ctx *c, int n_agents, const srb12_sim *d, const srb_sizes *sz,
                                               int cycle, void *stream)
 {
-    return sim12_call(c, n_agents, d, cycle, stream, false, sz);
+    return srb12_sim_metrics_agents_device(c, n_agents, d, sz, nullptr, cycle, stream);
 }
 
 extern "C" int srb12_sim_metrics_device(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream)
@@ -616,13 +678,16 @@ extern "C" int srb12_obstacles_advance_device(srb12_ctx *c, int n_obs, double *o
 
 // pl: the plans fed forward (srb12_rollout_plans_device), or NULL (srb12_rollout_device: today's launches); mv: the
 // moving obstacles (srb12_rollout_moving_device), or NULL; sz: the obstacle sizes (srb12_rollout_sized_device), or
-// NULL -- the tables do not change over a rollout: the same pointers serve every cycle
+// NULL; ag: the agent sizes (srb12_rollout_agents_device), or NULL -- the tables do not change over a rollout: the same
+// pointers serve every cycle
 static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, const srb12_plans *pl,
-                     bool plans, int cycles, void *stream, const srb_moving *mv = nullptr, const srb_sizes *sz = nullptr)
+                     bool plans, int cycles, void *stream, const srb_moving *mv = nullptr, const srb_sizes *sz = nullptr,
+                     const srb_agent_sizes *ag = nullptr)
 {
     if (int rc = srb_check_struct(b, "srb12_batch")) return rc;
     if (int rc0 = check_moving12(mv, b, true)) return rc0;
     if (int rc0 = srb_check_sizes(sz)) return rc0;
+    if (int rc0 = srb_check_agent_sizes(ag, true)) return rc0;    // (the driver's neighbour table is the team itself)
     if (plans)
         if (int rc = srb_check_struct(pl, "srb12_plans")) return rc;
     // (the layout and null checks of check_sim12 only: the driver's first cycle is c_first itself)
@@ -669,21 +734,25 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
     const int hsel = mv ? mv->horizon_selection : 0;
     const double *eps = sz ? sz->obs_eps : nullptr, *radius = sz ? sz->obs_radius : nullptr;
     const int csel = sz ? sz->clearance_selection : 0;
+    const double *rad = ag ? ag->agent_rad : nullptr, *pad = ag ? ag->agent_pad : nullptr;
+    const double *body = ag ? ag->agent_body : nullptr;
+    int *collide = ag ? ag->collide_cycle : nullptr;
+    const int nsel = ag ? ag->clearance_selection : 0;
     for (int i = 0; i <= cycles && !rc; i++) {
         const int cyc = d->c_first + i;
         rc = launch_advance12(c, n_agents, &sim, cyc, s);
         if (rc || i == cycles) break;
         if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
-        if (!rc) rc = launch_metrics12(c, n_agents, &sim, cyc, s, radius);
+        if (!rc) rc = launch_metrics12(c, n_agents, &sim, cyc, s, radius, body, collide);
         if (!pl) {
-            if (!rc) rc = launch12(c, n_agents, &bat, s, nullptr, vel, hsel, eps, csel);
+            if (!rc) rc = launch12(c, n_agents, &bat, s, nullptr, vel, hsel, eps, csel, rad, pad, nsel);
             continue;
         }
         // the first solve against the caller's table (or none), every later one against last cycle's shifted plans
         srb12_plans cur = *pl;
         if (i > 0) cur.nbr_plan = pl->plan_table;
         if (!cur.nbr_plan) cur.plan_selection = 0;
-        if (!rc) rc = launch12(c, n_agents, &bat, s, &cur, vel, hsel, eps, csel);
+        if (!rc) rc = launch12(c, n_agents, &bat, s, &cur, vel, hsel, eps, csel, rad, pad, nsel);
         if (!rc) rc = launch_shift12(c, n_agents, pl->plan, SRB12_SIM_NDOMAIN, pl->plan_table, s);
     }
     const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier cycles run
@@ -714,7 +783,15 @@ extern "C" int srb12_rollout_sized_device(srb12_ctx *c, int n_agents, const srb1
                                           const srb12_plans *pl, const srb_moving *mv, const srb_sizes *sz, int cycles,
                                           void *stream)
 {
-    return rollout12(c, n_agents, b, d, pl, pl != nullptr, cycles, stream, mv, sz);
+    return srb12_rollout_agents_device(c, n_agents, b, d, pl, mv, sz, nullptr, cycles, stream);
+}
+
+// pl, mv and sz may be NULL, as in srb12_rollout_sized_device; ag NULL (or without a table): that entry point itself
+extern "C" int srb12_rollout_agents_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d,
+                                           const srb12_plans *pl, const srb_moving *mv, const srb_sizes *sz,
+                                           const srb_agent_sizes *ag, int cycles, void *stream)
+{
+    return rollout12(c, n_agents, b, d, pl, pl != nullptr, cycles, stream, mv, sz, ag);
 }
 
 // diagnostics (not in the public header): agent >= 0 records a per-iteration trace on the next

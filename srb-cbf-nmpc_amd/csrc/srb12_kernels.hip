@@ -225,7 +225,7 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
         double *__restrict__ x_qp_out, double *__restrict__ x_out, double *__restrict__ obj_out,
         int *__restrict__ status_out, int *__restrict__ iters_out, const double *__restrict__ nbr_plan,
         double *__restrict__ plan_out, const double *__restrict__ obs_vel, const double *__restrict__ obs_eps,
-        double *lds)
+        const double *__restrict__ agent_rad, const double *__restrict__ agent_pad, int agent_offset, double *lds)
 {
     const int tid = threadIdx.x, lane = tid;
     const int N = NC > 0 ? NC : prm.N, K = K1 > 0 ? K1 - 1 : prm.K_obs + prm.K_nbr;
@@ -333,6 +333,27 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
     // the neighbour columns keep eps_nbr.  With scenes sel holds global rows.  The QP-only solve never reads the table.
     if (MV && obs_eps && prm.use_nlp) {
         if (tid < prm.K_obs && L.sel[tid] >= 0) L.eps[tid] = obs_eps[L.sel[tid]];
+    }
+    // agent sizes (srb_agent_sizes.agent_rad / agent_pad; the srb12_kernel_mv_* instances only, kernel arguments: the
+    // branches are wave-uniform), rad then pad, each lane again on the entry it wrote itself, so no barrier is added
+    // here either.  rad: the level of neighbour column j is the squared sum of the agent's own safety radius (table
+    // row agent_offset + agent, which the host has checked against n_all) and the neighbour's (row sel[j]); a -1 column
+    // keeps eps_nbr.  pad: the safety radius sqrt(level) of every static column, a -1 column included, grows by the
+    // agent's own pad; the level is read after the gather above.  One rounded operation each, uncontracted: the bits
+    // of the LIP mode's prologue.  With scenes sel holds global rows.  The QP-only solve never reads the tables.
+    if (MV && agent_rad && prm.use_nlp) {
+#pragma clang fp contract(off)
+        if (tid >= prm.K_obs && tid < K && L.sel[tid] >= 0) {
+            const double s_ = agent_rad[(size_t)agent_offset + agent] + agent_rad[L.sel[tid]];
+            L.eps[tid] = s_ * s_;
+        }
+    }
+    if (MV && agent_pad && prm.use_nlp) {
+#pragma clang fp contract(off)
+        if (tid < prm.K_obs) {
+            const double t_ = sqrt(L.eps[tid]) + agent_pad[(size_t)agent_offset + agent];
+            L.eps[tid] = t_ * t_;
+        }
     }
     // start: gravity-compensating forces on the stance legs, the dynamics rolled out, s = 0
     for (int e = tid; e < 12 * N; e += 64) {
@@ -1461,14 +1482,16 @@ __device__ __forceinline__ void srb12_agent(const Srb12KParams &prm, int agent, 
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         srb12_agent<TL, TO, NC, K1, 0>(prm, agent, x0g, xrefg, footg, contactg, obstacles, nbr_state, sel_g, x_qp_out,  \
-                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, nullptr, nullptr, lds); \
+                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, nullptr, nullptr, nullptr, nullptr, 0, \
+                            lds);                                                                              \
     }
 SRB12_INSTANCES(SRB12_KERNEL)
 #endif
 #if defined(SRB12_MOVING) || defined(SRB12_ALL)
-// The obstacle-table instances (srb_moving.obs_vel, srb_sizes.obs_eps; MV = 1), srb12_kernel_mv_*: the same kernels with
-// the velocity table and the level table as two more arguments (either may be null) and the arms of the prologue that
-// read them compiled in.  In the product a code object of their own
+// The table instances (srb_moving.obs_vel, srb_sizes.obs_eps, srb_agent_sizes.agent_rad / agent_pad; MV = 1),
+// srb12_kernel_mv_*: the same kernels with the four tables (each may be null) and the agent_offset of the agent tables'
+// own row as five more arguments and the arms of the prologue that read them compiled in.  In the product a code
+// object of their own
 // (this file compiled a second time under -DSRB12_MOVING, which emits only them), so the default instances keep their argument
 // list and their code: the LIP mode measured the extra argument alone at +0.5 % of its step.
 #define SRB12_KERNEL_MV(TL, TO, NC, K1)                                                                         \
@@ -1478,13 +1501,15 @@ SRB12_INSTANCES(SRB12_KERNEL)
         const double *__restrict__ nbr_state, const int *__restrict__ sel_g, double *__restrict__ x_qp_out,      \
         double *__restrict__ x_out, double *__restrict__ obj_out, int *__restrict__ status_out,                \
         int *__restrict__ iters_out, const double *__restrict__ nbr_plan, double *__restrict__ plan_out,       \
-        const double *__restrict__ obs_vel, const double *__restrict__ obs_eps)                                \
+        const double *__restrict__ obs_vel, const double *__restrict__ obs_eps,                                \
+        const double *__restrict__ agent_rad, const double *__restrict__ agent_pad, int agent_offset)          \
     {                                                                                                          \
         extern __shared__ __attribute__((aligned(16))) double lds[];                                           \
         const int agent = xcd_agent(blockIdx.x, gridDim.x);                                                   \
         if (agent >= n_agents) return;                                                                         \
         srb12_agent<TL, TO, NC, K1, 1>(prm, agent, x0g, xrefg, footg, contactg, obstacles, nbr_state, sel_g, x_qp_out,  \
-                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, obs_vel, obs_eps, lds); \
+                            x_out, obj_out, status_out, iters_out, nbr_plan, plan_out, obs_vel, obs_eps, agent_rad, \
+                            agent_pad, agent_offset, lds);                                                     \
     }
 SRB12_INSTANCES(SRB12_KERNEL_MV)
 #endif

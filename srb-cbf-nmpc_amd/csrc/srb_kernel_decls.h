@@ -192,14 +192,16 @@ extern "C" __global__ void srb_ll_kernel(SrbLLKParams prm, int n_agents, SrbLLDe
         const double *nbr_plan, double *plan_out);
 SRB12_INSTANCES(SRB_DECL12)
 #undef SRB_DECL12
-// the obstacle-table instances (srb12_kernels.hip under -DSRB12_MOVING): two more arguments, the velocity table of
-// srb_moving and the level table of srb_sizes (either may be null)
+// the table instances (srb12_kernels.hip under -DSRB12_MOVING): five more arguments, the velocity table of srb_moving,
+// the level table of srb_sizes, the safety-radius and pad tables of srb_agent_sizes (each may be null) and the
+// agent_offset of the agent tables' own row
 #define SRB_DECL12_MV(TL, TO, NC, K1)                                                                          \
     extern "C" __global__ void srb12_kernel_mv_##TL##_##TO##_##NC##_##K1(                                    \
         Srb12KParams prm, int n_agents, const double *x0g, const double *xrefg, const double *footg,           \
         const int *contactg, const double *obstacles, const double *nbr_state, const int *sel_g,              \
         double *x_qp_out, double *x_out, double *obj_out, int *status_out, int *iters_out,                    \
-        const double *nbr_plan, double *plan_out, const double *obs_vel, const double *obs_eps);
+        const double *nbr_plan, double *plan_out, const double *obs_vel, const double *obs_eps,               \
+        const double *agent_rad, const double *agent_pad, int agent_offset);
 SRB12_INSTANCES(SRB_DECL12_MV)
 #undef SRB_DECL12_MV
 extern "C" __global__ void srb12_pos_kernel(int n_agents, const double *x0g, double *pos);

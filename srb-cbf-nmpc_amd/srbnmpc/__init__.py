@@ -289,8 +289,8 @@ def _agent_args(agent_rad, agent_pad, agent_body, nbr_clearance, n_all, dtype, p
 
 
 class _SolverBase:
-    """What BatchSolver and srb12.Solver12 share: the context's life, the stream of a launch, the scene partition
-    and the Jacobi loop of solve_coupled_device.  A mode names the prefix of its entry points (_abi) and, where
+    """What BatchSolver and srb12.Solver12 share: the context's life, the stream of a launch, the scene partition,
+    the record of the validated agent-size tensors and the Jacobi loop of solve_coupled_device.  A mode names the prefix of its entry points (_abi) and, where
     they are bound on first use, the function that loads the library (_lib)."""
     _abi = "srb"
     _lib = staticmethod(lib)
@@ -306,6 +306,13 @@ class _SolverBase:
 
     def _entry(self, name: str):
         return getattr(self._lib(), f"{self._abi}_{name}")
+
+    def _agent_checked(self) -> set:
+        """The agent-size tensors whose values this solver has validated (looking at a device tensor's values
+        synchronises with the host: once per tensor and version, not once per solve)."""
+        if not hasattr(self, "_agent_ok"):
+            self._agent_ok = set()
+        return self._agent_ok
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -593,13 +600,6 @@ class BatchSolver(_SolverBase):
                                    stream, lambda table: {"alpha_buf": alpha_buf}, obstacles_version=obstacles_version,
                                    obs_vel=obs_vel, obs_horizon=obs_horizon, obs_eps=obs_eps, obs_clearance=obs_clearance,
                                    agent_rad=agent_rad, agent_pad=agent_pad, nbr_clearance=nbr_clearance)
-
-    def _agent_checked(self) -> set:
-        """The agent-size tensors whose values this solver has validated (looking at a device tensor's values
-        synchronises with the host: once per tensor and version, not once per solve)."""
-        if not hasattr(self, "_agent_ok"):
-            self._agent_ok = set()
-        return self._agent_ok
 
     def prepare_device(self, Pr, Prd, gait_domain, contact, toe, start, q, dq, out, agent_id=None,
                        agent_offset: int = 0, stream=None):

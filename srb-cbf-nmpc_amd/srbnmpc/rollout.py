@@ -27,14 +27,14 @@ rollout.
 With agent_rad / agent_pad ([n_all], m) every agent has its own safety radius towards its neighbours and its own pad on
 the static obstacles' safety radii in the solve, with nbr_clearance the neighbour columns are selected by clearance
 dist - agent_rad, and with agent_body ([n_all], m) d_agent is the clearance between bodies and collide_cycle the first
-cycle with d_agent < 0 (srb_agent_sizes, srb_rollout_agents_device).  The tables do not change over a rollout and every
-shard holds them whole.  LIP mode only.
+cycle with d_agent < 0 (srb_agent_sizes, srb_rollout_agents_device; srb12.Rollout12 likewise,
+srb12_rollout_agents_device).  The tables do not change over a rollout and every shard holds them whole.
 
 _RolloutBase is what this class and srb12.Rollout12 share: the checks of goal / phase / obstacles / obs_vel and of the
-size tables, the moving table's clone and its restore, the srb_moving and srb_sizes of a call, the metrics call, the
-solve, metrics and log buffers, reset / advance / results / scene_results and the preconditions of run().  A mode
-adds its state width, its own buffers, its srb_sim (_sim), step() and the driver call of run() (_drive); the entry
-points are the solver's own (its _entry).
+obstacle and agent size tables, the moving table's clone and its restore, the srb_moving, srb_sizes and
+srb_agent_sizes of a call, the metrics call, the solve, metrics and log buffers, reset / advance / results /
+scene_results and the preconditions of run().  A mode adds its state width, its own buffers, its srb_sim (_sim),
+step() and the driver call of run() (_drive); the entry points are the solver's own (its _entry).
 """
 from __future__ import annotations
 
@@ -149,10 +149,37 @@ class _RolloutBase:
     def _sizes(self) -> Sizes:
         return Sizes(_dptr(self.obs_eps), _dptr(self.obs_radius), int(self.obs_clearance))
 
+    agent_rad = agent_pad = agent_body = None     # the agent tables (_set_agent_sizes)
+    nbr_clearance = agents = False
+
+    def _set_agent_sizes(self, agent_rad, agent_pad, agent_body, nbr_clearance, n_all):
+        """The agent tables of a rollout ([n_all] each, or None) after their checks, and with agent_body the
+        collide_cycle buffer.  Called by the mode's __init__ once it knows n_all."""
+        import torch
+        for name, tab in (("agent_rad", agent_rad), ("agent_pad", agent_pad), ("agent_body", agent_body)):
+            if tab is not None:
+                _check_agent_array(tab, n_all, torch.float64, name, self.device, self.solver._agent_checked())
+        if nbr_clearance and agent_rad is None:
+            raise ValueError("nbr_clearance needs agent_rad (the clearance selection reads the radius table)")
+        self.agent_rad, self.agent_pad, self.agent_body = agent_rad, agent_pad, agent_body
+        self.nbr_clearance = bool(nbr_clearance)
+        self.agents = agent_rad is not None or agent_pad is not None or agent_body is not None   # run(): the _agents driver
+        if agent_body is not None:
+            self.metrics["collide_cycle"] = torch.full((self.A,), -1, dtype=torch.int32, device=self.device)
+
+    def _agent_sizes(self) -> AgentSizes:
+        return AgentSizes(_dptr(self.agent_rad), _dptr(self.agent_pad), _dptr(self.agent_body), int(self.nbr_clearance),
+                          _iptr(self.metrics.get("collide_cycle")))
+
     def _metrics(self, sim, stream):
-        """The metrics of the current cycle on `sim` (the mode's srb_sim): with obs_radius the sized entry point."""
+        """The metrics of the current cycle on `sim` (the mode's srb_sim): with agent_body the agents entry point
+        (obs_radius may be absent), with obs_radius alone the sized one."""
         s = self.solver
-        if self.obs_radius is not None:
+        if self.agent_body is not None:
+            sz = ctypes.byref(self._sizes()) if self.obs_radius is not None else None
+            _check(s._entry("sim_metrics_agents_device")(s._h, self.A, ctypes.byref(sim), sz,
+                                                         ctypes.byref(self._agent_sizes()), self.c, s._stream(stream)))
+        elif self.obs_radius is not None:
             _check(s._entry("sim_metrics_sized_device")(s._h, self.A, ctypes.byref(sim), ctypes.byref(self._sizes()),
                                                         self.c, s._stream(stream)))
         else:
@@ -264,7 +291,7 @@ class Rollout(_RolloutBase):
               d_agent < 0, else -1) and scene_results() n_collided (None: centre distances)
     nbr_clearance  True: the neighbour columns by clearance dist - agent_rad (needs agent_rad)
               The agent tables (srb_agent_sizes) are finite, agent_rad and agent_body not negative, and do not change
-              over a rollout; every shard holds the whole tables.  LIP mode only.
+              over a rollout; every shard holds the whole tables.
     agent_offset, n_all   a shard of a larger team: this batch is rows agent_offset .. agent_offset + A of the
               n_all-row neighbour table that step(exchange) gathers (default: the whole team)
     All tensors are float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
@@ -281,16 +308,7 @@ class Rollout(_RolloutBase):
         self.n_all = A if n_all is None else int(n_all)
         if self.agent_offset < 0 or self.agent_offset + A > self.n_all:
             raise ValueError("agent_offset + A exceeds n_all")
-        for name, tab in (("agent_rad", agent_rad), ("agent_pad", agent_pad), ("agent_body", agent_body)):
-            if tab is not None:
-                _check_agent_array(tab, self.n_all, torch.float64, name, self.device, solver._agent_checked())
-        if nbr_clearance and agent_rad is None:
-            raise ValueError("nbr_clearance needs agent_rad (the clearance selection reads the radius table)")
-        self.agent_rad, self.agent_pad, self.agent_body = agent_rad, agent_pad, agent_body
-        self.nbr_clearance = bool(nbr_clearance)
-        self.agents = agent_rad is not None or agent_pad is not None or agent_body is not None   # run(): the _agents driver
-        if agent_body is not None:
-            self.metrics["collide_cycle"] = torch.full((A,), -1, dtype=torch.int32, device=self.device)
+        self._set_agent_sizes(agent_rad, agent_pad, agent_body, nbr_clearance, self.n_all)
         self.sharded = self.agent_offset != 0 or self.n_all != A
         f8 = dict(dtype=torch.float64, device=self.device)
         self.alpha_buf = torch.zeros((A, 4), **f8)
@@ -309,19 +327,6 @@ class Rollout(_RolloutBase):
                    0 if self.obstacles is None else self.obstacles.shape[0], nbr.shape[0], self.agent_offset,
                    _dptr(m["d_obs"]), _dptr(m["d_agent"]), _dptr(m["min_d_obs"]), _dptr(m["min_d_agent"]),
                    _iptr(m["fail_cycle"]), _dptr(m["distance_to_fail"]))
-
-    def _agent_sizes(self) -> AgentSizes:
-        return AgentSizes(_dptr(self.agent_rad), _dptr(self.agent_pad), _dptr(self.agent_body), int(self.nbr_clearance),
-                          _iptr(self.metrics.get("collide_cycle")))
-
-    def _metrics(self, sim, stream):
-        """With agent_body the metrics of srb_sim_metrics_agents_device (obs_radius may be absent); else as ever."""
-        if self.agent_body is None:
-            return super()._metrics(sim, stream)
-        s = self.solver
-        sz = ctypes.byref(self._sizes()) if self.obs_radius is not None else None
-        _check(lib().srb_sim_metrics_agents_device(s._h, self.A, ctypes.byref(sim), sz, ctypes.byref(self._agent_sizes()),
-                                                   self.c, s._stream(stream)))
 
     def step(self, exchange=None, plan_exchange=None, stream=None):
         """One cycle: advance, metrics, solve.  exchange (a dist.NeighbourExchange, or any callable

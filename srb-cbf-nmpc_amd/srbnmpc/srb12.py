@@ -14,12 +14,14 @@ Jacobi driver over the plans, and Rollout12(plans=True) feeds last cycle's plans
 obstacles (srb_moving): obs_vel / obs_horizon on Solver12.solve, solve_device, solve_coupled_device
 and Rollout12, Solver12.advance_obstacles_device; velocities from workload.obstacle_velocities.  Obstacle sizes
 (srb_sizes): obs_eps / obs_clearance on the same three solver calls, obs_eps / obs_radius /
-obs_clearance on Rollout12; tables from workload.obstacle_sizes.
+obs_clearance on Rollout12; tables from workload.obstacle_sizes.  Agent sizes (srb_agent_sizes):
+agent_rad / agent_pad / nbr_clearance on the same three solver calls, those and agent_body on Rollout12; tables from
+workload.agent_sizes.
 
 The host layer of these features is written once for both modes: Solver12 is a _SolverBase (srbnmpc/__init__.py: the
 context's life, _stream, set_scenes, the Jacobi loop), Rollout12 a rollout._RolloutBase (the checks, buffers, logs,
-reset / advance / run / results, the size tables' checks and the metrics call), and the pointer casts, the (Ko, Kn)
-clamp and the srb_moving / srb_sizes checks are the package's.
+reset / advance / run / results, the obstacle and agent size tables' checks and the metrics call), and the pointer
+casts, the (Ko, Kn) clamp and the srb_moving / srb_sizes / srb_agent_sizes checks are the package's.
 """
 from __future__ import annotations
 
@@ -27,8 +29,8 @@ import ctypes
 
 import numpy as np
 
-from . import (Moving, Sizes, _SolverBase, _check, _check_plan_array, _check_vel_array, _clamp_selected, _dp, _dptr, _ip,
-               _iptr, _moving_args, _p, _sizes_args, lib, workload)
+from . import (AgentSizes, Moving, Sizes, _SolverBase, _agent_args, _check, _check_plan_array, _check_vel_array,
+               _clamp_selected, _dp, _dptr, _ip, _iptr, _moving_args, _p, _sizes_args, lib, workload)
 from .rollout import _RolloutBase
 
 _p12_fields = [("N", ctypes.c_int), ("K_obs", ctypes.c_int), ("K_nbr", ctypes.c_int),
@@ -134,6 +136,13 @@ def _lib():
         L.srb12_sim_metrics_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, S, SZ, ctypes.c_int, ctypes.c_void_p]
         L.srb12_rollout_sized_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, S, PL, MV, SZ, ctypes.c_int,
                                                  ctypes.c_void_p]
+        AG = ctypes.POINTER(AgentSizes)
+        L.srb12_solve_batch_agents.argtypes = [ctypes.c_void_p, ctypes.c_int, B, PL, MV, SZ, AG]
+        L.srb12_solve_batch_agents_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, PL, MV, SZ, AG, ctypes.c_void_p]
+        L.srb12_sim_metrics_agents_device.argtypes = [ctypes.c_void_p, ctypes.c_int, S, SZ, AG, ctypes.c_int,
+                                                      ctypes.c_void_p]
+        L.srb12_rollout_agents_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, S, PL, MV, SZ, AG, ctypes.c_int,
+                                                  ctypes.c_void_p]
         _bound = True
     return L
 
@@ -163,7 +172,7 @@ class Solver12(_SolverBase):
 
     def solve(self, x0, xref, foot, contact, obstacles=None, nbr_state=None, agent_offset: int = 0, nbr_plan=None,
               plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
-              obs_clearance: bool = False):
+              obs_clearance: bool = False, agent_rad=None, agent_pad=None, nbr_clearance: bool = False):
         """Host numpy: x0 [A,12], xref [A,N,12], foot [A,N,4,3], contact [A,N,4] int.  Returns
         dict x_qp, x [A, 24N+1], obj, status [A,2], iters [A,2], sel [A, Ko+Kn], plan [A,N,2] (the (x, y) of
         X at every grid).  nbr_plan ([n_all][N][2], float64, C-contiguous) makes the neighbour rows follow the
@@ -173,7 +182,10 @@ class Solver12(_SolverBase):
         selects the static columns by closest predicted approach (needs obs_vel).  obs_eps ([n_obs], float64,
         C-contiguous): the CBF level of each obstacle row in squared metres, the unit of eps_obs
         (srb12_solve_batch_sized); obs_clearance=True additionally selects the static columns by clearance to the level
-        set (needs obs_eps)."""
+        set (needs obs_eps).  agent_rad, agent_pad ([n_all], float64, C-contiguous, finite; agent_rad >= 0): a safety
+        radius and a pad per row of nbr_state (srb12_solve_batch_agents): neighbour column j at the level
+        (agent_rad[g] + agent_rad[sel[j]])^2, every static column of agent g at (sqrt(level) + agent_pad[g])^2;
+        nbr_clearance=True additionally selects the neighbour columns by clearance dist - agent_rad (needs agent_rad)."""
         p = self.params
         x0 = np.ascontiguousarray(x0, np.float64); A = x0.shape[0]
         xref = np.ascontiguousarray(xref, np.float64); foot = np.ascontiguousarray(foot, np.float64)
@@ -195,6 +207,15 @@ class Solver12(_SolverBase):
         pl = Plans12(_p(nbr_plan) if nbr_plan is not None else None, _p(out["plan"]), 1 if plan_selection else 0, None)
         moving = obs_vel is not None or obs_horizon
         mv = _moving_args(obs_vel, obs_horizon, ob.shape[0], np.float64, _p, p.use_nlp) if moving else None
+        if agent_rad is not None or agent_pad is not None or nbr_clearance:
+            sized = obs_eps is not None or obs_clearance
+            sz = _sizes_args(obs_eps, None, obs_clearance, ob.shape[0], np.float64, _p, p.use_nlp) if sized else None
+            ag = _agent_args(agent_rad, agent_pad, None, nbr_clearance, nb.shape[0] if nb is not None else 0, np.float64,
+                             _p, p.use_nlp)
+            _check(_lib().srb12_solve_batch_agents(self._h, A, ctypes.byref(b), ctypes.byref(pl),
+                                                   ctypes.byref(mv) if moving else None,
+                                                   ctypes.byref(sz) if sized else None, ctypes.byref(ag)))
+            return out
         if obs_eps is not None or obs_clearance:
             sz = _sizes_args(obs_eps, None, obs_clearance, ob.shape[0], np.float64, _p, p.use_nlp)
             _check(_lib().srb12_solve_batch_sized(self._h, A, ctypes.byref(b), ctypes.byref(pl),
@@ -208,7 +229,8 @@ class Solver12(_SolverBase):
 
     def solve_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, agent_offset: int = 0, stream=None,
                      obstacles_version: int = 0, nbr_plan=None, plan_selection: bool = False, plan=None, obs_vel=None,
-                     obs_horizon: bool = False, obs_eps=None, obs_clearance: bool = False):
+                     obs_horizon: bool = False, obs_eps=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
+                     nbr_clearance: bool = False):
         """torch tensors on this device (float64 / int32), contiguous; out holds x_qp (or None), x, obj,
         status, iters and optionally sel [A, Ko+Kn] and plan [A, N, 2] (written when the key is present; the
         `plan` argument overrides it).  nbr_plan ([n_all][N][2] float64, contiguous): the neighbours' plans for the
@@ -217,8 +239,11 @@ class Solver12(_SolverBase):
         velocities (srb12_solve_batch_moving_device; needs obstacles_version 0); obs_horizon=True selects the static
         columns by closest predicted approach (needs obs_vel).  obs_eps ([n_obs] float64, contiguous): the CBF level of
         each obstacle row (srb12_solve_batch_sized_device; goes together with obstacles_version); obs_clearance=True
-        selects the static columns by clearance to the level set (needs obs_eps).  Asynchronous on `stream` (default:
-        torch's current)."""
+        selects the static columns by clearance to the level set (needs obs_eps).  agent_rad, agent_pad ([n_all]
+        float64, contiguous, finite; agent_rad >= 0): a safety radius and a pad per row of nbr_state
+        (srb12_solve_batch_agents_device; the values of a tensor are looked at once, on its first use with this solver);
+        nbr_clearance=True selects the neighbour columns by clearance dist - agent_rad (needs agent_rad).  Asynchronous
+        on `stream` (default: torch's current)."""
         A = x0.shape[0]
         import torch
         Ko, Kn = n_selected(self.params, 0 if obstacles is None else obstacles.shape[0],
@@ -245,6 +270,18 @@ class Solver12(_SolverBase):
         n_obs = 0 if obstacles is None else obstacles.shape[0]
         moving = obs_vel is not None or obs_horizon
         mv = _moving_args(obs_vel, obs_horizon, n_obs, torch.float64, _dptr, self.params.use_nlp) if moving else None
+        if agent_rad is not None or agent_pad is not None or nbr_clearance:
+            sized = obs_eps is not None or obs_clearance
+            sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch.float64, _dptr, self.params.use_nlp,
+                             device=x0.device) if sized else None
+            ag = _agent_args(agent_rad, agent_pad, None, nbr_clearance, 0 if nbr_state is None else nbr_state.shape[0],
+                             torch.float64, _dptr, self.params.use_nlp, device=x0.device, checked=self._agent_checked())
+            pl = None if no_plans else ctypes.byref(Plans12(_dptr(nbr_plan), _dptr(plan), 1 if plan_selection else 0, None))
+            _check(_lib().srb12_solve_batch_agents_device(self._h, A, ctypes.byref(b), pl,
+                                                          ctypes.byref(mv) if moving else None,
+                                                          ctypes.byref(sz) if sized else None, ctypes.byref(ag),
+                                                          self._stream(stream)))
+            return
         if obs_eps is not None or obs_clearance:
             sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch.float64, _dptr, self.params.use_nlp, device=x0.device)
             pl = None if no_plans else ctypes.byref(Plans12(_dptr(nbr_plan), _dptr(plan), 1 if plan_selection else 0, None))
@@ -284,7 +321,7 @@ class Solver12(_SolverBase):
     def solve_coupled_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, outer: int = 2, exchange=None,
                              nbr_plan=None, agent_offset: int = 0, stream=None, obstacles_version: int = 0,
                              plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False, obs_eps=None,
-                             obs_clearance: bool = False):
+                             obs_clearance: bool = False, agent_rad=None, agent_pad=None, nbr_clearance: bool = False):
         """Jacobi iteration over the agents' plans (BatchSolver.solve_coupled_device for the 12-state body):
         `outer` solves of the same cycle, each against the plans the agents wrote in the round before.  Round 0
         solves against nbr_plan (None: the constant-velocity rows); every later round r reads table =
@@ -293,12 +330,14 @@ class Solver12(_SolverBase):
         required) and a second buffer of this solver; the last round's results are in `out`.  Returns
         plan_change, a device tensor [outer - 1]: max |plan_r - plan_{r-1}| per round (torch reductions; nothing
         synchronises with the host inside the loop).  plan_selection applies to every round that has a table; obs_vel,
-        obs_horizon, obs_eps and obs_clearance as solve_device (every round solves against the same obstacle tables)."""
+        obs_horizon, obs_eps, obs_clearance, agent_rad, agent_pad and nbr_clearance as solve_device (every round solves
+        against the same obstacle and agent tables)."""
         return self._solve_coupled((x0, xref, foot, contact, obstacles, nbr_state, out), outer, exchange, nbr_plan,
                                    agent_offset, stream,
                                    lambda table: {"plan_selection": plan_selection and table is not None},
                                    obstacles_version=obstacles_version, obs_vel=obs_vel, obs_horizon=obs_horizon,
-                                   obs_eps=obs_eps, obs_clearance=obs_clearance)
+                                   obs_eps=obs_eps, obs_clearance=obs_clearance, agent_rad=agent_rad, agent_pad=agent_pad,
+                                   nbr_clearance=nbr_clearance)
 
     def last_kernel_ms(self):
         a, b = ctypes.c_float(), ctypes.c_float()
@@ -351,6 +390,15 @@ class Rollout12(_RolloutBase):
                 on the CoM rows and fail_cycle the first cycle with d_obs < 0 (None: centre distances and the 0.5 m test)
     obs_clearance  True: the static columns by clearance to the level set (needs obs_eps).  With any of the three run()
                 is srb12_rollout_sized_device; the tables do not change over a rollout
+    agent_rad   [A] or None: the safety radius (m) of each agent: neighbour column j of agent g at the level
+                (agent_rad[g] + agent_rad[sel[j]])^2 (None: eps_nbr for every pair)
+    agent_pad   [A] or None: metres added to the safety radius of every static column of each agent
+    agent_body  [A] or None: the body radius (m) of each agent: d_agent is then
+                min_i (dist_i - (agent_body[g] + agent_body[i])) on the CoM rows, results() gains collide_cycle (the first
+                cycle with d_agent < 0, else -1) and scene_results() n_collided (None: centre distances)
+    nbr_clearance  True: the neighbour columns by clearance dist - agent_rad (needs agent_rad).  With any of the three
+                tables run() is srb12_rollout_agents_device; the tables are finite, agent_rad and agent_body not
+                negative, and do not change over a rollout
     A whole team on one GPU (the SRB-12 mode has no sharded stepping).  All tensors are
     float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
     _nx = 12
@@ -359,12 +407,14 @@ class Rollout12(_RolloutBase):
     def __init__(self, solver, goal, vref: float = 0.27, phase=None, gait: str = "trot", log_x: bool = False,
                  obstacles=None, hcom: float = workload.HCOM12, yaw_step: float = 0.1, hold_radius: float = 0.05,
                  plans: bool = False, plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False,
-                 obs_eps=None, obs_radius=None, obs_clearance: bool = False):
+                 obs_eps=None, obs_radius=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
+                 agent_body=None, nbr_clearance: bool = False):
         import torch
         if gait not in GAITS:
             raise ValueError(f"gait must be one of {sorted(GAITS)}, got {gait!r}")
         super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps, obs_radius,
                          obs_clearance)
+        self._set_agent_sizes(agent_rad, agent_pad, agent_body, nbr_clearance, self.A)
         self.gait, self.hcom = gait, float(hcom)
         self.plan_selection = bool(plan_selection)
         if self.plan_selection and not self.plans:
@@ -402,7 +452,8 @@ class Rollout12(_RolloutBase):
         s.solve_device(self.x0, self.xref, self.foot, self.contact, self.obstacles, self.last_state, self.out,
                        stream=stream, nbr_plan=table, plan_selection=self.plan_selection and table is not None,
                        obs_vel=self.obs_vel, obs_horizon=self.obs_horizon, obs_eps=self.obs_eps,
-                       obs_clearance=self.obs_clearance)
+                       obs_clearance=self.obs_clearance, agent_rad=self.agent_rad, agent_pad=self.agent_pad,
+                       nbr_clearance=self.nbr_clearance)
         if self.plans:
             s.shift_plans_device(self.out["plan"], self.plan_table, SHIFT_GRIDS, stream=stream)
         self.c += 1
@@ -416,7 +467,12 @@ class Rollout12(_RolloutBase):
         pl = None
         if self.plans:
             pl = ctypes.byref(Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table)))
-        if self.sized:
+        if self.agents:
+            mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
+            sz = ctypes.byref(self._sizes()) if self.sized else None
+            _check(_lib().srb12_rollout_agents_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl, mv, sz,
+                                                      ctypes.byref(self._agent_sizes()), T, s._stream(stream)))
+        elif self.sized:
             mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
             _check(_lib().srb12_rollout_sized_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl, mv,
                                                      ctypes.byref(self._sizes()), T, s._stream(stream)))

@@ -38,6 +38,15 @@ bodies, the agents inside a body and the non-converged solves of the three solve
 The three solves are three different NLPs -- other levels, other rows -- so their times have no target.
 
     python tools/bench_rollout12.py --sizes [--out profiles/bench_rollout12_sizes.json]
+
+--agents (without a number; --agent-sizes is the same switch) measures the agent sizes instead (srb_agent_sizes,
+DESIGN.md 10.11), the rows of the --sizes table with the agent tables: the rollout cycle without a table, with
+agent_rad + agent_pad, and with those + nbr_clearance, each with and without agent_body (tables
+workload.agent_sizes(n_all, 1234)), for the 1024-agent team and for the 128 x 8 scene batch; and the separation over T
+cycles: the smallest and the median clearance between bodies, the agents that touched another body and the
+non-converged solves of the three solves (all measured with agent_body).  Three different NLPs again: no target.
+
+    python tools/bench_rollout12.py --agents [--out profiles/bench_rollout12_agents.json]
 """
 import argparse
 import ctypes
@@ -237,12 +246,96 @@ def sizes(args):
         w["solver"].close()
 
 
+def agent_sizes(args):
+    """--agents without a number: see the module docstring."""
+    dev = torch.device("cuda", 0)
+    A, N, Ko, Kn, T = args.agents, 10, 3, 8, args.cycles
+    team, scene_obs = 8, 20
+    S = A // team
+    D = lambda v, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(v), dtype=dt, device=dev)
+    p = srb12.default_params(N, K_obs=Ko, K_nbr=Kn)
+    b = workload.make_batch12(A, N, "trot", seed=1234)
+    sb = workload.make_scenes12(S, team, N, "trot", seed=1234, n_obs=scene_obs)
+    goal = D(np.tile(workload.GOAL * np.array([workload.arena_scale(A), 1.0]), (A, 1)))
+    solves = (("no_table", False, False), ("agent_rad_pad", True, False), ("agent_rad_pad_clearance", True, True))
+    worlds = {}
+    for name, x0, g, phase, ob, scenes in (("one_team", b["x0"], goal, None, b["obstacles"], (0, 0)),
+                                           ("scenes", sb["x0"], D(sb["goal"]), D(sb["phase"], torch.int32), sb["obstacles"],
+                                            (team, scene_obs))):
+        solver = srb12.Solver12(p, x0.shape[0], 0)
+        solver.set_timing(False)
+        solver.set_scenes(*scenes)
+        ob = D(ob)
+        rad, pad, body = (D(v) for v in workload.agent_sizes(x0.shape[0], 1234))
+        mk = lambda t, c, r: srb12.Rollout12(solver, g, vref=workload.VREF, phase=phase, obstacles=ob,
+                                             agent_rad=rad if t else None, agent_pad=pad if t else None, nbr_clearance=c,
+                                             agent_body=body if r else None)
+        worlds[name] = dict(solver=solver, x0=D(x0), ob=ob,
+                            rolls={f"{k}{'_body' if r else ''}": mk(t, c, r) for k, t, c in solves for r in (False, True)})
+
+    def cycle(w, r):
+        def f():
+            r.reset(w["x0"])
+            r.run(T)
+        return f
+    modes = [(f"{name}_{k}", cycle(w, r)) for name, w in worlds.items() for k, r in w["rolls"].items()]
+    for _ in range(args.warmup):
+        for _, f in modes:
+            f()
+    torch.cuda.synchronize(dev)
+    ms = {name: [] for name, _ in modes}
+    for _ in range(args.rounds):
+        for name, f in modes:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize(dev)
+            ms[name].append(1e3 * (time.perf_counter() - t0) / T)
+
+    def stats(r):
+        res = r.results()
+        torch.cuda.synchronize(dev)
+        d, cc, st = res["min_d_agent"].cpu().numpy(), res["collide_cycle"].cpu().numpy(), res["status"].cpu().numpy()
+        ok = np.isin(st[..., 0], (0, 4)) & (st[..., 1] == 0)
+        return {"clearance_between_bodies_m": {"smallest": float(d.min()), "median": float(np.median(d))},
+                "agents_touching_a_body": {"at_cycle_0": int((cc == 0).sum()), "later": int((cc > 0).sum()),
+                                           "never": int((cc < 0).sum())},
+                "non_converged_solves": int((~ok).sum()), "solves": int(ok.size)}
+    sep = {}
+    for name, w in worlds.items():
+        sep[name] = {}
+        for k, _, _ in solves:
+            cycle(w, w["rolls"][k + "_body"])()
+            sep[name][k] = stats(w["rolls"][k + "_body"])
+    spread = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+    res = {"tool": "tools/bench_rollout12.py --agents", "agents": A, "horizon": N, "K_obs": Ko, "K_nbr": Kn,
+           "scenes": {"n_scenes": S, "scene_agents": team, "scene_obs": scene_obs},
+           "one_team_obstacles": int(worlds["one_team"]["ob"].shape[0]), "cycles_per_window": T, "rounds": args.rounds,
+           "n_gpus": 1, "ms_per_cycle": {k: spread(v) for k, v in ms.items()},
+           "separation_over_cycles": T, "separation": sep,
+           "note": "ms_per_cycle: Rollout12.run(T), reset included, per cycle; *_no_table no agent table, *_agent_rad_pad the "
+                   "drawn radii and pads, *_agent_rad_pad_clearance those with the neighbour clearance selection; *_body: "
+                   "the metrics with the body radii.  The three solves are three different NLPs: no target for these "
+                   "times.  separation: one run each with agent_body, the same world and the same bodies."}
+    print(json.dumps(res), flush=True)
+    out = args.out if args.out is not None else os.path.join(ROOT, "profiles", "bench_rollout12_agents.json")
+    if out:
+        with open(out, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    for w in worlds.values():
+        w["solver"].close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=20, help="T: cycles per window")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warmup", type=int, default=1, help="untimed windows per mode")
-    ap.add_argument("--agents", type=int, default=1024)
+    ap.add_argument("--agents", nargs="?", const="tables", default="1024",
+                    help="with a number: the agent count (default 1024); without one: the agent-size measurement alone "
+                         "(see above)")
+    ap.add_argument("--agent-sizes", action="store_true", help="the agent-size measurement alone (as --agents without "
+                                                               "a number; combines with --agents N)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--plans", action="store_true", help="add the plans-on modes (see above)")
     ap.add_argument("--outer", type=int, default=4, help="--plans: Jacobi rounds of the plan_change measurement")
@@ -250,12 +343,17 @@ def main():
     ap.add_argument("--vmax", type=float, default=1.0, help="--moving: the obstacles' top speed (m/s)")
     ap.add_argument("--sizes", action="store_true", help="the obstacle-size measurement alone (see above)")
     args = ap.parse_args()
+    if args.agents == "tables":
+        args.agent_sizes, args.agents = True, "1024"
+    args.agents = int(args.agents)
     if not torch.cuda.is_available():
         sys.exit("bench_rollout12.py needs a GPU (no CPU fallback)")
     if args.moving:
         return moving(args)
     if args.sizes:
         return sizes(args)
+    if args.agent_sizes:
+        return agent_sizes(args)
     dev = torch.device("cuda", 0)
     A, N, Ko, Kn, T = args.agents, 10, 3, 8, args.cycles
     team, scene_obs = 8, 20
