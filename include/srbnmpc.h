@@ -299,7 +299,8 @@ int srb_prepare_batch_device(srb_ctx *ctx, int n_agents, const srb_prep *dev_io,
 /*
  * Closed-loop team rollout on the device: the step from one cycle's solution to the next cycle's inputs, and the
  * team's safety log, so that T control cycles run without a host round trip.  One cycle is
- * one gait domain of NDOMAIN = 4 grids (global_loco_opts.h:9), so N >= 4.  The plant is nominal: the state that
+ * one gait domain of NDOMAIN = 4 grids (global_loco_opts.h:9), so N >= 4.  The plant of these entry points is nominal
+ * (srb_plant, further down, disturbs it through entry points of its own): the state that
  * starts cycle c + 1 is the X the solve of cycle c predicted at grid index 3, the domain's end -- what the
  * reference buffers (MPC_dist.cpp:798) -- whatever that solve's status.  All pointers are device pointers, fp64
  * unless noted; cycles count from c_first, and log rows are indexed by c - c_first.
@@ -547,6 +548,71 @@ int srb_sim_metrics_agents_device(srb_ctx *ctx, int n_agents, const srb_sim *sim
 int srb_rollout_agents_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_sim *sim,
                               const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag, int cycles,
                               void *stream);
+
+/*
+ * Disturbed plant (LIP mode; DESIGN.md 3 "Disturbed plant", 9, 10.12): kicks, pushes and a plant whose CoM height is
+ * not the model's, so that a rollout can say whether the safety rows hold when the robot is shoved, its velocity is
+ * noisy or the model is wrong.  As with srb_agent_sizes, SRB_ABI_VERSION and every existing struct stay: the tables
+ * travel in a struct of their own through entry points of their own, which extend srb_sim_advance_device and
+ * srb_rollout_agents_device (mv, sz, ag may be NULL) and otherwise behave as those.  Every table has n_all rows in
+ * the row order of nbr_state (scene-major with scenes); global agent g = agent_offset + a owns row g (srb_sim's
+ * agent_offset / n_all; n_all == 0 reads as n_agents rows).  All pointers are device pointers.  All arithmetic is
+ * fp64, uncontracted, with one stated grouping (csrc/srb_plant.hip; tests/plant_oracle.py restates it bit for bit).
+ *
+ * The plant acts in the advance of a cycle c > c_first (at c_first the state is the caller's, as ever) and replaces
+ * "state = x[a][12..15]" by state = z + d, one rounded add per component:
+ *   z, the base state
+ *     plant_hcom NULL       x[a][12..15], the nominal prediction.
+ *     plant_hcom [n_all]    the four-step roll z <- Ad_g z + Bd_g u of the plant's own LIP, from the state that
+ *                           started cycle c - 1 -- read from `state` before it is overwritten, so this advance is
+ *                           NOT idempotent: call it once per cycle -- under the four inputs the model applied over
+ *                           the domain, u = (x[4N + 2k], x[4N + 2k + 1]) for k = 0 .. 3 (the U_k of the equality row
+ *                           X_k = Ad X_{k-1} + Bd U_k).  Ad_g, Bd_g are computed on the device from
+ *                           grav / plant_hcom[g] and Ts by the arithmetic of the library's own discretisation (the
+ *                           third-order series for Ad, A^-1 (Ad - I) B for Bd), operation for operation.  Each
+ *                           matrix-vector product is a row sum in index order: Ad's four terms, then Bd's two.
+ *   d = (dpx, dvx, dpy, dvy), the disturbance, from +0.0
+ *     kick_v, kick_p [n_all]  bounds (m/s, m) of a uniform kick per cycle.  Philox4x32-10 with key
+ *                           ((uint32)seed, (uint32)(seed >> 32)) and counter ((uint32)c, (uint32)g, 0, 0) gives
+ *                           words w0 .. w3, and u_i = ((double)(int32_t)w_i + 0.5) * 2^-31 lies in (-1, 1), is
+ *                           never 0 and is exact.  dvx += kick_v[g] u0, dvy += kick_v[g] u1, dpx += kick_p[g] u2,
+ *                           dpy += kick_p[g] u3, each one rounded multiply and one rounded add.  Bounded and
+ *                           uniform on purpose: a CBF margin is stated against a bounded disturbance.  The counter
+ *                           holds the caller's cycle number c (not c - c_first) and the global row g (not a), so a
+ *                           shard, a scene and a rollout continued cycle by cycle draw what the whole team draws in
+ *                           one rollout call.
+ *     pushes                every entry p, in table order, with push_cycle[p] == c and push_agent[p] == g adds
+ *                           push_dv[p] to (dvx, dvy), one rounded add each, after the kick.  Brute force per agent.
+ *                           An entry whose cycle is <= c_first, or is never reached, does not fire.
+ *   dist_log [T][A][4]      out, optional: row c - c_first - 1 gets d.
+ * Everything an advance derives from the state -- x0, last_state, alpha_buf, the reference, the footholds, the traj
+ * row -- follows from the new state; the plan shift and the logs of the previous solve are unchanged, so a
+ * neighbour's shifted plan is stale by the disturbance, as it would be on a robot.
+ *
+ * With plant == NULL, or every table NULL and n_push == 0, each entry point is the one it extends, output bits
+ * included (dist_log is then not written).  SRB_ERR_ARG, by name, before anything is launched and before a context is
+ * needed: a wrong struct_size; n_push outside 0 .. 4096; n_push > 0 with push_cycle, push_agent or push_dv missing;
+ * plant_hcom with srb_sim.x missing (the advance; the rollout reads batch.x).  With a context: agent_offset +
+ * n_agents beyond n_all.  The contents of the tables are NOT checked: a NaN or negative bound or height goes
+ * through the arithmetic above as it is.  srb_rollout_plant_device refuses a shard, as srb_rollout_device does; the
+ * tables do not change over a rollout.  The SRB-12 mode and the MPC_dist shims have no disturbed plant.
+ */
+typedef struct srb_plant {
+    int struct_size;            /* sizeof(srb_plant) (ABI check) */
+    unsigned long long seed;    /* the Philox key */
+    const double *kick_v;       /* [n_all] m/s bound per cycle, or NULL */
+    const double *kick_p;       /* [n_all] m bound per cycle, or NULL */
+    const double *plant_hcom;   /* [n_all] the plant's CoM height (m), or NULL: the nominal prediction */
+    int n_push;                 /* 0 .. 4096 */
+    const int *push_cycle, *push_agent;   /* [n_push]; agent = global row */
+    const double *push_dv;      /* [n_push][2] m/s */
+    double *dist_log;           /* [T][A][4] out, optional */
+} srb_plant;
+int srb_sim_advance_plant_device(srb_ctx *ctx, int n_agents, const srb_sim *sim, const srb_plant *plant, int cycle,
+                                 void *stream);
+int srb_rollout_plant_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_sim *sim,
+                             const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
+                             const srb_plant *plant, int cycles, void *stream);
 
 /*
  * HL reference planner (generateReferenceTrajectory, MPC_dist.cpp:930-1104; SURVEY.md 8(f)

@@ -1013,12 +1013,46 @@ static int check_sim(const srb_sim *d, int cycle, bool advance)
     return SRB_OK;
 }
 
-static int launch_advance(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s)
+// The argument errors of srb_plant that need no context, before anything is launched.  has_x: the call has the
+// previous solve's x (srb_sim.x for the advance; the rollout wires batch.x in and reports that itself).
+#define SRB_PLANT_MAX_PUSH 4096
+static int check_plant(const srb_plant *pl, bool has_x)
+{
+    if (int rc = srb_check_struct(pl, "srb_plant")) return rc;
+    if (!pl) return SRB_OK;
+    if (pl->n_push < 0 || pl->n_push > SRB_PLANT_MAX_PUSH)
+        return fail(SRB_ERR_ARG, "srb_plant.n_push: 0 .. 4096 (every agent scans the whole push table)");
+    if (pl->n_push > 0 && (!pl->push_cycle || !pl->push_agent || !pl->push_dv))
+        return fail(SRB_ERR_ARG, "srb_plant.n_push > 0 needs push_cycle, push_agent and push_dv");
+    if (pl->plant_hcom && !has_x)
+        return fail(SRB_ERR_ARG, "srb_plant.plant_hcom needs srb_sim.x (the plant is driven by the inputs the model applied)");
+    return SRB_OK;
+}
+
+// the struct disturbs the plant at all (else every entry point is the one it extends; dist_log alone is not written)
+static bool plant_on(const srb_plant *pl) { return pl && (pl->kick_v || pl->kick_p || pl->plant_hcom || pl->n_push > 0); }
+
+// pl: the disturbed plant (null: nominal).  It acts from the second cycle on; at c_first the state is the caller's.
+static int launch_advance(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s,
+                          const srb_plant *pl = nullptr)
 {
     const srb_params *p = &c->p;
     if (p->N < 4) return fail(SRB_ERR_ARG, "the rollout needs N >= 4 (one cycle is one gait domain of 4 grids)");
     if (!d->state || !d->x0 || !d->ref || !d->foot || !d->last_state)
         return fail(SRB_ERR_ARG, "srb_sim: missing buffer (state, x0, ref, foot, last_state)");
+    if (pl && cycle != d->c_first) {
+        const int n_all = d->n_all > 0 ? d->n_all : n_agents;
+        if (d->agent_offset < 0 || d->agent_offset + n_agents > n_all)
+            return fail(SRB_ERR_ARG, "srb_plant: agent_offset + n_agents exceeds n_all (the plant tables' rows)");
+        hipLaunchKernelGGL(srb_sim_advance_plant_kernel, dim3((n_agents + 255) / 256), dim3(256), 0, s, n_agents, p->N,
+                           p->C, srb_nv(p), p->Ts, d->vref, cycle, d->c_first, d->state, d->goal, d->phase, d->x,
+                           d->status, d->iters, d->x0, d->ref, d->foot, d->last_state, d->alpha_buf, d->plan_table,
+                           d->traj, d->status_log, d->iters_log, d->x_log, d->agent_offset, p->grav,
+                           (unsigned)(pl->seed & 0xffffffffull), (unsigned)(pl->seed >> 32), pl->kick_v, pl->kick_p,
+                           pl->plant_hcom, pl->n_push, pl->push_cycle, pl->push_agent, pl->push_dv, pl->dist_log);
+        HIPCHK(hipGetLastError());
+        return SRB_OK;
+    }
     hipLaunchKernelGGL(srb_sim_advance_kernel, dim3((n_agents + 255) / 256), dim3(256), 0, s, n_agents, p->N, p->C,
                        srb_nv(p), p->Ts, d->vref, cycle, d->c_first, d->state, d->goal, d->phase, d->x, d->status,
                        d->iters, d->x0, d->ref, d->foot, d->last_state, d->alpha_buf, d->plan_table, d->traj,
@@ -1092,9 +1126,11 @@ int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cyc
 }
 
 static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream, bool advance,
-                    const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr)
+                    const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr, const srb_plant *pl = nullptr)
 {
     if (int rc = check_sim(d, cycle, advance)) return rc;
+    if (int rc = check_plant(pl, d->x != nullptr)) return rc;
+    if (!plant_on(pl)) pl = nullptr;
     if (int rc = srb_check_sizes(sz)) return rc;
     if (int rc = srb_check_agent_sizes(ag, d->nbr_state && d->n_all > 0)) return rc;
     if (!c) return fail(SRB_ERR_ARG, "null argument");
@@ -1102,7 +1138,7 @@ static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void 
     if (n_agents == 0) return SRB_OK;
     hipStream_t s = (hipStream_t)stream;
     return c->order.run(c->device, s, [&] {
-        return advance ? launch_advance(c, n_agents, d, cycle, s)
+        return advance ? launch_advance(c, n_agents, d, cycle, s, pl)
                        : launch_metrics(c, n_agents, d, cycle, s, sz ? sz->obs_radius : nullptr,
                                         ag ? ag->agent_body : nullptr, ag ? ag->collide_cycle : nullptr);
     });
@@ -1111,6 +1147,12 @@ static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void 
 extern "C" int srb_sim_advance_device(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream)
 {
     return sim_call(c, n_agents, d, cycle, stream, true);
+}
+
+extern "C" int srb_sim_advance_plant_device(srb_ctx *c, int n_agents, const srb_sim *d, const srb_plant *pl, int cycle,
+                                            void *stream)
+{
+    return sim_call(c, n_agents, d, cycle, stream, true, nullptr, nullptr, pl);
 }
 
 extern "C" int srb_sim_metrics_agents_device(srb_ctx *c, int n_agents, const srb_sim *d, const srb_sizes *sz,
@@ -1131,12 +1173,14 @@ extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d
 }
 
 static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, const srb_moving *mv,
-                   const srb_sizes *sz, const srb_agent_sizes *ag, int cycles, void *stream)
+                   const srb_sizes *sz, const srb_agent_sizes *ag, const srb_plant *pl, int cycles, void *stream)
 {
     if (int rc0 = srb_check_struct(b, "srb_batch")) return rc0;
     if (int rc0 = check_moving(mv, b, true)) return rc0;
     if (int rc0 = srb_check_sizes(sz)) return rc0;
     if (int rc0 = srb_check_agent_sizes(ag, true)) return rc0;    // (the driver's neighbour table is the team itself)
+    if (int rc0 = check_plant(pl, true)) return rc0;              // (batch.x missing is reported below, as ever)
+    if (!plant_on(pl)) pl = nullptr;
     // (the layout and null checks of check_sim only: the driver's first cycle is c_first itself)
     if (int rc = check_sim(d, d && d->struct_size == (int)sizeof(srb_sim) ? d->c_first : 0, false)) return rc;
     if (!b) return fail(SRB_ERR_ARG, "null argument");
@@ -1177,7 +1221,7 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
     const double *vel = (mv && b->n_obs > 0) ? mv->obs_vel : nullptr;
     for (int i = 0; i <= cycles && !rc; i++) {
         const int cyc = d->c_first + i;
-        rc = launch_advance(c, n_agents, &sim, cyc, s);
+        rc = launch_advance(c, n_agents, &sim, cyc, s, pl);
         if (rc || i == cycles) break;
         if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
         if (!rc) rc = launch_metrics(c, n_agents, &sim, cyc, s, sz ? sz->obs_radius : nullptr,
@@ -1191,12 +1235,20 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
     return rc ? rc : rc_mark;
 }
 
-// the tables of srb_sizes and srb_agent_sizes do not change over a rollout: the same pointers serve every cycle
+// the tables of srb_sizes, srb_agent_sizes and srb_plant do not change over a rollout: the same pointers serve every
+// cycle
+extern "C" int srb_rollout_plant_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
+                                        const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
+                                        const srb_plant *pl, int cycles, void *stream)
+{
+    return rollout(c, n_agents, b, d, mv, sz, ag, pl, cycles, stream);
+}
+
 extern "C" int srb_rollout_agents_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
                                          const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag, int cycles,
                                          void *stream)
 {
-    return rollout(c, n_agents, b, d, mv, sz, ag, cycles, stream);
+    return srb_rollout_plant_device(c, n_agents, b, d, mv, sz, ag, nullptr, cycles, stream);
 }
 
 extern "C" int srb_rollout_sized_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,

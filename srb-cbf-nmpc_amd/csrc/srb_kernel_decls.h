@@ -98,6 +98,16 @@ extern "C" __global__ void srb_sim_advance_kernel(int n_agents, int N, int C, in
                                                   double *ref, double *foot, double *last_state, double *alpha_buf,
                                                   double *plan_table, double *traj, int *status_log, int *iters_log,
                                                   double *x_log);
+// srb_plant.hip (compiled as part of srb_sim.hip): the advance of a cycle c > c_first through the disturbed plant of
+// srb_plant -- srb_sim_advance_kernel's arguments, then the row offset of the tables, gravity, the seed's halves
+// and the struct's tables (each may be null, n_push 0)
+extern "C" __global__ void srb_sim_advance_plant_kernel(
+    int n_agents, int N, int C, int nv, double Ts, double vref, int c, int c_first, double *state, const double *goal,
+    const int *phase, const double *x, const int *status, const int *iters, double *x0, double *ref, double *foot,
+    double *last_state, double *alpha_buf, double *plan_table, double *traj, int *status_log, int *iters_log,
+    double *x_log, int agent_offset, double grav, unsigned seed_lo, unsigned seed_hi, const double *kick_v,
+    const double *kick_p, const double *plant_hcom, int n_push, const int *push_cycle, const int *push_agent,
+    const double *push_dv, double *dist_log);
 #define SRB_SIM_AGENTS_PER_BLOCK 16      // srb_sim_metrics_kernel: agents per block of 256 threads (16 threads each)
 extern "C" __global__ void srb_sim_metrics_kernel(int n_agents, int c, int c_first, const double *state,
                                                   const double *obstacles, int n_obs, const double *nbr_state, int n_all,

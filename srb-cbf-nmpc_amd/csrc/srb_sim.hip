@@ -3,7 +3,9 @@
 //   srb_sim_advance_kernel   one thread per agent: the nominal plant (the next state is the solution's X at grid
 //                            index 3, the end of the gait domain -- what the reference buffers, MPC_dist.cpp:798),
 //                            the goal-directed reference and trot footholds of workload.make_batch re-centred on
-//                            the new position, last cycle's plans shifted by one domain, and the logs
+//                            the new position, last cycle's plans shifted by one domain, and the logs; all but the
+//                            choice of the state is sim_advance_from_state, which srb_plant.hip (included below:
+//                            srb_sim_advance_plant_kernel, the disturbed plant) calls with a state of its own
 //   srb_sim_metrics_kernel   brute force over the obstacle table and the neighbour snapshot: nearest obstacle,
 //                            nearest other agent, their running minima and the reference's distance_to_fail
 //                            (updateDistance_to_fail, MPC_dist.cpp:21-40); its scan and its update rules are in
@@ -22,29 +24,19 @@
 // MPC_dist.cpp:1206-1209: FR, FL, RR, RL offsets of the default stance (as srb_prepare.hip)
 __constant__ double c_sim_foot[4][2] = {{0.2188, -0.1320}, {0.2188, 0.1320}, {-0.1472, -0.1320}, {-0.1472, 0.1320}};
 
-extern "C" __global__ void __launch_bounds__(256) srb_sim_advance_kernel(
-    int n_agents, int N, int C, int nv, double Ts, double vref, int c, int c_first, double *__restrict__ state,
-    const double *__restrict__ goal, const int *__restrict__ phase, const double *__restrict__ x,
-    const int *__restrict__ status, const int *__restrict__ iters, double *__restrict__ x0, double *__restrict__ ref,
-    double *__restrict__ foot, double *__restrict__ last_state, double *__restrict__ alpha_buf,
-    double *__restrict__ plan_table, double *__restrict__ traj, int *__restrict__ status_log,
-    int *__restrict__ iters_log, double *__restrict__ x_log)
+// What an advance derives from the state (px, vx, py, vy) that starts cycle c, for agent a of A: alpha_buf, x0, the
+// snapshot row, the reference, the footholds, the traj row, and for c != c_first last cycle's plans shifted and the
+// previous solve's logs.  xa: the agent's previous decision vector (null at c_first).  Shared by the nominal
+// advance below and the disturbed plant of srb_plant.hip, which differ in the state they hand in.
+__device__ __forceinline__ void sim_advance_from_state(
+    const int a, const size_t A, const int N, const int C, const int nv, const double Ts, const double vref,
+    const int c, const int c_first, const double px, const double vx, const double py, const double vy,
+    const double *goal, const int *phase, const double *xa,
+    const int *status, const int *iters, double *x0, double *ref,
+    double *foot, double *last_state, double *alpha_buf,
+    double *plan_table, double *traj, int *status_log,
+    int *iters_log, double *x_log)
 {
-    const int a = blockIdx.x * blockDim.x + threadIdx.x;
-    if (a >= n_agents) return;
-    const size_t A = (size_t)n_agents;
-    const double *xa = x ? x + (size_t)a * nv : nullptr;
-    double *sa = state + 4 * (size_t)a;
-    // the state: the caller's before the first solve, else X at grid index 3 of the previous solution,
-    // whatever its status (a non-optimal exit returns the last iterate, as the reference does)
-    double px, vx, py, vy;
-    if (c == c_first) {
-        px = sa[0]; vx = sa[1]; py = sa[2]; vy = sa[3];
-    } else {
-        const double *X3 = xa + 4 * (SIM_NDOMAIN - 1);
-        px = X3[0]; vx = X3[1]; py = X3[2]; vy = X3[3];
-        sa[0] = px; sa[1] = vx; sa[2] = py; sa[3] = vy;
-    }
     if (alpha_buf) {
         double *ab = alpha_buf + 4 * (size_t)a;
         ab[0] = px; ab[1] = vx; ab[2] = py; ab[3] = vy;
@@ -124,6 +116,35 @@ extern "C" __global__ void __launch_bounds__(256) srb_sim_advance_kernel(
         for (int i = 0; i < nv; i++) xl[i] = xa[i];
     }
 }
+
+extern "C" __global__ void __launch_bounds__(256) srb_sim_advance_kernel(
+    int n_agents, int N, int C, int nv, double Ts, double vref, int c, int c_first, double *__restrict__ state,
+    const double *__restrict__ goal, const int *__restrict__ phase, const double *__restrict__ x,
+    const int *__restrict__ status, const int *__restrict__ iters, double *__restrict__ x0, double *__restrict__ ref,
+    double *__restrict__ foot, double *__restrict__ last_state, double *__restrict__ alpha_buf,
+    double *__restrict__ plan_table, double *__restrict__ traj, int *__restrict__ status_log,
+    int *__restrict__ iters_log, double *__restrict__ x_log)
+{
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    if (a >= n_agents) return;
+    const size_t A = (size_t)n_agents;
+    const double *xa = x ? x + (size_t)a * nv : nullptr;
+    double *sa = state + 4 * (size_t)a;
+    // the state: the caller's before the first solve, else X at grid index 3 of the previous solution,
+    // whatever its status (a non-optimal exit returns the last iterate, as the reference does)
+    double px, vx, py, vy;
+    if (c == c_first) {
+        px = sa[0]; vx = sa[1]; py = sa[2]; vy = sa[3];
+    } else {
+        const double *X3 = xa + 4 * (SIM_NDOMAIN - 1);
+        px = X3[0]; vx = X3[1]; py = X3[2]; vy = X3[3];
+        sa[0] = px; sa[1] = vx; sa[2] = py; sa[3] = vy;
+    }
+    sim_advance_from_state(a, A, N, C, nv, Ts, vref, c, c_first, px, vx, py, vy, goal, phase, xa, status, iters,
+                           x0, ref, foot, last_state, alpha_buf, plan_table, traj, status_log, iters_log, x_log);
+}
+
+#include "srb_plant.hip"       // the disturbed plant (srb_plant): srb_sim_advance_plant_kernel, on the body above
 
 #include "srb_sim_scan.h"      // SIM_TILE, SIM_AG, SIM_SL and sim_nearest2, the tiled scan (shared with srb_scenes.hip)
 

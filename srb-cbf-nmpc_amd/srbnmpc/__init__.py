@@ -123,6 +123,16 @@ class AgentSizes(ctypes.Structure):
         super().__init__(ctypes.sizeof(AgentSizes), *args, **kw)
 
 
+class Plant(ctypes.Structure):
+    """Mirror of srb_plant (the disturbed plant of the LIP rollout; struct_size filled in)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("seed", ctypes.c_ulonglong), ("kick_v", _dp), ("kick_p", _dp),
+                ("plant_hcom", _dp), ("n_push", ctypes.c_int), ("push_cycle", _ip), ("push_agent", _ip), ("push_dv", _dp),
+                ("dist_log", _dp)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(ctypes.sizeof(Plant), *args, **kw)
+
+
 _lib = None
 
 
@@ -197,6 +207,11 @@ def lib():
                                                     ctypes.c_void_p]
         L.srb_rollout_agents_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim), MV,
                                                 SZ, AG, ctypes.c_int, ctypes.c_void_p]
+        PL = ctypes.POINTER(Plant)
+        L.srb_sim_advance_plant_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Sim), PL, ctypes.c_int,
+                                                   ctypes.c_void_p]
+        L.srb_rollout_plant_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim), MV,
+                                               SZ, AG, PL, ctypes.c_int, ctypes.c_void_p]
         L.srb_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.srb_fit_bezier.argtypes = [_dp, _dp, _dp]
         L.srb_last_error.restype = ctypes.c_char_p

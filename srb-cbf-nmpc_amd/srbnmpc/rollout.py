@@ -30,6 +30,14 @@ dist - agent_rad, and with agent_body ([n_all], m) d_agent is the clearance betw
 cycle with d_agent < 0 (srb_agent_sizes, srb_rollout_agents_device; srb12.Rollout12 likewise,
 srb12_rollout_agents_device).  The tables do not change over a rollout and every shard holds them whole.
 
+With kick_v / kick_p ([n_all], m/s and m), plant_hcom ([n_all], m) or pushes the plant is disturbed (srb_plant,
+srb_sim_advance_plant_device / srb_rollout_plant_device; LIP mode only): from the second cycle on the state that starts
+a cycle is the model's prediction -- or, with plant_hcom, the roll of a LIP of that CoM height under the inputs the model
+applied -- plus a bounded uniform kick per cycle (Philox4x32-10 keyed by plant_seed, counter (cycle, global row)) and the
+pushes due.  results()["disturbance"] logs what was added.  The tables do not change over a rollout and every shard
+holds them whole; workload.plant_tables draws a set, workload.replicate_scenes tiles a scene for a Monte-Carlo over
+the draws.
+
 _RolloutBase is what this class and srb12.Rollout12 share: the checks of goal / phase / obstacles / obs_vel and of the
 obstacle and agent size tables, the moving table's clone and its restore, the srb_moving, srb_sizes and
 srb_agent_sizes of a call, the metrics call, the solve, metrics and log buffers, reset / advance / results /
@@ -40,8 +48,8 @@ from __future__ import annotations
 
 import ctypes
 
-from . import (AgentSizes, Batch, Moving, Sim, Sizes, _check, _check_agent_array, _check_size_array, _check_vel_array,
-               _dptr, _iptr, lib)
+from . import (AgentSizes, Batch, Moving, Plant, Sim, Sizes, _check, _check_agent_array, _check_size_array,
+               _check_vel_array, _dptr, _iptr, lib)
 
 
 def _check_tensor(t, shape, name, dtype, device):
@@ -292,6 +300,17 @@ class Rollout(_RolloutBase):
     nbr_clearance  True: the neighbour columns by clearance dist - agent_rad (needs agent_rad)
               The agent tables (srb_agent_sizes) are finite, agent_rad and agent_body not negative, and do not change
               over a rollout; every shard holds the whole tables.
+    plant_seed  the key of the kicks' draws (0 .. 2^64 - 1); a rollout is reproducible per seed
+    kick_v, kick_p  [n_all] or None: the bound (m/s, m) of the uniform kick every cycle adds to each agent's
+              velocity / position (finite, not negative)
+    plant_hcom  [n_all] or None: the CoM height (m, finite, positive) of each agent's plant; the state then follows
+              the plant's own LIP under the model's inputs instead of the model's prediction (None: the prediction)
+    pushes    None or (cycle int32 [P], agent int32 [P], dv float64 [P][2]), P <= 4096: entry p adds dv[p] (m/s) to the
+              velocity of global row agent[p] at the start of cycle cycle[p] (>= 1: the first cycle starts from
+              reset()'s state); entries on one agent and cycle add up in table order
+              With any of these set advance(), step() and run() go through the plant entry points and results() gains
+              disturbance [T][A][4] (dpx, dvx, dpy, dvy; row c - 1 is what the start of cycle c added).  Every shard
+              holds the whole tables and draws by global row, so shards reproduce the team.
     agent_offset, n_all   a shard of a larger team: this batch is rows agent_offset .. agent_offset + A of the
               n_all-row neighbour table that step(exchange) gathers (default: the whole team)
     All tensors are float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
@@ -299,7 +318,8 @@ class Rollout(_RolloutBase):
     def __init__(self, solver, goal, vref: float = 0.27, phase=None, plans: bool = False, log_x: bool = False, *,
                  obstacles=None, agent_offset: int = 0, n_all: int | None = None, obs_vel=None, obs_horizon: bool = False,
                  obs_eps=None, obs_radius=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
-                 agent_body=None, nbr_clearance: bool = False):
+                 agent_body=None, nbr_clearance: bool = False, plant_seed: int = 0, kick_v=None, kick_p=None,
+                 plant_hcom=None, pushes=None):
         import torch
         super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps, obs_radius,
                          obs_clearance)
@@ -309,12 +329,92 @@ class Rollout(_RolloutBase):
         if self.agent_offset < 0 or self.agent_offset + A > self.n_all:
             raise ValueError("agent_offset + A exceeds n_all")
         self._set_agent_sizes(agent_rad, agent_pad, agent_body, nbr_clearance, self.n_all)
+        self._set_plant(plant_seed, kick_v, kick_p, plant_hcom, pushes)
         self.sharded = self.agent_offset != 0 or self.n_all != A
         f8 = dict(dtype=torch.float64, device=self.device)
         self.alpha_buf = torch.zeros((A, 4), **f8)
         self.ref = torch.zeros((A, 4 * p.N), **f8)
         self.foot = torch.zeros((A, p.N, 2, p.C), **f8)
         self.out["alpha"] = torch.zeros((A, 20), **f8)
+
+    # ------------------------------------------------------------------ the disturbed plant (srb_plant)
+    def _set_plant(self, seed, kick_v, kick_p, plant_hcom, pushes):
+        """The plant tables ([n_all] each, or None) and the push table after their checks, by name."""
+        import torch
+        seed = int(seed)
+        if seed < 0 or seed >= 1 << 64:
+            raise ValueError("plant_seed must be 0 .. 2^64 - 1 (the 64-bit Philox key)")
+        for name, tab in (("kick_v", kick_v), ("kick_p", kick_p), ("plant_hcom", plant_hcom)):
+            if tab is None:
+                continue
+            _check_size_array(tab, self.n_all, torch.float64, name, self.device)
+            if not bool(tab.isfinite().all()):
+                raise ValueError(f"{name} must be finite")
+            if name == "plant_hcom" and bool((tab <= 0).any()):
+                raise ValueError("plant_hcom must be > 0 (a CoM height in metres)")
+            if name != "plant_hcom" and bool((tab < 0).any()):
+                raise ValueError(f"{name} must be >= 0 (the bound of a uniform kick)")
+        if pushes is not None:
+            if not isinstance(pushes, (tuple, list)) or len(pushes) != 3:
+                raise ValueError("pushes must be a triple (cycle int32 [P], agent int32 [P], dv float64 [P][2])")
+            cyc, agent, dv = pushes
+            P = int(cyc.shape[0]) if hasattr(cyc, "shape") and len(cyc.shape) == 1 else -1
+            if P < 0 or P > 4096:
+                raise ValueError("pushes: cycle must be an int32 tensor [P], P <= 4096")
+            _check_tensor(cyc, (P,), "pushes: cycle", torch.int32, self.device)
+            _check_tensor(agent, (P,), "pushes: agent", torch.int32, self.device)
+            _check_tensor(dv, (P, 2), "pushes: dv", torch.float64, self.device)
+            if P and (bool((agent < 0).any()) or bool((agent >= self.n_all).any())):
+                raise ValueError(f"pushes: agent must be a global row 0 .. {self.n_all - 1}")
+            pushes = (cyc, agent, dv) if P else None
+        self.plant_seed, self.kick_v, self.kick_p, self.plant_hcom, self.pushes = seed, kick_v, kick_p, plant_hcom, pushes
+        self.plant = kick_v is not None or kick_p is not None or plant_hcom is not None or pushes is not None
+        self.dist_log = None
+        self._advanced = -1             # the cycle whose advance has run (the plant's advance is not idempotent)
+
+    def _plant(self) -> Plant:
+        cyc, agent, dv = self.pushes if self.pushes is not None else (None, None, None)
+        return Plant(self.plant_seed, _dptr(self.kick_v), _dptr(self.kick_p), _dptr(self.plant_hcom),
+                     0 if cyc is None else cyc.shape[0], _iptr(cyc), _iptr(agent), _dptr(dv), _dptr(self.dist_log))
+
+    def _reserve(self, cycles: int):
+        super()._reserve(cycles)
+        if self.plant and (self.dist_log is None or self.dist_log.shape[0] < self.cap):
+            import torch
+            new = torch.zeros((self.cap, self.A, 4), dtype=torch.float64, device=self.device)
+            if self.dist_log is not None:
+                new[:self.dist_log.shape[0]] = self.dist_log
+            self.dist_log = new
+
+    def reset(self, state):
+        super().reset(state)
+        self._advanced = -1
+
+    def advance(self, stream=None):
+        """As _RolloutBase.advance; with a disturbed plant through srb_sim_advance_plant_device, and once per cycle:
+        the plant rolls on from the state of the previous cycle, so a second call for the same cycle is skipped
+        (everything it would write is already there)."""
+        if not self.plant:
+            return super().advance(stream)
+        if not self._ready:
+            raise RuntimeError("Rollout.advance before reset(state)")
+        if self._advanced == self.c:
+            return
+        s = self.solver
+        self._reserve(self.c + 1)
+        sim = self._sim()
+        sim.n_all = self.n_all               # the rows of the plant tables (an advance reads no neighbour table)
+        _check(lib().srb_sim_advance_plant_device(s._h, self.A, ctypes.byref(sim), ctypes.byref(self._plant()),
+                                                  self.c, s._stream(stream)))
+        self._advanced = self.c
+
+    def results(self, stream=None):
+        """As _RolloutBase.results; with a disturbed plant also disturbance [T][A][4]: row c - 1 is the (dpx, dvx, dpy,
+        dvy) that the start of cycle c added to the plant's base state."""
+        out = super().results(stream)
+        if self.plant:
+            out["disturbance"] = self.dist_log[:self.c]
+        return out
 
     def _sim(self, nbr_state=None) -> Sim:
         nbr = self.last_state if nbr_state is None else nbr_state
@@ -363,7 +463,14 @@ class Rollout(_RolloutBase):
                   0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                   None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]),
                   None, _dptr(o["alpha"]), None, 0, None, _dptr(o.get("plan")))
-        if self.agents:
+        if self.plant:
+            mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
+            sz = ctypes.byref(self._sizes()) if self.sized else None
+            ag = ctypes.byref(self._agent_sizes()) if self.agents else None
+            _check(lib().srb_rollout_plant_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), mv, sz, ag,
+                                                  ctypes.byref(self._plant()), T, s._stream(stream)))
+            self._advanced = T               # the driver's final advance was cycle T's
+        elif self.agents:
             mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
             sz = ctypes.byref(self._sizes()) if self.sized else None
             _check(lib().srb_rollout_agents_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), mv, sz,

@@ -408,8 +408,14 @@ class Rollout12(_RolloutBase):
                  obstacles=None, hcom: float = workload.HCOM12, yaw_step: float = 0.1, hold_radius: float = 0.05,
                  plans: bool = False, plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False,
                  obs_eps=None, obs_radius=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
-                 agent_body=None, nbr_clearance: bool = False):
+                 agent_body=None, nbr_clearance: bool = False, *, plant_seed: int = 0, kick_v=None, kick_p=None,
+                 plant_hcom=None, pushes=None):
         import torch
+        for name, arg in (("plant_seed", plant_seed or None), ("kick_v", kick_v), ("kick_p", kick_p),
+                          ("plant_hcom", plant_hcom), ("pushes", pushes)):
+            if arg is not None:
+                raise ValueError(f"Rollout12: {name} is not available: the disturbed plant (srb_plant) is built for the "
+                                 "LIP mode only (rollout.Rollout)")
         if gait not in GAITS:
             raise ValueError(f"gait must be one of {sorted(GAITS)}, got {gait!r}")
         super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps, obs_radius,

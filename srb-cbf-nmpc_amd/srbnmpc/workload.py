@@ -182,6 +182,34 @@ def make_scenes(n_scenes: int, team: int, N: int = 10, C: int = 2, seed: int = 0
     return out
 
 
+HCOM = 0.29       # srb_params.hcom: the model's CoM height (MPC_dist.cpp:90-104)
+
+
+def plant_tables(n_all: int, seed: int):
+    """(kick_v, kick_p, plant_hcom), each [n_all], for a disturbed plant (Rollout(kick_v=..., kick_p=...,
+    plant_hcom=...)), deterministic per seed.  kick_v ~ U[0.02, 0.08] m/s per cycle: 7 % to 30 % of the reference
+    speed VREF = 0.27 m/s, velocity noise that is felt and that a walking robot still absorbs.  kick_p ~ U[0, 0.01] m
+    per cycle: at most what VREF covers in one grid step (0.27 * 0.043 = 0.0116 m), a foot that slipped.  plant_hcom ~
+    HCOM * U[0.85, 1.15] = 0.2465 .. 0.3335 m: a payload or a crouch the model does not know of, 15 % either way of
+    the nominal 0.29 m.  From a generator of their own (400 + seed), so every other draw of this module is what it
+    was."""
+    g = np.random.default_rng(400 + seed)
+    kick_v = g.uniform(0.02, 0.08, n_all)
+    kick_p = g.uniform(0.0, 0.01, n_all)
+    return kick_v, kick_p, HCOM * g.uniform(0.85, 1.15, n_all)
+
+
+def replicate_scenes(scenes: dict, copies: int):
+    """A make_scenes dict tiled `copies` times, scene-major: every array's rows repeated as a block, so rows
+    [i * R, (i + 1) * R) of a table of R rows are replica i.  One scene (or set of scenes) then runs `copies` times in
+    one launch with the same set_scenes(team, n_obs); under a disturbed plant each replica has draws of its own,
+    because its global rows differ: the Monte-Carlo over disturbances that Rollout.scene_results() reduces."""
+    copies = int(copies)
+    if copies < 1:
+        raise ValueError("replicate_scenes: copies >= 1")
+    return {k: np.tile(np.asarray(v), (copies,) + (1,) * (np.asarray(v).ndim - 1)) for k, v in scenes.items()}
+
+
 HCOM12 = 0.3      # SRB-12 mode: nominal CoM height of the synthetic batches
 
 
