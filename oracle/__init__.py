@@ -188,8 +188,23 @@ def nlp_solve(p: OrcParams, x0, foot, Pd, c, A, b, G, h, obs, eps, x_init):
     return x, f, it.value
 
 
-def solve_batch(p: OrcParams, x0, ref, foot, obstacles, nbr_state=None, agent_offset=0, nthreads=1):
-    """Whole run_NMPC hot path for a batch (agent-major arrays, see include/srbnmpc.h)."""
+# columns of the per-agent inertia-shift statistics (oracle.h ORC_ST_*) and the exit rules (ORC_EXIT_*)
+STAT_COLS = ("shift_iters", "failed", "max_tries", "max_delta", "exit", "polish_npd")
+EXIT_RULES = ("converged", "provisional", "near_shifted", "near_blocked", "left_near", "near_wait", "tries", "lu",
+              "maxit", "diverged")
+
+
+def _stats_dict(st):
+    """[A, ORC_NSTAT] doubles -> named columns; `exit` is an index into EXIT_RULES (-1: the NLP stage did not run)."""
+    d = {k: st[:, i].astype(np.int64) for i, k in enumerate(STAT_COLS) if k != "max_delta"}
+    d["max_delta"] = st[:, STAT_COLS.index("max_delta")].copy()
+    d["polish_npd"] = d["polish_npd"].astype(bool)
+    return d
+
+
+def solve_batch(p: OrcParams, x0, ref, foot, obstacles, nbr_state=None, agent_offset=0, nthreads=1, stats=False):
+    """Whole run_NMPC hot path for a batch (agent-major arrays, see include/srbnmpc.h).  stats=True adds
+    out["stats"]: the NLP stage's inertia-shift statistics per agent (STAT_COLS)."""
     nv = sizes(p)[0]
     x0 = _c(x0).reshape(-1, 4); A_ = x0.shape[0]
     ref = _c(ref).reshape(A_, -1); foot = _c(foot).reshape(A_, -1)
@@ -197,6 +212,12 @@ def solve_batch(p: OrcParams, x0, ref, foot, obstacles, nbr_state=None, agent_of
     nb = _c(nbr_state if nbr_state is not None else np.zeros((0, 4))).reshape(-1, 4)
     xq = np.zeros((A_, nv)); x = np.zeros((A_, nv)); obj = np.zeros(A_)
     st = np.zeros((A_, 2), np.int32); it = np.zeros((A_, 2), np.int32)
+    if stats:
+        sa = np.zeros((A_, len(STAT_COLS)))
+        lib().orc_solve_batch_stats(ctypes.byref(p), A_, _ptr(x0), _ptr(ref), _ptr(foot), _ptr(ob), ob.shape[0], _ptr(nb),
+                                    nb.shape[0], agent_offset, _ptr(xq), _ptr(x), _ptr(obj), _ptr(st), _ptr(it), nthreads,
+                                    _ptr(sa))
+        return dict(x_qp=xq, x=x, obj=obj, status=st, iters=it, stats=_stats_dict(sa))
     lib().orc_solve_batch(ctypes.byref(p), A_, _ptr(x0), _ptr(ref), _ptr(foot), _ptr(ob), ob.shape[0], _ptr(nb),
                           nb.shape[0], agent_offset, _ptr(xq), _ptr(x), _ptr(obj), _ptr(st), _ptr(it), nthreads)
     return dict(x_qp=xq, x=x, obj=obj, status=st, iters=it)
@@ -359,16 +380,22 @@ def dynamics12(p: Orc12Params, x0, xref, foot, contact):
 
 
 def solve_batch12(p: Orc12Params, x0, xref, foot, contact, obstacles=None, nbr_state=None, agent_offset=0,
-                  nthreads=8):
+                  nthreads=8, stats=False):
     """SRB-12 solves of a batch: x0 [A,12], xref [A,N,12], foot [A,N,4,3], contact [A,N,4] int.
-    Returns x_qp, x [A, 24N+1], obj, status [A,2], iters [A,2]."""
+    Returns x_qp, x [A, 24N+1], obj, status [A,2], iters [A,2]; stats=True adds "stats" as solve_batch does."""
     x0 = _c(x0); A_ = x0.shape[0]; nv = nv12(p)
     ob = _c(obstacles if obstacles is not None else np.zeros((0, 2)))
     nb = _c(nbr_state) if nbr_state is not None else None
     out = dict(x_qp=np.zeros((A_, nv)), x=np.zeros((A_, nv)), obj=np.zeros(A_),
                status=np.zeros((A_, 2), np.int32), iters=np.zeros((A_, 2), np.int32))
-    lib().orc12_solve_batch(ctypes.byref(p), A_, _ptr(x0), _ptr(_c(xref)), _ptr(_c(foot)), _ptr(_c(contact, np.int32)),
-                            _ptr(ob), ob.shape[0], _ptr(nb) if nb is not None else None,
-                            nb.shape[0] if nb is not None else 0, int(agent_offset), _ptr(out["x_qp"]), _ptr(out["x"]),
-                            _ptr(out["obj"]), _ptr(out["status"]), _ptr(out["iters"]), int(nthreads))
+    args = (ctypes.byref(p), A_, _ptr(x0), _ptr(_c(xref)), _ptr(_c(foot)), _ptr(_c(contact, np.int32)),
+            _ptr(ob), ob.shape[0], _ptr(nb) if nb is not None else None,
+            nb.shape[0] if nb is not None else 0, int(agent_offset), _ptr(out["x_qp"]), _ptr(out["x"]),
+            _ptr(out["obj"]), _ptr(out["status"]), _ptr(out["iters"]), int(nthreads))
+    if stats:
+        sa = np.zeros((A_, len(STAT_COLS)))
+        lib().orc12_solve_batch_stats(*args, _ptr(sa))
+        out["stats"] = _stats_dict(sa)
+    else:
+        lib().orc12_solve_batch(*args)
     return out

@@ -49,6 +49,7 @@ typedef struct {
     const orc_params *p; int lo, hi;
     const double *x0, *ref, *foot, *obstacles, *nbr; int n_obs, n_all, off;
     double *x_qp, *x_out, *obj; int *status, *iters;
+    double *stats;
 } job_t;
 
 static void *worker(void *arg)
@@ -56,18 +57,26 @@ static void *worker(void *arg)
     job_t *j = (job_t *)arg;
     const orc_params *p = j->p;
     const int nv = orc_nv(p), N = p->N, C = p->C;
-    for (int a = j->lo; a < j->hi; a++)
+    for (int a = j->lo; a < j->hi; a++) {
+        if (j->stats) {
+            orc_stats_sink = j->stats + (size_t)ORC_NSTAT * a;
+            memset(orc_stats_sink, 0, sizeof(double) * ORC_NSTAT);
+            orc_stats_sink[ORC_ST_EXIT] = -1.0;
+        }
         orc_solve_agent(p, j->x0 + 4 * a, j->ref + (size_t)4 * N * a, j->foot + (size_t)2 * N * C * a,
                         j->obstacles, j->n_obs, j->nbr, j->n_all, j->off + a,
                         j->x_qp ? j->x_qp + (size_t)nv * a : NULL, j->x_out + (size_t)nv * a, j->obj + a,
                         j->status + 2 * a, j->iters + 2 * a);
+    }
+    orc_stats_sink = NULL;
     return NULL;
 }
 
-int orc_solve_batch(const orc_params *p, int n_agents, const double *x0, const double *ref,
-                    const double *foot, const double *obstacles, int n_obs,
-                    const double *nbr_state, int n_all, int agent_offset,
-                    double *x_qp, double *x_out, double *obj, int *status, int *iters, int nthreads)
+int orc_solve_batch_stats(const orc_params *p, int n_agents, const double *x0, const double *ref,
+                          const double *foot, const double *obstacles, int n_obs,
+                          const double *nbr_state, int n_all, int agent_offset,
+                          double *x_qp, double *x_out, double *obj, int *status, int *iters, int nthreads,
+                          double *stats)
 {
     if (nthreads < 1) nthreads = 1;
     if (nthreads > n_agents) nthreads = n_agents > 0 ? n_agents : 1;
@@ -79,9 +88,19 @@ int orc_solve_batch(const orc_params *p, int n_agents, const double *x0, const d
         j->x0 = x0; j->ref = ref; j->foot = foot; j->obstacles = obstacles; j->nbr = nbr_state;
         j->n_obs = n_obs; j->n_all = n_all; j->off = agent_offset;
         j->x_qp = x_qp; j->x_out = x_out; j->obj = obj; j->status = status; j->iters = iters;
+        j->stats = stats;
         pthread_create(&th[t], NULL, worker, j);
     }
     for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
     free(th); free(jobs);
     return 0;
+}
+
+int orc_solve_batch(const orc_params *p, int n_agents, const double *x0, const double *ref,
+                    const double *foot, const double *obstacles, int n_obs,
+                    const double *nbr_state, int n_all, int agent_offset,
+                    double *x_qp, double *x_out, double *obj, int *status, int *iters, int nthreads)
+{
+    return orc_solve_batch_stats(p, n_agents, x0, ref, foot, obstacles, n_obs, nbr_state, n_all, agent_offset,
+                                 x_qp, x_out, obj, status, iters, nthreads, NULL);
 }

@@ -174,11 +174,12 @@ int orc_early_stats[2];          /* exploration counters: early polish attempts 
 unsigned long long orc_polish_stat_max[2];   /* exploration: the largest reduced stationarity / scale of an accepted (0) /
                                                 rejected (1) pass, as the bits of a non-negative double (ordered as the values) */
 int orc_polish_stats[16];        /* exploration counters: [0] rejected, [1 + p] accepted after pass p */
+__thread double *orc_stats_sink; /* the agent's statistics row (oracle.h ORC_NSTAT), NULL: not recorded */
 static int g_polish_it = ORC_POLISH_IT, g_polish_passes = ORC_POLISH_PASSES;
 static double g_polish_omcap = ORC_POLISH_OMCAP;
 
 /* Newton steps of the regularised equality-constrained KKT for the active set `act`; returns 0
- * on success, -1 when the reduced matrix is not positive definite */
+ * on success, -1 when the reduced matrix is not positive definite, -2 when the full-space LU fails */
 static int polish_newton(const nlp_t *P, const double *hh, const double *Z, int nz, const int *act, const double *om,
                          double *xt, double *za, double *g, double *Jv, int *Ji, double *Hl, double *K, double *rhs,
                          double *cA, double *Hr, double *HZ, int *piv, double *lastdx, int trace)
@@ -231,7 +232,7 @@ static int polish_newton(const nlp_t *P, const double *hh, const double *Z, int 
             for (int j = 0; j < n; j++) { K[(n + k) * dim + j] = P->A[(size_t)k * n + j]; K[j * dim + n + k] = P->A[(size_t)k * n + j]; }
             rhs[n + k] = P->b[k] - dotv(P->A + (size_t)k * n, xt, n);
         }
-        if (orc_lu(dim, K, piv)) return -1;
+        if (orc_lu(dim, K, piv)) return -2;
         orc_lu_solve(dim, K, piv, rhs);
         double mdx = 0.0;
         for (int r = 0; r < m; r++) {
@@ -266,7 +267,9 @@ static int polish(const nlp_t *P, const double *hh, const double *Z, int nz, dou
     for (int pass = 0; pass < g_polish_passes && !ok; pass++, npass++) {
         memcpy(xt, x, sizeof(double) * n);
         double lastdx = 1e300;
-        if (polish_newton(P, hh, Z, nz, act, om, xt, za, g, Jv, Ji, Hl, K, rhs, cA, Hr, HZ, piv, &lastdx, trace)) {
+        const int pn = polish_newton(P, hh, Z, nz, act, om, xt, za, g, Jv, Ji, Hl, K, rhs, cA, Hr, HZ, piv, &lastdx, trace);
+        if (pn) {
+            if (pn == -1 && orc_stats_sink) orc_stats_sink[ORC_ST_POLISH_NPD] = 1.0;
             if (trace) fprintf(stderr, "  polish pass %d: reduced matrix not positive definite -> rejected\n", pass);
             break;
         }
@@ -393,6 +396,9 @@ int orc_nlp_solve(const orc_params *pp, const double x0[4], const double *foot,
     double *Z = malloc(sizeof(double) * (size_t)n * nz), *Hr = malloc(sizeof(double) * nz * nz), *HZ = malloc(sizeof(double) * (size_t)n * nz);
     int *piv = malloc(sizeof(int) * dim);
     int flag = 2, it = 0;
+    /* statistics (orc_stats_sink): the exit rule and the inertia loop's counts; they steer nothing */
+    int st_exit = ORC_EXIT_MAXIT, st_shift_iters = 0, st_failed = 0, st_max_tries = 0;
+    double st_max_delta = 0.0;
     build_Z(pp, foot, Z, n, nz);
 
     memcpy(x, x_init, sizeof(double) * n);
@@ -455,11 +461,11 @@ int orc_nlp_solve(const orc_params *pp, const double x0[4], const double *foot,
         for (int r = 0; r < m; r++) rz[r] = hh[r] - s[r] - g[r];
         double nrx = sqrt(dotv(rx, rx, n)), nrz = sqrt(dotv(rz, rz, m)), nry = sqrt(dotv(ry, ry, p));
         double sz = dotv(s, z, m);
-        if (!isfinite(nrx) || !isfinite(nrz) || !isfinite(sz)) { flag = 3; break; }
+        if (!isfinite(nrx) || !isfinite(nrz) || !isfinite(sz)) { flag = 3; st_exit = ORC_EXIT_DIVERGED; break; }
         {                                          /* divergence: ORC_Z_DIV (qp_ipm.c) */
             double zm = 0.0;
             for (int r = 0; r < m; r++) zm = fmax(zm, z[r]);
-            if (!(zm <= ORC_Z_DIV)) { flag = 3; break; }
+            if (!(zm <= ORC_Z_DIV)) { flag = 3; st_exit = ORC_EXIT_DIVERGED; break; }
         }
         /* dual residual scaled by the objective gradient (the NLP's own criterion; the
          * QP stage keeps iSWIFT's absolute test): max(1, ||Q x + f||_inf) */
@@ -470,13 +476,13 @@ int orc_nlp_solve(const orc_params *pp, const double x0[4], const double *foot,
             /* the loosened tests (ORC_NLP_EXITF) rely on the polish: met only by them, the result is
              * provisional -- ACCEPTABLE unless the polish is accepted (the kernel, same rule) */
             provisional = !(nrx < th * gmax && nrz < th && nry < th && sz / m < tol);
-            flag = 0; break;
+            flag = 0; st_exit = provisional ? ORC_EXIT_PROVISIONAL : ORC_EXIT_CONVERGED; break;
         }
         /* exploration: one early polish attempt once the complementarity gap is below early_mu */
         if (early_mu > 0 && !early_tried && sz / m < early_mu && nrz < early_rz) {
             early_tried = 1;
             memcpy(xe, x, sizeof(double) * n); memcpy(ze, z, sizeof(double) * m);
-            if (polish(&P, hh, Z, nz, xe, s, ze, trace)) { memcpy(x, xe, sizeof(double) * n); flag = 0; early_done = 1; __atomic_add_fetch(&orc_early_stats[1], 1, __ATOMIC_RELAXED); break; }
+            if (polish(&P, hh, Z, nz, xe, s, ze, trace)) { memcpy(x, xe, sizeof(double) * n); flag = 0; early_done = 1; st_exit = ORC_EXIT_CONVERGED; __atomic_add_fetch(&orc_early_stats[1], 1, __ATOMIC_RELAXED); break; }
             __atomic_add_fetch(&orc_early_stats[0], 1, __ATOMIC_RELAXED);
         }
         /* near the optimum: primal and complementarity met, dual residual within 100x of its
@@ -485,7 +491,7 @@ int orc_nlp_solve(const orc_params *pp, const double x0[4], const double *foot,
         const int near = nrz < th && nry < th && sz / m < fmu * tol && nrx < facc * fx * th * gmax;
         /* a solve that reached the near-optimal region and then left it is past its round-off
          * floor: ACCEPTABLE at the best near-optimal iterate */
-        if (saved && !near) { restore = 1; flag = 4; break; }
+        if (saved && !near) { restore = 1; flag = 4; st_exit = ORC_EXIT_LEFT_NEAR; break; }
         /* the saved iterate is the best near-optimal one (smallest scaled dual residual); the
          * polish starts from its s, z too */
         if (near && nrx / gmax <= best_rx) {
@@ -493,7 +499,7 @@ int orc_nlp_solve(const orc_params *pp, const double x0[4], const double *foot,
             memcpy(xsave, x, sizeof(double) * n); memcpy(ssave, s, sizeof(double) * m); memcpy(zsave, z, sizeof(double) * m);
             saved = 1;
         }
-        if (near && ++npassed >= nearwait) { flag = 4; break; }
+        if (near && ++npassed >= nearwait) { flag = 4; st_exit = ORC_EXIT_NEAR_WAIT; break; }
         for (int r = 0; r < m; r++) { lam[r] = sqrt(s[r] * z[r]); wgt[r] = s[r] / z[r]; }
         double mu = dotv(lam, lam, m) / m;
 
@@ -514,7 +520,7 @@ int orc_nlp_solve(const orc_params *pp, const double x0[4], const double *foot,
             }
         }
         /* inertia correction: reduced Hessian Z'(H + delta I)Z must be PD */
-        double delta = 0.0, dstart = 0.0; int ok = 0;
+        double delta = 0.0, dstart = 0.0; int ok = 0, ntried = 0;
         for (int tries = 0; tries < 14; tries++) {
             for (int i = 0; i < n; i++)
                 for (int a = 0; a < nz; a++) {
@@ -533,16 +539,19 @@ int orc_nlp_solve(const orc_params *pp, const double x0[4], const double *foot,
                 for (int a = 0; a < nz; a++) if (Hr[a * nz + a] > dstart) dstart = Hr[a * nz + a];
                 dstart *= 1e-10;
             }
+            if (delta > st_max_delta) st_max_delta = delta;
             if (orc_chol(nz, Hr) == 0) { ok = 1; break; }
             delta = (delta == 0.0) ? dstart : delta * 10.0;
+            ntried++;
         }
-        if (!ok) { flag = 1; break; }
-        if (near && delta != 0.0) { flag = 4; break; }
+        if (ntried) { st_shift_iters++; st_failed += ntried; if (ntried > st_max_tries) st_max_tries = ntried; }
+        if (!ok) { flag = 1; st_exit = ORC_EXIT_TRIES; break; }
+        if (near && delta != 0.0) { flag = 4; st_exit = ORC_EXIT_NEAR_SHIFTED; break; }
         /* full-space KKT [H + delta I, A'; A, 0] */
         memset(K, 0, sizeof(double) * dim * dim);
         for (int i = 0; i < n; i++) { for (int j = 0; j < n; j++) K[i * dim + j] = Hl[i * n + j]; K[i * dim + i] += delta; }
         for (int k = 0; k < p; k++) for (int j = 0; j < n; j++) { K[(n + k) * dim + j] = A[(size_t)k * n + j]; K[j * dim + n + k] = A[(size_t)k * n + j]; }
-        if (orc_lu(dim, K, piv)) { flag = 1; break; }
+        if (orc_lu(dim, K, piv)) { flag = 1; st_exit = ORC_EXIT_LU; break; }
 
         for (int pass = 0; pass < 2; pass++) {
             if (pass == 0) for (int r = 0; r < m; r++) ds[r] = -lam[r] * lam[r];
@@ -581,13 +590,18 @@ int orc_nlp_solve(const orc_params *pp, const double x0[4], const double *foot,
         if (trace)
             fprintf(stderr, "  %2d %10.3e %10.3e %10.3e %10.3e %10.3e %10.3e %10.3e %10.3e\n", iter, nrx, th * gmax, nrz, sz / m,
                     ap, ad, delta, tr_sigma);
-        if (near && (ap < ORC_NLP_BLOCKED || ad < ORC_NLP_BLOCKED)) { flag = 4; break; }
+        if (near && (ap < ORC_NLP_BLOCKED || ad < ORC_NLP_BLOCKED)) { flag = 4; st_exit = ORC_EXIT_NEAR_BLOCKED; break; }
         ap = 0.99 * ap < 1.0 ? 0.99 * ap : 1.0;
         ad = 0.99 * ad < 1.0 ? 0.99 * ad : 1.0;
         dxlast = 0.0;
         for (int j = 0; j < n; j++) { x[j] += ap * dx[j]; q[j] += ad * dq[j]; dxlast = fmax(dxlast, fabs(ap * dx[j])); }
         for (int r = 0; r < m; r++) { s[r] += ap * dsv[r]; z[r] += ad * dz[r]; }
         it++;
+    }
+    if (orc_stats_sink) {
+        orc_stats_sink[ORC_ST_SHIFT_ITERS] = st_shift_iters; orc_stats_sink[ORC_ST_FAILED] = st_failed;
+        orc_stats_sink[ORC_ST_MAX_TRIES] = st_max_tries; orc_stats_sink[ORC_ST_MAX_DELTA] = st_max_delta;
+        orc_stats_sink[ORC_ST_EXIT] = st_exit; orc_stats_sink[ORC_ST_POLISH_NPD] = 0.0;
     }
     if (flag == 0 && provisional) flag = 4;
     if (saved && !provisional && (restore || flag == 2 || flag == 4)) {   /* ACCEPTABLE / MAXIT: the best saved iterate */

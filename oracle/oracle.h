@@ -115,6 +115,39 @@ int orc_solve_batch(const orc_params *p, int n_agents, const double *x0, const d
                     const double *nbr_state, int n_all, int agent_offset,
                     double *x_qp, double *x_out, double *obj, int *status, int *iters, int nthreads);
 
+/*
+ * Inertia-shift statistics of one agent's NLP stage (tests/shift_cases.py selects its cases by them).
+ * ORC_NSTAT doubles per agent, every one an exactly represented count, code or the shift itself:
+ *   [ORC_ST_SHIFT_ITERS] NLP iterations with at least one failed factorisation of the reduced matrix
+ *   [ORC_ST_FAILED]      failed factorisations in all
+ *   [ORC_ST_MAX_TRIES]   most failed factorisations of one iteration (14: the tries ran out)
+ *   [ORC_ST_MAX_DELTA]   largest shift delta a factorisation was tried with
+ *   [ORC_ST_EXIT]        the rule that ended the NLP loop, ORC_EXIT_* below (-1: the stage did not run)
+ *   [ORC_ST_POLISH_NPD]  1: the polish was rejected because its reduced matrix was not positive definite
+ * The solvers write them through orc_stats_sink, a per-thread pointer the *_stats batch drivers aim at the
+ * agent's row (NULL everywhere else: nothing is recorded, and no result depends on it either way).
+ */
+#define ORC_NSTAT 6
+enum { ORC_ST_SHIFT_ITERS, ORC_ST_FAILED, ORC_ST_MAX_TRIES, ORC_ST_MAX_DELTA, ORC_ST_EXIT, ORC_ST_POLISH_NPD };
+enum {
+    ORC_EXIT_CONVERGED = 0,     /* the residual tests met at the full tolerances */
+    ORC_EXIT_PROVISIONAL = 1,   /* met only at the loosened ones (ORC_NLP_EXITF): OPTIMAL if the polish is accepted */
+    ORC_EXIT_NEAR_SHIFTED = 2,  /* near && delta != 0 */
+    ORC_EXIT_NEAR_BLOCKED = 3,  /* near and a step shorter than ORC_NLP_BLOCKED */
+    ORC_EXIT_LEFT_NEAR = 4,     /* a near-optimal iterate was saved and the next one is not near */
+    ORC_EXIT_NEAR_WAIT = 5,     /* ORC_NLP_NEARWAIT near-optimal iterates */
+    ORC_EXIT_TRIES = 6,         /* 14 failed factorisations: KKTFAIL */
+    ORC_EXIT_LU = 7,            /* the full-space LU failed: KKTFAIL */
+    ORC_EXIT_MAXIT = 8,
+    ORC_EXIT_DIVERGED = 9       /* non-finite residuals or a dual beyond ORC_Z_DIV: FATAL */
+};
+extern __thread double *orc_stats_sink;
+int orc_solve_batch_stats(const orc_params *p, int n_agents, const double *x0, const double *ref,
+                          const double *foot, const double *obstacles, int n_obs,
+                          const double *nbr_state, int n_all, int agent_offset,
+                          double *x_qp, double *x_out, double *obj, int *status, int *iters, int nthreads,
+                          double *stats /* [n_agents][ORC_NSTAT] */);
+
 /* fitComTrajectory_eventbase restated (MPC_dist.cpp:784-855): alpha[4][5] (row-major)
  * from the buffer state (4) and the first 4 predicted states X[0..3]. */
 void orc_fit_bezier(const double buf[4], const double *X, double alpha[20]);
@@ -203,6 +236,12 @@ int orc12_solve_agent(const orc12_params *p, const double x0[12], const double *
 int orc12_solve_batch(const orc12_params *p, int n_agents, const double *x0, const double *xref, const double *foot,
                       const int *contact, const double *obstacles, int n_obs, const double *nbr_state, int n_all,
                       int agent_offset, double *x_qp, double *x_out, double *obj, int *status, int *iters, int nthreads);
+/* ... with the NLP stage's inertia-shift statistics (ORC_NSTAT per agent, above; the SRB-12 loop has the exits
+ * CONVERGED, TRIES, LU, MAXIT and DIVERGED only) */
+int orc12_solve_batch_stats(const orc12_params *p, int n_agents, const double *x0, const double *xref, const double *foot,
+                            const int *contact, const double *obstacles, int n_obs, const double *nbr_state, int n_all,
+                            int agent_offset, double *x_qp, double *x_out, double *obj, int *status, int *iters,
+                            int nthreads, double *stats);
 
 /* dense helpers (linalg.c) */
 int orc_chol(int n, double *A);                               /* in place, lower */

@@ -256,7 +256,7 @@ static int polish12(const p12_t *P, int nl, double *x, const double *s, const do
                 }
             }
             const int frz = it > 0;          /* later steps of a pass reuse the first step's factor */
-            if (!frz && !reduced_pd(P, Hf)) { bad = 1; break; }          /* the kernel's Riccati pivots fail there */
+            if (!frz && !reduced_pd(P, Hf)) { bad = 1; if (orc_stats_sink) orc_stats_sink[ORC_ST_POLISH_NPD] = 1.0; break; }          /* the kernel's Riccati pivots fail there */
             if (!frz) memset(KK, 0, sizeof(double) * (size_t)nk * nk);
             if (!frz) for (int i = 0; i < n; i++) memcpy(KK + (size_t)i * nk, Hf + (size_t)i * n, sizeof(double) * n);
             for (int r = 0; r < p; r++) {
@@ -342,6 +342,9 @@ static int ipm(const p12_t *P, int nl, double *z, double *lam, int *iters)
     double *dzd = malloc(sizeof(double) * m), *dsa = malloc(sizeof(double) * m), *dza = malloc(sizeof(double) * m);
     int *piv = malloc(sizeof(int) * nk);
     int flag = 2, it = 0;
+    /* statistics of the NLP stage (orc_stats_sink, oracle.h): they steer nothing */
+    int st_exit = ORC_EXIT_MAXIT, st_shift_iters = 0, st_failed = 0, st_max_tries = 0;
+    double st_max_delta = 0.0;
     /* slacks and duals: QP start s = h - g (the gravity-compensating start is strictly feasible),
      * z = 1 / max(s, 1); NLP start shifted so that min s = 1 when a row is violated, z = z0 / max(s, 1) */
     rows_eval(P, z, nl, g, NULL);
@@ -397,11 +400,11 @@ static int ipm(const p12_t *P, int nl, double *z, double *lam, int *iters)
         {                                          /* divergence: ORC_Z_DIV (the LIP mode's rule) */
             double zm = 0.0;
             for (int r = 0; r < m; r++) zm = fmax(zm, zd[r]);
-            if (!isfinite(nrd) || !isfinite(nrp) || !isfinite(sz) || !(zm <= ORC_Z_DIV)) { flag = 3; break; }
+            if (!isfinite(nrd) || !isfinite(nrp) || !isfinite(sz) || !(zm <= ORC_Z_DIV)) { flag = 3; st_exit = ORC_EXIT_DIVERGED; break; }
         }
         if (getenv("ORC12_TRACE"))
             fprintf(stderr, "  %s it %2d |rd| %.3e (th %.3e) |rp| %.3e mu %.3e sigma %.3e\n", nl ? "nlp" : "qp ", it, nrd, th * gm, nrp, mu, sigma);
-        if (nrd < th * gm && nrp < th && mu < mtol) { flag = 0; break; }
+        if (nrd < th * gm && nrp < th && mu < mtol) { flag = 0; st_exit = ORC_EXIT_CONVERGED; break; }
         /* Hessian of the Lagrangian + J' W J */
         memset(Hf, 0, sizeof(double) * (size_t)n * n);
         for (int i = 0; i < n; i++) Hf[(size_t)i * n + i] = P->Pd[i];
@@ -426,22 +429,25 @@ static int ipm(const p12_t *P, int nl, double *z, double *lam, int *iters)
             double dm = 1.0;
             for (int i = 0; i < n; i++) dm = fmax(dm, Hf[(size_t)i * n + i]);
             const double dstart = 1e-10 * dm;
-            int ok = 0;
+            int ok = 0, ntried = 0;
             for (int tries = 0; tries < 14; tries++) {
                 if (tries > 0) {
                     const double nd = (delta == 0.0) ? dstart : delta * 10.0;
                     for (int i = 0; i < n; i++) Hf[(size_t)i * n + i] += nd - delta;
                     delta = nd;
                 }
+                if (delta > st_max_delta) st_max_delta = delta;
                 if (reduced_pd(P, Hf)) { ok = 1; break; }
+                ntried++;
             }
-            if (!ok) { flag = 1; break; }
+            if (ntried) { st_shift_iters++; st_failed += ntried; if (ntried > st_max_tries) st_max_tries = ntried; }
+            if (!ok) { flag = 1; st_exit = ORC_EXIT_TRIES; break; }
         }
         memset(KK, 0, sizeof(double) * (size_t)nk * nk);
         for (int i = 0; i < n; i++) memcpy(KK + (size_t)i * nk, Hf + (size_t)i * n, sizeof(double) * n);
         for (int r = 0; r < p; r++)
             for (int j = 0; j < n; j++) { KK[(size_t)(n + r) * nk + j] = P->Aeq[(size_t)r * n + j]; KK[(size_t)j * nk + n + r] = P->Aeq[(size_t)r * n + j]; }
-        if (orc_lu(nk, KK, piv) != 0) { flag = 1; break; }
+        if (orc_lu(nk, KK, piv) != 0) { flag = 1; st_exit = ORC_EXIT_LU; break; }
         double ap = 1, ad = 1;
         for (int pass = 0; pass < 2; pass++) {
             /* complementarity target r3 = -s z (predictor), - s z - ds_a dz_a + sigma mu (corrector) */
@@ -480,6 +486,11 @@ static int ipm(const p12_t *P, int nl, double *z, double *lam, int *iters)
         for (int r = 0; r < m; r++) { s[r] += ap * ds[r]; zd[r] += ad * dzd[r]; }
     }
     *iters = it;
+    if (nl && orc_stats_sink) {
+        orc_stats_sink[ORC_ST_SHIFT_ITERS] = st_shift_iters; orc_stats_sink[ORC_ST_FAILED] = st_failed;
+        orc_stats_sink[ORC_ST_MAX_TRIES] = st_max_tries; orc_stats_sink[ORC_ST_MAX_DELTA] = st_max_delta;
+        orc_stats_sink[ORC_ST_EXIT] = st_exit; orc_stats_sink[ORC_ST_POLISH_NPD] = 0.0;
+    }
     if (flag == 0 && (nl || !prm->use_nlp) && prm->polish) {         /* the last stage: exact active-set point */
         int steps = 0;
         const int acc = polish12(P, nl, z, s, zd, &steps);
@@ -625,23 +636,32 @@ typedef struct {
     const orc12_params *p; int lo, hi;
     const double *x0, *xref, *foot, *obstacles, *nbr; const int *contact; int n_obs, n_all, off;
     double *x_qp, *x_out, *obj; int *status, *iters;
+    double *stats;
 } job12_t;
 
 static void *worker12(void *arg)
 {
     job12_t *j = (job12_t *)arg;
     const int nv = orc12_nv(j->p), N = j->p->N;
-    for (int a = j->lo; a < j->hi; a++)
+    for (int a = j->lo; a < j->hi; a++) {
+        if (j->stats) {
+            orc_stats_sink = j->stats + (size_t)ORC_NSTAT * a;
+            memset(orc_stats_sink, 0, sizeof(double) * ORC_NSTAT);
+            orc_stats_sink[ORC_ST_EXIT] = -1.0;
+        }
         orc12_solve_agent(j->p, j->x0 + 12 * (size_t)a, j->xref + (size_t)12 * N * a, j->foot + (size_t)12 * N * a,
                           j->contact + (size_t)4 * N * a, j->obstacles, j->n_obs, j->nbr, j->n_all, j->off + a,
                           j->x_qp ? j->x_qp + (size_t)nv * a : NULL, j->x_out + (size_t)nv * a, j->obj + a,
                           j->status + 2 * a, j->iters + 2 * a);
+    }
+    orc_stats_sink = NULL;
     return NULL;
 }
 
-int orc12_solve_batch(const orc12_params *p, int n_agents, const double *x0, const double *xref, const double *foot,
-                      const int *contact, const double *obstacles, int n_obs, const double *nbr_state, int n_all,
-                      int agent_offset, double *x_qp, double *x_out, double *obj, int *status, int *iters, int nthreads)
+int orc12_solve_batch_stats(const orc12_params *p, int n_agents, const double *x0, const double *xref, const double *foot,
+                            const int *contact, const double *obstacles, int n_obs, const double *nbr_state, int n_all,
+                            int agent_offset, double *x_qp, double *x_out, double *obj, int *status, int *iters,
+                            int nthreads, double *stats)
 {
     if (nthreads < 1) nthreads = 1;
     if (nthreads > n_agents) nthreads = n_agents > 0 ? n_agents : 1;
@@ -653,9 +673,18 @@ int orc12_solve_batch(const orc12_params *p, int n_agents, const double *x0, con
         j->x0 = x0; j->xref = xref; j->foot = foot; j->contact = contact; j->obstacles = obstacles; j->nbr = nbr_state;
         j->n_obs = n_obs; j->n_all = n_all; j->off = agent_offset;
         j->x_qp = x_qp; j->x_out = x_out; j->obj = obj; j->status = status; j->iters = iters;
+        j->stats = stats;
         pthread_create(&th[t], NULL, worker12, j);
     }
     for (int t = 0; t < nthreads; t++) pthread_join(th[t], NULL);
     free(th); free(jobs);
     return 0;
+}
+
+int orc12_solve_batch(const orc12_params *p, int n_agents, const double *x0, const double *xref, const double *foot,
+                      const int *contact, const double *obstacles, int n_obs, const double *nbr_state, int n_all,
+                      int agent_offset, double *x_qp, double *x_out, double *obj, int *status, int *iters, int nthreads)
+{
+    return orc12_solve_batch_stats(p, n_agents, x0, xref, foot, contact, obstacles, n_obs, nbr_state, n_all, agent_offset,
+                                   x_qp, x_out, obj, status, iters, nthreads, NULL);
 }

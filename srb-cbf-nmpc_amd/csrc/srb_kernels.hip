@@ -2148,7 +2148,7 @@ __device__ __forceinline__ void nmpc_agent(const SrbKParams &prm, int agent,
                     // KF instances: the inverse in fp32 while mu > kkt32_mu (then nref fp64 refinement steps per solve)
                     int cf = (KF && f32) ? gj_invert_f32<NZL>(Mi, mrow<NZL>(lane), !nl) : gj_factor<NZL, NZE>(Mi, nz, lane, !nl);
 #ifdef SRB_DIAG_FORCE_SHIFT        // diagnostic builds only: every NLP iteration's first factorisation counts as failed,
-#ifndef SRB_DIAG_BUILD             // so the shift path runs (no batch found so far reaches it; profiles/factor_chain_ab.txt)
+#ifndef SRB_DIAG_BUILD             // so the shift path runs on any batch (the suite reaches it with a raised Sw: tests/shift_cases.py)
 #error "SRB_DIAG_FORCE_SHIFT is a diagnostic-build option"
 #endif
                     if (nl && tries == 0) cf = 1;
