@@ -595,7 +595,8 @@ int srb_rollout_agents_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_i
  * plant_hcom with srb_sim.x missing (the advance; the rollout reads batch.x).  With a context: agent_offset +
  * n_agents beyond n_all.  The contents of the tables are NOT checked: a NaN or negative bound or height goes
  * through the arithmetic above as it is.  srb_rollout_plant_device refuses a shard, as srb_rollout_device does; the
- * tables do not change over a rollout.  The SRB-12 mode and the MPC_dist shims have no disturbed plant.
+ * tables do not change over a rollout.  The SRB-12 mode has a plant of its own (srb12_plant, below); the MPC_dist shims
+ * have none.
  */
 typedef struct srb_plant {
     int struct_size;            /* sizeof(srb_plant) (ABI check) */
@@ -782,7 +783,8 @@ int srb12_ctx_scenes(srb12_ctx *ctx, int *scene_agents, int *scene_obs);
 
 /*
  * Closed-loop team rollout of the SRB-12 mode on the device: srb_sim's step and safety log for
- * the 12-state body.  One cycle is one gait domain of NDOMAIN = 4 grids, so N >= 4.  The plant is nominal: the state
+ * the 12-state body.  One cycle is one gait domain of NDOMAIN = 4 grids, so N >= 4.  The plant of these entry points
+ * is nominal (srb12_plant, further down, disturbs it through entry points of its own): the state
  * that starts cycle c + 1 is the X the solve of cycle c predicted at grid index 3, x[a][36..47], whatever that
  * solve's status.  All pointers are device pointers, fp64 unless noted; cycles count from c_first, and log rows are
  * indexed by c - c_first.
@@ -1004,6 +1006,78 @@ int srb12_sim_metrics_agents_device(srb12_ctx *ctx, int n_agents, const srb12_si
 int srb12_rollout_agents_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
                                 const srb12_plans *plans, const srb_moving *mv, const srb_sizes *sz,
                                 const srb_agent_sizes *ag, int cycles, void *stream);
+
+/*
+ * Disturbed plant of the SRB-12 mode (DESIGN.md 3 "Disturbed plant", 9, 10.13): srb_plant for the 12-state body -- kicks
+ * on velocity, position and angular velocity, pushes, and a body whose mass and inertia are not the model's, or whose
+ * dynamics are evaluated where it is and not where the model linearised.  SRB_ABI_VERSION and every existing struct
+ * stay; the struct travels through entry points of its own, which extend srb12_sim_advance_device and
+ * srb12_rollout_agents_device (plans, mv, sz, ag may be NULL) and otherwise behave as those.  Every table has n_all
+ * rows in the row order of nbr_state (scene-major with scenes); global agent g = agent_offset + a owns row g
+ * (srb12_sim's agent_offset / n_all; n_all == 0 reads as n_agents rows).  All pointers are device pointers.  All
+ * arithmetic is fp64, uncontracted, with one stated grouping (csrc/srb12_plant.hip; tests/plant12_oracle.py restates
+ * it: bit for bit, except what passes through the roll's cos / sin).
+ *
+ * The plant acts in the advance of a cycle c > c_first (at c_first the state is the caller's, as ever) and replaces
+ * "state = x[a][36..47]" by state = z + d, one rounded add per component (srb12_plant_state_kernel, one thread per
+ * agent; then srb12_sim_advance_plant_kernel, the advance on that state):
+ *   z, the base state
+ *     plant_mass, plant_inertia NULL and at_state 0    x[a][36..47], the nominal prediction.
+ *     otherwise             a four-step roll from the state that started cycle c - 1 -- read from `state` before it is
+ *                           overwritten, together with the xref, foot and contact of cycle c - 1, which the advance
+ *                           then overwrites, so this advance is NOT idempotent: call it once per cycle.  Step
+ *                           k = 0 .. 3 applies the input the model applied, U_k = x[a][12N + 12k .. 12N + 12k + 11],
+ *                           with the footholds and contact flags of grid k, by orc12_dynamics' forward-Euler map:
+ *                             p' = p + Ts v;  Theta' = Theta + Ts Rz(psi)^T omega;
+ *                             v' = v + (Ts / m_g) sum_on f_l + (0, 0, -Ts grav);
+ *                             omega' = omega + sum_on Ts I_w^-1 [r_l]x f_l,
+ *                           I_w = Rz (s_g I_b) Rz^T, r_l = foot_kl - p^; a leg with contact 0 contributes nothing.
+ *                           m_g = plant_mass[g] (NULL: the context's mass), s_g = plant_inertia[g] (NULL: 1).  The
+ *                           linearisation point (psi, p^) is, with at_state 0, the model's -- the start state for
+ *                           k = 0, sim.xref[a][k - 1] of cycle c - 1 for k >= 1 -- and with at_state 1 the plant's
+ *                           own current state z at every step.  No gyroscopic term, no sub-stepping.
+ *   d, the disturbance in state order (p, Theta, v, omega), from +0.0
+ *     kick_v, kick_p [n_all]  srb_plant's planar kicks, word for word: Philox4x32-10, key ((uint32)seed,
+ *                           (uint32)(seed >> 32)), counter ((uint32)c, (uint32)g, 0, 0) gives w0 .. w3,
+ *                           u_i = ((double)(int32_t)w_i + 0.5) * 2^-31; dv_x += kick_v[g] u0, dv_y += kick_v[g] u1,
+ *                           dp_x += kick_p[g] u2, dp_y += kick_p[g] u3.  A LIP rollout and an SRB-12 rollout with one
+ *                           seed therefore get the same planar kicks.
+ *     kick_w [n_all]        counter (c, g, 1, 0): domega_i += kick_w[g] u_i for i = 0 .. 2 (w3 is unused).
+ *     pushes                every entry p, in table order, with push_cycle[p] == c and push_agent[p] == g adds
+ *                           push_dv[p][0..2] to dv and push_dv[p][3..5] to domega, after the kicks.  An entry whose
+ *                           cycle is <= c_first, or is never reached, does not fire.
+ *                           Each of these steps is one rounded multiply and / or one rounded add.
+ *   dist_log [T][A][12]     out, optional: row c - c_first - 1 gets d (columns 2 .. 5 are always 0).
+ * Everything an advance derives from the state follows from the new state; the plan shift and the logs of the previous
+ * solve are untouched, so a neighbour's shifted plan is stale by the disturbance, as it would be on a robot.
+ *
+ * With plant == NULL, or every table NULL, at_state 0 and n_push 0, each entry point is the one it extends
+ * (srb12_sim_advance_device, srb12_rollout_agents_device): it launches the existing kernels and gives their bits
+ * (dist_log is then not written).  SRB_ERR_ARG, by name, before anything is launched: a wrong struct_size; n_push
+ * outside 0 .. 4096; n_push > 0 with push_cycle, push_agent or push_dv missing; at_state other than 0 or 1; a roll
+ * with srb12_sim.x, xref, foot or contact missing (the advance; the rollout wires them itself).  With a context:
+ * agent_offset + n_agents beyond n_all.  The contents of the tables are NOT checked.  srb12_rollout_plant_device
+ * refuses a shard, as srb12_rollout_device does; the tables do not change over a rollout.
+ */
+typedef struct srb12_plant {
+    int struct_size;                 /* sizeof(srb12_plant) (ABI check) */
+    unsigned long long seed;         /* the Philox key, as srb_plant */
+    const double *kick_v;            /* [n_all] m/s   bound on (v_x, v_y) per cycle, or NULL */
+    const double *kick_p;            /* [n_all] m     bound on (p_x, p_y) per cycle, or NULL */
+    const double *kick_w;            /* [n_all] rad/s bound on omega (3) per cycle, or NULL */
+    const double *plant_mass;        /* [n_all] kg, or NULL: the model's mass */
+    const double *plant_inertia;     /* [n_all] factor on the model's I_b, or NULL: 1 */
+    int at_state;                    /* 1: the plant's dynamics are evaluated at its own state */
+    int n_push;                      /* 0 .. 4096 */
+    const int *push_cycle, *push_agent;   /* [n_push]; agent = global row */
+    const double *push_dv;           /* [n_push][6]: dv (3) m/s, domega (3) rad/s */
+    double *dist_log;                /* [T][A][12] out, optional: d in state order */
+} srb12_plant;
+int srb12_sim_advance_plant_device(srb12_ctx *ctx, int n_agents, const srb12_sim *sim, const srb12_plant *plant,
+                                   int cycle, void *stream);
+int srb12_rollout_plant_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
+                               const srb12_plans *plans, const srb_moving *mv, const srb_sizes *sz,
+                               const srb_agent_sizes *ag, const srb12_plant *plant, int cycles, void *stream);
 
 const char *srb_last_error(void);
 

@@ -564,7 +564,37 @@ static int check_sim12(const srb12_sim *d, int cycle, bool advance)
     return SRB_OK;
 }
 
-static int launch_advance12(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, hipStream_t s)
+// The argument errors of srb12_plant that need no context, before anything is launched.  d: the advance's srb12_sim,
+// whose x, xref, foot and contact a roll reads (null: the rollout, which wires them in and reports what is missing
+// itself).
+#define SRB12_PLANT_MAX_PUSH 4096
+static bool plant12_rolls(const srb12_plant *pl) { return pl->plant_mass || pl->plant_inertia || pl->at_state != 0; }
+static int check_plant12(const srb12_plant *pl, const srb12_sim *d)
+{
+    if (int rc = srb_check_struct(pl, "srb12_plant")) return rc;
+    if (!pl) return SRB_OK;
+    if (pl->n_push < 0 || pl->n_push > SRB12_PLANT_MAX_PUSH)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_plant.n_push: 0 .. 4096 (every agent scans the whole push table)");
+    if (pl->n_push > 0 && (!pl->push_cycle || !pl->push_agent || !pl->push_dv))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_plant.n_push > 0 needs push_cycle, push_agent and push_dv");
+    if (pl->at_state != 0 && pl->at_state != 1)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_plant.at_state: 0 the model's linearisation point, 1 the plant's own state");
+    if (d && plant12_rolls(pl) && (!d->x || !d->xref || !d->foot || !d->contact))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_plant: plant_mass, plant_inertia and at_state need srb12_sim.x, xref, foot "
+                                              "and contact (the plant is driven by the inputs, footholds and contact flags the "
+                                              "model applied)");
+    return SRB_OK;
+}
+
+// the struct disturbs the plant at all (else every entry point is the one it extends; dist_log alone is not written)
+static bool plant12_on(const srb12_plant *pl)
+{
+    return pl && (pl->kick_v || pl->kick_p || pl->kick_w || plant12_rolls(pl) || pl->n_push > 0);
+}
+
+// pl: the disturbed plant (null: nominal).  It acts from the second cycle on; at c_first the state is the caller's.
+static int launch_advance12(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, hipStream_t s,
+                            const srb12_plant *pl = nullptr)
 {
     const srb12_params *p = &c->p;
     if (p->N < 4) return srb_internal_fail(SRB_ERR_ARG, "the rollout needs N >= 4 (one cycle is one gait domain of 4 grids)");
@@ -572,6 +602,27 @@ static int launch_advance12(srb12_ctx *c, int n_agents, const srb12_sim *d, int 
         return srb_internal_fail(SRB_ERR_ARG, "srb12_sim: missing buffer (state, x0, xref, foot, contact, last_state, com)");
     if (d->gait != 0 && d->gait != 1) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.gait: 0 trot, 1 stand");
     const int threads = n_agents * p->N;                  // one per (agent, grid): at most max_agents * 24
+    if (pl && cycle != d->c_first) {
+        const int n_all = d->n_all > 0 ? d->n_all : n_agents;
+        if (d->agent_offset < 0 || d->agent_offset + n_agents > n_all)
+            return srb_internal_fail(SRB_ERR_ARG, "srb12_plant: agent_offset + n_agents exceeds n_all (the plant tables' rows)");
+        Srb12PlantIb Ib;
+        for (int i = 0; i < 9; i++) Ib.v[i] = p->Ib[i];
+        // the state z + d, one thread per agent, then the advance on it, one thread per (agent, grid)
+        hipLaunchKernelGGL(srb12_plant_state_kernel, dim3((n_agents + 255) / 256), dim3(256), 0, s, n_agents, p->N, p->Ts,
+                           p->mass, Ib, p->grav, cycle, d->c_first, d->state, d->x, (const double *)d->xref,
+                           (const double *)d->foot, (const int *)d->contact, d->agent_offset,
+                           (unsigned)(pl->seed & 0xffffffffull), (unsigned)(pl->seed >> 32), pl->kick_v, pl->kick_p,
+                           pl->kick_w, pl->plant_mass, pl->plant_inertia, pl->at_state, plant12_rolls(pl) ? 1 : 0,
+                           pl->n_push, pl->push_cycle, pl->push_agent, pl->push_dv, pl->dist_log);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(srb12_sim_advance_plant_kernel, dim3((threads + 255) / 256), dim3(256), 0, s, n_agents, p->N,
+                           p->Ts, d->vref, d->hcom, d->yaw_step, d->hold_radius, d->gait, cycle, d->c_first, d->state,
+                           d->goal, d->phase, d->x, d->status, d->iters, d->x0, d->xref, d->foot, d->contact,
+                           d->last_state, d->com, d->traj, d->status_log, d->iters_log, d->x_log);
+        HIPCHK(hipGetLastError());
+        return SRB_OK;
+    }
     hipLaunchKernelGGL(srb12_sim_advance_kernel, dim3((threads + 255) / 256), dim3(256), 0, s, n_agents, p->N, p->Ts,
                        d->vref, d->hcom, d->yaw_step, d->hold_radius, d->gait, cycle, d->c_first, d->state, d->goal,
                        d->phase, d->x, d->status, d->iters, d->x0, d->xref, d->foot, d->contact, d->last_state, d->com,
@@ -601,9 +652,11 @@ static int launch_metrics12(srb12_ctx *c, int n_agents, const srb12_sim *d, int 
 }
 
 static int sim12_call(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream, bool advance,
-                      const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr)
+                      const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr, const srb12_plant *pl = nullptr)
 {
     if (int rc = check_sim12(d, cycle, advance)) return rc;
+    if (int rc = check_plant12(pl, d)) return rc;
+    if (!plant12_on(pl)) pl = nullptr;
     if (int rc = srb_check_sizes(sz)) return rc;
     if (int rc = srb_check_agent_sizes(ag, d->nbr_state && d->n_all > 0)) return rc;
     if (!c) return srb_internal_fail(SRB_ERR_ARG, "null argument");
@@ -611,7 +664,7 @@ static int sim12_call(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle,
     if (n_agents == 0) return SRB_OK;
     hipStream_t s = (hipStream_t)stream;
     return c->order.run(c->device, s, [&] {
-        return advance ? launch_advance12(c, n_agents, d, cycle, s)
+        return advance ? launch_advance12(c, n_agents, d, cycle, s, pl)
                        : launch_metrics12(c, n_agents, d, cycle, s, sz ? sz->obs_radius : nullptr,
                                           ag ? ag->agent_body : nullptr, ag ? ag->collide_cycle : nullptr);
     });
@@ -620,6 +673,12 @@ static int sim12_call(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle,
 extern "C" int srb12_sim_advance_device(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream)
 {
     return sim12_call(c, n_agents, d, cycle, stream, true);
+}
+
+extern "C" int srb12_sim_advance_plant_device(srb12_ctx *c, int n_agents, const srb12_sim *d, const srb12_plant *pl,
+                                              int cycle, void *stream)
+{
+    return sim12_call(c, n_agents, d, cycle, stream, true, nullptr, nullptr, pl);
 }
 
 extern "C" int srb12_sim_metrics_agents_device(srb12_ctx *c, int n_agents, const srb12_sim *d, const srb_sizes *sz,
@@ -678,16 +737,18 @@ extern "C" int srb12_obstacles_advance_device(srb12_ctx *c, int n_obs, double *o
 
 // pl: the plans fed forward (srb12_rollout_plans_device), or NULL (srb12_rollout_device: today's launches); mv: the
 // moving obstacles (srb12_rollout_moving_device), or NULL; sz: the obstacle sizes (srb12_rollout_sized_device), or
-// NULL; ag: the agent sizes (srb12_rollout_agents_device), or NULL -- the tables do not change over a rollout: the same
-// pointers serve every cycle
+// NULL; ag: the agent sizes (srb12_rollout_agents_device), or NULL; pt: the disturbed plant
+// (srb12_rollout_plant_device), or NULL -- the tables do not change over a rollout: the same pointers serve every cycle
 static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, const srb12_plans *pl,
                      bool plans, int cycles, void *stream, const srb_moving *mv = nullptr, const srb_sizes *sz = nullptr,
-                     const srb_agent_sizes *ag = nullptr)
+                     const srb_agent_sizes *ag = nullptr, const srb12_plant *pt = nullptr)
 {
     if (int rc = srb_check_struct(b, "srb12_batch")) return rc;
     if (int rc0 = check_moving12(mv, b, true)) return rc0;
     if (int rc0 = srb_check_sizes(sz)) return rc0;
     if (int rc0 = srb_check_agent_sizes(ag, true)) return rc0;    // (the driver's neighbour table is the team itself)
+    if (int rc0 = check_plant12(pt, nullptr)) return rc0;         // (a missing buffer of the roll is reported below, as ever)
+    if (!plant12_on(pt)) pt = nullptr;
     if (plans)
         if (int rc = srb_check_struct(pl, "srb12_plans")) return rc;
     // (the layout and null checks of check_sim12 only: the driver's first cycle is c_first itself)
@@ -740,7 +801,7 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
     const int nsel = ag ? ag->clearance_selection : 0;
     for (int i = 0; i <= cycles && !rc; i++) {
         const int cyc = d->c_first + i;
-        rc = launch_advance12(c, n_agents, &sim, cyc, s);
+        rc = launch_advance12(c, n_agents, &sim, cyc, s, pt);
         if (rc || i == cycles) break;
         if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
         if (!rc) rc = launch_metrics12(c, n_agents, &sim, cyc, s, radius, body, collide);
@@ -791,7 +852,15 @@ extern "C" int srb12_rollout_agents_device(srb12_ctx *c, int n_agents, const srb
                                            const srb12_plans *pl, const srb_moving *mv, const srb_sizes *sz,
                                            const srb_agent_sizes *ag, int cycles, void *stream)
 {
-    return rollout12(c, n_agents, b, d, pl, pl != nullptr, cycles, stream, mv, sz, ag);
+    return srb12_rollout_plant_device(c, n_agents, b, d, pl, mv, sz, ag, nullptr, cycles, stream);
+}
+
+// pl, mv, sz and ag may be NULL, as in srb12_rollout_agents_device; pt NULL (or with nothing set): that entry point itself
+extern "C" int srb12_rollout_plant_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d,
+                                          const srb12_plans *pl, const srb_moving *mv, const srb_sizes *sz,
+                                          const srb_agent_sizes *ag, const srb12_plant *pt, int cycles, void *stream)
+{
+    return rollout12(c, n_agents, b, d, pl, pl != nullptr, cycles, stream, mv, sz, ag, pt);
 }
 
 // diagnostics (not in the public header): agent >= 0 records a per-iteration trace on the next

@@ -25,7 +25,11 @@ static __constant__ double c_sim12_foot[4][2] = {{0.2188, -0.1320}, {0.2188, 0.1
 // state itself (a square root, a division, one atan2 and one sincos: nothing next to its stores), so there is no
 // exchange between threads and no barrier.  (One thread per agent writes 24 N + 1 + 28 N words at a stride of
 // that many between neighbouring lanes.)
-extern "C" __global__ void __launch_bounds__(256) srb12_sim_advance_kernel(
+// The body is shared with srb12_sim_advance_plant_kernel (srb12_plant.hip) through FROM_STATE: false, the nominal
+// plant (the state of a cycle c > c_first is X at grid index 3 of the previous solution); true, the state is what
+// srb12_plant_state_kernel left in `state` (read by every thread of the agent, written by none).
+template <bool FROM_STATE>
+__device__ __forceinline__ void sim12_advance_body(
     int n_agents, int N, double Ts, double vref, double hcom, double yaw_step, double hold_radius, int gait, int c,
     int c_first, double *__restrict__ state, const double *__restrict__ goal, const int *__restrict__ phase,
     const double *__restrict__ x, const int *__restrict__ status, const int *__restrict__ iters,
@@ -41,7 +45,7 @@ extern "C" __global__ void __launch_bounds__(256) srb12_sim_advance_kernel(
     const double *xa = x ? x + (size_t)a * nv : nullptr;
     // the state: the caller's before the first solve (read only then), else X at grid index 3 of the previous
     // solution, whatever its status
-    const double *src = c == c_first ? state + 12 * (size_t)a : xa + 12 * (SIM12_NDOMAIN - 1);
+    const double *src = (FROM_STATE || c == c_first) ? state + 12 * (size_t)a : xa + 12 * (SIM12_NDOMAIN - 1);
     double st[12];
     for (int i = 0; i < 12; i++) st[i] = src[i];
     const double px = st[0], py = st[1], yaw = st[5];
@@ -93,7 +97,7 @@ extern "C" __global__ void __launch_bounds__(256) srb12_sim_advance_kernel(
 
     const int r = c - c_first;                            // row of the logs
     if (k == 0) {
-        if (c != c_first) {
+        if (!FROM_STATE && c != c_first) {
             double *sa = state + 12 * (size_t)a;
             for (int i = 0; i < 12; i++) sa[i] = st[i];
         }
@@ -127,6 +131,18 @@ extern "C" __global__ void __launch_bounds__(256) srb12_sim_advance_kernel(
     }
 }
 
+extern "C" __global__ void __launch_bounds__(256) srb12_sim_advance_kernel(
+    int n_agents, int N, double Ts, double vref, double hcom, double yaw_step, double hold_radius, int gait, int c,
+    int c_first, double *__restrict__ state, const double *__restrict__ goal, const int *__restrict__ phase,
+    const double *__restrict__ x, const int *__restrict__ status, const int *__restrict__ iters,
+    double *__restrict__ x0, double *__restrict__ xref, double *__restrict__ foot, int *__restrict__ contact,
+    double *__restrict__ last_state, double *__restrict__ com, double *__restrict__ traj,
+    int *__restrict__ status_log, int *__restrict__ iters_log, double *__restrict__ x_log)
+{
+    sim12_advance_body<false>(n_agents, N, Ts, vref, hcom, yaw_step, hold_radius, gait, c, c_first, state, goal, phase, x,
+                              status, iters, x0, xref, foot, contact, last_state, com, traj, status_log, iters_log, x_log);
+}
+
 // Last cycle's plans as this cycle's table (dist.shift_plans on the device): the new cycle starts `grids` grids
 // later, so its grid k is the old grid k + grids; past the horizon the plan goes on along its last finite
 // difference, last + m (last - previous) with m = k + grids - N + 1 -- the operation order of
@@ -154,3 +170,6 @@ extern "C" __global__ void __launch_bounds__(256) srb12_plan_shift_kernel(int n_
         pt[1] = ly + m * ey;
     }
 }
+
+// the disturbed plant (srb12_plant; compiled here, so that it shares the body above and this file's pragma)
+#include "srb12_plant.hip"

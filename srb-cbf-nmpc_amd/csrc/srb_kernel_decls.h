@@ -224,5 +224,23 @@ extern "C" __global__ void srb12_sim_advance_kernel(int n_agents, int N, double 
                                                     double *xref, double *foot, int *contact, double *last_state,
                                                     double *com, double *traj, int *status_log, int *iters_log,
                                                     double *x_log);
+// ---- srb12_plant.hip (compiled inside srb12_sim.hip): the disturbed plant, cycles c > c_first.  The state kernel is one
+// thread per agent, the advance one per (agent, grid) as srb12_sim_advance_kernel, whose arguments it takes
+struct Srb12PlantIb { double v[9]; };                     // the model's body inertia, row-major, by value
+extern "C" __global__ void srb12_plant_state_kernel(int n_agents, int N, double Ts, double mass, Srb12PlantIb Ib,
+                                                    double grav, int c, int c_first, double *state, const double *x,
+                                                    const double *xref, const double *foot, const int *contact,
+                                                    int agent_offset, unsigned seed_lo, unsigned seed_hi,
+                                                    const double *kick_v, const double *kick_p, const double *kick_w,
+                                                    const double *plant_mass, const double *plant_inertia, int at_state,
+                                                    int roll, int n_push, const int *push_cycle, const int *push_agent,
+                                                    const double *push_dv, double *dist_log);
+extern "C" __global__ void srb12_sim_advance_plant_kernel(int n_agents, int N, double Ts, double vref, double hcom,
+                                                          double yaw_step, double hold_radius, int gait, int c,
+                                                          int c_first, double *state, const double *goal,
+                                                          const int *phase, const double *x, const int *status,
+                                                          const int *iters, double *x0, double *xref, double *foot,
+                                                          int *contact, double *last_state, double *com, double *traj,
+                                                          int *status_log, int *iters_log, double *x_log);
 // last cycle's plans as this cycle's table (dist.shift_plans), one thread per (agent, grid)
 extern "C" __global__ void srb12_plan_shift_kernel(int n_agents, int N, int grids, const double *plan, double *table);

@@ -124,7 +124,8 @@ class AgentSizes(ctypes.Structure):
 
 
 class Plant(ctypes.Structure):
-    """Mirror of srb_plant (the disturbed plant of the LIP rollout; struct_size filled in)."""
+    """Mirror of srb_plant (the disturbed plant of the LIP rollout; struct_size filled in).  The SRB-12 mode's is
+    srb12.PlantStruct12, filled from a srb12.Plant12."""
     _fields_ = [("struct_size", ctypes.c_int), ("seed", ctypes.c_ulonglong), ("kick_v", _dp), ("kick_p", _dp),
                 ("plant_hcom", _dp), ("n_push", ctypes.c_int), ("push_cycle", _ip), ("push_agent", _ip), ("push_dv", _dp),
                 ("dist_log", _dp)]

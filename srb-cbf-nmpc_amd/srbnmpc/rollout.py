@@ -31,9 +31,9 @@ cycle with d_agent < 0 (srb_agent_sizes, srb_rollout_agents_device; srb12.Rollou
 srb12_rollout_agents_device).  The tables do not change over a rollout and every shard holds them whole.
 
 With kick_v / kick_p ([n_all], m/s and m), plant_hcom ([n_all], m) or pushes the plant is disturbed (srb_plant,
-srb_sim_advance_plant_device / srb_rollout_plant_device; LIP mode only): from the second cycle on the state that starts
-a cycle is the model's prediction -- or, with plant_hcom, the roll of a LIP of that CoM height under the inputs the model
-applied -- plus a bounded uniform kick per cycle (Philox4x32-10 keyed by plant_seed, counter (cycle, global row)) and the
+srb_sim_advance_plant_device / srb_rollout_plant_device; the SRB-12 mode's is Rollout12(plant=srb12.Plant12(...)),
+srb12_plant): from the second cycle on the state that starts a cycle is the model's prediction -- or, with plant_hcom,
+the roll of a LIP of that CoM height under the inputs the model applied -- plus a bounded uniform kick per cycle (Philox4x32-10 keyed by plant_seed, counter (cycle, global row)) and the
 pushes due.  results()["disturbance"] logs what was added.  The tables do not change over a rollout and every shard
 holds them whole; workload.plant_tables draws a set, workload.replicate_scenes tiles a scene for a Monte-Carlo over
 the draws.

@@ -89,6 +89,107 @@ class Plans12(ctypes.Structure):
         super().__init__(ctypes.sizeof(Plans12), *args, **kw)
 
 
+class PlantStruct12(ctypes.Structure):
+    """Mirror of srb12_plant (the disturbed plant of the SRB-12 rollout; struct_size filled in)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("seed", ctypes.c_ulonglong), ("kick_v", _dp), ("kick_p", _dp),
+                ("kick_w", _dp), ("plant_mass", _dp), ("plant_inertia", _dp), ("at_state", ctypes.c_int),
+                ("n_push", ctypes.c_int), ("push_cycle", _ip), ("push_agent", _ip), ("push_dv", _dp), ("dist_log", _dp)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(ctypes.sizeof(PlantStruct12), *args, **kw)
+
+
+class Plant12:
+    """The disturbed plant of a Rollout12 (srb12_plant; Rollout12(..., plant=Plant12(...))): from the second cycle on
+    the state that starts a cycle is z + d instead of the model's prediction.
+
+    seed      the key of the kicks' draws (0 .. 2^64 - 1): a rollout is reproducible per seed, and a LIP Rollout with
+              the same plant_seed, kick_v and kick_p draws the same planar kicks
+    kick_v, kick_p, kick_w   [A] float64 or None: the bounds (m/s, m, rad/s; finite, >= 0) of a uniform kick per cycle on
+              (v_x, v_y), (p_x, p_y) and the three components of omega
+    mass      [A] or None: the mass (kg, finite, > 0) of each agent's body (None: the model's)
+    inertia   [A] or None: a factor (finite, > 0) on the model's body inertia (None: 1).  With either, z is the four-step
+              roll of that body under the forces, footholds and contact flags the model applied
+    at_state  True: every step of the roll evaluates the model's equations at the plant's own yaw and position
+              instead of the model's linearisation point (the start state, then the reference)
+    pushes    (cycle [P] int32, agent [P] int32, dv [P][6] float64) or None, P <= 4096: push p adds dv[p][0:3] to v and
+              dv[p][3:6] to omega of agent[p] at the start of cycle[p] (cycles count from 0 at reset(); cycle 0 never
+              fires: the start state is the caller's)
+    All tensors are contiguous and on the solver's device (the device is checked by Rollout12, which also checks
+    that every table has A rows).  Nothing set -- Plant12() -- is the nominal plant: the launches and bits of a
+    Rollout12 without one."""
+
+    def __init__(self, seed: int = 0, kick_v=None, kick_p=None, kick_w=None, mass=None, inertia=None,
+                 at_state: bool = False, pushes=None):
+        import torch
+        seed = int(seed)
+        if seed < 0 or seed >= 1 << 64:
+            raise ValueError("Plant12: seed must be 0 .. 2^64 - 1 (the 64-bit Philox key)")
+        for name, tab in (("kick_v", kick_v), ("kick_p", kick_p), ("kick_w", kick_w), ("mass", mass),
+                          ("inertia", inertia)):
+            if tab is None:
+                continue
+            if not isinstance(tab, torch.Tensor) or tab.dtype != torch.float64 or tab.dim() != 1 or not tab.is_contiguous():
+                raise ValueError(f"Plant12: {name} must be a contiguous float64 tensor [A], got "
+                                 f"{getattr(tab, 'dtype', type(tab).__name__)} {tuple(getattr(tab, 'shape', ()))}")
+            if bool(tab.isnan().any()):
+                raise ValueError(f"Plant12: {name} holds a NaN")
+            if not bool(tab.isfinite().all()):
+                raise ValueError(f"Plant12: {name} must be finite")
+            if name in ("mass", "inertia"):
+                if bool((tab <= 0).any()):
+                    raise ValueError(f"Plant12: {name} must be > 0 ({'kg' if name == 'mass' else 'a factor on I_b'})")
+            elif bool((tab < 0).any()):
+                raise ValueError(f"Plant12: {name} must be >= 0 (the bound of a uniform kick)")
+        if pushes is not None:
+            if not isinstance(pushes, (tuple, list)) or len(pushes) != 3:
+                raise ValueError("Plant12: pushes must be a triple (cycle int32 [P], agent int32 [P], dv float64 [P][6])")
+            cyc, agent, dv = pushes
+            P = int(cyc.shape[0]) if hasattr(cyc, "shape") and len(cyc.shape) == 1 else -1
+            if P < 0 or P > 4096:
+                raise ValueError("Plant12: pushes: cycle must be an int32 tensor [P], P <= 4096")
+            for name, t, shape, dt in (("cycle", cyc, (P,), torch.int32), ("agent", agent, (P,), torch.int32),
+                                       ("dv", dv, (P, 6), torch.float64)):
+                if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError(f"Plant12: pushes: {name} must be a contiguous {dt} tensor of shape {shape}, got "
+                                     f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+            if P and bool(dv.isnan().any()):
+                raise ValueError("Plant12: pushes: dv holds a NaN")
+            pushes = (cyc, agent, dv) if P else None
+        self.seed, self.kick_v, self.kick_p, self.kick_w, self.mass, self.inertia = seed, kick_v, kick_p, kick_w, mass, inertia
+        self.at_state, self.pushes = bool(at_state), pushes
+
+    @property
+    def rolls(self) -> bool:
+        """z is the four-step roll of the plant's own body (else the model's prediction)."""
+        return self.mass is not None or self.inertia is not None or self.at_state
+
+    @property
+    def on(self) -> bool:
+        """The plant is disturbed at all (else every call is the nominal one)."""
+        return (self.kick_v is not None or self.kick_p is not None or self.kick_w is not None or self.rolls
+                or self.pushes is not None)
+
+    def check(self, A: int, device):
+        """The checks that need the rollout: every table of A rows and, as the push tensors, on `device`; the pushed
+        agents are rows 0 .. A - 1.  By name."""
+        for name in ("kick_v", "kick_p", "kick_w", "mass", "inertia"):
+            tab = getattr(self, name)
+            if tab is None:
+                continue
+            if tab.shape[0] != A:
+                raise ValueError(f"Plant12: {name} must have one row per agent ({A}), got {tab.shape[0]}")
+            if tab.device != device:
+                raise ValueError(f"Plant12: {name} must be on {device}, got {tab.device}")
+        if self.pushes is not None:
+            for name, t in zip(("cycle", "agent", "dv"), self.pushes):
+                if t.device != device:
+                    raise ValueError(f"Plant12: pushes: {name} must be on {device}, got {t.device}")
+            agent = self.pushes[1]
+            if bool((agent < 0).any()) or bool((agent >= A).any()):
+                raise ValueError(f"Plant12: pushes: agent must be a row 0 .. {A - 1}")
+
+
 GAITS = {"trot": 0, "stand": 1}       # srb12_sim.gait
 SHIFT_GRIDS = 4                       # grids a cycle (one gait domain): the shift of the plans between cycles
 
@@ -143,6 +244,10 @@ def _lib():
                                                       ctypes.c_void_p]
         L.srb12_rollout_agents_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, S, PL, MV, SZ, AG, ctypes.c_int,
                                                   ctypes.c_void_p]
+        PT = ctypes.POINTER(PlantStruct12)
+        L.srb12_sim_advance_plant_device.argtypes = [ctypes.c_void_p, ctypes.c_int, S, PT, ctypes.c_int, ctypes.c_void_p]
+        L.srb12_rollout_plant_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, S, PL, MV, SZ, AG, PT, ctypes.c_int,
+                                                 ctypes.c_void_p]
         _bound = True
     return L
 
@@ -359,7 +464,7 @@ def split(p: Params12, x):
 class Rollout12(_RolloutBase):
     """The closed loop of `solver` (a Solver12 with N >= 4) for the agents whose goals are `goal` [A][2]
     (srb12_sim_advance_device / srb12_sim_metrics_device / srb12_rollout_device): srbnmpc.Rollout for the 12-state
-    body, with the nominal plant, the goal-directed reference of workload.make_batch12 re-centred every cycle and
+    body, with the nominal plant (or, with plant=, a disturbed one), the goal-directed reference of workload.make_batch12 re-centred every cycle and
     the team's safety log.
 
         r = Rollout12(solver, goal, obstacles=obstacles)
@@ -399,6 +504,12 @@ class Rollout12(_RolloutBase):
     nbr_clearance  True: the neighbour columns by clearance dist - agent_rad (needs agent_rad).  With any of the three
                 tables run() is srb12_rollout_agents_device; the tables are finite, agent_rad and agent_body not
                 negative, and do not change over a rollout
+    plant       a Plant12 or None: the disturbed plant (srb12_plant) -- kicks on v, p and omega, pushes, a body of
+                another mass or inertia, or the model's equations evaluated at the plant's own state.  advance(), step()
+                and run() then go through srb12_sim_advance_plant_device / srb12_rollout_plant_device (the same bits),
+                and results() gains disturbance [T][A][12] (state order; row c - 1 is what the start of cycle c added).
+                None, or a Plant12 with nothing set: the nominal plant, the launches and bits as ever.  The LIP
+                rollout's keyword arguments plant_seed, kick_v, kick_p, plant_hcom and pushes are refused by name
     A whole team on one GPU (the SRB-12 mode has no sharded stepping).  All tensors are
     float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
     _nx = 12
@@ -408,14 +519,17 @@ class Rollout12(_RolloutBase):
                  obstacles=None, hcom: float = workload.HCOM12, yaw_step: float = 0.1, hold_radius: float = 0.05,
                  plans: bool = False, plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False,
                  obs_eps=None, obs_radius=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
-                 agent_body=None, nbr_clearance: bool = False, *, plant_seed: int = 0, kick_v=None, kick_p=None,
-                 plant_hcom=None, pushes=None):
+                 agent_body=None, nbr_clearance: bool = False, *, plant=None, plant_seed: int = 0, kick_v=None,
+                 kick_p=None, plant_hcom=None, pushes=None):
         import torch
         for name, arg in (("plant_seed", plant_seed or None), ("kick_v", kick_v), ("kick_p", kick_p),
                           ("plant_hcom", plant_hcom), ("pushes", pushes)):
             if arg is not None:
-                raise ValueError(f"Rollout12: {name} is not available: the disturbed plant (srb_plant) is built for the "
-                                 "LIP mode only (rollout.Rollout)")
+                raise ValueError(f"Rollout12: {name} is not available: it is an argument of the LIP rollout's plant "
+                                 "(rollout.Rollout); the SRB-12 mode takes plant=Plant12(...) (srb12.Plant12: seed, kick_v, "
+                                 "kick_p, kick_w, mass, inertia, at_state, pushes)")
+        if plant is not None and not isinstance(plant, Plant12):
+            raise ValueError(f"Rollout12: plant must be a srb12.Plant12 or None, got {type(plant).__name__}")
         if gait not in GAITS:
             raise ValueError(f"gait must be one of {sorted(GAITS)}, got {gait!r}")
         super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps, obs_radius,
@@ -432,6 +546,56 @@ class Rollout12(_RolloutBase):
         self.xref = torch.zeros((A, N, 12), **f8)
         self.foot = torch.zeros((A, N, 4, 3), **f8)
         self.contact = torch.zeros((A, N, 4), dtype=torch.int32, device=self.device)
+        if plant is not None:
+            plant.check(A, self.device)
+        self.plant = plant if plant is not None and plant.on else None
+        self.dist_log = None
+        self._advanced = -1             # the cycle whose advance has run (the plant's advance is not idempotent)
+
+    # ------------------------------------------------------------------ the disturbed plant (srb12_plant)
+    def _plant(self) -> PlantStruct12:
+        pt = self.plant
+        cyc, agent, dv = pt.pushes if pt.pushes is not None else (None, None, None)
+        return PlantStruct12(pt.seed, _dptr(pt.kick_v), _dptr(pt.kick_p), _dptr(pt.kick_w), _dptr(pt.mass),
+                             _dptr(pt.inertia), int(pt.at_state), 0 if cyc is None else cyc.shape[0], _iptr(cyc),
+                             _iptr(agent), _dptr(dv), _dptr(self.dist_log))
+
+    def _reserve(self, cycles: int):
+        super()._reserve(cycles)
+        if self.plant is not None and (self.dist_log is None or self.dist_log.shape[0] < self.cap):
+            import torch
+            new = torch.zeros((self.cap, self.A, 12), dtype=torch.float64, device=self.device)
+            if self.dist_log is not None:
+                new[:self.dist_log.shape[0]] = self.dist_log
+            self.dist_log = new
+
+    def reset(self, state):
+        super().reset(state)
+        self._advanced = -1               # (dist_log needs no clearing: results() returns the rows rewritten since)
+
+    def advance(self, stream=None):
+        """As _RolloutBase.advance; with a disturbed plant through srb12_sim_advance_plant_device, and once per cycle:
+        the plant rolls on from the state and the inputs of the previous cycle, which the advance overwrites, so a
+        second call for the same cycle is skipped (everything it would write is already there)."""
+        if self.plant is None:
+            return super().advance(stream)
+        if not self._ready:
+            raise RuntimeError("Rollout12.advance before reset(state)")
+        if self._advanced == self.c:
+            return
+        s = self.solver
+        self._reserve(self.c + 1)
+        _check(_lib().srb12_sim_advance_plant_device(s._h, self.A, ctypes.byref(self._sim()), ctypes.byref(self._plant()),
+                                                     self.c, s._stream(stream)))
+        self._advanced = self.c
+
+    def results(self, stream=None):
+        """As _RolloutBase.results; with a disturbed plant also disturbance [T][A][12]: row c - 1 is the d (state order:
+        p, roll/pitch/yaw, v, omega) that the start of cycle c added to the plant's base state."""
+        out = super().results(stream)
+        if self.plant is not None:
+            out["disturbance"] = self.dist_log[:self.c]
+        return out
 
     def _sim(self) -> Sim12:
         m, o = self.metrics, self.out
@@ -473,7 +637,14 @@ class Rollout12(_RolloutBase):
         pl = None
         if self.plans:
             pl = ctypes.byref(Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table)))
-        if self.agents:
+        if self.plant is not None:
+            mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
+            sz = ctypes.byref(self._sizes()) if self.sized else None
+            ag = ctypes.byref(self._agent_sizes()) if self.agents else None
+            _check(_lib().srb12_rollout_plant_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl, mv, sz,
+                                                     ag, ctypes.byref(self._plant()), T, s._stream(stream)))
+            self._advanced = T               # the driver's final advance was cycle T's
+        elif self.agents:
             mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
             sz = ctypes.byref(self._sizes()) if self.sized else None
             _check(_lib().srb12_rollout_agents_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl, mv, sz,

@@ -200,7 +200,7 @@ def plant_tables(n_all: int, seed: int):
 
 
 def replicate_scenes(scenes: dict, copies: int):
-    """A make_scenes dict tiled `copies` times, scene-major: every array's rows repeated as a block, so rows
+    """A make_scenes (or make_scenes12) dict tiled `copies` times, scene-major: every array's rows repeated as a block, so rows
     [i * R, (i + 1) * R) of a table of R rows are replica i.  One scene (or set of scenes) then runs `copies` times in
     one launch with the same set_scenes(team, n_obs); under a disturbed plant each replica has draws of its own,
     because its global rows differ: the Monte-Carlo over disturbances that Rollout.scene_results() reduces."""
@@ -261,6 +261,27 @@ def make_batch12(n_agents: int, N: int = 10, gait: str = "trot", seed: int = 0, 
     obstacles = make_obstacles(rng, n_obs, sc)
     nbr_state = np.stack([x0[:, 0], x0[:, 1], x0[:, 6], x0[:, 7]], 1)
     return dict(x0=x0, xref=xref, foot=foot, contact=contact, obstacles=obstacles, nbr_state=nbr_state)
+
+
+MASS12 = 12.453   # srb12_params.mass: the model's body mass (kg)
+
+
+def plant_tables12(n_all: int, seed: int):
+    """(kick_v, kick_p, kick_w, mass, inertia), each [n_all], for a disturbed plant of the SRB-12 mode
+    (srb12.Plant12(kick_v=..., kick_p=..., kick_w=..., mass=..., inertia=...)), deterministic per seed.  kick_v ~
+    U[0.02, 0.08] m/s and kick_p ~ U[0, 0.01] m per cycle: plant_tables' ranges for its reasons (7 % to 30 % of VREF; at
+    most what VREF covers in one grid step).  kick_w ~ U[0.02, 0.1] rad/s per cycle, on each axis: from under half to
+    twice the +-0.05 rad/s that make_batch12 draws for a start state's angular velocity, a body that is knocked and not
+    tipped (0.1 rad/s held for a cycle of 0.172 s turns it by 1 degree).  mass ~ MASS12 * U[0.85, 1.15] = 10.6 ..
+    14.3 kg: a payload the model does not know of, or a lighter battery, 15 % either way as plant_tables' CoM height.
+    inertia ~ U[0.8, 1.25], a factor on the model's I_b: a payload away from the CoM changes the inertia by more than
+    the mass, and the range is reciprocal so that lighter and heavier are equally likely in ratio.  From a generator of
+    their own (500 + seed), so every other draw of this module is what it was."""
+    g = np.random.default_rng(500 + seed)
+    kick_v = g.uniform(0.02, 0.08, n_all)
+    kick_p = g.uniform(0.0, 0.01, n_all)
+    kick_w = g.uniform(0.02, 0.1, n_all)
+    return kick_v, kick_p, kick_w, MASS12 * g.uniform(0.85, 1.15, n_all), g.uniform(0.8, 1.25, n_all)
 
 
 def make_scenes12(n_scenes: int, team: int, N: int = 10, gait: str = "trot", seed: int = 0, n_obs: int = 20,

@@ -47,6 +47,18 @@ cycles: the smallest and the median clearance between bodies, the agents that to
 non-converged solves of the three solves (all measured with agent_body).  Three different NLPs again: no target.
 
     python tools/bench_rollout12.py --agents [--out profiles/bench_rollout12_agents.json]
+
+--plant measures the disturbed plant instead (srb12_plant): one workload.make_scenes12 scene (8 agents,
+20 obstacles, seed 1234) tiled by workload.replicate_scenes to --agents agents under set_scenes(8, 20), T cycles by
+run().  Cost, by the method above (Rollout12.run(T), reset included): nominal (the parent's path); the plant with zero
+bounds and one zero push per scene; that with mass = the model's, which runs the roll; that with at_state; and the drawn
+tables of workload.plant_tables12 with one push per scene.  The tool checks that the zero rows reproduce the nominal
+traj: bit for bit without a roll, within the polish's dynamics tolerance carried over the rollout with one (at_state
+is another plant: its departure is reported, not checked).  Safety: the sweep over kick_v bounds of 10.12.
+Linearisation: with no kicks, at_state 1 against 0 -- the largest departure of the plant from the prediction,
+min_d_obs and the scenes with a failure.
+
+    python tools/bench_rollout12.py --plant [--out profiles/bench_rollout12_plant.json]
 """
 import argparse
 import ctypes
@@ -326,6 +338,130 @@ def agent_sizes(args):
         w["solver"].close()
 
 
+KICKS = (0.0, 0.02, 0.05, 0.1, 0.2)      # kick_v bounds (m/s per cycle): none, 7 %, 19 %, 37 %, 74 % of VREF
+DYNTOL = 1e-8                            # SRB12_POL_DYNTOL: the dynamics residual of an accepted polish
+
+
+def plant(args):
+    """--plant: see the module docstring."""
+    dev = torch.device("cuda", 0)
+    A, N, Ko, Kn, T = args.agents, 10, 3, 8, args.cycles
+    team, scene_obs, seed = 8, 20, 1234
+    S = A // team
+    A = S * team
+    D = lambda v, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(v), dtype=dt, device=dev)
+    p = srb12.default_params(N, K_obs=Ko, K_nbr=Kn)
+    sc = workload.replicate_scenes(workload.make_scenes12(1, team, N, "trot", seed=seed, n_obs=scene_obs), S)
+    goal, phase, ob, x0 = D(sc["goal"]), D(sc["phase"], torch.int32), D(sc["obstacles"]), D(sc["x0"])
+    solver = srb12.Solver12(p, A, 0)
+    solver.set_timing(False)
+    solver.set_scenes(team, scene_obs)
+    P = srb12.Plant12
+
+    def rollout(pl=None):
+        return srb12.Rollout12(solver, goal, vref=workload.VREF, phase=phase, obstacles=ob, plant=pl)
+
+    def run(r):
+        r.reset(x0)
+        r.run(T)
+
+    def dist(v):
+        v = np.asarray(v, dtype=float)
+        return {"min": float(v.min()), "p05": float(np.quantile(v, 0.05)), "median": float(np.median(v)),
+                "p95": float(np.quantile(v, 0.95)), "max": float(v.max())}
+
+    def scene_stats(r):
+        sr = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.scene_results().items()}
+        z = r.results()["traj"][:, :, 2]
+        return {"scenes_with_a_failure": int((sr["n_failed"] > 0).sum()), "n_failed": int(sr["n_failed"].sum()),
+                "n_not_converged": int(sr["n_not_converged"].sum()), "solves": int(T * A),
+                "min_d_obs": dist(sr["min_d_obs"]), "min_d_agent": dist(sr["min_d_agent"]),
+                "height_m": {"min": float(z.min().item()), "max": float(z.max().item())}}
+
+    # ---- safety: the sweep over kick_v bounds
+    sweep = []
+    for kick in KICKS:
+        r = rollout(P(seed, kick_v=D(np.full(A, kick))))
+        run(r)
+        sweep.append(dict(kick_v=kick, **scene_stats(r)))
+
+    # ---- linearisation: no kicks, the plant's equations at the model's point and at its own state
+    lin = {}
+    for name, at in (("at_state_0", False), ("at_state_1", True)):
+        r = rollout(P(seed, mass=D(np.full(A, p.mass)), at_state=at))
+        run(r)
+        res = r.results()
+        r2 = srb12.Rollout12(solver, goal, vref=workload.VREF, phase=phase, obstacles=ob, log_x=True,
+                             plant=P(seed, mass=D(np.full(A, p.mass)), at_state=at))
+        run(r2)
+        res2 = r2.results()
+        dep = (res2["traj"][1:] - res2["x"][:, :, 36:48]).abs()
+        lin[name] = dict(scene_stats(r), largest_departure_from_the_prediction={
+            "p_m": float(dep[:, :, 0:3].max().item()), "theta_rad": float(dep[:, :, 3:6].max().item()),
+            "v_m_s": float(dep[:, :, 6:9].max().item()), "omega_rad_s": float(dep[:, :, 9:12].max().item()),
+            "first_cycle_omega_rad_s": float(dep[0, :, 9:12].max().item())})
+        del r2, res2, dep
+
+    # ---- cost: interleaved
+    kv, kp, kw, mass, inertia = (D(v) for v in workload.plant_tables12(A, seed))
+    zero, mmodel = D(np.zeros(A)), D(np.full(A, p.mass))
+    when, who = D(np.full(S, T // 2), torch.int32), D(team * np.arange(S), torch.int32)
+    push = (when, who, D(np.tile([0.2, 0.1, 0.0, 0.0, 0.0, 0.3], (S, 1))))
+    push0 = (when, who, D(np.zeros((S, 6))))
+    modes = [("nominal", rollout()),
+             ("plant_zero", rollout(P(seed, zero, zero, zero, pushes=push0))),
+             ("plant_zero_mass", rollout(P(seed, zero, zero, zero, mass=mmodel, pushes=push0))),
+             ("plant_zero_mass_at_state", rollout(P(seed, zero, zero, zero, mass=mmodel, at_state=True, pushes=push0))),
+             ("plant", rollout(P(seed, kv, kp, kw, mass, inertia, pushes=push)))]
+    for _ in range(args.warmup):
+        for _, r in modes:
+            run(r)
+    torch.cuda.synchronize(dev)
+    ms = {name: [] for name, _ in modes}
+    for _ in range(args.rounds):
+        for name, r in modes:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            run(r)
+            torch.cuda.synchronize(dev)
+            ms[name].append(1e3 * (time.perf_counter() - t0) / T)
+    out = {name: r.results() for name, r in modes}
+    torch.cuda.synchronize(dev)
+    iters = {name: float(o["iters"].double().sum(2).mean().item()) for name, o in out.items()}
+    same = bool(torch.equal(out["nominal"]["traj"], out["plant_zero"]["traj"]))
+    # a roll restarts every cycle from the logged state: per cycle it is within DYNTOL (1 + a + a^2 + a^3) of the
+    # prediction where the solve was polished (DESIGN.md 10.13); the closed loop then carries the difference on, so the
+    # trajectories are compared over the first cycle, where the two rollouts solved the same problems
+    a = 1.0 + p.Ts * np.sqrt(2.0)
+    tol = DYNTOL * (1 + a + a * a + a ** 3)
+    ok0 = (out["nominal"]["status"][0, :, 1] == 0)
+    d1 = (out["nominal"]["traj"][1] - out["plant_zero_mass"]["traj"][1]).abs().max(1).values
+    roll_err = float(d1[ok0].max().item())
+    roll_all = float((out["nominal"]["traj"] - out["plant_zero_mass"]["traj"]).abs().max().item())
+    spread = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+    res = {"tool": "tools/bench_rollout12.py --plant", "agents": A, "horizon": N, "K_obs": Ko, "K_nbr": Kn,
+           "batch": {"replicas": S, "team": team, "obstacles_per_scene": scene_obs}, "cycles": T, "rounds": args.rounds,
+           "n_gpus": 1, "seed": seed, "ms_per_cycle": {k: spread(v) for k, v in ms.items()},
+           "mean_iterations_per_solve": iters, "plant_zero_traj_equals_nominal": same,
+           "plant_zero_mass_first_cycle_max_abs_diff_optimal": roll_err, "roll_tolerance": tol,
+           "plant_zero_mass_traj_max_abs_diff_all_cycles": roll_all, "sweep": sweep, "linearisation": lin,
+           "note": "ms_per_cycle: run(T) / T, reset included, interleaved: nominal (no plant: srb12_rollout_agents_device); "
+                   "plant_zero (zero kick_v, kick_p, kick_w, one zero push per scene at cycle T / 2: the plant's two "
+                   "kernels on nominal's states); plant_zero_mass (mass = the model's besides: the roll); "
+                   "plant_zero_mass_at_state (the roll about the plant's own state: another plant, other NLPs); plant "
+                   "(workload.plant_tables12 and one push per scene).  sweep: one rollout per kick_v bound (kick_v alone, "
+                   "uniform over the agents), per-scene minima over the replicas.  linearisation: mass = the model's, no "
+                   "kicks; the departure is max |next state - X at grid index 3| over the cycles and agents."}
+    print(json.dumps(res), flush=True)
+    out_path = args.out if args.out is not None else os.path.join(ROOT, "profiles", "bench_rollout12_plant.json")
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    solver.close()
+    assert same, "the zero plant does not reproduce the nominal trajectory bit for bit"
+    assert roll_err <= tol, f"the model's own roll leaves the prediction by {roll_err} (tolerance {tol})"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=20, help="T: cycles per window")
@@ -342,6 +478,7 @@ def main():
     ap.add_argument("--moving", action="store_true", help="the moving-obstacle measurement alone (see above)")
     ap.add_argument("--vmax", type=float, default=1.0, help="--moving: the obstacles' top speed (m/s)")
     ap.add_argument("--sizes", action="store_true", help="the obstacle-size measurement alone (see above)")
+    ap.add_argument("--plant", action="store_true", help="the disturbed-plant measurement alone (see above)")
     args = ap.parse_args()
     if args.agents == "tables":
         args.agent_sizes, args.agents = True, "1024"
@@ -354,6 +491,8 @@ def main():
         return sizes(args)
     if args.agent_sizes:
         return agent_sizes(args)
+    if args.plant:
+        return plant(args)
     dev = torch.device("cuda", 0)
     A, N, Ko, Kn, T = args.agents, 10, 3, 8, args.cycles
     team, scene_obs = 8, 20
