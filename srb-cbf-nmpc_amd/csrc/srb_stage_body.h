@@ -41,7 +41,8 @@
                     if (SK_ISP(q, t, K_VAR) || SK_ISP(q, t, K_COP)) { W[q.r] = wgt; CF[q.r] = cfv; }
                 }
             SYNC();
-            gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, H0, vg, nz, tid, part, bmask);
+            if constexpr (GVEC) gram_rhs_vec<NZL, true, GSH, SRB_GRAM_FORM>(R, W, CF, OF, nko, H0, vg, nz, lane);
+            else gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, H0, vg, nz, tid, part, bmask);
             SYNC();
             gj_load<NZL, NZE>(Mi, H0, ZZ, 0.0, nz, lane);
             if (gj_factor<NZL, NZE>(Mi, nz, lane, 1) != 0) {
@@ -175,7 +176,8 @@
             // the first write of ZZ: the obstacle positions it may alias (SRB_OBS_IN_ZZ) were read by the slots'
             // setup above, and until here every ZZ operand was scaled by a zero shift, never read (gj_load / la_solve
             // test delta != 0; the LDS-check build asserts it, bit 7)
-            gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, ZZ, vg, nz, tid, part, bmask);
+            if constexpr (GVEC) gram_rhs_vec<NZL, true, GSH, SRB_GRAM_FORM>(R, W, CF, OF, nko, ZZ, vg, nz, lane);
+            else gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, ZZ, vg, nz, tid, part, bmask);
             SYNC();
             gj_load<NZL, NZE>(Mi, ZZ, ZZ, 0.0, nz, lane);
             gj_factor<NZL, NZE>(Mi, nz, lane, 0);
@@ -408,7 +410,8 @@
                 set_rhs(0);
                 SYNC();
                 STAMP_END(17);
-                gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, H0, vg, nz, tid, part, bmask);
+                if constexpr (GVEC) gram_rhs_vec<NZL, true, GSH, SRB_GRAM_FORM>(R, W, CF, OF, nko, H0, vg, nz, lane);
+                else gram_rhs<NZL, true, NW>(R, W, CF, cnt, OF, nko, H0, vg, nz, tid, part, bmask);
                 SYNC();
                 STAMP_END(4);
                 int ok = 0;

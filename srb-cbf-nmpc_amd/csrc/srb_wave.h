@@ -26,6 +26,28 @@ __device__ __forceinline__ int xcd_agent(int b, int n)
     return x * q + min(x, r) + (b >> 3);
 }
 
+// Barrier of the NW-wave workgroup.  NW = 1 (one agent per wave, the large-batch instances): the LDS
+// accesses of one wavefront execute in issue order, so a wavefront-scope fence (no s_waitcnt) and a wave
+// barrier suffice -- __syncthreads would wait for every outstanding LDS store first.  (Every SYNC site
+// sits in a function templated on NW.)
+// What this relies on: (1) LLVM IR -- a fence, whatever its scope, orders the thread's memory
+// operations: no load or store is moved across it (an acq_rel fence is a read-write of all memory for
+// alias analysis), so the ISA keeps the source order of the LDS accesses around SYNC; the wave barrier
+// is IntrNoMem (a convergence point only) and is not what orders them.  (2) The AMDGPU memory model
+// (LLVM AMDGPUUsage, memory model for GFX942 / GFX950): the LDS operations of one wavefront are performed
+// in issue order, so a ds_read by any lane observes an earlier ds_write of the same wave without an
+// s_waitcnt; the compiler still waits (lgkmcnt) before a loaded value is used.
+template <int NW>
+__device__ __forceinline__ void srb_sync()
+{
+    if constexpr (NW == 1) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    } else {
+        __syncthreads();
+    }
+}
+
 // --------------------------------------------------------------------------- wave helpers
 // Cross-lane traffic stays in the VALU: DPP row permutations for the 16-lane rows and
 // gfx950's v_permlane16/32_swap across rows.  Every lane ends with the bit-identical
