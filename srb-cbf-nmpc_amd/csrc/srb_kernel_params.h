@@ -273,6 +273,12 @@ struct SrbLLKParams {
 #ifndef SRB_LL_WPE        // waves per SIMD the low-level kernel is compiled for (min, max)
 #define SRB_LL_WPE 2, 8
 #endif
+#ifndef SRB_LL_REFINE     // most refinement steps of a Newton solve of the low-level kernel (srb_llctrl.hip kkt_solve)
+#define SRB_LL_REFINE 3
+#endif
+#ifndef SRB_LL_REFINE_TOL // a correction below this fraction of the step ends the refinement
+#define SRB_LL_REFINE_TOL 1e-6
+#endif
 
 // device layout of one agent (srb_ll_io, include/srbnmpc.h): column-major matrices with fixed
 // leading dimensions

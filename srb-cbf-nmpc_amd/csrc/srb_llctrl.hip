@@ -20,7 +20,8 @@
 //           (Sherman-Morrison; the stiff CLF row's right-hand side enters through
 //            v r3 / (w + u'v), never as omega * r3);
 //     Y = H^-1 A' (31 x 18), S = A Y (18 x 18, SPD), inverted by register Gauss-Jordan;
-//     dy = S^-1 (A H^-1 g - r2), dx = H^-1 g - Y dy, dz = Omega (G dx - r3).
+//     dy = S^-1 (A H^-1 g - r2), dx = H^-1 (g - A' dy), dz = Omega (G dx - r3),
+//     then one to SRB_LL_REFINE steps of iterative refinement on the unreduced system (kkt_solve).
 // A (18 x 31) is assembled once per agent: [Jc; H0] Dinv [Jc' B] on the VALU from LDS.
 //
 // Inputs/outputs are agent-major fp64 arrays in HBM (srb_ll_io, include/srbnmpc.h).
@@ -431,7 +432,8 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
 
     // ------------------------------------------------------------------ Newton solve
     // [P A' G'; A 0 0; G 0 -W] [dx; dy; dz] = [r1; r2; r3]; om_r = z/s per row (register)
-    auto kkt_solve = [&](double r1, double r2, double r3, double om, double &dx, double &dy, double &dz) {
+    // one pass through the factor; kkt_solve below refines it
+    auto kkt_solve1 = [&](double r1, double r2, double r3, double om, double &dx, double &dy, double &dz) {
         // t = Omega r3 (rows); the CLF row's r3 itself goes to sc[0]
         if (isr) sh.vr[lane] = om * r3;
         if (isclf) sh.sc[0] = r3;
@@ -467,14 +469,25 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
         SYNC();
         if (ise) sh.ve[lane] = dyk;
         SYNC();
-        // dx = u - Y dy
-        double dxj = uj;
+        // dx = H^-1 (r1 - A' dy + G' Omega r3): the block solves once more, on the combined right-hand side.
+        // u - Y dy is the same vector, but u and every column of Y carry their own rounding, of the size of the
+        // soft directions of a leg block; on a stiff cone row (G dx)_r - r3 is O(1/omega) and is lost in it, and
+        // dz = omega (G dx - r3) then stalls the solve at active bounds
+        const double rho = isv ? r1 - acol(sh.ve) : 0.0;
+        double vg2 = (isv && vtype >= 2) ? vj * rho : 0.0, d1 = 0.0;
+        wsum2(vg2, d1);
+        if (isv) sh.vg[lane] = rho + gtcol(sh.vr);
+        SYNC();
+        double dxj = 0.0;
         if (isv) {
-            const double *Yj = sh.u.ip.Y + lane * LDJ;
-            double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-            for (int k = 0; k < NQ; k += 2) { s0 = fma(Yj[k], sh.ve[k], s0); s1 = fma(Yj[k + 1], sh.ve[k + 1], s1); }
-            dxj = uj - (s0 + s1);
+            if (vtype == 0) {
+                const int c0 = 3 * lf;
+                dxj = fsolve(sh.vg[c0], sh.vg[c0 + 1], sh.vg[c0 + 2]);
+            } else if (vtype == 1) {
+                dxj = sh.vg[lane] * hinv;
+            } else {
+                dxj = rho * iDj + gam * vj * (sh.sc[0] - vg2);
+            }
         }
         SYNC();
         if (isv) sh.vx[lane] = dxj;
@@ -483,6 +496,32 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
         dy = ise ? dyk : 0.0;
         dz = isr ? (grow(sh.vx) - r3) * om : 0.0;
         SYNC();
+    };
+    // wr = s/z per row (W of the unreduced system, 1 / om).  Iterative refinement on the unreduced system: its
+    // residual at (dx, dy, dz) costs no division by a small slack, and the correction comes through the same
+    // factor.  The Schur complement S (condition 1e8 .. 1e10 on these QPs) alone leaves dy, and with it the
+    // step, at 1e-8 .. 1e-6 relative, and a stiff row's dz worse.  At least one step, and further ones (at most
+    // SRB_LL_REFINE) while a correction is above SRB_LL_REFINE_TOL of its part of the step (wave-uniform)
+    auto kkt_solve = [&](double r1, double r2, double r3, double om, double wr, double &dx, double &dy, double &dz) {
+        kkt_solve1(r1, r2, r3, om, dx, dy, dz);
+#pragma unroll 1
+        for (int q = 0; q < SRB_LL_REFINE; q++) {
+            if (isv) sh.vx[lane] = dx;
+            if (ise) sh.ve[lane] = dy;
+            if (isr) sh.vr[lane] = dz;
+            SYNC();
+            const double e1 = isv ? r1 - (Pj * dx + acol(sh.ve) + gtcol(sh.vr)) : 0.0;
+            const double e2 = ise ? r2 - arow(sh.vx) : 0.0;
+            const double e3 = isr ? r3 - (grow(sh.vx) - wr * dz) : 0.0;
+            SYNC();
+            double ex, ey, ez;
+            kkt_solve1(e1, e2, e3, om, ex, ey, ez);
+            dx += ex; dy += ey; dz += ez;
+            double cn[6] = {fabs(ex), fabs(dx), fabs(ey), fabs(dy), fabs(ez), fabs(dz)};
+            wred<6, 0x3fu>(cn);
+            if (!(cn[0] > SRB_LL_REFINE_TOL * cn[1] || cn[2] > SRB_LL_REFINE_TOL * cn[3] || cn[4] > SRB_LL_REFINE_TOL * cn[5]))
+                break;
+        }
     };
 
     // ------------------------------------------------------------------ kkt_initialize (Auxilary.c:680-755)
@@ -494,7 +533,7 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
         flag = 1;
     } else {
         double dzt;
-        kkt_solve(isv ? -cj : 0.0, ise ? bk : 0.0, isr ? hr : 0.0, isr ? 1.0 : 0.0, xj, yk, dzt);
+        kkt_solve(isv ? -cj : 0.0, ise ? bk : 0.0, isr ? hr : 0.0, isr ? 1.0 : 0.0, 1.0, xj, yk, dzt);
         if (isv) sh.vx[lane] = xj;
         SYNC();
         const double zi = isr ? hr - grow(sh.vx) : 0.0;
@@ -543,7 +582,7 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
             if (factor(sh.sc[1])) { flag = 1; break; }
             // predictor
             ds = -lam * lam;
-            kkt_solve(rx, ry, isr ? rz - ds * iz : 0.0, omf, dx, dy, dz);
+            kkt_solve(rx, ry, isr ? rz - ds * iz : 0.0, omf, s * iz, dx, dy, dz);
             LLST(6);   // predictor solve
             dsv = isr ? (ds - s * dz) * iz : 0.0;
             st[0] = (isr && dsv < 0) ? s / dsv : -1e300;   // max(v/dv) = -min(-v/dv) (findsteplength)
@@ -563,7 +602,7 @@ extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per
             }
             LLST(7);   // predictor steps, rho
             // corrector (kktsolve_2)
-            kkt_solve(rx, ry, isr ? rz - ds * iz : 0.0, omf, dx, dy, dz);
+            kkt_solve(rx, ry, isr ? rz - ds * iz : 0.0, omf, s * iz, dx, dy, dz);
             LLST(8);   // corrector solve
             dsv = isr ? (ds - s * dz) * iz : 0.0;
             st[0] = (isr && dsv < 0) ? s / dsv : -1e300;

@@ -8,7 +8,8 @@ Pins:
   * assembly: block structure and the CLF scalars against closed forms derived here
     independently of the oracle's explicit-matrix products;
   * epilogue (swing PD, integration, swingInvKin): restatement only (the reference needs
-    Eigen, absent) -- checked here against numpy formulas of the same source lines.
+    Eigen, absent) -- checked here against numpy formulas of the same source lines
+    (tests/ll_reference.py epilogue_np, shared with the GPU stress tests).
 """
 import os
 
@@ -17,6 +18,9 @@ import pytest
 
 import oracle
 from srbnmpc import ll_workload
+
+import ll_cases
+import ll_reference
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "ll_ctrl.npz")
 
@@ -42,8 +46,14 @@ def test_ll_qp_matches_genuine_iswift(clf):
 
 
 def test_ll_assembly_structure_and_clf_closed_form():
+    """At the default parameters and at one non-default set (the "gains" case of tests/ll_cases.py)."""
+    _assembly_checks({})
+    _assembly_checks(ll_cases.case_params("gains"))
+
+
+def _assembly_checks(prm):
     g = _gold()
-    p = oracle.ll_params()
+    p = oracle.ll_params(**prm)
     for a in range(g["ind"].shape[0]):
         ind = g["ind"][a]
         c_ = int((ind == 1).sum())
@@ -90,50 +100,12 @@ def test_ll_epilogue_matches_numpy():
     p = oracle.ll_params()
     o = oracle.ll_calc_torque(p, g)
     for a in range(g["ind"].shape[0]):
-        ind = g["ind"][a]
-        c_ = int((ind == 1).sum())
-        con, sw = 3 * c_, 12 - 3 * c_
-        Dinv = _mat(g, "Dinv", a, 18, 18, 18)
-        B = _mat(g, "B", a, 18, 18, 12)
-        Jtoe = _mat(g, "Jtoe", a, 12, 12, 18)
-        Jhip = _mat(g, "Jhip", a, 12, 12, 18)
-        Js = _mat(g, "Js", a, sw, 12, 18)
-        toe = g["toePos"][a].reshape(4, 3); hip = g["hipPos"][a].reshape(4, 3)
-        q, dq, hd, dhd = g["q"][a], g["dq"][a], g["hd"][a], g["dhd"][a]
-        x = o["x"][a]
-        F = np.zeros(12); k = 0
-        for i in range(4):
-            if ind[i] == 1:
-                F[3 * i:3 * i + 3] = x[k:k + 3]; k += 3
-        np.testing.assert_array_equal(o["QP_force"][a], F)
-        tau = np.array(g["tau"][a], float)
-        tau[6:] = x[con:con + 12]
-        if sw:
-            Delta = np.linalg.inv(Js @ Dinv @ Js.T)
-            pd = np.zeros(sw); vd = np.zeros(sw); cs = 0
-            for i in range(4):
-                if ind[i] == 0:
-                    pd[cs:cs + 3] = hd[6 + cs:9 + cs] - toe[i]
-                    vd[cs:cs + 3] = dhd[6 + cs:9 + cs] - Jtoe[3 * i:3 * i + 3] @ dq
-                    cs += 3
-            tau += Js.T @ (1600 * np.diag(Delta) * pd + 40 * vd)
-        np.testing.assert_allclose(o["tau"][a], tau, rtol=1e-10, atol=1e-9)
-        ddq = Dinv @ (B @ tau[6:] + Jtoe.T @ F - g["Hv"][a])
-        np.testing.assert_allclose(o["ddq"][a], ddq, rtol=1e-10, atol=1e-9)
-        dqn = dq + ddq / 1000
-        qn = q + dqn / 1000 + 0.5e-6 * ddq
-        cs = 0
-        for i in range(4):
-            if ind[i] == 0:
-                Jt = Jtoe[3 * i:3 * i + 3] - Jhip[3 * i:3 * i + 3]
-                r = (dhd[6 + cs:9 + cs] - Jhip[cs:cs + 3] @ dq) + 20 * ((hd[6 + cs:9 + cs] - hip[i]) - (toe[i] - hip[i])) \
-                    - Jt[:, 3:6] @ dq[3:6]
-                v = np.linalg.solve(Jt[:, 6 + 3 * i:9 + 3 * i], r)
-                dqn[6 + 3 * i:9 + 3 * i] = v
-                qn[6 + 3 * i:9 + 3 * i] = q[6 + 3 * i:9 + 3 * i] + v / 1000
-                cs += 3
-        np.testing.assert_allclose(o["dq"][a], dqn, rtol=1e-10, atol=1e-9)
-        np.testing.assert_allclose(o["q"][a], qn, rtol=1e-10, atol=1e-12)
+        e = ll_reference.epilogue_np(g, a, o["x"][a])
+        np.testing.assert_array_equal(o["QP_force"][a], e["QP_force"])
+        np.testing.assert_allclose(o["tau"][a], e["tau"], rtol=1e-10, atol=1e-9)
+        np.testing.assert_allclose(o["ddq"][a], e["ddq"], rtol=1e-10, atol=1e-9)
+        np.testing.assert_allclose(o["dq"][a], e["dq"], rtol=1e-10, atol=1e-9)
+        np.testing.assert_allclose(o["q"][a], e["q"], rtol=1e-10, atol=1e-12)
 
 
 def test_ll_oracle_vs_genuine_iswift_random():
