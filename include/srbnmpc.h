@@ -616,6 +616,90 @@ int srb_rollout_plant_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io
                              const srb_plant *plant, int cycles, void *stream);
 
 /*
+ * Degraded neighbour link (LIP mode; DESIGN.md 3 "Degraded link", 9, 10.14): what an agent knows about its neighbours
+ * is late, lossy and noisy, so that a rollout can say whether the inter-agent CBF rows keep separation when snapshots
+ * are cycles old, broadcasts are lost or positions are off by centimetres.  As with srb_plant, SRB_ABI_VERSION and
+ * every existing struct stay.  The solve and its selection read the PERCEIVED tables seen_state / seen_plan; the
+ * metrics, traj and every log keep reading the truth.  All pointers are device pointers; every table has n_all rows
+ * in the row order of nbr_state, global row g.  All arithmetic is fp64, uncontracted, with one stated grouping
+ * (csrc/srb_link.hip; tests/link_oracle.py restates it bit for bit).
+ *
+ * One broadcast per agent per cycle, and every receiver sees the same fate of a message (a per-sender model: the
+ * perceived tables keep n_all rows).  At every cycle s >= c_first row g sends its snapshot row last_state[g]
+ * (x, y, xdot, ydot) and, for s > c_first with a plan table, its shifted plan plan_table[g] [N][2].
+ *   noise_p, noise_v [n_all]  at the sender: Philox4x32-10 with key ((uint32)seed, (uint32)(seed >> 32)) and counter
+ *                         ((uint32)s, (uint32)g, 3, 0) gives w0 .. w3, u_i = ((double)(int32_t)w_i + 0.5) * 2^-31, and
+ *                         the message's state is (x + noise_p[g] u0, y + noise_p[g] u1, xdot + noise_v[g] u2,
+ *                         ydot + noise_v[g] u3), each one rounded multiply and one rounded add.  A NULL table leaves its
+ *                         components untouched (it does not add 0.0).  Plans carry no noise.
+ *   drop [n_all]          message (s, g) is lost iff s > c_first and 0.5 * u0 + 0.5 < drop[g], u0 from the counter
+ *                         ((uint32)s, (uint32)g, 2, 0).  The left side is exact and inside (0, 1): 0 never loses, 1
+ *                         always does.  The message of c_first is never lost and arrives at once.
+ *                         (srb_plant draws with third counter words 0 and 1: one seed may serve both.)
+ *   delay [n_all] int     0 .. max_delay cycles (NULL: 0), clamped into that range by the kernel; max_delay <= 16.
+ *                         The message of cycle s is kept in slot (s - c_first) mod (max_delay + 1) of the ring.  At
+ *                         cycle c > c_first the message of s = c - delay[g] arrives if s > c_first and it was not lost:
+ *                         it becomes the held message and held_cycle[g] = s.  Otherwise the receiver keeps what it
+ *                         holds.  age = c - held_cycle[g].
+ *   extrapolate           0: seen_state[g] / seen_plan[g] are the held state / plan as they are.  1: the receiver
+ *                         dead-reckons: position + velocity * ((double)(4 age) * Ts), velocities as held, and the held
+ *                         plan shifted by 4 age grids with the rule of srb_sim.plan_table: grid k is the held grid
+ *                         k + 4 age while that lies inside the horizon, beyond it
+ *                         last + (double)(k + 4 age - N + 1) * (last - previous); age 0 is a copy of both.
+ *   With either setting a row that holds no plan yet (held_cycle == c_first) at a cycle c > c_first with a plan table
+ *   gets the constant-velocity line from its SEEN state, p + v * (Ts * (double)(k + 1)).  At c_first no plan is sent
+ *   and seen_plan, held_plan and ring_plan are not written: the first solve reads batch.nbr_plan as ever.
+ *   age_log [T][n_all] int  out, optional: row c - c_first gets age.
+ * The draws key on the caller's cycle number and the global row, so a shard, a scene replica and a rollout continued
+ * cycle by cycle draw what the whole team draws in one call.
+ *
+ * srb_link_update_device(ctx, n_all, link, last_state, plan_table, cycle, c_first, stream): the update of one cycle
+ * (srb_link_update_kernel), always over all n_all rows -- every shard computes the whole perceived table itself from the
+ * gathered truth (last_state [n_all][4], plan_table [n_all][N][2] or NULL).  Call it once per cycle, from c_first on,
+ * with the same max_delay throughout.  Asynchronous on `stream`, ordered by the context like the other device calls.
+ * srb_rollout_link_device extends srb_rollout_plant_device (which is this call with link == NULL): after the metrics
+ * of every cycle the update runs on sim.last_state / sim.plan_table, the solve reads link->seen_state as its nbr_state
+ * and, from the second cycle with a plan table, link->seen_plan as its nbr_plan.
+ *
+ * A link is on when any of delay, drop, noise_p, noise_v is set.  With link == NULL or all four NULL nothing is
+ * launched and every output has the bits it had (age_log then stays unwritten).  SRB_ERR_ARG, by name, before anything
+ * is launched and before a context is needed: a wrong struct_size; max_delay outside 0 .. 16; extrapolate not 0 / 1; a
+ * link that is on without ring_state, held_state, held_cycle or seen_state; a plan table without ring_plan, held_plan
+ * or seen_plan; seen_state overlapping last_state.  With a context (the ranges need N): seen_plan overlapping
+ * plan_table or batch.plan; SRB_OPT_PLAN_SELECTION = 1 with a link on (that selection reads the agent's own previous
+ * plan from its row of the table, which would be a stale copy of what the agent knows exactly: not built); a shard in
+ * the rollout driver, as ever.  The contents of the tables are NOT checked otherwise.  The SRB-12 mode and the
+ * MPC_dist shims have no link.
+ */
+typedef struct srb_link {
+    int struct_size;            /* sizeof(srb_link) (ABI check) */
+    unsigned long long seed;    /* the Philox key */
+    const int *delay;           /* [n_all] cycles, 0 .. max_delay, or NULL */
+    const double *drop;         /* [n_all] loss probability per message, or NULL */
+    const double *noise_p;      /* [n_all] m bound on the sent position, or NULL */
+    const double *noise_v;      /* [n_all] m/s bound on the sent velocity, or NULL */
+    int max_delay;              /* 0 .. 16: the ring holds max_delay + 1 cycles */
+    int extrapolate;            /* 0 / 1 */
+    double *ring_state;         /* [(max_delay + 1)][n_all][4]     caller-owned state of the link ... */
+    double *ring_plan;          /* [(max_delay + 1)][n_all][N][2] */
+    double *held_state;         /* [n_all][4] */
+    double *held_plan;          /* [n_all][N][2] */
+    int *held_cycle;            /* [n_all] */
+    double *seen_state;         /* [n_all][4] out: the perceived snapshot table */
+    double *seen_plan;          /* [n_all][N][2] out: the perceived plan table */
+    int *age_log;               /* [T][n_all] out, optional */
+} srb_link;
+int srb_link_update_device(srb_ctx *ctx, int n_all, const srb_link *link, const double *last_state,
+                           const double *plan_table, int cycle, int c_first, void *stream);
+/* the same update by a stated thread mapping, for tools/bench_link.py and the tests: lanes threads per row, 1, 8 or 16
+ * (srb_link_update_device uses the measured choice); every mapping gives the same bits */
+int srb_link_update_lanes_device(srb_ctx *ctx, int n_all, const srb_link *link, const double *last_state,
+                                 const double *plan_table, int cycle, int c_first, int lanes, void *stream);
+int srb_rollout_link_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io, const srb_sim *sim,
+                            const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
+                            const srb_plant *plant, const srb_link *link, int cycles, void *stream);
+
+/*
  * HL reference planner (generateReferenceTrajectory, MPC_dist.cpp:930-1104; SURVEY.md 8(f)
  * row 3) on HIP device `device`, host buffers, synchronous.  NA agents (1..2^20; up to 1024 in
  * one persistent workgroup, more -- one coupled swarm -- as one launch per step) starting at

@@ -1172,8 +1172,91 @@ extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d
     return srb_sim_metrics_sized_device(c, n_agents, d, nullptr, cycle, stream);
 }
 
+// ---- degraded neighbour link (srb_link.hip).  The struct degrades the link at all (else every entry point is the one
+// it extends and nothing is launched; age_log alone is not written)
+static bool link_on(const srb_link *ln) { return ln && (ln->delay || ln->drop || ln->noise_p || ln->noise_v); }
+
+// The argument errors of srb_link that need no context, before anything is launched.  last_state, plan_table: the
+// truth tables of the call ([n_all][4]; [n_all][N][2] or null)
+#define SRB_LINK_MAX_DELAY 16
+static int check_link(const srb_link *ln, int n_all, const double *last_state, const double *plan_table)
+{
+    if (int rc = srb_check_struct(ln, "srb_link")) return rc;
+    if (!ln) return SRB_OK;
+    if (ln->max_delay < 0 || ln->max_delay > SRB_LINK_MAX_DELAY)
+        return fail(SRB_ERR_ARG, "srb_link.max_delay: 0 .. 16 (the ring holds max_delay + 1 cycles)");
+    if (ln->extrapolate != 0 && ln->extrapolate != 1)
+        return fail(SRB_ERR_ARG, "srb_link.extrapolate: 0 (the held message as it is) or 1 (dead-reckoned by its age)");
+    if (!link_on(ln)) return SRB_OK;
+    if (!ln->ring_state || !ln->held_state || !ln->held_cycle || !ln->seen_state)
+        return fail(SRB_ERR_ARG, "srb_link: a link that is on needs ring_state, held_state, held_cycle and seen_state");
+    if (plan_table && (!ln->ring_plan || !ln->held_plan || !ln->seen_plan))
+        return fail(SRB_ERR_ARG, "srb_link: a plan table needs ring_plan, held_plan and seen_plan");
+    if (n_all > 0 && srb_overlap(ln->seen_state, (size_t)n_all * 4, last_state, (size_t)n_all * 4))
+        return fail(SRB_ERR_ARG, "srb_link.seen_state overlaps last_state (the metrics read the truth while the solve "
+                                 "reads what is seen: use two buffers)");
+    return SRB_OK;
+}
+
+// ... and those that need the context: the plan ranges (N) and the selection that reads the agent's own table row.
+// plan: the solve's plan output (srb_batch.plan) or null
+static int check_link_ctx(const srb_ctx *c, const srb_link *ln, int n_all, const double *plan_table, const double *plan)
+{
+    if (!link_on(ln)) return SRB_OK;
+    if (c->plan_selection)
+        return fail(SRB_ERR_ARG, "SRB_OPT_PLAN_SELECTION = 1 with a srb_link that is on: the horizon-aware selection reads "
+                                 "the agent's own previous plan from its row of the table, which would be a stale copy "
+                                 "(not built)");
+    if (plan_table && c->p.N < 2) return fail(SRB_ERR_ARG, "srb_link: a plan table needs N >= 2 (the plan shift)");
+    const size_t rows = (size_t)std::max(n_all, 0) * 2 * c->p.N;
+    if (srb_overlap(ln->seen_plan, rows, plan_table, rows))
+        return fail(SRB_ERR_ARG, "srb_link.seen_plan overlaps plan_table (the truth the next cycle's messages carry: use "
+                                 "two buffers)");
+    if (srb_overlap(ln->seen_plan, rows, plan, rows))
+        return fail(SRB_ERR_ARG, "srb_link.seen_plan overlaps srb_batch.plan (the solve reads the table while it writes "
+                                 "its plans: use two buffers)");
+    return SRB_OK;
+}
+
+// one cycle's update (launch only: the caller orders the stream); ln is on
+static int launch_link(srb_ctx *c, int n_all, const srb_link *ln, const double *last_state, const double *plan_table,
+                       int cycle, int c_first, hipStream_t s, int lanes = SRB_LINK_LANES)
+{
+    const int slot = (int)(((long long)cycle - c_first) % (ln->max_delay + 1));
+    int *age_row = ln->age_log ? ln->age_log + (size_t)(cycle - c_first) * (size_t)n_all : nullptr;
+    if (srb_launch_link_update(lanes, n_all, c->p.N, c->p.Ts, cycle, c_first, ln->max_delay, slot, ln->extrapolate,
+                               (unsigned)(ln->seed & 0xffffffffull), (unsigned)(ln->seed >> 32), ln->delay, ln->drop,
+                               ln->noise_p, ln->noise_v, last_state, plan_table, ln->ring_state, ln->ring_plan,
+                               ln->held_state, ln->held_plan, ln->held_cycle, ln->seen_state, ln->seen_plan, age_row, s))
+        return fail(SRB_ERR_ARG, "srb_link_update_lanes_device: lanes is 1, 8 or 16");
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+extern "C" int srb_link_update_lanes_device(srb_ctx *c, int n_all, const srb_link *ln, const double *last_state,
+                                            const double *plan_table, int cycle, int c_first, int lanes, void *stream)
+{
+    if (int rc = check_link(ln, n_all, last_state, plan_table)) return rc;
+    if (cycle < c_first) return fail(SRB_ERR_ARG, "srb_link: cycle precedes c_first");
+    if (lanes != 1 && lanes != 8 && lanes != 16) return fail(SRB_ERR_ARG, "srb_link_update_lanes_device: lanes is 1, 8 or 16");
+    if (!c) return fail(SRB_ERR_ARG, "null argument");
+    if (n_all < 0) return fail(SRB_ERR_ARG, "srb_link: negative n_all");
+    if (int rc = check_link_ctx(c, ln, n_all, plan_table, nullptr)) return rc;
+    if (!link_on(ln) || n_all == 0) return SRB_OK;
+    if (!last_state) return fail(SRB_ERR_ARG, "srb_link: last_state missing");
+    hipStream_t s = (hipStream_t)stream;
+    return c->order.run(c->device, s, [&] { return launch_link(c, n_all, ln, last_state, plan_table, cycle, c_first, s, lanes); });
+}
+
+extern "C" int srb_link_update_device(srb_ctx *c, int n_all, const srb_link *ln, const double *last_state,
+                                      const double *plan_table, int cycle, int c_first, void *stream)
+{
+    return srb_link_update_lanes_device(c, n_all, ln, last_state, plan_table, cycle, c_first, SRB_LINK_LANES, stream);
+}
+
 static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, const srb_moving *mv,
-                   const srb_sizes *sz, const srb_agent_sizes *ag, const srb_plant *pl, int cycles, void *stream)
+                   const srb_sizes *sz, const srb_agent_sizes *ag, const srb_plant *pl, const srb_link *ln, int cycles,
+                   void *stream)
 {
     if (int rc0 = srb_check_struct(b, "srb_batch")) return rc0;
     if (int rc0 = check_moving(mv, b, true)) return rc0;
@@ -1183,6 +1266,7 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
     if (!plant_on(pl)) pl = nullptr;
     // (the layout and null checks of check_sim only: the driver's first cycle is c_first itself)
     if (int rc = check_sim(d, d && d->struct_size == (int)sizeof(srb_sim) ? d->c_first : 0, false)) return rc;
+    if (int rc0 = check_link(ln, n_agents, d->last_state, d->plan_table)) return rc0;
     if (!b) return fail(SRB_ERR_ARG, "null argument");
     if (!d->goal) return fail(SRB_ERR_ARG, "srb_sim.goal missing");
     if (!c) return fail(SRB_ERR_ARG, "null argument");
@@ -1195,6 +1279,8 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
     if (srb_overlap(b->plan, (size_t)n_agents * 2 * c->p.N, d->plan_table, (size_t)n_agents * 2 * c->p.N))
         return fail(SRB_ERR_ARG, "srb_sim.plan_table overlaps srb_batch.plan (the solve reads the table while it writes "
                                  "its plans: use two buffers)");
+    if (int rc0 = check_link_ctx(c, ln, n_agents, d->plan_table, b->plan)) return rc0;
+    if (!link_on(ln)) ln = nullptr;
     if (c->scene_agents > 0) {
         if (n_agents % c->scene_agents != 0)
             return fail(SRB_ERR_ARG, "scenes: srb_rollout_device rolls out whole scenes, n_agents (" + std::to_string(n_agents) +
@@ -1211,6 +1297,7 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
     bat.x0 = d->x0; bat.ref = d->ref; bat.foot = d->foot;
     bat.nbr_state = d->last_state; bat.n_all = n_agents; bat.agent_offset = 0;
     bat.alpha_buf = b->alpha ? d->alpha_buf : nullptr;
+    if (ln) bat.nbr_state = ln->seen_state;               // the solve reads what is seen, the metrics the truth
     if (!sim.x) return fail(SRB_ERR_ARG, "srb_batch.x missing");
     hipStream_t s = (hipStream_t)stream;
     HIPCHK(hipSetDevice(c->device));
@@ -1226,7 +1313,8 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
         if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
         if (!rc) rc = launch_metrics(c, n_agents, &sim, cyc, s, sz ? sz->obs_radius : nullptr,
                                      ag ? ag->agent_body : nullptr, ag ? ag->collide_cycle : nullptr);
-        if (i > 0 && d->plan_table) bat.nbr_plan = d->plan_table;
+        if (!rc && ln) rc = launch_link(c, n_agents, ln, d->last_state, d->plan_table, cyc, d->c_first, s);
+        if (i > 0 && d->plan_table) bat.nbr_plan = ln ? ln->seen_plan : d->plan_table;
         if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp, vel, mv ? mv->horizon_selection : 0,
                              sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0, ag ? ag->agent_rad : nullptr,
                              ag ? ag->agent_pad : nullptr, ag ? ag->clearance_selection : 0);
@@ -1235,13 +1323,20 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
     return rc ? rc : rc_mark;
 }
 
-// the tables of srb_sizes, srb_agent_sizes and srb_plant do not change over a rollout: the same pointers serve every
-// cycle
+// the tables of srb_sizes, srb_agent_sizes, srb_plant and srb_link do not change over a rollout: the same pointers
+// serve every cycle
+extern "C" int srb_rollout_link_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
+                                       const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
+                                       const srb_plant *pl, const srb_link *ln, int cycles, void *stream)
+{
+    return rollout(c, n_agents, b, d, mv, sz, ag, pl, ln, cycles, stream);
+}
+
 extern "C" int srb_rollout_plant_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
                                         const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
                                         const srb_plant *pl, int cycles, void *stream)
 {
-    return rollout(c, n_agents, b, d, mv, sz, ag, pl, cycles, stream);
+    return srb_rollout_link_device(c, n_agents, b, d, mv, sz, ag, pl, nullptr, cycles, stream);
 }
 
 extern "C" int srb_rollout_agents_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,

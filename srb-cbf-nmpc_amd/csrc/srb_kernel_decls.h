@@ -108,7 +108,17 @@ extern "C" __global__ void srb_sim_advance_plant_kernel(
     double *x_log, int agent_offset, double grav, unsigned seed_lo, unsigned seed_hi, const double *kick_v,
     const double *kick_p, const double *plant_hcom, int n_push, const int *push_cycle, const int *push_agent,
     const double *push_dv, double *dist_log);
-#define SRB_SIM_AGENTS_PER_BLOCK 16      // srb_sim_metrics_kernel: agents per block of 256 threads (16 threads each)
+// srb_link.hip: the degraded neighbour link (srb_link), one cycle's update of all n_all rows.  slot_c: the ring slot
+// of cycle c, (c - c_first) mod (max_delay + 1); age_row: age_log's row of cycle c or null.  LPR threads per row:
+// launch it through srb_launch_link_update (the grid follows from lanes)
+#define SRB_LINK_LANES 8                 // srb_link_update_device's mapping (measured: DESIGN.md 10.14)
+int srb_launch_link_update(int lanes, int n_all, int N, double Ts, int c, int c_first, int max_delay, int slot_c,
+                           int extrapolate, unsigned seed_lo, unsigned seed_hi, const int *delay, const double *drop,
+                           const double *noise_p, const double *noise_v, const double *last_state,
+                           const double *plan_table, double *ring_state, double *ring_plan, double *held_state,
+                           double *held_plan, int *held_cycle, double *seen_state, double *seen_plan, int *age_row,
+                           hipStream_t s);
+#define SRB_SIM_AGENTS_PER_BLOCK 16    // srb_sim_metrics_kernel: agents per block of 256 threads (16 threads each)
 extern "C" __global__ void srb_sim_metrics_kernel(int n_agents, int c, int c_first, const double *state,
                                                   const double *obstacles, int n_obs, const double *nbr_state, int n_all,
                                                   int agent_offset, double *d_obs, double *d_agent, double *min_d_obs,

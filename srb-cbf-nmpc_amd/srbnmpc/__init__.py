@@ -134,6 +134,41 @@ class Plant(ctypes.Structure):
         super().__init__(ctypes.sizeof(Plant), *args, **kw)
 
 
+class Link(ctypes.Structure):
+    """Mirror of srb_link (the degraded neighbour link of the LIP rollout; struct_size filled in).  A Rollout fills it
+    from a LinkModel and buffers of its own."""
+    _fields_ = [("struct_size", ctypes.c_int), ("seed", ctypes.c_ulonglong), ("delay", _ip), ("drop", _dp),
+                ("noise_p", _dp), ("noise_v", _dp), ("max_delay", ctypes.c_int), ("extrapolate", ctypes.c_int),
+                ("ring_state", _dp), ("ring_plan", _dp), ("held_state", _dp), ("held_plan", _dp), ("held_cycle", _ip),
+                ("seen_state", _dp), ("seen_plan", _dp), ("age_log", _ip)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(ctypes.sizeof(Link), *args, **kw)
+
+
+class LinkModel:
+    """What degrades the neighbour link of a Rollout (Rollout(link=LinkModel(...)); srb_link of include/srbnmpc.h): one
+    broadcast per agent per cycle, and every receiver sees the same fate of it.
+
+    seed      the key of the loss and noise draws (0 .. 2^64 - 1; Philox4x32-10, counters (cycle, global row, 2 / 3, 0):
+              the plant's kicks use other counters, so one seed may serve both)
+    delay     [n_all] int32 or None: cycles a row's messages are late, 0 .. 16
+    drop      [n_all] float64 or None: the probability that a message of the row is lost, 0 .. 1
+    noise_p, noise_v  [n_all] float64 or None: the bound (m, m/s) of the uniform error on the sent position / velocity
+    extrapolate  True: the receivers dead-reckon a held message by its age (position along the held velocity, the
+              held plan shifted by 4 grids per cycle of age); False: they use it as it is
+    The tables are torch tensors on the rollout's device (checked there, by name) and do not change over a rollout; every
+    shard holds them whole.  With every table None the link degrades nothing and the rollout is the plain one."""
+
+    def __init__(self, seed: int = 0, delay=None, drop=None, noise_p=None, noise_v=None, extrapolate: bool = False):
+        self.seed, self.delay, self.drop, self.noise_p, self.noise_v = seed, delay, drop, noise_p, noise_v
+        self.extrapolate = extrapolate
+
+    @property
+    def on(self) -> bool:
+        return any(t is not None for t in (self.delay, self.drop, self.noise_p, self.noise_v))
+
+
 _lib = None
 
 
@@ -213,6 +248,13 @@ def lib():
                                                    ctypes.c_void_p]
         L.srb_rollout_plant_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim), MV,
                                                SZ, AG, PL, ctypes.c_int, ctypes.c_void_p]
+        LN = ctypes.POINTER(Link)
+        L.srb_link_update_device.argtypes = [ctypes.c_void_p, ctypes.c_int, LN, _dp, _dp, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_void_p]
+        L.srb_link_update_lanes_device.argtypes = [ctypes.c_void_p, ctypes.c_int, LN, _dp, _dp, ctypes.c_int, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_void_p]
+        L.srb_rollout_link_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(Batch), ctypes.POINTER(Sim), MV,
+                                              SZ, AG, PL, LN, ctypes.c_int, ctypes.c_void_p]
         L.srb_last_kernel_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]
         L.srb_fit_bezier.argtypes = [_dp, _dp, _dp]
         L.srb_last_error.restype = ctypes.c_char_p

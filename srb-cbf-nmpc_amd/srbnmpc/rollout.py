@@ -38,6 +38,14 @@ pushes due.  results()["disturbance"] logs what was added.  The tables do not ch
 holds them whole; workload.plant_tables draws a set, workload.replicate_scenes tiles a scene for a Monte-Carlo over
 the draws.
 
+With link=srbnmpc.LinkModel(...) the neighbour link is degraded (srb_link, srb_link_update_device /
+srb_rollout_link_device; LIP mode only): every agent broadcasts its snapshot row and its shifted plan once per cycle, and
+what the others hold of it is late by delay cycles, lost with probability drop and noisy by noise_p / noise_v at the
+sender.  The solve and its selection read the perceived tables (Rollout.seen_state / seen_plan, readable after a step);
+the metrics, traj and every log keep the truth.  results()["link_age"] logs the age of what was held.  The draws key on
+(cycle, global row), so shards reproduce the team and the replicas of workload.replicate_scenes are a Monte-Carlo over
+the link's draws as they are over the plant's; workload.link_tables draws a set of tables.
+
 _RolloutBase is what this class and srb12.Rollout12 share: the checks of goal / phase / obstacles / obs_vel and of the
 obstacle and agent size tables, the moving table's clone and its restore, the srb_moving, srb_sizes and
 srb_agent_sizes of a call, the metrics call, the solve, metrics and log buffers, reset / advance / results /
@@ -48,8 +56,10 @@ from __future__ import annotations
 
 import ctypes
 
-from . import (AgentSizes, Batch, Moving, Plant, Sim, Sizes, _check, _check_agent_array, _check_size_array,
-               _check_vel_array, _dptr, _iptr, lib)
+from . import (AgentSizes, Batch, Link, LinkModel, Moving, Plant, Sim, Sizes, _check, _check_agent_array,
+               _check_size_array, _check_vel_array, _dptr, _iptr, lib)
+
+LINK_MAX_DELAY = 16                      # srb_link.max_delay's bound
 
 
 def _check_tensor(t, shape, name, dtype, device):
@@ -311,6 +321,13 @@ class Rollout(_RolloutBase):
               With any of these set advance(), step() and run() go through the plant entry points and results() gains
               disturbance [T][A][4] (dpx, dvx, dpy, dvy; row c - 1 is what the start of cycle c added).  Every shard
               holds the whole tables and draws by global row, so shards reproduce the team.
+    link      None or a srbnmpc.LinkModel: the degraded neighbour link (seed, delay int32 [n_all] 0 .. 16, drop [n_all]
+              0 .. 1, noise_p / noise_v [n_all] >= 0, extrapolate).  With any table set the solve and its selection read
+              seen_state [n_all][4] / seen_plan [n_all][N][2] (attributes, readable after a step) instead of the
+              gathered truth; the metrics and the logs keep the truth, and results() gains link_age [T][n_all] (cycles
+              since the held message of each row was sent).  The rollout owns the link's ring, held and seen buffers,
+              sized from max(delay), and reset() restarts the link.  Every shard holds the whole tables and computes
+              the whole perceived table itself.  Not with the solver's plan_selection option (refused by name)
     agent_offset, n_all   a shard of a larger team: this batch is rows agent_offset .. agent_offset + A of the
               n_all-row neighbour table that step(exchange) gathers (default: the whole team)
     All tensors are float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
@@ -319,7 +336,7 @@ class Rollout(_RolloutBase):
                  obstacles=None, agent_offset: int = 0, n_all: int | None = None, obs_vel=None, obs_horizon: bool = False,
                  obs_eps=None, obs_radius=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
                  agent_body=None, nbr_clearance: bool = False, plant_seed: int = 0, kick_v=None, kick_p=None,
-                 plant_hcom=None, pushes=None):
+                 plant_hcom=None, pushes=None, link=None):
         import torch
         super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps, obs_radius,
                          obs_clearance)
@@ -330,6 +347,7 @@ class Rollout(_RolloutBase):
             raise ValueError("agent_offset + A exceeds n_all")
         self._set_agent_sizes(agent_rad, agent_pad, agent_body, nbr_clearance, self.n_all)
         self._set_plant(plant_seed, kick_v, kick_p, plant_hcom, pushes)
+        self._set_link(link)
         self.sharded = self.agent_offset != 0 or self.n_all != A
         f8 = dict(dtype=torch.float64, device=self.device)
         self.alpha_buf = torch.zeros((A, 4), **f8)
@@ -377,8 +395,64 @@ class Rollout(_RolloutBase):
         return Plant(self.plant_seed, _dptr(self.kick_v), _dptr(self.kick_p), _dptr(self.plant_hcom),
                      0 if cyc is None else cyc.shape[0], _iptr(cyc), _iptr(agent), _dptr(dv), _dptr(self.dist_log))
 
+    # ------------------------------------------------------------------ the degraded link (srb_link)
+    def _set_link(self, link):
+        """The link's tables ([n_all] each, or None) after their checks, by name, and the link's own buffers."""
+        import torch
+        self.link = None
+        self.seen_state = self.seen_plan = self.age_log = None
+        if link is None:
+            return
+        if not isinstance(link, LinkModel):
+            raise ValueError("link must be a srbnmpc.LinkModel (or None)")
+        seed = int(link.seed)
+        if seed < 0 or seed >= 1 << 64:
+            raise ValueError("link: seed must be 0 .. 2^64 - 1 (the 64-bit Philox key)")
+        n = self.n_all
+        if link.delay is not None:
+            _check_tensor(link.delay, (n,), "link: delay", torch.int32, self.device)
+            if bool((link.delay < 0).any()) or bool((link.delay > LINK_MAX_DELAY).any()):
+                raise ValueError(f"link: delay must be 0 .. {LINK_MAX_DELAY} cycles")
+        for name, tab in (("drop", link.drop), ("noise_p", link.noise_p), ("noise_v", link.noise_v)):
+            if tab is None:
+                continue
+            _check_tensor(tab, (n,), f"link: {name}", torch.float64, self.device)
+            if not bool(tab.isfinite().all()):
+                raise ValueError(f"link: {name} must be finite")
+            if bool((tab < 0).any()):
+                raise ValueError(f"link: {name} must be >= 0")
+            if name == "drop" and bool((tab > 1).any()):
+                raise ValueError("link: drop must be <= 1 (a probability)")
+        if not link.on:
+            return                                   # nothing degrades: the plain rollout
+        self.link = link
+        self._link_seed, self._link_extrapolate = seed, int(bool(link.extrapolate))
+        D = self._link_delay = 0 if link.delay is None else int(link.delay.max())
+        N = self.solver.params.N
+        f8 = dict(dtype=torch.float64, device=self.device)
+        self._ring_state, self._held_state = torch.zeros((D + 1, n, 4), **f8), torch.zeros((n, 4), **f8)
+        self._held_cycle = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.seen_state = torch.zeros((n, 4), **f8)
+        self._ring_plan = self._held_plan = None
+        if self.plans:
+            self._ring_plan, self._held_plan = torch.zeros((D + 1, n, N, 2), **f8), torch.zeros((n, N, 2), **f8)
+            self.seen_plan = torch.zeros((n, N, 2), **f8)
+
+    def _link(self) -> Link:
+        ln = self.link
+        return Link(self._link_seed, _iptr(ln.delay), _dptr(ln.drop), _dptr(ln.noise_p), _dptr(ln.noise_v),
+                    self._link_delay, self._link_extrapolate, _dptr(self._ring_state), _dptr(self._ring_plan),
+                    _dptr(self._held_state), _dptr(self._held_plan), _iptr(self._held_cycle), _dptr(self.seen_state),
+                    _dptr(self.seen_plan), _iptr(self.age_log))
+
     def _reserve(self, cycles: int):
         super()._reserve(cycles)
+        if self.link is not None and (self.age_log is None or self.age_log.shape[0] < self.cap):
+            import torch
+            new = torch.zeros((self.cap, self.n_all), dtype=torch.int32, device=self.device)
+            if self.age_log is not None:
+                new[:self.age_log.shape[0]] = self.age_log
+            self.age_log = new
         if self.plant and (self.dist_log is None or self.dist_log.shape[0] < self.cap):
             import torch
             new = torch.zeros((self.cap, self.A, 4), dtype=torch.float64, device=self.device)
@@ -387,6 +461,8 @@ class Rollout(_RolloutBase):
             self.dist_log = new
 
     def reset(self, state):
+        """As _RolloutBase.reset; the plant and the link start over (the link's first update, at cycle 0, is the
+        complete exchange every row starts from: nothing of an earlier rollout is read)."""
         super().reset(state)
         self._advanced = -1
 
@@ -410,10 +486,13 @@ class Rollout(_RolloutBase):
 
     def results(self, stream=None):
         """As _RolloutBase.results; with a disturbed plant also disturbance [T][A][4]: row c - 1 is the (dpx, dvx, dpy,
-        dvy) that the start of cycle c added to the plant's base state."""
+        dvy) that the start of cycle c added to the plant's base state; with a link also link_age [T][n_all] int32: row c
+        is, per global row, how many cycles before c the message the team holds of it was sent."""
         out = super().results(stream)
         if self.plant:
             out["disturbance"] = self.dist_log[:self.c]
+        if self.link is not None:
+            out["link_age"] = self.age_log[:self.c]
         return out
 
     def _sim(self, nbr_state=None) -> Sim:
@@ -450,6 +529,13 @@ class Rollout(_RolloutBase):
         table = None
         if self.plans and self.c > 0:
             table = self.plan_table if plan_exchange is None else plan_exchange(self.plan_table)
+        if self.link is not None:                # the solve reads what is seen of the gathered truth
+            if table is not None:
+                _check_tensor(table, (self.n_all, s.params.N, 2), "the exchanged plan table", torch.float64, self.device)
+            _check(lib().srb_link_update_device(s._h, self.n_all, ctypes.byref(self._link()), _dptr(nbr), _dptr(table),
+                                                self.c, 0, s._stream(stream)))
+            nbr = self.seen_state
+            table = None if table is None else self.seen_plan
         s.solve_device(self.x0, self.ref, self.foot, self.obstacles, nbr, self.out, agent_offset=self.agent_offset,
                        stream=stream, alpha_buf=self.alpha_buf, nbr_plan=table, obs_vel=self.obs_vel,
                        obs_horizon=self.obs_horizon, obs_eps=self.obs_eps, obs_clearance=self.obs_clearance,
@@ -463,7 +549,16 @@ class Rollout(_RolloutBase):
                   0 if self.obstacles is None else self.obstacles.shape[0], self.A, 0,
                   None, _dptr(o["x"]), _dptr(o["obj"]), _iptr(o["status"]), _iptr(o["iters"]),
                   None, _dptr(o["alpha"]), None, 0, None, _dptr(o.get("plan")))
-        if self.plant:
+        if self.link is not None:
+            mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
+            sz = ctypes.byref(self._sizes()) if self.sized else None
+            ag = ctypes.byref(self._agent_sizes()) if self.agents else None
+            pl = ctypes.byref(self._plant()) if self.plant else None
+            _check(lib().srb_rollout_link_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), mv, sz, ag, pl,
+                                                 ctypes.byref(self._link()), T, s._stream(stream)))
+            if self.plant:
+                self._advanced = T
+        elif self.plant:
             mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
             sz = ctypes.byref(self._sizes()) if self.sized else None
             ag = ctypes.byref(self._agent_sizes()) if self.agents else None

@@ -199,11 +199,29 @@ def plant_tables(n_all: int, seed: int):
     return kick_v, kick_p, HCOM * g.uniform(0.85, 1.15, n_all)
 
 
+def link_tables(n_all: int, seed: int):
+    """(delay int32, drop, noise_p, noise_v), each [n_all], for a degraded neighbour link
+    (Rollout(link=srbnmpc.LinkModel(delay=..., drop=..., noise_p=..., noise_v=...))), deterministic per seed.  delay is
+    0, 1 or 2 cycles, each equally likely: a snapshot up to 2 * 4 Ts = 0.344 s old (one control cycle is 4 Ts = 0.172 s),
+    over which a neighbour at VREF = 0.27 m/s covers 0.093 m.  drop ~ U[0, 0.3]: up to three broadcasts in ten lost, a
+    busy wireless channel.  noise_p ~ U[0, 0.03] m: up to 3 cm on each position component, about two thirds of what
+    VREF covers in one cycle (0.27 * 0.172 = 0.046 m).  noise_v ~ U[0, 0.03] m/s: up to 11 % of VREF, which over the
+    horizon of ten grids (0.43 s) misplaces the constant-velocity guess by 0.013 m.  From a generator of their own
+    (600 + seed), so every other draw of this module is what it was."""
+    g = np.random.default_rng(600 + seed)
+    delay = g.integers(0, 3, n_all).astype(np.int32)
+    drop = g.uniform(0.0, 0.3, n_all)
+    noise_p = g.uniform(0.0, 0.03, n_all)
+    return delay, drop, noise_p, g.uniform(0.0, 0.03, n_all)
+
+
 def replicate_scenes(scenes: dict, copies: int):
     """A make_scenes (or make_scenes12) dict tiled `copies` times, scene-major: every array's rows repeated as a block, so rows
     [i * R, (i + 1) * R) of a table of R rows are replica i.  One scene (or set of scenes) then runs `copies` times in
     one launch with the same set_scenes(team, n_obs); under a disturbed plant each replica has draws of its own,
-    because its global rows differ: the Monte-Carlo over disturbances that Rollout.scene_results() reduces."""
+    because its global rows differ: the Monte-Carlo over disturbances that Rollout.scene_results() reduces.  The
+    same holds under a degraded link (Rollout(link=...)): its loss and noise draws key on the global row too, so the
+    replicas are a Monte-Carlo over the link's draws (tile the link's tables with np.tile likewise)."""
     copies = int(copies)
     if copies < 1:
         raise ValueError("replicate_scenes: copies >= 1")
