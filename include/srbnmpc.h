@@ -151,6 +151,25 @@ int srb_ctx_destroy(srb_ctx *ctx);
 int srb_ctx_set_waves(srb_ctx *ctx, int nw);
 int srb_ctx_waves(srb_ctx *ctx);
 
+/* The kernels the last launch of srb_solve_batch* / srb_solve_qp* ran, by name (read only; the strings are static
+ * storage): *solve the solve kernel (srb_nmpc_kernel_<NZL>_<TS>_<NW>_<NC>_<CC>_<KC>, its _mv_ form when a table of
+ * srb_moving / srb_sizes / srb_agent_sizes was given, its f32_ form under SRB_OPT_KKT_FP32_MU), *polish the polish
+ * kernel launched after it (srb_polish_kernel[_mv]_*), or "" where the polish ran fused into the solve kernel or
+ * not at all.  The record is written where the kernels are launched, not recomputed; "" before the first launch.
+ * The polish kernel is the solve instance's own only when SRB_OPT_POLISH_WAVES equals the solve's waves: at the
+ * default (0) a one-wave solve is polished by the two-wave instance of the same NZL.  Either pointer may be NULL. */
+int srb_ctx_last_kernels(srb_ctx *ctx, const char **solve, const char **polish);
+/* The shipped solve-kernel instances, host only (no device needed): entry i's dims (NZL, TS, NW, NC, CC, KC: the
+ * reduced-system bound, slot trips per thread, waves per agent and the compiled shape N, C, K_obs + K_nbr, 0 = read
+ * at run time) and its solve kernel's name; the fp32-factor entries follow the fp64 ones.  SRB_ERR_ARG past the end. */
+int srb_kernel_table(int i, int dims[6], const char **name);
+/* The dims of the fp64 instance a launch of problem p wanting `waves` (1, 2 or 4) waves per agent picks, with
+ * 160 KiB of LDS per workgroup; host only.  SRB_ERR_SIZE where no instance fits. */
+int srb_pick_kernel(const srb_params *p, int waves, int dims[6]);
+/* The parameter checks of srb_ctx_create alone, host only: SRB_OK, or the error srb_ctx_create would return
+ * (srb_last_error() says why). */
+int srb_check_params(const srb_params *p);
+
 /* Scenes: the batch is a set of independent teams of scene_agents agents, each with scene_obs obstacle rows.
  * Global agent g = agent_offset + a belongs to scene g / scene_agents.  Its static rows are selected from
  * obstacles[scene*scene_obs .. +scene_obs), its neighbour rows from nbr_state (and nbr_plan) rows
@@ -857,6 +876,15 @@ int srb12_last_kernel_ms(srb12_ctx *ctx, float *select_ms, float *solve_ms);
 /* 1 (default): HIP events around the selection and solve kernels (srb12_last_kernel_ms); 0: none */
 int srb12_ctx_set_timing(srb12_ctx *ctx, int on);
 int srb12_lds_bytes(const srb12_params *p);
+/* The solve kernel the last launch ran, by name (srb12_kernel_<TL>_<TO>_<NC>_<K1>, srb12_kernel_mv_* with a table):
+ * static storage, written at the launch; "" before the first.  srb12_kernel_table / srb12_pick_kernel: the shipped
+ * instances (dims TL, TO, NC, K1; SRB_ERR_ARG past the end) and the one that horizon N with K rows per grid picks
+ * (SRB_ERR_SIZE where none fits); host only, as srb_kernel_table / srb_pick_kernel. */
+int srb12_ctx_last_kernel(srb12_ctx *ctx, const char **solve);
+int srb12_kernel_table(int i, int dims[4], const char **name);
+int srb12_pick_kernel(int N, int K, int dims[4]);
+/* The parameter checks of srb12_ctx_create alone (the 160 KiB LDS bound among them), host only. */
+int srb12_check_params(const srb12_params *p);
 
 /* Scenes in the SRB-12 mode: srb_ctx_set_scenes / srb_ctx_scenes forwarded to the context's selection.  The rules,
  * the per-call refusals and their messages are those of the LIP mode (see srb_ctx_set_scenes); they are honoured by

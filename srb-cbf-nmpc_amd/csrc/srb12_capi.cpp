@@ -26,10 +26,13 @@ typedef void (*srb12_mv_fn)(Srb12KParams, int, const double *, const double *, c
                             const double *, const double *, const int *, double *, double *, double *, int *, int *,
                             const double *, double *, const double *, const double *, const double *, const double *,
                             int);
-struct srb12_inst { int tl, to, nc, k1; srb12_fn fn; srb12_mv_fn fn_mv; };
-#define ENTRY12(TL, TO, NC, K1) {TL, TO, NC, K1, srb12_kernel_##TL##_##TO##_##NC##_##K1, srb12_kernel_mv_##TL##_##TO##_##NC##_##K1},
+// (each kernel's name stands beside its pointer, both from the one pasted token: srb12_ctx_last_kernel reports it)
+struct srb12_inst { int tl, to, nc, k1; srb12_fn fn; const char *fn_name; srb12_mv_fn fn_mv; const char *fn_mv_name; };
+#define ENTRY12_FN_(f) f, #f
+#define ENTRY12(TL, TO, NC, K1) {TL, TO, NC, K1, ENTRY12_FN_(srb12_kernel_##TL##_##TO##_##NC##_##K1), ENTRY12_FN_(srb12_kernel_mv_##TL##_##TO##_##NC##_##K1)},
 static const srb12_inst g_inst12[] = {SRB12_INSTANCES(ENTRY12)};
 #undef ENTRY12
+#undef ENTRY12_FN_
 
 struct srb12_ctx {
     srb12_params p;
@@ -55,6 +58,7 @@ struct srb12_ctx {
     size_t cap_rad, cap_pad;
     int dbg_agent;                 // diagnostics: srb12_debug_trace
     double *dbg;
+    const char *last_solve_name;   // the solve kernel the last launch ran (srb12_ctx_last_kernel)
 };
 
 extern "C" void srb12_params_default(srb12_params *p, int N)
@@ -109,6 +113,35 @@ static int validate12(const srb12_params *p)
     if (!pick12(p->N, p->K_obs + p->K_nbr)) return srb_internal_fail(SRB_ERR_SIZE, "no SRB-12 kernel instance covers the row slots");
     if ((size_t)srb12_lds_doubles(p->N, p->K_obs + p->K_nbr) * sizeof(double) > 160 * 1024)
         return srb_internal_fail(SRB_ERR_SIZE, "per-agent LDS exceeds 160 KiB");
+    return SRB_OK;
+}
+
+// the parameter checks of srb12_ctx_create alone (no device needed)
+extern "C" int srb12_check_params(const srb12_params *p) { return validate12(p); }
+
+// the instance table and the pick, host only (no HIP call: usable without a device)
+extern "C" int srb12_kernel_table(int i, int dims[4], const char **name)
+{
+    if (i < 0 || i >= (int)(sizeof g_inst12 / sizeof g_inst12[0])) return srb_internal_fail(SRB_ERR_ARG, "srb12_kernel_table: index past the end");
+    const srb12_inst &in = g_inst12[i];
+    if (dims) { dims[0] = in.tl; dims[1] = in.to; dims[2] = in.nc; dims[3] = in.k1; }
+    if (name) *name = in.fn_name;
+    return SRB_OK;
+}
+
+extern "C" int srb12_pick_kernel(int N, int K, int dims[4])
+{
+    if (!dims || N < 1 || K < 0) return srb_internal_fail(SRB_ERR_ARG, "srb12_pick_kernel: bad argument");
+    const srb12_inst *in = pick12(N, K);
+    if (!in) return srb_internal_fail(SRB_ERR_SIZE, "no SRB-12 kernel instance covers the row slots");
+    dims[0] = in->tl; dims[1] = in->to; dims[2] = in->nc; dims[3] = in->k1;
+    return SRB_OK;
+}
+
+extern "C" int srb12_ctx_last_kernel(srb12_ctx *c, const char **solve)
+{
+    if (!c) return srb_internal_fail(SRB_ERR_ARG, "null ctx");
+    if (solve) *solve = c->last_solve_name ? c->last_solve_name : "";
     return SRB_OK;
 }
 
@@ -299,6 +332,7 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[1], s));
     // with any of the four tables the instance's table kernel (five more arguments); without, the launch as ever
+    c->last_solve_name = (vel || eps || rad || pad) ? in->fn_mv_name : in->fn_name;
     if (vel || eps || rad || pad)
         hipLaunchKernelGGL(in->fn_mv, dim3(n_agents), dim3(64), lds, s, k, n_agents, d->x0, d->xref, d->foot, d->contact,
                            d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters,

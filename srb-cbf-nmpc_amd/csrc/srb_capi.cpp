@@ -33,14 +33,23 @@ typedef void (*srb_polish_mv_fn)(SrbKParams, int, const double *, const double *
                                  const double *, double *, double *, int *, const double *, double *, const int *,
                                  const float *, int, const double *, double *, const double *, const double *,
                                  const double *, const double *, int);
-struct srb_instance { int nzl, ts, nw, nc, cc, kc; srb_kernel_fn fn; srb_polish_fn polish; srb_kernel_mv_fn fn_mv; srb_polish_mv_fn polish_mv; };
-// solve kernel (INFIX empty, or f32_) and polish kernel of one instance, then their moving-obstacle instances
-#define ENTRY_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC) NZL, TS, NW, NC, CC, KC, srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
-#define ENTRY_POLISH_(NZL, TS, NW, NC, CC, KC) srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
-#define ENTRY_MV_(INFIX, NZL, TS, NW, NC, CC, KC) srb_nmpc_kernel_mv_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
-#define ENTRY_POLISH_MV_(NZL, TS, NW, NC, CC, KC) srb_polish_kernel_mv_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC
+// (each kernel's name stands beside its pointer: srb_ctx_last_kernels reports the name of what was launched)
+struct srb_instance {
+    int nzl, ts, nw, nc, cc, kc;
+    srb_kernel_fn fn; const char *fn_name;
+    srb_polish_fn polish; const char *polish_name;
+    srb_kernel_mv_fn fn_mv; const char *fn_mv_name;
+    srb_polish_mv_fn polish_mv; const char *polish_mv_name;
+};
+// solve kernel (INFIX empty, or f32_) and polish kernel of one instance, then their moving-obstacle instances; the
+// pointer and its name as a string come from the one pasted token (ENTRY_FN_), so the two cannot drift apart
+#define ENTRY_FN_(f) f, #f
+#define ENTRY_NMPC_(INFIX, NZL, TS, NW, NC, CC, KC) NZL, TS, NW, NC, CC, KC, ENTRY_FN_(srb_nmpc_kernel_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC)
+#define ENTRY_POLISH_(NZL, TS, NW, NC, CC, KC) ENTRY_FN_(srb_polish_kernel_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC)
+#define ENTRY_MV_(INFIX, NZL, TS, NW, NC, CC, KC) ENTRY_FN_(srb_nmpc_kernel_mv_##INFIX##NZL##_##TS##_##NW##_##NC##_##CC##_##KC)
+#define ENTRY_POLISH_MV_(NZL, TS, NW, NC, CC, KC) ENTRY_FN_(srb_polish_kernel_mv_##NZL##_##TS##_##NW##_##NC##_##CC##_##KC)
 #define ENTRY_NMPC(...) {ENTRY_NMPC_(, __VA_ARGS__), ENTRY_POLISH_(__VA_ARGS__), ENTRY_MV_(, __VA_ARGS__), ENTRY_POLISH_MV_(__VA_ARGS__)},
-#define ENTRY_F32(...) {ENTRY_NMPC_(f32_, __VA_ARGS__), nullptr, ENTRY_MV_(f32_, __VA_ARGS__), nullptr},
+#define ENTRY_F32(...) {ENTRY_NMPC_(f32_, __VA_ARGS__), nullptr, "", ENTRY_MV_(f32_, __VA_ARGS__), nullptr, ""},
 static const srb_instance g_instances[] = {SRB_KERNEL_INSTANCES(ENTRY_NMPC)};
 // the fp32-factor variant of an instance (SRB_OPT_KKT_FP32_MU > 0), or null; these entries carry no polish kernel
 static const srb_instance g_instances_f32[] = {SRB_KF32_INSTANCES(ENTRY_F32)};
@@ -71,7 +80,7 @@ static int wanted_waves(int n_agents, int slots, int ctx_nw)
     return (slots > 5 * 64) ? 2 : 1;
 }
 
-static const srb_instance *pick_instance(const SrbKParams &k, int nw = 1)
+static const srb_instance *pick_instance(const SrbKParams &k, int nw = 1, size_t lds_max = g_lds_max)
 {
     const int S = srb_slots(k.N, k.C, k.K_obs + k.K_nbr);
     for (int pass = 0; pass < 3; pass++) {
@@ -80,7 +89,7 @@ static const srb_instance *pick_instance(const SrbKParams &k, int nw = 1)
             if (in.nw == want && in.nzl >= k.nz && 64 * in.nw * in.ts >= S &&
                 (in.nc == 0 || in.nc == k.N) && (in.cc == 0 || in.cc == k.C) &&
                 (in.kc == 0 || in.kc == k.K_obs + k.K_nbr) &&
-                (size_t)srb_lds_doubles(k, in.nzl, in.nw) * sizeof(double) <= g_lds_max)
+                (size_t)srb_lds_doubles(k, in.nzl, in.nw) * sizeof(double) <= lds_max)
                 return &in;
     }
     return nullptr;
@@ -126,6 +135,7 @@ struct srb_ctx {
     // agent, the selection-grid thresholds
     int polish, polish_waves, grid_min_rows, grid_min_rows_static, polish_fused;
     int last_polish;               // how the last launch polished: 0 no, 1 polish kernel, 2 fused
+    const char *last_solve_name, *last_polish_name;   // the kernels the last launch ran (srb_ctx_last_kernels)
     int timing;                    // 1: HIP events around the kernels (srb_last_kernel_ms); 0: none
     int selection;                 // SRB_OPT_SELECTION: 1 the solve launches the selection, 0 the caller did
     int last_f32;                  // the last launch ran an fp32-factor instance (SRB_OPT_LAST_KKT_FP32, read only)
@@ -264,6 +274,9 @@ static int validate(const srb_params *p)
     return SRB_OK;
 }
 
+// the parameter checks of srb_ctx_create alone (no device needed)
+extern "C" int srb_check_params(const srb_params *p) { return validate(p); }
+
 extern "C" int srb_lds_bytes(const srb_params *p)
 {
     SrbKParams k = make_kparams(p, p->use_nlp);
@@ -295,7 +308,7 @@ extern "C" int srb_ctx_create(const srb_params *p, int max_agents, int device, s
     for (auto &g : c->grid) g = srb_ctx::grid_buf{nullptr, nullptr, nullptr, nullptr, 0};
     c->grid_src = nullptr; c->grid_n = 0; c->grid_ver = 0;
     c->qp_init = 1; c->polish_ms = 0.0f;
-    c->polish = 1; c->polish_rho = SRB_POLISH_RHO; c->qp_warm_tol = SRB_QP_WARM_TOL; c->polish_waves = 0; c->polish_fused = 1; c->last_polish = 0; c->timing = 1; c->selection = 1;
+    c->polish = 1; c->polish_rho = SRB_POLISH_RHO; c->qp_warm_tol = SRB_QP_WARM_TOL; c->polish_waves = 0; c->polish_fused = 1; c->last_polish = 0; c->last_solve_name = ""; c->last_polish_name = ""; c->timing = 1; c->selection = 1;
     c->kkt32_mu = 0.0; c->kkt32_ref = 3;
     c->nbr_plan = nullptr; c->cap_plan = 0; c->plan_selection = 0;
     c->grid_min_rows = SRB_GRID_MIN_ROWS; c->grid_min_rows_static = SRB_GRID_MIN_ROWS_STATIC;
@@ -663,11 +676,14 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     // SRB_OPT_KKT_FP32_MU > 0: the instance's fp32-factor variant where one is compiled (else the fp64 one)
     srb_kernel_fn fn = in->fn;
     srb_kernel_mv_fn fn_mv = in->fn_mv;
+    const char *fn_name = in->fn_name, *fn_mv_name = in->fn_mv_name;
     c->last_f32 = 0;
     if (c->kkt32_mu > 0.0) {
         const srb_instance *f = f32_variant(in);
-        if (f) { fn = f->fn; fn_mv = f->fn_mv; c->last_f32 = 1; }
+        if (f) { fn = f->fn; fn_mv = f->fn_mv; fn_name = f->fn_name; fn_mv_name = f->fn_mv_name; c->last_f32 = 1; }
     }
+    c->last_solve_name = tabled ? fn_mv_name : fn_name;      // what the launch below runs (srb_ctx_last_kernels)
+    c->last_polish_name = "";
     // with any of the four tables the instance's table kernels (further arguments); without, the launches as ever
     if (tabled)
         hipLaunchKernelGGL(fn_mv, dim3(n_agents), dim3(64 * in->nw), lds, s, k, n_agents, d->x0, d->ref, d->foot, d->obstacles,
@@ -692,6 +708,7 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         const srb_instance *pin = pnw == in->nw ? in : pick_instance(k, pnw);
         if (!pin || pin->nzl != in->nzl) pin = in;
         const size_t plds = (size_t)srb_lds_doubles(k, pin->nzl, pin->nw) * sizeof(double);
+        c->last_polish_name = tabled ? pin->polish_mv_name : pin->polish_name;
         if (tabled)
             hipLaunchKernelGGL(pin->polish_mv, dim3(n_agents), dim3(64 * pin->nw), plds, s, k, n_agents, d->x0, d->ref, d->foot,
                                d->obstacles, d->nbr_state, d->x, d->obj, d->status, d->alpha ? d->alpha_buf : nullptr,
@@ -717,6 +734,36 @@ extern "C" int srb_ctx_set_waves(srb_ctx *c, int nw)
 }
 
 extern "C" int srb_ctx_waves(srb_ctx *c) { return c ? c->last_nw : 0; }
+
+extern "C" int srb_ctx_last_kernels(srb_ctx *c, const char **solve, const char **polish)
+{
+    if (!c) return fail(SRB_ERR_ARG, "null ctx");
+    if (solve) *solve = c->last_solve_name;
+    if (polish) *polish = c->last_polish_name;
+    return SRB_OK;
+}
+
+// the instance table and the pick, host only (no HIP call: usable without a device)
+extern "C" int srb_kernel_table(int i, int dims[6], const char **name)
+{
+    const int n64 = (int)(sizeof g_instances / sizeof g_instances[0]), n32 = (int)(sizeof g_instances_f32 / sizeof g_instances_f32[0]);
+    if (i < 0 || i >= n64 + n32) return fail(SRB_ERR_ARG, "srb_kernel_table: index past the end");
+    const srb_instance &in = i < n64 ? g_instances[i] : g_instances_f32[i - n64];
+    if (dims) { dims[0] = in.nzl; dims[1] = in.ts; dims[2] = in.nw; dims[3] = in.nc; dims[4] = in.cc; dims[5] = in.kc; }
+    if (name) *name = in.fn_name;
+    return SRB_OK;
+}
+
+extern "C" int srb_pick_kernel(const srb_params *p, int waves, int dims[6])
+{
+    if (!p || !dims) return fail(SRB_ERR_ARG, "srb_pick_kernel: null argument");
+    if (waves != 1 && waves != 2 && waves != 4) return fail(SRB_ERR_ARG, "waves per agent: 1, 2 or 4");
+    const SrbKParams k = make_kparams(p, p->use_nlp);
+    const srb_instance *in = pick_instance(k, waves, (size_t)160 * 1024);
+    if (!in) return fail(SRB_ERR_SIZE, "no kernel instance covers this problem");
+    dims[0] = in->nzl; dims[1] = in->ts; dims[2] = in->nw; dims[3] = in->nc; dims[4] = in->cc; dims[5] = in->kc;
+    return SRB_OK;
+}
 
 extern "C" int srb_ctx_set_scenes(srb_ctx *c, int scene_agents, int scene_obs)
 {

@@ -204,6 +204,11 @@ def lib():
         L.srb_sync.argtypes = [ctypes.c_void_p]
         L.srb_ctx_set_waves.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.srb_ctx_waves.argtypes = [ctypes.c_void_p]
+        _cpp = ctypes.POINTER(ctypes.c_char_p)
+        L.srb_ctx_last_kernels.argtypes = [ctypes.c_void_p, _cpp, _cpp]
+        L.srb_kernel_table.argtypes = [ctypes.c_int, _ip, _cpp]
+        L.srb_pick_kernel.argtypes = [ctypes.POINTER(Params), ctypes.c_int, _ip]
+        L.srb_check_params.argtypes = [ctypes.POINTER(Params)]
         L.srb_ctx_set_scenes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
         L.srb_ctx_scenes.argtypes = [ctypes.c_void_p, _ip, _ip]
         L.srb_ctx_set_qp_init.argtypes = [ctypes.c_void_p, ctypes.c_int]
@@ -274,6 +279,30 @@ def default_params(N: int = 4, C: int = 4, **overrides) -> Params:
 
 def lds_bytes(p: Params) -> int:
     return lib().srb_lds_bytes(ctypes.byref(p))
+
+
+def check_params(p: Params) -> bool:
+    """True where srb_ctx_create would accept p (srb_check_params; no device needed)."""
+    return lib().srb_check_params(ctypes.byref(p)) == 0
+
+
+def kernel_table():
+    """The shipped solve-kernel instances (srb_kernel_table; no device needed): a list of
+    ((NZL, TS, NW, NC, CC, KC), solve kernel name), the fp32-factor entries after the fp64 ones."""
+    out = []
+    while True:
+        d = (ctypes.c_int * 6)(); name = ctypes.c_char_p()
+        if lib().srb_kernel_table(len(out), d, ctypes.byref(name)) != 0:
+            return out
+        out.append((tuple(d), name.value.decode()))
+
+
+def pick_kernel(p: Params, waves: int):
+    """(NZL, TS, NW, NC, CC, KC) of the fp64 instance a launch of problem p wanting `waves` waves per agent picks
+    with 160 KiB of LDS (srb_pick_kernel; no device needed); raises where no instance fits."""
+    d = (ctypes.c_int * 6)()
+    _check(lib().srb_pick_kernel(ctypes.byref(p), int(waves), d))
+    return tuple(d)
 
 
 def _check(rc: int):
@@ -708,6 +737,13 @@ class BatchSolver(_SolverBase):
     def waves(self) -> int:
         """Waves per agent of the last launch."""
         return lib().srb_ctx_waves(self._h)
+
+    def last_kernels(self):
+        """(solve, polish): names of the kernels the last launch ran (srb_ctx_last_kernels); polish is "" where
+        the polish ran fused into the solve kernel or not at all."""
+        a = ctypes.c_char_p(); b = ctypes.c_char_p()
+        _check(lib().srb_ctx_last_kernels(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value.decode(), b.value.decode()
 
     def last_kernel_ms(self):
         a = ctypes.c_float(); b = ctypes.c_float()

@@ -202,6 +202,10 @@ def _lib():
     if not _bound:
         L.srb12_params_default.argtypes = [ctypes.POINTER(Params12), ctypes.c_int]
         L.srb12_lds_bytes.argtypes = [ctypes.POINTER(Params12)]
+        L.srb12_ctx_last_kernel.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p)]
+        L.srb12_kernel_table.argtypes = [ctypes.c_int, _ip, ctypes.POINTER(ctypes.c_char_p)]
+        L.srb12_pick_kernel.argtypes = [ctypes.c_int, ctypes.c_int, _ip]
+        L.srb12_check_params.argtypes = [ctypes.POINTER(Params12)]
         L.srb12_ctx_create.argtypes = [ctypes.POINTER(Params12), ctypes.c_int, ctypes.c_int,
                                        ctypes.POINTER(ctypes.c_void_p)]
         L.srb12_ctx_destroy.argtypes = [ctypes.c_void_p]
@@ -262,6 +266,30 @@ def default_params(N: int = 10, **overrides) -> Params12:
 
 def lds_bytes(p: Params12) -> int:
     return _lib().srb12_lds_bytes(ctypes.byref(p))
+
+
+def check_params(p: Params12) -> bool:
+    """True where srb12_ctx_create would accept p (srb12_check_params; no device needed)."""
+    return _lib().srb12_check_params(ctypes.byref(p)) == 0
+
+
+def kernel_table():
+    """The shipped SRB-12 solve-kernel instances (srb12_kernel_table; no device needed): a list of
+    ((TL, TO, NC, K1), solve kernel name)."""
+    out = []
+    while True:
+        d = (ctypes.c_int * 4)(); name = ctypes.c_char_p()
+        if _lib().srb12_kernel_table(len(out), d, ctypes.byref(name)) != 0:
+            return out
+        out.append((tuple(d), name.value.decode()))
+
+
+def pick_kernel(N: int, K: int):
+    """(TL, TO, NC, K1) of the instance that horizon N with K rows per grid picks (srb12_pick_kernel; no device
+    needed); raises where no instance fits."""
+    d = (ctypes.c_int * 4)()
+    _check(_lib().srb12_pick_kernel(int(N), int(K), d))
+    return tuple(d)
 
 
 def n_selected(p: Params12, n_obs: int, n_all: int, scenes=(0, 0)):
@@ -443,6 +471,12 @@ class Solver12(_SolverBase):
                                    obstacles_version=obstacles_version, obs_vel=obs_vel, obs_horizon=obs_horizon,
                                    obs_eps=obs_eps, obs_clearance=obs_clearance, agent_rad=agent_rad, agent_pad=agent_pad,
                                    nbr_clearance=nbr_clearance)
+
+    def last_kernel(self) -> str:
+        """Name of the solve kernel the last launch ran (srb12_ctx_last_kernel)."""
+        a = ctypes.c_char_p()
+        _check(_lib().srb12_ctx_last_kernel(self._h, ctypes.byref(a)))
+        return a.value.decode()
 
     def last_kernel_ms(self):
         a, b = ctypes.c_float(), ctypes.c_float()

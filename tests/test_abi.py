@@ -26,6 +26,21 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, n), n
 
 
+def test_kernel_report_entry_points_are_declared_and_exported():
+    """The read-only record of what a launch ran and the host-only instance tables (include/srbnmpc.h)."""
+    names = _declared_functions()
+    lib = ctypes.CDLL(srbnmpc.LIB_PATH)
+    for n in ("srb_ctx_last_kernels", "srb_kernel_table", "srb_pick_kernel", "srb_check_params", "srb12_ctx_last_kernel",
+              "srb12_kernel_table", "srb12_pick_kernel", "srb12_check_params"):
+        assert n in names and hasattr(lib, n), n
+    # without a context the record is refused, not guessed
+    a, b = ctypes.c_char_p(), ctypes.c_char_p()
+    lib.srb_ctx_last_kernels.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_char_p)]
+    lib.srb12_ctx_last_kernel.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p)]
+    assert lib.srb_ctx_last_kernels(None, ctypes.byref(a), ctypes.byref(b)) == -1
+    assert lib.srb12_ctx_last_kernel(None, ctypes.byref(a)) == -1
+
+
 def test_library_contains_gfx950_code_object():
     data = open(srbnmpc.LIB_PATH, "rb").read()
     assert b"gfx950" in data

@@ -38,7 +38,8 @@ def crowded(A, N, C, seed):
 SHAPES = {
     # name: N, C, K_obs, K_nbr, agents, waves asked for (0 automatic), waves expected
     # nz = 3, the smallest horizon the library accepts (srb_ctx_create: N >= 2; N = 1, nz = 2, is refused, see
-    # test_horizon_one_is_refused): the (k + 1 + jj) % NZE column order wraps after one column, nine padded steps
+    # test_horizon_one_is_refused): the (k + 1 + jj) % NZE column order wraps after one column; 45 slots fit one trip, so
+    # this is 8_1_1 (NZL 8), five padded steps -- no N = 2 shape reaches an NZL 12 instance
     "n2": (2, 2, 3, 8, 32, 1, 1),
     # nz = 4 in NZL 12 at run time, NZE = NZL: identity steps after the last real pivot
     "n3": (3, 2, 3, 8, 32, 1, 1),
@@ -50,11 +51,15 @@ SHAPES = {
     "default": (10, 2, 3, 8, 64, 1, 1),
     # 12_1_4_10_2_3, four waves: every wave factors redundantly; the failure branch stays uniform over the workgroup
     "w4": (10, 2, 3, 0, 8, 0, 4),
-    # 24_4_2, NZL 24: rows not replicated (the readlane form), the LEAN body, the folded obstacle range
+    # 24_4_2_20_2_11, NZL 24: rows not replicated (the readlane form), the LEAN body, the folded obstacle range
     "n20": (20, 2, 3, 8, 16, 2, 2),
     # crowded(16, 10, 2, seed=5): agents leave the loop through the FATAL / ACCEPTABLE breaks between a factor and its use
     "crowded": (10, 2, 3, 8, 16, 1, 1),
 }
+
+# the instance each case launches, asserted through BatchSolver.last_kernels() beside the waves
+INSTANCE = {"n2": "8_1_1_0_0_0", "n3": "12_3_1_0_0_0", "n11": "12_4_1_0_0_0", "c4": "16_4_1_0_0_0", "default": "12_4_1_10_2_11",
+            "w4": "12_1_4_10_2_3", "n20": "24_4_2_20_2_11", "crowded": "12_4_1_10_2_11"}
 
 _cache = {}
 
@@ -87,6 +92,7 @@ def gpu_solve(name, use_nlp=1, solves=1):
             out = s.solve(b["x0"], b["ref"], b["foot"], b["obstacles"], b["nbr_state"], qp_only=not use_nlp)
             outs.append({k: np.array(v, copy=True) for k, v in out.items() if v is not None})
         assert s.waves() == want
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + INSTANCE[name], ""), s.last_kernels()
     finally:
         s.close()
     return outs if solves > 1 else outs[0]

@@ -62,6 +62,13 @@ SHAPES = {
     "crowded": (10, 2, 3, 8, 16, 1, 1),
 }
 
+# the instance each case launches, asserted through BatchSolver.last_kernels() beside the waves
+INSTANCE = {"n3": "12_3_1_0_0_0", "n4": "12_3_1_0_0_0", "n11": "12_4_1_0_0_0", "k1": "12_3_1_0_0_0", "c4": "16_4_1_0_0_0",
+            "default": "12_4_1_10_2_11", "w4": "12_1_4_10_2_3", "n20": "24_4_2_20_2_11", "crowded": "12_4_1_10_2_11"}
+# the polish kernel of polish_fused = 0 at the default polish_waves: a one-wave solve is polished at two waves, by the
+# first two-wave instance of the same NZL
+POLISH_KERNEL = {"default": "srb_polish_kernel_12_2_2_0_0_0", "n3": "srb_polish_kernel_12_2_2_0_0_0"}
+
 _cache = {}
 
 
@@ -94,6 +101,8 @@ def gpu_solve(name, fused=1, use_nlp=1, solves=1):
             out = s.solve(b["x0"], b["ref"], b["foot"], b["obstacles"], b["nbr_state"], qp_only=not use_nlp)
             outs.append({k: np.array(v, copy=True) for k, v in out.items() if v is not None})
         assert s.waves() == want
+        polish = POLISH_KERNEL[name] if use_nlp and not fused else ""
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + INSTANCE[name], polish), s.last_kernels()
     finally:
         s.close()
     return outs if solves > 1 else outs[0]

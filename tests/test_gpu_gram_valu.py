@@ -40,6 +40,9 @@ SHAPES = {
     "default": (10, 2, 3, 8, 64),   # the compiled instance 12_4_1_10_2_11: the vector form
     "crowded": (10, 2, 3, 8, 16),   # crowded(16, 10, 2, seed=5): large active weights; exits between a Gram and its use
 }
+# the instance each case launches at one wave an agent, asserted through BatchSolver.last_kernels()
+INSTANCE = {"n2": "8_1_1_0_0_0", "n2k1": "8_1_1_0_0_0", "n3": "12_3_1_0_0_0", "n4": "12_3_1_0_0_0", "n11": "12_4_1_0_0_0",
+            "k1": "12_3_1_0_0_0", "default": "12_4_1_10_2_11", "crowded": "12_4_1_10_2_11"}
 # every agent of these ends QP OPTIMAL (warm tolerance: status 4) / NLP OPTIMAL on the oracle, so the rule's
 # "both OPTIMAL" set is the whole batch
 ALL_OPTIMAL = ["n2", "n2k1", "n3", "n11", "k1"]
@@ -82,7 +85,9 @@ def reference(name, use_nlp=1):
     return _cache[("r", name, use_nlp)]
 
 
-def gpu_solve(name, use_nlp=1, solves=1, options=None, want_option=None, **kw):
+def gpu_solve(name, use_nlp=1, solves=1, options=None, want_option=None, form="", polish="", **kw):
+    """form: the infix of the solve kernel expected ("", "f32_", "mv_"); polish: the polish kernel expected, as
+    "<prefix><instance>" ("" where the polish runs fused or not at all)."""
     N, C, Ko, Kn, A = SHAPES[name]
     b = batch(name)
     s = srbnmpc.BatchSolver(srbnmpc.default_params(N, C, K_obs=Ko, K_nbr=Kn, use_nlp=use_nlp), A)
@@ -95,6 +100,7 @@ def gpu_solve(name, use_nlp=1, solves=1, options=None, want_option=None, **kw):
             out = s.solve(b["x0"], b["ref"], b["foot"], b["obstacles"], b["nbr_state"], qp_only=not use_nlp, **kw)
             outs.append({k: np.array(v, copy=True) for k, v in out.items() if v is not None})
         assert s.waves() == 1                   # no case may silently run another instance family
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + form + INSTANCE[name], polish), s.last_kernels()
         for k, v in (want_option or {}).items():
             assert s.get_option(k) == v, (k, s.get_option(k))
     finally:
@@ -149,16 +155,20 @@ def test_qp_only_touches_no_obstacle_range(name):
     check_parity(SHAPES[name][0], gpu_solve(name, use_nlp=0), r, nlp=False)
 
 
-def test_polish_kernel_gram():
-    """polish_fused = 0: the polish runs in srb_polish_kernel_12_4_1_10_2_11, whose own Gram is the vector one."""
-    out = gpu_solve("default", options={"polish_fused": 0}, want_option={"last_polish": 1.0})
+@pytest.mark.parametrize("polish_waves,kernel", [(1, "srb_polish_kernel_12_4_1_10_2_11"), (0, "srb_polish_kernel_12_2_2_0_0_0")])
+def test_polish_kernel_gram(polish_waves, kernel):
+    """polish_fused = 0 with polish_waves = 1: the polish runs in srb_polish_kernel_12_4_1_10_2_11, whose own Gram is the
+    vector one.  At the default polish_waves = 0 a one-wave solve is polished at two waves, by the first two-wave
+    instance of the same NZL: srb_polish_kernel_12_2_2_0_0_0, whose Gram is the MFMA one."""
+    out = gpu_solve("default", options={"polish_fused": 0, "polish_waves": polish_waves}, want_option={"last_polish": 1.0},
+                    polish=kernel)
     check_parity(SHAPES["default"][0], out, reference("default"))
 
 
 def test_fp32_factor_form():
     """kkt_fp32_mu = 0.1: srb_nmpc_kernel_f32_12_4_1_10_2_11 (the reduced matrix inverted in fp32 above the threshold,
     every solve refined in fp64 against the fp64 H this Gram forms), by the same rule."""
-    out = gpu_solve("default", options={"kkt_fp32_mu": 0.1}, want_option={"last_kkt_fp32": 1.0})
+    out = gpu_solve("default", options={"kkt_fp32_mu": 0.1}, want_option={"last_kkt_fp32": 1.0}, form="f32_")
     check_parity(SHAPES["default"][0], out, reference("default"))
 
 
@@ -169,7 +179,7 @@ def test_moving_obstacle_form():
     N = SHAPES["default"][0]
     b, r = batch("default"), reference("default")
     vel = np.zeros((b["obstacles"].shape[0], 2))
-    out = gpu_solve("default", obs_vel=vel)
+    out = gpu_solve("default", form="mv_", obs_vel=vel)
     check_parity(N, out, r)
     Ko, Kn = SHAPES["default"][2:4]
     m = moving_oracle.solve(oracle.params(N, 2, K_obs=Ko, K_nbr=Kn), b, vel)

@@ -31,12 +31,13 @@ def xus(N, x):
     return np.concatenate([x[..., :6 * N], x[..., -1:]], -1)
 
 
-def check_vs_oracle(N, C, Ko, Kn, b, waves, want_waves):
+def check_vs_oracle(N, C, Ko, Kn, b, waves, want_waves, instance):
     s = srbnmpc.BatchSolver(srbnmpc.default_params(N, C, K_obs=Ko, K_nbr=Kn, use_nlp=1), b["x0"].shape[0])
     try:
         s.set_waves(waves)
         out = s.solve(b["x0"], b["ref"], b["foot"], b["obstacles"], b["nbr_state"])
         assert s.waves() == want_waves
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + instance, ""), s.last_kernels()
     finally:
         s.close()
     r = oracle.solve_batch(oracle.params(N, C, K_obs=Ko, K_nbr=Kn, use_nlp=1), b["x0"], b["ref"], b["foot"],
@@ -60,15 +61,20 @@ SHAPES = [
     (11, 2, 3, 8, 32, 1, 1),     # nz = 12 = NZL, run-time instance: even row length, a full row, no padding column
     (5, 4, 3, 8, 32, 1, 1),      # nz = 16: the NZL 16 instance and the C = 4 basis
     (10, 2, 3, 8, 64, 1, 1),     # the compiled default instance 12_4_1_10_2_11 itself
-    (10, 2, 3, 0, 8, 0, 4),      # four waves per agent (12_1_4): the staging must not cross a barrier
-    (20, 2, 3, 8, 16, 2, 2),     # 24_4_2: the folded obstacle path, LEAN
+    (10, 2, 3, 0, 8, 0, 4),      # four waves per agent (the compiled 12_1_4): the staging must not cross a barrier
+    (20, 2, 3, 8, 16, 2, 2),     # the compiled 24_4_2: the folded obstacle path, LEAN
 ]
+
+
+# the instance each shape launches, by (N, C, K_obs + K_nbr, waves): asserted through BatchSolver.last_kernels()
+INSTANCE = {(3, 2, 11, 1): "12_3_1_0_0_0", (11, 2, 11, 1): "12_4_1_0_0_0", (5, 4, 11, 1): "16_4_1_0_0_0",
+            (10, 2, 11, 1): "12_4_1_10_2_11", (10, 2, 3, 4): "12_1_4_10_2_3", (20, 2, 11, 2): "24_4_2_20_2_11"}
 
 
 @pytest.mark.parametrize("N,C,Ko,Kn,A,waves,want", SHAPES)
 def test_staged_loads_match_oracle(N, C, Ko, Kn, A, waves, want):
     b = workload.make_batch(A, N, C, seed=11 * N + C + Kn)
-    check_vs_oracle(N, C, Ko, Kn, b, waves, want)
+    check_vs_oracle(N, C, Ko, Kn, b, waves, want, INSTANCE[(N, C, Ko + Kn, want)])
 
 
 def test_crowded_arena_break_paths_match_oracle():
@@ -78,6 +84,6 @@ def test_crowded_arena_break_paths_match_oracle():
     present, asserted below.)"""
     N, C, Ko, Kn = 10, 2, 3, 8
     b = workload.make_batch(1024, N, C, seed=5, n_obs=int(round(80 * workload.arena_scale(1024) ** 2)))
-    out, r = check_vs_oracle(N, C, Ko, Kn, b, 0, 1)
+    out, r = check_vs_oracle(N, C, Ko, Kn, b, 0, 1, "12_4_1_10_2_11")
     assert (r["status"][:, 1] != 0).any(), "the workload must drive some agents off the OPTIMAL exit"
     np.testing.assert_array_equal(out["status"], r["status"])

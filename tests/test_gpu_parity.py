@@ -140,7 +140,10 @@ CONFIGS = [
 @pytest.mark.parametrize("N,C,Ko,Kn,A,nlp", CONFIGS)
 def test_gpu_matches_oracle(N, C, Ko, Kn, A, nlp):
     b = workload.make_batch(A, N, C, seed=7 * N + C + Kn)
-    out = solver(N, C, Ko, Kn, nlp).solve(b["x0"], b["ref"], b["foot"], b["obstacles"], b["nbr_state"])
+    s = solver(N, C, Ko, Kn, nlp)
+    out = s.solve(b["x0"], b["ref"], b["foot"], b["obstacles"], b["nbr_state"])
+    if A == 512:                                # the line of CONFIGS that names its instance: one wave, fused polish
+        assert s.waves() == 1 and s.last_kernels() == ("srb_nmpc_kernel_12_4_1_10_2_11", ""), s.last_kernels()
     r = oracle.solve_batch(oracle.params(N, C, K_obs=Ko, K_nbr=Kn, use_nlp=nlp), b["x0"], b["ref"], b["foot"],
                            b["obstacles"], b["nbr_state"], nthreads=8)
     bad = np.where((conv(out["status"]) != conv(r["status"])).any(1))[0]

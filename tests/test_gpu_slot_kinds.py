@@ -55,7 +55,9 @@ def reference(key, N, Kn, b, use_nlp=1):
     return _cache[key]
 
 
-def gpu_solve(N, Kn, b, waves, fused=1, use_nlp=1):
+def gpu_solve(N, Kn, b, waves, instance, fused=1, use_nlp=1, polish=""):
+    """instance: the solve kernel's instance, polish: the polish kernel's name ("": fused or none), both asserted
+    through BatchSolver.last_kernels()."""
     A = b["x0"].shape[0]
     s = srbnmpc.BatchSolver(srbnmpc.default_params(N, C, K_obs=KO, K_nbr=Kn, use_nlp=use_nlp), A)
     try:
@@ -63,6 +65,7 @@ def gpu_solve(N, Kn, b, waves, fused=1, use_nlp=1):
         s.set_option("polish_fused", fused)
         out = s.solve(b["x0"], b["ref"], b["foot"], b["obstacles"], b["nbr_state"], qp_only=not use_nlp)
         assert s.waves() == waves
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + instance, polish), s.last_kernels()
         out["last_polish"] = s.get_option("last_polish")
     finally:
         s.close()
@@ -100,11 +103,12 @@ def active_obstacle_rows(N, Kn, b, x):
 def test_compiled_one_wave_instance_with_active_obstacle_rows(fused):
     """16 agents, N = 10, K = 3 + 8 at one wave per agent (12_4_1_10_2_11) in a crowded arena: obstacle rows are
     active, so the single-row trips carry non-zero duals through the iteration, the carried dual sum and the polish
-    (fused = 1: at the end of the solve kernel; 0: srb_polish_kernel)."""
+    (fused = 1: at the end of the solve kernel; 0: a polish kernel -- at the default polish_waves the two-wave
+    srb_polish_kernel_12_2_2_0_0_0, not the instance's own)."""
     b = batch16()
     r = reference("c16", 10, 8, b)
     assert active_obstacle_rows(10, 8, b, r["x"]) >= 4          # the workload does what it is for
-    out = gpu_solve(10, 8, b, waves=1, fused=fused)
+    out = gpu_solve(10, 8, b, 1, "12_4_1_10_2_11", fused=fused, polish="" if fused else "srb_polish_kernel_12_2_2_0_0_0")
     assert out["last_polish"] == (2.0 if fused else 1.0)
     check_parity(10, out, r)
 
@@ -113,7 +117,7 @@ def test_qp_only_two_trip_path():
     """The same batch, QP only (use_nlp = 0): the stage that runs the VAR and the mixed trip alone."""
     b = batch16()
     r = reference("q16", 10, 8, b, use_nlp=0)
-    out = gpu_solve(10, 8, b, waves=1, use_nlp=0)
+    out = gpu_solve(10, 8, b, 1, "12_4_1_10_2_11", use_nlp=0)
     check_parity(10, out, r, nlp=False)
 
 
@@ -125,16 +129,19 @@ def test_small_tables_leave_sentinel_rows():
     b["obstacles"] = np.vstack([b["obstacles"][:2], [[np.nan, np.nan]]])
     b["nbr_state"] = np.vstack([b["nbr_state"], np.full((6, 4), np.nan)])
     r = reference("small", 10, 8, b)
-    out = gpu_solve(10, 8, b, waves=1)
+    out = gpu_solve(10, 8, b, 1, "12_4_1_10_2_11")
     assert out["sel"].shape == (3, 11) and ((out["sel"][:, KO:] == -1).sum(1) == 6).all(), out["sel"]
     check_parity(10, out, r)
 
 
 def test_config5_instance_two_waves():
-    """8 agents, N = 20 at two waves per agent: 24_4_2_20_2_11 (folded obstacle rows, recomputed reciprocals)."""
+    """8 agents, N = 20 at two waves per agent: 24_4_2_20_2_11 (folded obstacle rows, recomputed reciprocals).  The
+    neighbour table is padded with one NaN row, as in test_small_tables_leave_sentinel_rows: eight rows would clamp K_nbr
+    to 7 and launch the run-time 24_4_2_0_0_0 (which this test did until it asserted the kernel's name)."""
     b = crowded(8, 20, seed=3)
+    b["nbr_state"] = np.vstack([b["nbr_state"], np.full((1, 4), np.nan)])
     r = reference("n20", 20, 8, b)
-    out = gpu_solve(20, 8, b, waves=2)
+    out = gpu_solve(20, 8, b, 2, "24_4_2_20_2_11")
     check_parity(20, out, r)
 
 
@@ -142,5 +149,5 @@ def test_run_time_instance_control():
     """The 16 agents with K_nbr = 7: no compiled shape has K = 10, so the run-time 12_4_1_0_0_0 solves it."""
     b = batch16()
     r = reference("ctl", 10, 7, b)
-    out = gpu_solve(10, 7, b, waves=1)
+    out = gpu_solve(10, 7, b, 1, "12_4_1_0_0_0")
     check_parity(10, out, r)

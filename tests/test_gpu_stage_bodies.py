@@ -47,6 +47,8 @@ CASES = {
     "n12": (12, 2, 3, 8, 32, 1, 1, 41),       # 24_5_1_0_0_0: nz = 13 > 12, 275 slots > 256 (run time, NZL 24, one loop)
 }
 COMPILED = ["c11", "w4"]
+# the instance each case launches, asserted through BatchSolver.last_kernels() beside the waves
+INSTANCE = {"c11": "12_4_1_10_2_11", "w4": "12_1_4_10_2_3", "n11": "12_4_1_0_0_0", "n12": "24_5_1_0_0_0"}
 
 _cache = {}
 
@@ -107,6 +109,7 @@ def gpu_solve(name, use_nlp=1, qp_init=None, **options):
             s.set_option(k, v)
         out = solve(s, batch(name), qp_only=not use_nlp)
         assert s.waves() == CASES[name][6]
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + INSTANCE[name], ""), s.last_kernels()
     finally:
         s.close()
     return out
@@ -183,10 +186,13 @@ def test_polish_after_the_split_body():
     try:
         fu = solve(s, batch("c11"))
         assert s.get_option("last_polish") == 2.0
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + INSTANCE["c11"], "")
         s.set_option("polish_fused", 0)
         se = solve(s, batch("c11"))
         assert s.get_option("last_polish") == 1.0
         assert s.waves() == 1
+        # (polish_waves at its default: the one-wave solve is polished by the two-wave instance of the same NZL)
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + INSTANCE["c11"], "srb_polish_kernel_12_2_2_0_0_0")
     finally:
         s.close()
     print("max |x fused - x kernel|:", np.abs(fu["x"] - se["x"]).max())
@@ -203,6 +209,7 @@ def test_nothing_leaks_across_stages_or_solves(name):
         b1 = solve(s, batch(name, seed=32))
         a2 = solve(s, batch(name))
         assert s.waves() == CASES[name][6]
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + INSTANCE[name], "")
     finally:
         s.close()
     assert set(a1) == set(a2)
@@ -219,6 +226,7 @@ def test_a_shard_equals_its_rows_of_the_whole_batch():
         whole = solve(s, batch("c11"))
         part = solve(s, batch("c11"), rows=slice(16, 32), agent_offset=16)
         assert s.waves() == 1
+        assert s.last_kernels() == ("srb_nmpc_kernel_" + INSTANCE["c11"], "")
     finally:
         s.close()
     for k in OUT_KEYS:
@@ -239,6 +247,7 @@ def test_moving_obstacle_form():
     try:
         out = solve(s, b, obs_vel=vel)
         assert s.waves() == 1
+        assert s.last_kernels() == ("srb_nmpc_kernel_mv_" + INSTANCE["c11"], "")
     finally:
         s.close()
     e = np.abs(xus(N, out["x"]) - xus(N, r["x"])).max()
