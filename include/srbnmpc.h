@@ -687,8 +687,9 @@ int srb_rollout_plant_device(srb_ctx *ctx, int n_agents, const srb_batch *dev_io
  * or seen_plan; seen_state overlapping last_state.  With a context (the ranges need N): seen_plan overlapping
  * plan_table or batch.plan; SRB_OPT_PLAN_SELECTION = 1 with a link on (that selection reads the agent's own previous
  * plan from its row of the table, which would be a stale copy of what the agent knows exactly: not built); a shard in
- * the rollout driver, as ever.  The contents of the tables are NOT checked otherwise.  The SRB-12 mode and the
- * MPC_dist shims have no link.
+ * the rollout driver, as ever.  The contents of the tables are NOT checked otherwise.  That refusal of the plan selection
+ * is the LIP mode's and stays as it is; the SRB-12 mode has the link with the selection (srb12_rollout_link_device
+ * below), whose own plan comes from the truth.  The MPC_dist shims have no link.
  */
 typedef struct srb_link {
     int struct_size;            /* sizeof(srb_link) (ABI check) */
@@ -1190,6 +1191,47 @@ int srb12_sim_advance_plant_device(srb12_ctx *ctx, int n_agents, const srb12_sim
 int srb12_rollout_plant_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
                                const srb12_plans *plans, const srb_moving *mv, const srb_sizes *sz,
                                const srb_agent_sizes *ag, const srb12_plant *plant, int cycles, void *stream);
+
+/*
+ * Degraded neighbour link of the SRB-12 mode (DESIGN.md 3 "Degraded link", 9, 10.15): srb_link, reused as it is, as
+ * srb_moving, srb_sizes and srb_agent_sizes are.  SRB_ABI_VERSION and every existing struct stay.  The SRB-12 snapshot
+ * row last_state [A][4] and the plan tables [A][N][2] have the LIP layouts and one cycle is 4 grids in both modes, so
+ * the update is srb_link_update_kernel unchanged (N and Ts are this context's) and gives the bits of
+ * tests/link_oracle.py.  The solve and its selection read the PERCEIVED tables; metrics, traj and every log keep the
+ * truth.
+ *
+ * Unlike the LIP mode (whose refusal of SRB_OPT_PLAN_SELECTION = 1 under a link stays as it is), this mode has the
+ * horizon-aware selection under a link: srb_knn_plan_kernel / srb_knn_plan_scene_kernel take an optional table
+ * own_plan [n_agents][N][2], indexed by the local agent, and read the agent's own plan points there instead of row
+ * agent_offset + a of nbr_plan -- which under a link is a stale, noisy copy of what the agent knows exactly.  The keys
+ * of all other rows still come from nbr_state / nbr_plan, and row agent_offset + a stays left out of the scan.
+ *
+ * srb12_link_update_device: srb_link_update_device on an SRB-12 context, ordered by it.
+ * srb12_solve_batch_link_device: srb12_solve_batch_agents_device (plans, mv, sz, ag may be NULL) with own_plan (a device
+ * pointer).  own_plan == NULL is that entry point, bit for bit and launch for launch.  SRB_ERR_ARG, by name, before
+ * anything is launched: own_plan without plans->plan_selection = 1; own_plan overlapping plans->plan; own_plan together
+ * with srb_agent_sizes.clearance_selection = 1 (that selection reads its own plan from the table: not built).
+ * srb12_rollout_link_device extends srb12_rollout_plant_device (which is this call with link == NULL): after the metrics
+ * of every cycle the update runs on sim.last_state / plans->plan_table, the solve reads link->seen_state as its
+ * nbr_state and, from the second cycle with plans, link->seen_plan as its nbr_plan, and with plans->plan_selection
+ * plans->plan_table (the truth) as its own_plan; the shift after the solve writes the truth plan_table as ever.  Plain
+ * launches, no host synchronisation; scenes are honoured (rows of a perceived table are global rows).
+ *
+ * With link == NULL or all four tables NULL nothing new is launched and every output has its old bits.  The refusals
+ * are srb_rollout_link_device's, by name and before anything is launched -- a wrong struct_size; max_delay outside
+ * 0 .. 16; extrapolate not 0 / 1; a link that is on without ring_state, held_state, held_cycle or seen_state; with
+ * plans, without ring_plan, held_plan or seen_plan; seen_state overlapping last_state; seen_plan overlapping plan_table
+ * or plans->plan; a shard in the driver -- except the plan selection's, which is built here.
+ */
+int srb12_link_update_device(srb12_ctx *ctx, int n_all, const srb_link *link, const double *last_state,
+                             const double *plan_table, int cycle, int c_first, void *stream);
+int srb12_solve_batch_link_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_plans *plans,
+                                  const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
+                                  const double *own_plan, void *stream);
+int srb12_rollout_link_device(srb12_ctx *ctx, int n_agents, const srb12_batch *dev_io, const srb12_sim *sim,
+                              const srb12_plans *plans, const srb_moving *mv, const srb_sizes *sz,
+                              const srb_agent_sizes *ag, const srb12_plant *plant, const srb_link *link, int cycles,
+                              void *stream);
 
 const char *srb_last_error(void);
 

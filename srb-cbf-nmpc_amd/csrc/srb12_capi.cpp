@@ -274,11 +274,13 @@ static int check_moving12(const srb_moving *mv, const srb12_batch *b, bool rollo
 // pl: the plan members of this launch (NULL: none, the launch of srb12_solve_batch[_device] as ever); obs_vel /
 // obs_horizon: the members of srb_moving (null / 0: static obstacles, every launch as before); obs_eps / obs_clear:
 // those of srb_sizes (null / 0: eps_obs for every row, the selection as before); agent_rad / agent_pad / nbr_clear:
-// those of srb_agent_sizes (null / 0: eps_nbr and the levels as they are, the selection as before)
+// those of srb_agent_sizes (null / 0: eps_nbr and the levels as they are, the selection as before); own_plan
+// [n_agents][N][2]: with pl->plan_selection the agent's own plan of the horizon-aware selection (null: row
+// agent_offset + a of pl->nbr_plan, the launch as before)
 static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_t s, const srb12_plans *pl = nullptr,
                     const double *obs_vel = nullptr, int obs_horizon = 0, const double *obs_eps = nullptr,
                     int obs_clear = 0, const double *agent_rad = nullptr, const double *agent_pad = nullptr,
-                    int nbr_clear = 0)
+                    int nbr_clear = 0, const double *own_plan = nullptr)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -299,6 +301,9 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         if (srb_overlap(pl->plan, rows, pl->nbr_plan, (size_t)(d->n_all > 0 ? d->n_all : 0) * 2 * p->N) ||
             srb_overlap(pl->plan, rows, pl->plan_table, rows))
             return srb_internal_fail(SRB_ERR_ARG, "plan overlaps the nbr_plan table or plan_table (use two buffers)");
+        if (srb_overlap(pl->plan, rows, own_plan, rows))
+            return srb_internal_fail(SRB_ERR_ARG, "own_plan overlaps srb12_plans.plan (the selection reads one while the solve "
+                                                  "writes the other: use two buffers)");
     }
     if (int rc = check_scenes12(c, n_agents, d)) return rc;
     int Ko = 0, Kn = 0;
@@ -324,7 +329,8 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
         int rc = srb_internal_select(c->sel_ctx, n_agents, c->pos, d->obstacles, Ko > 0 ? d->n_obs : 0, d->nbr_state,
                                      Kn > 0 ? d->n_all : 0, d->agent_offset, Ko, Kn, d->obstacles_version, sel, s,
                                      pl && pl->plan_selection ? nbr_plan : nullptr, p->N, vel, vel ? obs_horizon : 0, p->Ts,
-                                     eps, eps ? obs_clear : 0, rad, rad ? nbr_clear : 0);
+                                     eps, eps ? obs_clear : 0, rad, rad ? nbr_clear : 0,
+                                     pl && pl->plan_selection && nbr_plan ? own_plan : nullptr);
         if (rc) return rc;
         // the selection context's own ordering event: its grid buffers are reallocated only after
         // this launch (grid_reserve waits on it)
@@ -353,9 +359,26 @@ static bool has_nbr12(const srb12_batch *b)
     return b && b->struct_size == (int)sizeof(srb12_batch) && b->nbr_state && b->n_all > 0;
 }
 
+// The argument errors of an own plan that need no context (srb12_solve_batch_link_device; the driver hands over
+// plan_table, which check_plans12 keeps apart from plan)
+static int check_own_plan12(const double *own_plan, const srb12_plans *pl, const srb_agent_sizes *ag)
+{
+    if (!own_plan) return SRB_OK;
+    if (!pl || pl->plan_selection != 1)
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_solve_batch_link_device: own_plan needs srb12_plans.plan_selection = 1 "
+                                              "(only the horizon-aware selection reads the agent's own plan)");
+    if (own_plan == pl->plan)
+        return srb_internal_fail(SRB_ERR_ARG, "own_plan overlaps srb12_plans.plan (the selection reads one while the solve "
+                                              "writes the other: use two buffers)");
+    if (ag && ag->agent_rad && ag->clearance_selection)
+        return srb_internal_fail(SRB_ERR_ARG, "own_plan with srb_agent_sizes.clearance_selection = 1: the clearance selection "
+                                              "reads the agent's own plan from its row of the table (not built)");
+    return SRB_OK;
+}
+
 static int solve_device12(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl, bool plans, void *stream,
                           const srb_moving *mv = nullptr, const srb_sizes *sz = nullptr,
-                          const srb_agent_sizes *ag = nullptr)
+                          const srb_agent_sizes *ag = nullptr, const double *own_plan = nullptr)
 {
     if (int rc = srb_check_struct(d, "srb12_batch")) return rc;
     if (int rc0 = check_moving12(mv, d, false)) return rc0;
@@ -363,15 +386,24 @@ static int solve_device12(srb12_ctx *c, int n_agents, const srb12_batch *d, cons
     if (int rc0 = srb_check_agent_sizes(ag, has_nbr12(d))) return rc0;
     if (plans)
         if (int rc = check_plans12(d, pl, false)) return rc;
+    if (int rc0 = check_own_plan12(own_plan, pl, ag)) return rc0;
     if (!c || !d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     int rc = c->order.order_after_last(s);
     if (!rc) rc = launch12(c, n_agents, d, s, pl, mv ? mv->obs_vel : nullptr, mv ? mv->horizon_selection : 0,
                            sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0, ag ? ag->agent_rad : nullptr,
-                           ag ? ag->agent_pad : nullptr, ag ? ag->clearance_selection : 0);
+                           ag ? ag->agent_pad : nullptr, ag ? ag->clearance_selection : 0, own_plan);
     if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
+}
+
+// pl, mv, sz and ag may be NULL, as in srb12_solve_batch_agents_device; own_plan NULL: that entry point itself
+extern "C" int srb12_solve_batch_link_device(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl,
+                                             const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
+                                             const double *own_plan, void *stream)
+{
+    return solve_device12(c, n_agents, d, pl, pl != nullptr, stream, mv, sz, ag, own_plan);
 }
 
 // pl, mv and sz may be NULL, as in srb12_solve_batch_sized_device; ag NULL (or without a table): that entry point itself.
@@ -380,7 +412,7 @@ extern "C" int srb12_solve_batch_agents_device(srb12_ctx *c, int n_agents, const
                                                const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
                                                void *stream)
 {
-    return solve_device12(c, n_agents, d, pl, pl != nullptr, stream, mv, sz, ag);
+    return srb12_solve_batch_link_device(c, n_agents, d, pl, mv, sz, ag, nullptr, stream);
 }
 
 extern "C" int srb12_solve_batch_sized_device(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl,
@@ -769,13 +801,62 @@ extern "C" int srb12_obstacles_advance_device(srb12_ctx *c, int n_obs, double *o
     return c->order.run(c->device, s, [&] { return srb_launch_obstacles_advance(n_obs, c->p.Ts, obstacles, obs_vel, s); });
 }
 
+// ---- degraded neighbour link (srb_link, srb_link.hip): the LIP mode's struct, checks and kernel.  The snapshot row
+// last_state [A][4] and the plan tables [A][N][2] have the LIP layouts and one cycle is 4 grids in both modes; N and
+// Ts are this context's (the selection context's are placeholders).  The argument errors that need the context:
+// the plan ranges (N).  plan: the solve's plan output (srb12_plans.plan) or null
+static int check_link_ctx12(const srb12_ctx *c, const srb_link *ln, int n_all, const double *plan_table, const double *plan)
+{
+    if (!srb_link_on(ln)) return SRB_OK;
+    if (plan_table && c->p.N < 2) return srb_internal_fail(SRB_ERR_ARG, "srb_link: a plan table needs N >= 2 (the plan shift)");
+    const size_t rows = (size_t)(n_all > 0 ? n_all : 0) * 2 * c->p.N;
+    if (srb_overlap(ln->seen_plan, rows, plan_table, rows))
+        return srb_internal_fail(SRB_ERR_ARG, "srb_link.seen_plan overlaps plan_table (the truth the next cycle's messages "
+                                              "carry: use two buffers)");
+    if (srb_overlap(ln->seen_plan, rows, plan, rows))
+        return srb_internal_fail(SRB_ERR_ARG, "srb_link.seen_plan overlaps srb12_plans.plan (the solve reads the table while "
+                                              "it writes its plans: use two buffers)");
+    return SRB_OK;
+}
+
+// one cycle's update (launch only: the caller orders the stream); ln is on
+static int launch_link12(srb12_ctx *c, int n_all, const srb_link *ln, const double *last_state, const double *plan_table,
+                         int cycle, int c_first, hipStream_t s)
+{
+    const int slot = (int)(((long long)cycle - c_first) % (ln->max_delay + 1));
+    int *age_row = ln->age_log ? ln->age_log + (size_t)(cycle - c_first) * (size_t)n_all : nullptr;
+    if (srb_launch_link_update(SRB_LINK_LANES, n_all, c->p.N, c->p.Ts, cycle, c_first, ln->max_delay, slot,
+                               ln->extrapolate, (unsigned)(ln->seed & 0xffffffffull), (unsigned)(ln->seed >> 32),
+                               ln->delay, ln->drop, ln->noise_p, ln->noise_v, last_state, plan_table, ln->ring_state,
+                               ln->ring_plan, ln->held_state, ln->held_plan, ln->held_cycle, ln->seen_state,
+                               ln->seen_plan, age_row, s))
+        return srb_internal_fail(SRB_ERR_ARG, "srb12_link_update_device: no such thread mapping");
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+extern "C" int srb12_link_update_device(srb12_ctx *c, int n_all, const srb_link *ln, const double *last_state,
+                                        const double *plan_table, int cycle, int c_first, void *stream)
+{
+    if (int rc = srb_check_link(ln, n_all, last_state, plan_table)) return rc;
+    if (cycle < c_first) return srb_internal_fail(SRB_ERR_ARG, "srb_link: cycle precedes c_first");
+    if (!c) return srb_internal_fail(SRB_ERR_ARG, "null argument");
+    if (n_all < 0) return srb_internal_fail(SRB_ERR_ARG, "srb_link: negative n_all");
+    if (int rc = check_link_ctx12(c, ln, n_all, plan_table, nullptr)) return rc;
+    if (!srb_link_on(ln) || n_all == 0) return SRB_OK;
+    if (!last_state) return srb_internal_fail(SRB_ERR_ARG, "srb_link: last_state missing");
+    hipStream_t s = (hipStream_t)stream;
+    return c->order.run(c->device, s, [&] { return launch_link12(c, n_all, ln, last_state, plan_table, cycle, c_first, s); });
+}
+
 // pl: the plans fed forward (srb12_rollout_plans_device), or NULL (srb12_rollout_device: today's launches); mv: the
 // moving obstacles (srb12_rollout_moving_device), or NULL; sz: the obstacle sizes (srb12_rollout_sized_device), or
 // NULL; ag: the agent sizes (srb12_rollout_agents_device), or NULL; pt: the disturbed plant
-// (srb12_rollout_plant_device), or NULL -- the tables do not change over a rollout: the same pointers serve every cycle
+// (srb12_rollout_plant_device), or NULL; ln: the degraded link (srb12_rollout_link_device), or NULL -- the tables do
+// not change over a rollout: the same pointers serve every cycle
 static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, const srb12_plans *pl,
                      bool plans, int cycles, void *stream, const srb_moving *mv = nullptr, const srb_sizes *sz = nullptr,
-                     const srb_agent_sizes *ag = nullptr, const srb12_plant *pt = nullptr)
+                     const srb_agent_sizes *ag = nullptr, const srb12_plant *pt = nullptr, const srb_link *ln = nullptr)
 {
     if (int rc = srb_check_struct(b, "srb12_batch")) return rc;
     if (int rc0 = check_moving12(mv, b, true)) return rc0;
@@ -787,6 +868,8 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
         if (int rc = srb_check_struct(pl, "srb12_plans")) return rc;
     // (the layout and null checks of check_sim12 only: the driver's first cycle is c_first itself)
     if (int rc = check_sim12(d, d && d->struct_size == (int)sizeof(srb12_sim) ? d->c_first : 0, false)) return rc;
+    // (the truth plan table of the link is the plans' plan_table, whose struct_size was checked above)
+    if (int rc0 = srb_check_link(ln, n_agents, d->last_state, plans && pl ? pl->plan_table : nullptr)) return rc0;
     if (!b) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (!d->goal) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.goal missing");
     if (plans)
@@ -799,6 +882,10 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
         return srb_internal_fail(SRB_ERR_ARG, "srb12_rollout_device rolls out a whole team on one GPU: a sharded batch "
                                               "(agent_offset != 0 or n_all != n_agents) needs the neighbour exchange "
                                               "between advance and metrics");
+    if (int rc0 = check_link_ctx12(c, ln, n_agents, pl ? pl->plan_table : nullptr, pl ? pl->plan : nullptr)) return rc0;
+    if (srb_link_on(ln) && pl && pl->plan_selection)      // (the selection's own plan will be the truth plan_table)
+        if (int rc0 = check_own_plan12(pl->plan_table, pl, ag)) return rc0;
+    if (!srb_link_on(ln)) ln = nullptr;
     int sa = 0, so = 0;
     if (int rc = srb_ctx_scenes(c->sel_ctx, &sa, &so)) return rc;
     if (sa > 0) {
@@ -817,6 +904,7 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
     srb12_batch bat = *b;
     bat.x0 = d->x0; bat.xref = d->xref; bat.foot = d->foot; bat.contact = d->contact;
     bat.nbr_state = d->last_state; bat.n_all = n_agents; bat.agent_offset = 0;
+    if (ln) bat.nbr_state = ln->seen_state;               // the solve reads what is seen, the metrics the truth
     if (!b->x || !b->obj || !b->status || !b->iters)
         return srb_internal_fail(SRB_ERR_ARG, "srb12_batch: missing buffer (x, obj, status, iters)");
     hipStream_t s = (hipStream_t)stream;
@@ -839,15 +927,18 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
         if (rc || i == cycles) break;
         if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
         if (!rc) rc = launch_metrics12(c, n_agents, &sim, cyc, s, radius, body, collide);
+        if (!rc && ln) rc = launch_link12(c, n_agents, ln, d->last_state, pl ? pl->plan_table : nullptr, cyc, d->c_first, s);
         if (!pl) {
             if (!rc) rc = launch12(c, n_agents, &bat, s, nullptr, vel, hsel, eps, csel, rad, pad, nsel);
             continue;
         }
         // the first solve against the caller's table (or none), every later one against last cycle's shifted plans
+        // (under a link the perceived table; the selection then takes the agent's own plan from the truth)
         srb12_plans cur = *pl;
-        if (i > 0) cur.nbr_plan = pl->plan_table;
+        if (i > 0) cur.nbr_plan = ln ? ln->seen_plan : pl->plan_table;
         if (!cur.nbr_plan) cur.plan_selection = 0;
-        if (!rc) rc = launch12(c, n_agents, &bat, s, &cur, vel, hsel, eps, csel, rad, pad, nsel);
+        const double *own = (ln && i > 0 && cur.plan_selection) ? pl->plan_table : nullptr;
+        if (!rc) rc = launch12(c, n_agents, &bat, s, &cur, vel, hsel, eps, csel, rad, pad, nsel, own);
         if (!rc) rc = launch_shift12(c, n_agents, pl->plan, SRB12_SIM_NDOMAIN, pl->plan_table, s);
     }
     const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier cycles run
@@ -894,7 +985,17 @@ extern "C" int srb12_rollout_plant_device(srb12_ctx *c, int n_agents, const srb1
                                           const srb12_plans *pl, const srb_moving *mv, const srb_sizes *sz,
                                           const srb_agent_sizes *ag, const srb12_plant *pt, int cycles, void *stream)
 {
-    return rollout12(c, n_agents, b, d, pl, pl != nullptr, cycles, stream, mv, sz, ag, pt);
+    return srb12_rollout_link_device(c, n_agents, b, d, pl, mv, sz, ag, pt, nullptr, cycles, stream);
+}
+
+// pl, mv, sz, ag and pt may be NULL, as in srb12_rollout_plant_device; ln NULL (or with no table set): that entry point
+// itself
+extern "C" int srb12_rollout_link_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d,
+                                         const srb12_plans *pl, const srb_moving *mv, const srb_sizes *sz,
+                                         const srb_agent_sizes *ag, const srb12_plant *pt, const srb_link *ln, int cycles,
+                                         void *stream)
+{
+    return rollout12(c, n_agents, b, d, pl, pl != nullptr, cycles, stream, mv, sz, ag, pt, ln);
 }
 
 // diagnostics (not in the public header): agent >= 0 records a per-iteration trace on the next

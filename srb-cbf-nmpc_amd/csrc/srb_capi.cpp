@@ -411,7 +411,7 @@ static int check_scenes(const srb_ctx *c, int n_agents, int n_obs, bool has_nbr,
 static int launch_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                          const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
                          int obstacles_version, int *sel, hipStream_t s, int sel_stride = -1,
-                         const double *nbr_plan = nullptr, int N = 0)
+                         const double *nbr_plan = nullptr, int N = 0, const double *own_plan = nullptr)
 {
     if (sel_stride < 0) sel_stride = K_obs + K_nbr;
     // scenes: every agent's scene sub-tables brute force, no grid built or consulted (the cached static grid of
@@ -426,13 +426,15 @@ static int launch_select(srb_ctx *c, int n_agents, const double *x0, const doubl
         }
         if (by_plan) {
             hipLaunchKernelGGL(srb_knn_plan_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents, x0,
-                               nbr_state, nbr_plan, N, agent_offset, c->scene_agents, K_nbr, sel + K_obs, sel_stride);
+                               nbr_state, nbr_plan, N, agent_offset, c->scene_agents, K_nbr, sel + K_obs, sel_stride,
+                               own_plan);
             HIPCHK(hipGetLastError());
         }
         return SRB_OK;
     }
     // SRB_OPT_PLAN_SELECTION (the caller hands over nbr_plan only then): the neighbour columns by closest predicted
-    // approach (srb_knn_plan_kernel, brute force, no grid); the static columns from srb_knn_kernel as ever
+    // approach (srb_knn_plan_kernel, brute force, no grid); the static columns from srb_knn_kernel as ever.
+    // own_plan (the SRB-12 mode under a srb_link; else null): the agent's own plan rows, not row g of the table
     if (nbr_plan && K_nbr > 0) {
         if (K_obs > 0) {
             int rc = launch_select(c, n_agents, x0, obstacles, n_obs, nullptr, 0, agent_offset, K_obs, 0, obstacles_version,
@@ -440,7 +442,7 @@ static int launch_select(srb_ctx *c, int n_agents, const double *x0, const doubl
             if (rc) return rc;
         }
         hipLaunchKernelGGL(srb_knn_plan_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents, x0, nbr_state, nbr_plan,
-                           n_all, N, agent_offset, K_nbr, sel + K_obs, sel_stride);
+                           n_all, N, agent_offset, K_nbr, sel + K_obs, sel_stride, own_plan);
         HIPCHK(hipGetLastError());
         return SRB_OK;
     }
@@ -487,12 +489,13 @@ static int launch_nbr_clear(srb_ctx *c, int n_agents, const double *x0, const do
 // obs_clear (srb_sizes.clearance_selection): the static columns by clearance to the level set -- over the horizon
 // when obs_vel and obs_horizon say so, else now -- and the neighbour columns as without.  agent_rad with nbr_clear
 // (srb_agent_sizes.clearance_selection): the neighbour columns by clearance -- over the horizon when the caller hands
-// over nbr_plan, else now -- and the static columns as without
+// over nbr_plan, else now -- and the static columns as without.  own_plan with nbr_plan (srb12_solve_batch_link_device):
+// the plan selection takes the agent's own plan from own_plan[agent]; the caller refuses it together with nbr_clear
 int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
                         int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan, int N,
                         const double *obs_vel, int obs_horizon, double Ts, const double *obs_eps, int obs_clear,
-                        const double *agent_rad, int nbr_clear)
+                        const double *agent_rad, int nbr_clear, const double *own_plan)
 {
     const bool clear = obs_eps && obs_clear, horizon = obs_vel && obs_horizon, nclear = agent_rad && nbr_clear;
     if (clear || horizon || nclear) {
@@ -500,7 +503,7 @@ int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double
             const int rc = nclear ? launch_nbr_clear(c, n_agents, x0, nbr_state, nbr_plan, agent_rad, n_all, agent_offset,
                                                      K_nbr, sel + K_obs, K_obs + K_nbr, s, N)
                                   : launch_select(c, n_agents, x0, obstacles, 0, nbr_state, n_all, agent_offset, 0, K_nbr,
-                                                  0, sel + K_obs, s, K_obs + K_nbr, nbr_plan, N);
+                                                  0, sel + K_obs, s, K_obs + K_nbr, nbr_plan, N, own_plan);
             if (rc) return rc;
         }
         if (K_obs > 0 && clear)
@@ -515,7 +518,7 @@ int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double
         return SRB_OK;
     }
     return launch_select(c, n_agents, x0, obstacles, n_obs, nbr_state, n_all, agent_offset, K_obs, K_nbr,
-                         obstacles_version, sel, s, -1, nbr_plan, N);
+                         obstacles_version, sel, s, -1, nbr_plan, N, own_plan);
 }
 
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s) { return c->order.mark_done(s); }
@@ -1219,30 +1222,12 @@ extern "C" int srb_sim_metrics_device(srb_ctx *c, int n_agents, const srb_sim *d
     return srb_sim_metrics_sized_device(c, n_agents, d, nullptr, cycle, stream);
 }
 
-// ---- degraded neighbour link (srb_link.hip).  The struct degrades the link at all (else every entry point is the one
-// it extends and nothing is launched; age_log alone is not written)
-static bool link_on(const srb_link *ln) { return ln && (ln->delay || ln->drop || ln->noise_p || ln->noise_v); }
-
-// The argument errors of srb_link that need no context, before anything is launched.  last_state, plan_table: the
-// truth tables of the call ([n_all][4]; [n_all][N][2] or null)
-#define SRB_LINK_MAX_DELAY 16
+// ---- degraded neighbour link (srb_link.hip).  What needs no context -- "the struct degrades the link at all" and the
+// argument errors before anything is launched -- is srb_host.h's, shared with the SRB-12 mode
+static bool link_on(const srb_link *ln) { return srb_link_on(ln); }
 static int check_link(const srb_link *ln, int n_all, const double *last_state, const double *plan_table)
 {
-    if (int rc = srb_check_struct(ln, "srb_link")) return rc;
-    if (!ln) return SRB_OK;
-    if (ln->max_delay < 0 || ln->max_delay > SRB_LINK_MAX_DELAY)
-        return fail(SRB_ERR_ARG, "srb_link.max_delay: 0 .. 16 (the ring holds max_delay + 1 cycles)");
-    if (ln->extrapolate != 0 && ln->extrapolate != 1)
-        return fail(SRB_ERR_ARG, "srb_link.extrapolate: 0 (the held message as it is) or 1 (dead-reckoned by its age)");
-    if (!link_on(ln)) return SRB_OK;
-    if (!ln->ring_state || !ln->held_state || !ln->held_cycle || !ln->seen_state)
-        return fail(SRB_ERR_ARG, "srb_link: a link that is on needs ring_state, held_state, held_cycle and seen_state");
-    if (plan_table && (!ln->ring_plan || !ln->held_plan || !ln->seen_plan))
-        return fail(SRB_ERR_ARG, "srb_link: a plan table needs ring_plan, held_plan and seen_plan");
-    if (n_all > 0 && srb_overlap(ln->seen_state, (size_t)n_all * 4, last_state, (size_t)n_all * 4))
-        return fail(SRB_ERR_ARG, "srb_link.seen_state overlaps last_state (the metrics read the truth while the solve "
-                                 "reads what is seen: use two buffers)");
-    return SRB_OK;
+    return srb_check_link(ln, n_all, last_state, plan_table);
 }
 
 // ... and those that need the context: the plan ranges (N) and the selection that reads the agent's own table row.

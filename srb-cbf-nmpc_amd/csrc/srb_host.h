@@ -13,14 +13,16 @@
 // the horizon-aware selection of SRB_OPT_PLAN_SELECTION, whatever that option of the context says; obs_vel
 // [n_obs][2] with obs_horizon != 0: the static columns by srb_moving.horizon_selection over the grid (N, Ts);
 // obs_eps [n_obs] with obs_clear != 0: the static columns by srb_sizes.clearance_selection; agent_rad [n_all] with
-// nbr_clear != 0: the neighbour columns by srb_agent_sizes.clearance_selection, over the horizon with nbr_plan)
+// nbr_clear != 0: the neighbour columns by srb_agent_sizes.clearance_selection, over the horizon with nbr_plan;
+// own_plan [n_agents][N][2] with nbr_plan: the horizon-aware selection reads the agent's own plan there, not in row
+// g of the table)
 int srb_internal_fail(int code, const char *msg);
 int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
                         int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan = nullptr, int N = 0,
                         const double *obs_vel = nullptr, int obs_horizon = 0, double Ts = 0.0,
                         const double *obs_eps = nullptr, int obs_clear = 0, const double *agent_rad = nullptr,
-                        int nbr_clear = 0);
+                        int nbr_clear = 0, const double *own_plan = nullptr);
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s);
 // ... and its scene partition (srb_ctx_set_scenes): the per-call refusals, the "up to K nearest" clamp, and the
 // metrics launch (srb_sim_metrics_kernel, or with scenes srb_sim_scene_metrics_kernel) on d->state rows
@@ -163,6 +165,32 @@ static inline int srb_check_agent_sizes(const srb_agent_sizes *ag, bool has_nbr)
     if (ag->collide_cycle && !ag->agent_body)
         return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes.collide_cycle needs agent_body (a collision is two bodies "
                                               "overlapping)");
+    return SRB_OK;
+}
+
+// ---- degraded neighbour link (srb_link; srb_link.hip), both modes.  The struct degrades the link at all (else every
+// entry point is the one it extends and nothing is launched; age_log alone is not written)
+static inline bool srb_link_on(const srb_link *ln) { return ln && (ln->delay || ln->drop || ln->noise_p || ln->noise_v); }
+
+// The argument errors of srb_link that need no context, before anything is launched.  last_state, plan_table: the
+// truth tables of the call ([n_all][4]; [n_all][N][2] or null)
+#define SRB_LINK_MAX_DELAY 16
+static inline int srb_check_link(const srb_link *ln, int n_all, const double *last_state, const double *plan_table)
+{
+    if (int rc = srb_check_struct(ln, "srb_link")) return rc;
+    if (!ln) return SRB_OK;
+    if (ln->max_delay < 0 || ln->max_delay > SRB_LINK_MAX_DELAY)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_link.max_delay: 0 .. 16 (the ring holds max_delay + 1 cycles)");
+    if (ln->extrapolate != 0 && ln->extrapolate != 1)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_link.extrapolate: 0 (the held message as it is) or 1 (dead-reckoned by its age)");
+    if (!srb_link_on(ln)) return SRB_OK;
+    if (!ln->ring_state || !ln->held_state || !ln->held_cycle || !ln->seen_state)
+        return srb_internal_fail(SRB_ERR_ARG, "srb_link: a link that is on needs ring_state, held_state, held_cycle and seen_state");
+    if (plan_table && (!ln->ring_plan || !ln->held_plan || !ln->seen_plan))
+        return srb_internal_fail(SRB_ERR_ARG, "srb_link: a plan table needs ring_plan, held_plan and seen_plan");
+    if (n_all > 0 && srb_overlap(ln->seen_state, (size_t)n_all * 4, last_state, (size_t)n_all * 4))
+        return srb_internal_fail(SRB_ERR_ARG, "srb_link.seen_state overlaps last_state (the metrics read the truth while the "
+                                              "solve reads what is seen: use two buffers)");
     return SRB_OK;
 }
 

@@ -74,7 +74,7 @@ extern "C" __global__ void srb_knn_kernel(int n_agents, const double *x0g, const
                                           const int *inb);
 extern "C" __global__ void srb_knn_plan_kernel(int n_agents, const double *x0g, const double *nbr_state,
                                                const double *nbr_plan, int n_all, int N, int agent_offset, int K_nbr,
-                                               int *sel_out, int sel_stride);
+                                               int *sel_out, int sel_stride, const double *own_plan);
 extern "C" __global__ void srb_grid_build_kernel(const double *tab0, int stride0, int n0, SrbGrid *g0, int *off0,
                                                  double2 *spos0, int *sidx0, const double *tab1, int stride1, int n1,
                                                  SrbGrid *g1, int *off1, double2 *spos1, int *sidx1);
@@ -133,7 +133,7 @@ extern "C" __global__ void srb_knn_scene_kernel(int n_agents, const double *x0g,
                                                 int scene_obs, int K_obs, int K_nbr, int *sel_out, int sel_stride);
 extern "C" __global__ void srb_knn_plan_scene_kernel(int n_agents, const double *x0g, const double *nbr_state,
                                                      const double *nbr_plan, int N, int agent_offset, int scene_agents,
-                                                     int K_nbr, int *sel_out, int sel_stride);
+                                                     int K_nbr, int *sel_out, int sel_stride, const double *own_plan);
 extern "C" __global__ void srb_sim_scene_metrics_kernel(int n_agents, int c, int c_first, const double *state,
                                                         const double *obstacles, int obs_rows, const double *nbr_state,
                                                         int nbr_rows, int scene_agents, int agent_offset, int scene0,

@@ -86,11 +86,12 @@ extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_WAVES) srb_knn_scene_k
 }
 
 // The horizon-aware key of srb_knn_plan_kernel over the scene's rows only: own plan nbr_plan[g], rows nbr_plan[i]
-// for i in the scene; global indices to the neighbour columns.
+// for i in the scene; global indices to the neighbour columns.  own_plan [n_agents][N][2] (null: none), indexed by
+// the local agent, replaces nbr_plan[g] as the agent's own plan, as in srb_knn_plan_kernel.
 extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_PLAN_WAVES) srb_knn_plan_scene_kernel(int n_agents,
                 const double *__restrict__ x0g, const double *__restrict__ nbr_state,
                 const double *__restrict__ nbr_plan, int N, int agent_offset, int scene_agents, int K_nbr,
-                int *__restrict__ sel_out, int sel_stride)
+                int *__restrict__ sel_out, int sel_stride, const double *__restrict__ own_plan)
 {
     __shared__ double wd_lds[SRB_KNN_PLAN_WAVES];
     __shared__ int wi_lds[SRB_KNN_PLAN_WAVES];
@@ -98,8 +99,9 @@ extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_PLAN_WAVES) srb_knn_pl
     const int agent = xcd_agent(blockIdx.x, gridDim.x), tid = threadIdx.x;
     if (agent >= n_agents) return;                 // whole workgroup: the barriers stay uniform
     const int g = agent_offset + agent, nb0 = (g / scene_agents) * scene_agents, self = g - nb0;
+    const double *op = own_plan ? own_plan + 2 * (size_t)agent * N : nbr_plan + 2 * (size_t)g * N;
     if (tid < 2) own[tid] = x0g[4 * (size_t)agent + 2 * tid];
-    else if (tid < 2 * N + 2) own[tid] = nbr_plan[2 * (size_t)g * N + tid - 2];
+    else if (tid < 2 * N + 2) own[tid] = op[tid - 2];
     __syncthreads();
     const double *nb = nbr_state + 4 * (size_t)nb0, *pl = nbr_plan + 2 * (size_t)nb0 * N;
     int *sel = sel_out + (size_t)agent * sel_stride;

@@ -71,11 +71,15 @@ extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_WAVES) srb_knn_kernel(
 // static table's).  Brute force, one workgroup per agent: the agent's own N + 1 points in LDS, every thread scans
 // rows tid, tid + 64 KW, .. and keeps a sorted list (knn_insert); knn_pop merges them.  Only the neighbour
 // columns are written (sel_out points at them; rows of stride sel_stride).  The scan itself is knn_plan_select
-// (srb_knn.h), shared with the per-scene kernel of srb_scenes.hip.
+// (srb_knn.h), shared with the per-scene kernel of srb_scenes.hip.  own_plan [n_agents][N][2] (null: none), indexed
+// by the local agent: the agent's own N plan points come from own_plan[agent] instead of nbr_plan[g] -- under a
+// degraded link (srb_link) the table is what the agent perceives of the others, and its row g a stale, noisy copy
+// of a plan the agent knows exactly.  Still one stage of 2 N + 2 doubles per workgroup (the row's base pointer is
+// chosen before the load); the keys of every other row come from nbr_state / nbr_plan and row g stays left out.
 extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_PLAN_WAVES) srb_knn_plan_kernel(int n_agents,
                 const double *__restrict__ x0g, const double *__restrict__ nbr_state,
                 const double *__restrict__ nbr_plan, int n_all, int N, int agent_offset, int K_nbr,
-                int *__restrict__ sel_out, int sel_stride)
+                int *__restrict__ sel_out, int sel_stride, const double *__restrict__ own_plan)
 {
     __shared__ double wd_lds[SRB_KNN_PLAN_WAVES];
     __shared__ int wi_lds[SRB_KNN_PLAN_WAVES];
@@ -83,8 +87,9 @@ extern "C" __global__ void __launch_bounds__(64 * SRB_KNN_PLAN_WAVES) srb_knn_pl
     const int agent = xcd_agent(blockIdx.x, gridDim.x), tid = threadIdx.x;
     if (agent >= n_agents) return;                 // whole workgroup: the barriers stay uniform
     const int g = agent_offset + agent;
+    const double *op = own_plan ? own_plan + 2 * (size_t)agent * N : nbr_plan + 2 * (size_t)g * N;
     if (tid < 2) own[tid] = x0g[4 * (size_t)agent + 2 * tid];
-    else if (tid < 2 * N + 2) own[tid] = nbr_plan[2 * (size_t)g * N + tid - 2];
+    else if (tid < 2 * N + 2) own[tid] = op[tid - 2];
     __syncthreads();
     int *sel = sel_out + (size_t)agent * sel_stride;
     if (K_nbr <= 4) knn_plan_select<4>(tid, own, nbr_state, nbr_plan, n_all, N, g, K_nbr, sel, wd_lds, wi_lds);

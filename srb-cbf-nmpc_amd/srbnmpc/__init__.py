@@ -135,8 +135,8 @@ class Plant(ctypes.Structure):
 
 
 class Link(ctypes.Structure):
-    """Mirror of srb_link (the degraded neighbour link of the LIP rollout; struct_size filled in).  A Rollout fills it
-    from a LinkModel and buffers of its own."""
+    """Mirror of srb_link (the degraded neighbour link of a rollout, both modes; struct_size filled in).  A Rollout or
+    srb12.Rollout12 fills it from a LinkModel and buffers of its own."""
     _fields_ = [("struct_size", ctypes.c_int), ("seed", ctypes.c_ulonglong), ("delay", _ip), ("drop", _dp),
                 ("noise_p", _dp), ("noise_v", _dp), ("max_delay", ctypes.c_int), ("extrapolate", ctypes.c_int),
                 ("ring_state", _dp), ("ring_plan", _dp), ("held_state", _dp), ("held_plan", _dp), ("held_cycle", _ip),
@@ -147,8 +147,8 @@ class Link(ctypes.Structure):
 
 
 class LinkModel:
-    """What degrades the neighbour link of a Rollout (Rollout(link=LinkModel(...)); srb_link of include/srbnmpc.h): one
-    broadcast per agent per cycle, and every receiver sees the same fate of it.
+    """What degrades the neighbour link of a Rollout or a srb12.Rollout12 (Rollout(link=LinkModel(...)); srb_link of
+    include/srbnmpc.h): one broadcast per agent per cycle, and every receiver sees the same fate of it.
 
     seed      the key of the loss and noise draws (0 .. 2^64 - 1; Philox4x32-10, counters (cycle, global row, 2 / 3, 0):
               the plant's kicks use other counters, so one seed may serve both)

@@ -39,7 +39,7 @@ holds them whole; workload.plant_tables draws a set, workload.replicate_scenes t
 the draws.
 
 With link=srbnmpc.LinkModel(...) the neighbour link is degraded (srb_link, srb_link_update_device /
-srb_rollout_link_device; LIP mode only): every agent broadcasts its snapshot row and its shifted plan once per cycle, and
+srb_rollout_link_device; srb12.Rollout12 likewise, srb12_rollout_link_device): every agent broadcasts its snapshot row and its shifted plan once per cycle, and
 what the others hold of it is late by delay cycles, lost with probability drop and noisy by noise_p / noise_v at the
 sender.  The solve and its selection read the perceived tables (Rollout.seen_state / seen_plan, readable after a step);
 the metrics, traj and every log keep the truth.  results()["link_age"] logs the age of what was held.  The draws key on
@@ -48,7 +48,7 @@ the link's draws as they are over the plant's; workload.link_tables draws a set 
 
 _RolloutBase is what this class and srb12.Rollout12 share: the checks of goal / phase / obstacles / obs_vel and of the
 obstacle and agent size tables, the moving table's clone and its restore, the srb_moving, srb_sizes and
-srb_agent_sizes of a call, the metrics call, the solve, metrics and log buffers, reset / advance / results /
+srb_agent_sizes of a call, the link's table checks, buffers and srb_link, the metrics call, the solve, metrics and log buffers, reset / advance / results /
 scene_results and the preconditions of run().  A mode adds its state width, its own buffers, its srb_sim (_sim),
 step() and the driver call of run() (_drive); the entry points are the solver's own (its _entry).
 """
@@ -159,6 +159,8 @@ class _RolloutBase:
         self.iters_log = grow(self.iters_log, cap, (A, 2), torch.int32)
         if self.log_x:
             self.x_log = grow(self.x_log, cap, (A, nv), torch.float64)
+        if self.link is not None:
+            self.age_log = grow(self.age_log, cap, (self._link_rows,), torch.int32)
         self.cap = cap
 
     def _moving(self) -> Moving:
@@ -202,6 +204,59 @@ class _RolloutBase:
                                                         self.c, s._stream(stream)))
         else:
             _check(s._entry("sim_metrics_device")(s._h, self.A, ctypes.byref(sim), self.c, s._stream(stream)))
+
+    # ------------------------------------------------------------------ the degraded link (srb_link)
+    link = seen_state = seen_plan = age_log = None     # the degraded link (_set_link)
+
+    def _set_link(self, link, n_all):
+        """The link's tables ([n_all] each, or None) after their checks, by name, and the link's own buffers.  Called
+        by the mode's __init__ once it knows n_all."""
+        import torch
+        self.link = None
+        self.seen_state = self.seen_plan = self.age_log = None
+        if link is None:
+            return
+        if not isinstance(link, LinkModel):
+            raise ValueError("link must be a srbnmpc.LinkModel (or None)")
+        seed = int(link.seed)
+        if seed < 0 or seed >= 1 << 64:
+            raise ValueError("link: seed must be 0 .. 2^64 - 1 (the 64-bit Philox key)")
+        n = self._link_rows = int(n_all)
+        if link.delay is not None:
+            _check_tensor(link.delay, (n,), "link: delay", torch.int32, self.device)
+            if bool((link.delay < 0).any()) or bool((link.delay > LINK_MAX_DELAY).any()):
+                raise ValueError(f"link: delay must be 0 .. {LINK_MAX_DELAY} cycles")
+        for name, tab in (("drop", link.drop), ("noise_p", link.noise_p), ("noise_v", link.noise_v)):
+            if tab is None:
+                continue
+            _check_tensor(tab, (n,), f"link: {name}", torch.float64, self.device)
+            if not bool(tab.isfinite().all()):
+                raise ValueError(f"link: {name} must be finite")
+            if bool((tab < 0).any()):
+                raise ValueError(f"link: {name} must be >= 0")
+            if name == "drop" and bool((tab > 1).any()):
+                raise ValueError("link: drop must be <= 1 (a probability)")
+        if not link.on:
+            return                                   # nothing degrades: the plain rollout
+        self.link = link
+        self._link_seed, self._link_extrapolate = seed, int(bool(link.extrapolate))
+        D = self._link_delay = 0 if link.delay is None else int(link.delay.max())
+        N = self.solver.params.N
+        f8 = dict(dtype=torch.float64, device=self.device)
+        self._ring_state, self._held_state = torch.zeros((D + 1, n, 4), **f8), torch.zeros((n, 4), **f8)
+        self._held_cycle = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.seen_state = torch.zeros((n, 4), **f8)
+        self._ring_plan = self._held_plan = None
+        if self.plans:
+            self._ring_plan, self._held_plan = torch.zeros((D + 1, n, N, 2), **f8), torch.zeros((n, N, 2), **f8)
+            self.seen_plan = torch.zeros((n, N, 2), **f8)
+
+    def _link(self) -> Link:
+        ln = self.link
+        return Link(self._link_seed, _iptr(ln.delay), _dptr(ln.drop), _dptr(ln.noise_p), _dptr(ln.noise_v),
+                    self._link_delay, self._link_extrapolate, _dptr(self._ring_state), _dptr(self._ring_plan),
+                    _dptr(self._held_state), _dptr(self._held_plan), _iptr(self._held_cycle), _dptr(self.seen_state),
+                    _dptr(self.seen_plan), _iptr(self.age_log))
 
     # ------------------------------------------------------------------ driving
     def reset(self, state):
@@ -251,7 +306,9 @@ class _RolloutBase:
         """The logs and metrics so far, as tensors (views of this object's buffers; asynchronous like the
         launches -- synchronise before reading on the host): traj [T+1][A][nx] (nx 4, Rollout12: 12), status / iters
         [T][A][2], x [T][A][nv] (log_x), state [A][nx] (the end state), cycles, and d_obs, d_agent, min_d_obs,
-        min_d_agent, fail_cycle, distance_to_fail [A] (with agent_body also collide_cycle [A]); with obs_vel, obstacles [n_obs][2] (the current table: the
+        min_d_agent, fail_cycle, distance_to_fail [A] (with agent_body also collide_cycle [A]; with a link also link_age
+        [T][n_all] int32: row c is, per global row, how many cycles before c the message the team holds of it was
+        sent); with obs_vel, obstacles [n_obs][2] (the current table: the
         rows as the last cycle saw them)."""
         if not self._ready:
             raise RuntimeError(f"{self._name}.results before reset(state)")
@@ -268,6 +325,8 @@ class _RolloutBase:
             out["x"] = self.x_log[:T]
         if self.obs_vel is not None:
             out["obstacles"] = self.obstacles
+        if self.link is not None:
+            out["link_age"] = self.age_log[:T]
         return out
 
     def scene_results(self, stream=None):
@@ -347,7 +406,7 @@ class Rollout(_RolloutBase):
             raise ValueError("agent_offset + A exceeds n_all")
         self._set_agent_sizes(agent_rad, agent_pad, agent_body, nbr_clearance, self.n_all)
         self._set_plant(plant_seed, kick_v, kick_p, plant_hcom, pushes)
-        self._set_link(link)
+        self._set_link(link, self.n_all)
         self.sharded = self.agent_offset != 0 or self.n_all != A
         f8 = dict(dtype=torch.float64, device=self.device)
         self.alpha_buf = torch.zeros((A, 4), **f8)
@@ -395,64 +454,8 @@ class Rollout(_RolloutBase):
         return Plant(self.plant_seed, _dptr(self.kick_v), _dptr(self.kick_p), _dptr(self.plant_hcom),
                      0 if cyc is None else cyc.shape[0], _iptr(cyc), _iptr(agent), _dptr(dv), _dptr(self.dist_log))
 
-    # ------------------------------------------------------------------ the degraded link (srb_link)
-    def _set_link(self, link):
-        """The link's tables ([n_all] each, or None) after their checks, by name, and the link's own buffers."""
-        import torch
-        self.link = None
-        self.seen_state = self.seen_plan = self.age_log = None
-        if link is None:
-            return
-        if not isinstance(link, LinkModel):
-            raise ValueError("link must be a srbnmpc.LinkModel (or None)")
-        seed = int(link.seed)
-        if seed < 0 or seed >= 1 << 64:
-            raise ValueError("link: seed must be 0 .. 2^64 - 1 (the 64-bit Philox key)")
-        n = self.n_all
-        if link.delay is not None:
-            _check_tensor(link.delay, (n,), "link: delay", torch.int32, self.device)
-            if bool((link.delay < 0).any()) or bool((link.delay > LINK_MAX_DELAY).any()):
-                raise ValueError(f"link: delay must be 0 .. {LINK_MAX_DELAY} cycles")
-        for name, tab in (("drop", link.drop), ("noise_p", link.noise_p), ("noise_v", link.noise_v)):
-            if tab is None:
-                continue
-            _check_tensor(tab, (n,), f"link: {name}", torch.float64, self.device)
-            if not bool(tab.isfinite().all()):
-                raise ValueError(f"link: {name} must be finite")
-            if bool((tab < 0).any()):
-                raise ValueError(f"link: {name} must be >= 0")
-            if name == "drop" and bool((tab > 1).any()):
-                raise ValueError("link: drop must be <= 1 (a probability)")
-        if not link.on:
-            return                                   # nothing degrades: the plain rollout
-        self.link = link
-        self._link_seed, self._link_extrapolate = seed, int(bool(link.extrapolate))
-        D = self._link_delay = 0 if link.delay is None else int(link.delay.max())
-        N = self.solver.params.N
-        f8 = dict(dtype=torch.float64, device=self.device)
-        self._ring_state, self._held_state = torch.zeros((D + 1, n, 4), **f8), torch.zeros((n, 4), **f8)
-        self._held_cycle = torch.zeros(n, dtype=torch.int32, device=self.device)
-        self.seen_state = torch.zeros((n, 4), **f8)
-        self._ring_plan = self._held_plan = None
-        if self.plans:
-            self._ring_plan, self._held_plan = torch.zeros((D + 1, n, N, 2), **f8), torch.zeros((n, N, 2), **f8)
-            self.seen_plan = torch.zeros((n, N, 2), **f8)
-
-    def _link(self) -> Link:
-        ln = self.link
-        return Link(self._link_seed, _iptr(ln.delay), _dptr(ln.drop), _dptr(ln.noise_p), _dptr(ln.noise_v),
-                    self._link_delay, self._link_extrapolate, _dptr(self._ring_state), _dptr(self._ring_plan),
-                    _dptr(self._held_state), _dptr(self._held_plan), _iptr(self._held_cycle), _dptr(self.seen_state),
-                    _dptr(self.seen_plan), _iptr(self.age_log))
-
     def _reserve(self, cycles: int):
         super()._reserve(cycles)
-        if self.link is not None and (self.age_log is None or self.age_log.shape[0] < self.cap):
-            import torch
-            new = torch.zeros((self.cap, self.n_all), dtype=torch.int32, device=self.device)
-            if self.age_log is not None:
-                new[:self.age_log.shape[0]] = self.age_log
-            self.age_log = new
         if self.plant and (self.dist_log is None or self.dist_log.shape[0] < self.cap):
             import torch
             new = torch.zeros((self.cap, self.A, 4), dtype=torch.float64, device=self.device)
@@ -491,8 +494,6 @@ class Rollout(_RolloutBase):
         out = super().results(stream)
         if self.plant:
             out["disturbance"] = self.dist_log[:self.c]
-        if self.link is not None:
-            out["link_age"] = self.age_log[:self.c]
         return out
 
     def _sim(self, nbr_state=None) -> Sim:

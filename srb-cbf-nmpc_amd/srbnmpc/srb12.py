@@ -16,7 +16,8 @@ and Rollout12, Solver12.advance_obstacles_device; velocities from workload.obsta
 (srb_sizes): obs_eps / obs_clearance on the same three solver calls, obs_eps / obs_radius /
 obs_clearance on Rollout12; tables from workload.obstacle_sizes.  Agent sizes (srb_agent_sizes):
 agent_rad / agent_pad / nbr_clearance on the same three solver calls, those and agent_body on Rollout12; tables from
-workload.agent_sizes.
+workload.agent_sizes.  Degraded neighbour link (srb_link): Rollout12(link=srbnmpc.LinkModel(...)),
+Solver12.solve_device(own_plan=); tables from workload.link_tables.
 
 The host layer of these features is written once for both modes: Solver12 is a _SolverBase (srbnmpc/__init__.py: the
 context's life, _stream, set_scenes, the Jacobi loop), Rollout12 a rollout._RolloutBase (the checks, buffers, logs,
@@ -29,7 +30,7 @@ import ctypes
 
 import numpy as np
 
-from . import (AgentSizes, Moving, Sizes, _SolverBase, _agent_args, _check, _check_plan_array, _check_vel_array,
+from . import (AgentSizes, Link, Moving, Sizes, _SolverBase, _agent_args, _check, _check_plan_array, _check_vel_array,
                _clamp_selected, _dp, _dptr, _ip, _iptr, _moving_args, _p, _sizes_args, lib, workload)
 from .rollout import _RolloutBase
 
@@ -252,6 +253,12 @@ def _lib():
         L.srb12_sim_advance_plant_device.argtypes = [ctypes.c_void_p, ctypes.c_int, S, PT, ctypes.c_int, ctypes.c_void_p]
         L.srb12_rollout_plant_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, S, PL, MV, SZ, AG, PT, ctypes.c_int,
                                                  ctypes.c_void_p]
+        LN = ctypes.POINTER(Link)
+        L.srb12_link_update_device.argtypes = [ctypes.c_void_p, ctypes.c_int, LN, _dp, _dp, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p]
+        L.srb12_solve_batch_link_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, PL, MV, SZ, AG, _dp, ctypes.c_void_p]
+        L.srb12_rollout_link_device.argtypes = [ctypes.c_void_p, ctypes.c_int, B, S, PL, MV, SZ, AG, PT, LN, ctypes.c_int,
+                                                ctypes.c_void_p]
         _bound = True
     return L
 
@@ -363,7 +370,7 @@ class Solver12(_SolverBase):
     def solve_device(self, x0, xref, foot, contact, obstacles, nbr_state, out, agent_offset: int = 0, stream=None,
                      obstacles_version: int = 0, nbr_plan=None, plan_selection: bool = False, plan=None, obs_vel=None,
                      obs_horizon: bool = False, obs_eps=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
-                     nbr_clearance: bool = False):
+                     nbr_clearance: bool = False, own_plan=None):
         """torch tensors on this device (float64 / int32), contiguous; out holds x_qp (or None), x, obj,
         status, iters and optionally sel [A, Ko+Kn] and plan [A, N, 2] (written when the key is present; the
         `plan` argument overrides it).  nbr_plan ([n_all][N][2] float64, contiguous): the neighbours' plans for the
@@ -375,8 +382,11 @@ class Solver12(_SolverBase):
         selects the static columns by clearance to the level set (needs obs_eps).  agent_rad, agent_pad ([n_all]
         float64, contiguous, finite; agent_rad >= 0): a safety radius and a pad per row of nbr_state
         (srb12_solve_batch_agents_device; the values of a tensor are looked at once, on its first use with this solver);
-        nbr_clearance=True selects the neighbour columns by clearance dist - agent_rad (needs agent_rad).  Asynchronous
-        on `stream` (default: torch's current)."""
+        nbr_clearance=True selects the neighbour columns by clearance dist - agent_rad (needs agent_rad).  own_plan
+        ([A][N][2] float64, contiguous; needs plan_selection, must not overlap plan, not with nbr_clearance): the agents'
+        own plans for the horizon-aware selection, which otherwise reads row agent_offset + a of nbr_plan -- for a table
+        that is what the agent perceives of its neighbours (srb12_solve_batch_link_device).  Asynchronous on `stream`
+        (default: torch's current)."""
         A = x0.shape[0]
         import torch
         Ko, Kn = n_selected(self.params, 0 if obstacles is None else obstacles.shape[0],
@@ -403,6 +413,22 @@ class Solver12(_SolverBase):
         n_obs = 0 if obstacles is None else obstacles.shape[0]
         moving = obs_vel is not None or obs_horizon
         mv = _moving_args(obs_vel, obs_horizon, n_obs, torch.float64, _dptr, self.params.use_nlp) if moving else None
+        if own_plan is not None:                 # the entry point of its own; without, every launch as before
+            _check_plan_array(own_plan, (A, N, 2), "own_plan", torch.float64)
+            sized = obs_eps is not None or obs_clearance
+            sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch.float64, _dptr, self.params.use_nlp,
+                             device=x0.device) if sized else None
+            agents = agent_rad is not None or agent_pad is not None or nbr_clearance
+            ag = _agent_args(agent_rad, agent_pad, None, nbr_clearance, 0 if nbr_state is None else nbr_state.shape[0],
+                             torch.float64, _dptr, self.params.use_nlp, device=x0.device,
+                             checked=self._agent_checked()) if agents else None
+            pl = None if no_plans else ctypes.byref(Plans12(_dptr(nbr_plan), _dptr(plan), 1 if plan_selection else 0, None))
+            _check(_lib().srb12_solve_batch_link_device(self._h, A, ctypes.byref(b), pl,
+                                                        ctypes.byref(mv) if moving else None,
+                                                        ctypes.byref(sz) if sized else None,
+                                                        ctypes.byref(ag) if agents else None, _dptr(own_plan),
+                                                        self._stream(stream)))
+            return
         if agent_rad is not None or agent_pad is not None or nbr_clearance:
             sized = obs_eps is not None or obs_clearance
             sz = _sizes_args(obs_eps, None, obs_clearance, n_obs, torch.float64, _dptr, self.params.use_nlp,
@@ -544,6 +570,15 @@ class Rollout12(_RolloutBase):
                 and results() gains disturbance [T][A][12] (state order; row c - 1 is what the start of cycle c added).
                 None, or a Plant12 with nothing set: the nominal plant, the launches and bits as ever.  The LIP
                 rollout's keyword arguments plant_seed, kick_v, kick_p, plant_hcom and pushes are refused by name
+    link        None or a srbnmpc.LinkModel: the degraded neighbour link (srb_link; rollout.Rollout's argument, the same
+                tables, checks and draws).  With any table set the solve and its selection read seen_state [A][4] /
+                seen_plan [A][N][2] (attributes, readable after a step) instead of the truth; the metrics and the logs
+                keep the truth, results() gains link_age [T][A], and reset() restarts the link.  step() goes through
+                srb12_link_update_device and srb12_solve_batch_link_device, run() through srb12_rollout_link_device (the
+                same bits).  plan_selection goes together with it: the selection then takes each agent's own plan from
+                the truth (plan_table), not from its row of the perceived table.  Not with nbr_clearance and
+                plan_selection together (refused by name).  None, or a LinkModel with nothing set: the launches and bits
+                as ever
     A whole team on one GPU (the SRB-12 mode has no sharded stepping).  All tensors are
     float64 / int32, contiguous, on the solver's device.  Cycles count from 0 at reset()."""
     _nx = 12
@@ -554,7 +589,7 @@ class Rollout12(_RolloutBase):
                  plans: bool = False, plan_selection: bool = False, obs_vel=None, obs_horizon: bool = False,
                  obs_eps=None, obs_radius=None, obs_clearance: bool = False, agent_rad=None, agent_pad=None,
                  agent_body=None, nbr_clearance: bool = False, *, plant=None, plant_seed: int = 0, kick_v=None,
-                 kick_p=None, plant_hcom=None, pushes=None):
+                 kick_p=None, plant_hcom=None, pushes=None, link=None):
         import torch
         for name, arg in (("plant_seed", plant_seed or None), ("kick_v", kick_v), ("kick_p", kick_p),
                           ("plant_hcom", plant_hcom), ("pushes", pushes)):
@@ -569,10 +604,14 @@ class Rollout12(_RolloutBase):
         super().__init__(solver, goal, vref, phase, plans, log_x, obstacles, obs_vel, obs_horizon, obs_eps, obs_radius,
                          obs_clearance)
         self._set_agent_sizes(agent_rad, agent_pad, agent_body, nbr_clearance, self.A)
+        self._set_link(link, self.A)
         self.gait, self.hcom = gait, float(hcom)
         self.plan_selection = bool(plan_selection)
         if self.plan_selection and not self.plans:
             raise ValueError("plan_selection needs plans=True (the horizon-aware selection reads the plan table)")
+        if self.link is not None and self.plan_selection and self.nbr_clearance:
+            raise ValueError("link with plan_selection and nbr_clearance: the clearance selection reads the agent's own plan "
+                             "from its row of the perceived table (not built)")
         self.yaw_step, self.hold_radius = float(yaw_step), float(hold_radius)
         A, N = self.A, solver.params.N
         f8 = dict(dtype=torch.float64, device=self.device)
@@ -653,11 +692,19 @@ class Rollout12(_RolloutBase):
             s.advance_obstacles_device(self.obstacles, self.obs_vel, stream)
         self._metrics(self._sim(), stream)
         table = self.plan_table if self.plans and self.c > 0 else None
-        s.solve_device(self.x0, self.xref, self.foot, self.contact, self.obstacles, self.last_state, self.out,
+        nbr, own = self.last_state, None
+        if self.link is not None:                # the solve reads what is seen of the truth
+            _check(_lib().srb12_link_update_device(s._h, self.A, ctypes.byref(self._link()), _dptr(self.last_state),
+                                                   _dptr(table), self.c, 0, s._stream(stream)))
+            nbr = self.seen_state
+            if table is not None:                # ... and the selection its own plan from the truth
+                own = self.plan_table if self.plan_selection else None
+                table = self.seen_plan
+        s.solve_device(self.x0, self.xref, self.foot, self.contact, self.obstacles, nbr, self.out,
                        stream=stream, nbr_plan=table, plan_selection=self.plan_selection and table is not None,
                        obs_vel=self.obs_vel, obs_horizon=self.obs_horizon, obs_eps=self.obs_eps,
                        obs_clearance=self.obs_clearance, agent_rad=self.agent_rad, agent_pad=self.agent_pad,
-                       nbr_clearance=self.nbr_clearance)
+                       nbr_clearance=self.nbr_clearance, own_plan=own)
         if self.plans:
             s.shift_plans_device(self.out["plan"], self.plan_table, SHIFT_GRIDS, stream=stream)
         self.c += 1
@@ -671,7 +718,16 @@ class Rollout12(_RolloutBase):
         pl = None
         if self.plans:
             pl = ctypes.byref(Plans12(None, _dptr(o["plan"]), 1 if self.plan_selection else 0, _dptr(self.plan_table)))
-        if self.plant is not None:
+        if self.link is not None:
+            mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
+            sz = ctypes.byref(self._sizes()) if self.sized else None
+            ag = ctypes.byref(self._agent_sizes()) if self.agents else None
+            pt = ctypes.byref(self._plant()) if self.plant is not None else None
+            _check(_lib().srb12_rollout_link_device(s._h, self.A, ctypes.byref(b), ctypes.byref(self._sim()), pl, mv, sz,
+                                                    ag, pt, ctypes.byref(self._link()), T, s._stream(stream)))
+            if self.plant is not None:
+                self._advanced = T
+        elif self.plant is not None:
             mv = ctypes.byref(self._moving()) if self.obs_vel is not None else None
             sz = ctypes.byref(self._sizes()) if self.sized else None
             ag = ctypes.byref(self._agent_sizes()) if self.agents else None

@@ -228,6 +228,35 @@ def replicate_scenes(scenes: dict, copies: int):
     return {k: np.tile(np.asarray(v), (copies,) + (1,) * (np.asarray(v).ndim - 1)) for k, v in scenes.items()}
 
 
+def cross_goals(goals, scene_agents: int, seed: int = 0):
+    """Per-agent goals [n][2] exchanged within every scene of `scene_agents` rows: out[s * team + i] =
+    goals[s * team + perm[i]] with perm one derangement (a permutation without a fixed point) of 0 .. team - 1, drawn
+    from a generator of its own (700 + seed) and the same for every scene, so replicas of a scene
+    (replicate_scenes) stay replicas.  Nobody keeps a goal, and nobody shares one: the rows of a scene must differ,
+    or a ValueError names the scene.  make_scenes and make_scenes12 give a whole team ONE goal, which no exchange can
+    tell apart; hand over the starts instead, scenes["nbr_state"][:, :2] of either, and every agent walks to where
+    another one of its scene began, so that paths cross (the study DESIGN.md 10.14 asks for).  The input is not
+    modified; the result goes to Rollout / Rollout12 as `goal`."""
+    g = np.asarray(goals, dtype=np.float64)
+    A = int(scene_agents)
+    if g.ndim != 2 or g.shape[1] != 2:
+        raise ValueError(f"cross_goals: goals must be [n][2], got {g.shape}")
+    if A < 2 or g.shape[0] % A != 0:
+        raise ValueError(f"cross_goals: {g.shape[0]} rows are not whole scenes of scene_agents = {A} >= 2 (a derangement "
+                         "needs two)")
+    rng = np.random.default_rng(700 + int(seed))
+    while True:
+        perm = rng.permutation(A)
+        if not (perm == np.arange(A)).any():
+            break
+    sc = g.reshape(-1, A, 2)
+    for s in range(sc.shape[0]):
+        if len(np.unique(sc[s], axis=0)) != A:
+            raise ValueError(f"cross_goals: scene {s} has two agents with one goal, so an exchange leaves them sharing it "
+                             "(make_scenes gives a team one goal: hand over the starts, scenes['nbr_state'][:, :2])")
+    return np.ascontiguousarray(sc[:, perm].reshape(-1, 2))
+
+
 HCOM12 = 0.3      # SRB-12 mode: nominal CoM height of the synthetic batches
 
 

@@ -13,13 +13,16 @@ what delay, loss and noise do to the separation of a team.
              BatchSolver.set_scenes; 1024 agents, the replicas differ in the link's draws alone), --safety-cycles cycles (200:
              the agents of a scene share a goal and crowd there late in the rollout), bodies as in
              tools/bench_plant.py: per setting of delay (every row), drop and noise_p, one at a time, with and without
-             extrapolate, the per-scene min_d_agent distribution and the collided / failed / not-converged counts
+             extrapolate, the per-scene min_d_agent distribution and the collided / failed / not-converged counts.
+             --cross-goals: instead of the one goal of the scene, every agent walks to the start of another agent of its
+             scene (workload.cross_goals of the starts, one derangement for all replicas): paths cross and nobody shares
+             a goal, the study DESIGN.md 10.14 names and 10.15 records
 
 Method (as tools/bench_plant.py): the cost modes are warmed up, then timed in interleaved rounds -- one
 run(T) per mode per round, host clock around work that ends in a device synchronise, the library's timing events off --
 and the median over the rounds is reported with each mode's spread.  The kernel mappings are interleaved likewise.
 
-    python tools/bench_link.py [--cycles 20] [--safety-cycles 200] [--rounds 7] [--reps 200] [--out FILE]
+    python tools/bench_link.py [--cycles 20] [--safety-cycles 200] [--rounds 7] [--reps 200] [--cross-goals] [--out FILE]
 
 The result is printed as one JSON line and written to --out, by default profiles/bench_link.json.
 """
@@ -69,6 +72,8 @@ def main():
     ap.add_argument("--obs", type=int, default=20)
     ap.add_argument("--agents", type=int, default=0, help="cost, kernel: the team (default: the bench team's 1024)")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--cross-goals", action="store_true",
+                    help="safety: goals exchanged within the scene (workload.cross_goals of the starts)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_link.json"),
                     help="the record (default: profiles/bench_link.json of this tree; '' writes none)")
     args = ap.parse_args()
@@ -143,6 +148,8 @@ def main():
     A2 = S * sa
     sc = workload.replicate_scenes(workload.make_scenes(1, sa, N, C, seed=args.seed, n_obs=so), S)
     goal2, phase2, obstacles2, x02 = t(sc["goal"]), t(sc["phase"]), t(sc["obstacles"]), t(sc["x0"])
+    if args.cross_goals:
+        goal2 = t(workload.cross_goals(sc["nbr_state"][:, :2], sa, args.seed))
     body = t(np.full(A2, workload.FAIL_RADIUS * np.sqrt(workload.EPS_NBR) / (2 * np.sqrt(workload.EPS_OBS))))
     s2 = srbnmpc.BatchSolver(p, A2, 0)
     s2.set_option("timing", 0)
@@ -176,7 +183,7 @@ def main():
                       "us_per_update": {str(k): spread(v) for k, v in us.items()},
                       "product_lanes": "srb_link_update_device's mapping is SRB_LINK_LANES of csrc/srb_kernel_decls.h"},
            "safety": {"replicas": S, "team": sa, "obstacles_per_scene": so, "agents": A2, "cycles": args.safety_cycles,
-                      "sweep": sweep},
+                      "cross_goals": bool(args.cross_goals), "sweep": sweep},
            "note": "cost: run(T) / T, reset included, interleaved: nominal (no link: srb_rollout_plant_device's path), "
                    "link_zero (delay and drop tables of zeros: srb_rollout_link_device on nominal's states, the link's "
                    "launch and kernel alone), link (workload.link_tables with extrapolate: other NLPs from the second "

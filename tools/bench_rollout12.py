@@ -59,6 +59,19 @@ Linearisation: with no kicks, at_state 1 against 0 -- the largest departure of t
 min_d_obs and the scenes with a failure.
 
     python tools/bench_rollout12.py --plant [--out profiles/bench_rollout12_plant.json]
+
+--link measures the degraded neighbour link instead (srb_link on an SRB-12 context), with the protocol
+of tools/bench_link.py (10.14).  Cost, on the bench team above with plans on (Rollout12.run(T), reset included,
+interleaved rounds): nominal (no link: srb12_rollout_plant_device's path); link_zero (delay and drop tables of zeros:
+the link's launch and kernel on nominal's states, whose traj the tool checks to be the nominal one's); link
+(workload.link_tables with extrapolate); and nominal and link once more with the horizon-aware selection, whose own plan
+the link run takes from the truth.  Safety: one workload.make_scenes12 scene (8 agents, 20 obstacles, seed 1234) tiled to
+--agents agents under set_scenes(8, 20), bodies as in tools/bench_link.py, --safety-cycles cycles per rollout, the
+settings of tools/bench_link.py one factor at a time, each with and without extrapolate and with and without
+plan_selection, once per K_nbr of --safety-knbr (default 8 and 3).  --cross-goals: every agent walks to the start of another agent of its scene (workload.cross_goals)
+instead of to the scene's one goal.
+
+    python tools/bench_rollout12.py --link --cross-goals [--safety-cycles 200] [--out profiles/bench_rollout12_link.json]
 """
 import argparse
 import ctypes
@@ -462,6 +475,122 @@ def plant(args):
     assert roll_err <= tol, f"the model's own roll leaves the prediction by {roll_err} (tolerance {tol})"
 
 
+# (delay cycles, drop, noise_p m): tools/bench_link.py's settings, one factor at a time around the undegraded link
+LINK_SETTINGS = ((0, 0.0, 0.0), (1, 0.0, 0.0), (2, 0.0, 0.0), (4, 0.0, 0.0), (0, 0.2, 0.0), (0, 0.5, 0.0), (0, 0.0, 0.03),
+                 (0, 0.0, 0.1), (2, 0.2, 0.03))
+
+
+def link(args):
+    """--link: see the module docstring."""
+    dev = torch.device("cuda", 0)
+    A, N, Ko, Kn, T = args.agents, 10, 3, 8, args.cycles
+    team, scene_obs, seed = 8, 20, 1234
+    D = lambda v, dt=torch.float64: torch.as_tensor(np.ascontiguousarray(v), dtype=dt, device=dev)
+    p = srb12.default_params(N, K_obs=Ko, K_nbr=Kn)
+    spread = lambda v: {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v))}
+
+    def dist(v):
+        v = np.asarray(v, dtype=float)
+        return {"min": float(v.min()), "p05": float(np.quantile(v, 0.05)), "median": float(np.median(v)),
+                "p95": float(np.quantile(v, 0.95)), "max": float(v.max())}
+
+    # ---- cost: the bench team, plans on
+    b = workload.make_batch12(A, N, "trot", seed=seed)
+    goal = D(np.tile(workload.GOAL * np.array([workload.arena_scale(A), 1.0]), (A, 1)))
+    x0, ob = D(b["x0"]), D(b["obstacles"])
+    solver = srb12.Solver12(p, A, 0)
+    solver.set_timing(False)
+    delay, drop, noise_p, noise_v = workload.link_tables(A, seed)
+    M = srbnmpc.LinkModel
+    zero = lambda: M(seed=seed, delay=D(np.zeros(A, np.int32), torch.int32), drop=D(np.zeros(A)))
+    full = lambda: M(seed=seed, delay=D(delay, torch.int32), drop=D(drop), noise_p=D(noise_p), noise_v=D(noise_v),
+                     extrapolate=True)
+    modes = [(name, srb12.Rollout12(solver, goal, vref=workload.VREF, obstacles=ob, plans=True, plan_selection=sel, link=ln))
+             for name, sel, ln in (("nominal", False, None), ("link_zero", False, zero()), ("link", False, full()),
+                                   ("nominal_selection", True, None), ("link_zero_selection", True, zero()),
+                                   ("link_selection", True, full()))]
+
+    def run(r, state=x0, cycles=T):
+        r.reset(state)
+        r.run(cycles)
+    for _ in range(args.warmup):
+        for _, r in modes:
+            run(r)
+    torch.cuda.synchronize(dev)
+    ms = {name: [] for name, _ in modes}
+    for _ in range(args.rounds):
+        for name, r in modes:
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            run(r)
+            torch.cuda.synchronize(dev)
+            ms[name].append(1e3 * (time.perf_counter() - t0) / T)
+    out = {name: r.results() for name, r in modes}
+    torch.cuda.synchronize(dev)
+    iters = {name: float(o["iters"].double().sum(2).mean().item()) for name, o in out.items()}
+    same = bool(torch.equal(out["nominal"]["traj"], out["link_zero"]["traj"]))
+    same_sel = bool(torch.equal(out["nominal_selection"]["traj"], out["link_zero_selection"]["traj"]))
+    team_safety = {name: {"min_d_agent": float(o["min_d_agent"].min().item()), "min_d_obs": float(o["min_d_obs"].min().item())}
+                   for name, o in out.items()}
+    del modes, out
+    solver.close()
+
+    # ---- safety: replicas of one scene, one factor at a time, with and without the horizon-aware selection
+    S = A // team
+    A2 = S * team
+    sc = workload.replicate_scenes(workload.make_scenes12(1, team, N, "trot", seed=seed, n_obs=scene_obs), S)
+    goal2 = workload.cross_goals(sc["nbr_state"][:, :2], team, seed) if args.cross_goals else sc["goal"]
+    goal2, phase2, ob2, x02 = D(goal2), D(sc["phase"], torch.int32), D(sc["obstacles"]), D(sc["x0"])
+    body = D(np.full(A2, workload.FAIL_RADIUS * np.sqrt(workload.EPS_NBR) / (2 * np.sqrt(workload.EPS_OBS))))
+    sweep = []
+    for kn in args.safety_knbr:         # (K_nbr >= team - 1 selects every other agent of the scene, whatever the key)
+        s2 = srb12.Solver12(srb12.default_params(N, K_obs=Ko, K_nbr=kn), A2, 0)
+        s2.set_timing(False)
+        s2.set_scenes(team, scene_obs)
+        for d, q, e in LINK_SETTINGS:
+            for ext in (False, True):
+                if ext and d == 0 and q == 0.0:
+                    continue                                  # nothing ages: extrapolate changes nothing
+                for sel in (False, True):
+                    ln = M(seed=seed, delay=D(np.full(A2, d, np.int32), torch.int32), drop=D(np.full(A2, q)),
+                           noise_p=D(np.full(A2, e)), extrapolate=ext)
+                    r2 = srb12.Rollout12(s2, goal2, vref=workload.VREF, phase=phase2, obstacles=ob2, plans=True,
+                                         plan_selection=sel, agent_body=body, link=ln)
+                    run(r2, x02, args.safety_cycles)
+                    sr = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r2.scene_results().items()}
+                    sweep.append({"K_nbr": kn, "delay": d, "drop": q, "noise_p": e, "extrapolate": int(ext),
+                                  "plan_selection": int(sel), "agents_collided": int(sr["n_collided"].sum()),
+                                  "agents_failed": int(sr["n_failed"].sum()),
+                                  "solves_not_converged": int(sr["n_not_converged"].sum()),
+                                  "scenes_with_a_collision": int((sr["n_collided"] > 0).sum()),
+                                  "scenes_with_a_failure": int((sr["n_failed"] > 0).sum()),
+                                  "max_age": int(r2.results()["link_age"].max().item()),
+                                  "min_d_agent": dist(sr["min_d_agent"]), "min_d_obs": dist(sr["min_d_obs"])})
+        s2.close()
+    res = {"tool": "tools/bench_rollout12.py --link", "horizon": N, "K_obs": Ko, "K_nbr": Kn, "cycles": T,
+           "rounds": args.rounds, "n_gpus": 1, "seed": seed,
+           "cost": {"agents": A, "plans": True, "ms_per_cycle": {k: spread(v) for k, v in ms.items()},
+                    "mean_iterations_per_solve": iters, "link_zero_traj_equals_nominal": same,
+                    "link_zero_selection_traj_equals_nominal_selection": same_sel, "team": team_safety},
+           "safety": {"replicas": S, "team": team, "obstacles_per_scene": scene_obs, "agents": A2,
+                      "cycles": args.safety_cycles, "cross_goals": bool(args.cross_goals), "solves": int(A2 * args.safety_cycles),
+                      "sweep": sweep},
+           "note": "cost: run(T) / T, reset included, interleaved: nominal (no link: srb12_rollout_plant_device's path), "
+                   "link_zero (delay and drop tables of zeros: srb12_rollout_link_device on nominal's states, the link's "
+                   "launch and kernel alone), link (workload.link_tables with extrapolate: other NLPs from the second "
+                   "cycle on); *_selection: the same three with plan_selection (under a link the selection's own plan is "
+                   "the truth plan_table).  safety: one rollout of `safety.cycles` cycles per setting, every row at the "
+                   "same delay / drop / noise_p, the distribution of the per-scene min_d_agent (clearance between bodies) "
+                   "over the replicas, agents collided / failed and solves not converged summed over the replicas; "
+                   "cross_goals: every agent's goal is the start of another agent of its scene."}
+    print(json.dumps(res), flush=True)
+    out_path = args.out if args.out is not None else os.path.join(ROOT, "profiles", "bench_rollout12_link.json")
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+    assert same and same_sel, "a link of zero tables does not reproduce the nominal trajectory bit for bit"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cycles", type=int, default=20, help="T: cycles per window")
@@ -479,6 +608,12 @@ def main():
     ap.add_argument("--vmax", type=float, default=1.0, help="--moving: the obstacles' top speed (m/s)")
     ap.add_argument("--sizes", action="store_true", help="the obstacle-size measurement alone (see above)")
     ap.add_argument("--plant", action="store_true", help="the disturbed-plant measurement alone (see above)")
+    ap.add_argument("--link", action="store_true", help="the degraded-link measurement alone (see above)")
+    ap.add_argument("--cross-goals", action="store_true", help="--link: goals exchanged within the scene")
+    ap.add_argument("--safety-cycles", type=int, default=200, help="--link: cycles per rollout of the safety sweep")
+    ap.add_argument("--safety-knbr", type=int, nargs="+", default=[8, 3],
+                    help="--link: K_nbr of the safety sweep's solver, one sweep each (8 selects all 7 others of a scene of "
+                         "8, so the two selections can differ in column order alone; 3 makes them choose)")
     args = ap.parse_args()
     if args.agents == "tables":
         args.agent_sizes, args.agents = True, "1024"
@@ -493,6 +628,8 @@ def main():
         return agent_sizes(args)
     if args.plant:
         return plant(args)
+    if args.link:
+        return link(args)
     dev = torch.device("cuda", 0)
     A, N, Ko, Kn, T = args.agents, 10, 3, 8, args.cycles
     team, scene_obs = 8, 20
