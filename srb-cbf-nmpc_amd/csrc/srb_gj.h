@@ -14,8 +14,9 @@
 // the whole matrix (lane l: matrix row l & 15) for the DPP solves that follow (la_solve); the
 // broadcasts read the first copy, and each copy applies the same operations (bit-identical).
 // The solve kernels call gj_factor (below), which takes the DPP row_newbcast form of this elimination
-// (gj_invert_dpp) where the rows are replicated: 2642 against 3062 cycles for NZL = 12 on MI355X
-// (tools/ubench/gj_bench.hip; 3546 while the broadcast still zeroed its destination first).  A step here is
+// (gj_invert_dpp) where the rows are replicated: 2638 against 3114 cycles for NZL = 12 on MI355X, 2283 against 2702
+// with NZE = 11 (tools/ubench/gj_bench.hip, profiles/dpp_fold_ubench.txt; 3546 while the broadcast still zeroed its
+// destination first), and with the broadcast folded into the FMA (gj_invert_dpp_fold) 2210 and 1975.  A step here is
 // 22 v_readlane_b32 and 11 FMAs plus the pivot chain; the chain's dependent FMAs issue at the full 4-cycle
 // rate, so interleaving them with the step's bulk gains nothing (profiles/factor_chain_ubench.txt).
 __device__ __forceinline__ float readlane_f(float v, int lane)
@@ -124,13 +125,90 @@ __device__ __forceinline__ int gj_invert_dpp(double (&A)[NZL], int lane, int reg
     return fail != 0;
 }
 
+// gj_invert_dpp with the row broadcast folded into the FMA (SRB_DPP_FOLD): the compiler emits bc16() + fma() as a
+// v_mov_b64_dpp and a v_fma_f64 and does not fold them, so the NZE - 1 row updates of step K are one assembly statement
+// of   v_fmac_f64_dpp A[j], A[j], -f row_newbcast:K   (A[j] += bcast_K(A[j]) (-f): the same fused operation on the same
+// three values as fma(-f, bcast_K(A[j]), A[j]), bit-identical), in gj_invert_dpp's order (K + 1 + jj) % NZE.  The pivot
+// broadcast, the regularisation, the failure ballot, the reciprocal and the pivot column stay compiler code.
+// Wait states (as srb_gram.h gram_group; a missing one gives wrong values with no message): a DPP-read register needs two
+// wait states after a VALU write of it, and the compiler neither sees the DPP reads inside the string nor pads for them.
+// The statement opens with s_nop 1 -- A[j] may just have been written by compiler code (the loads' selects, the pivot
+// column of the step before, an AGPR un-spill) -- and closes with s_nop 1 -- the compiler's next instruction may be the
+// v_mov_b64_dpp of the next pivot, reading A[K + 1], which the statement wrote.  Inside the statement no instruction
+// reads by DPP what another one wrote.  One statement a step, so that the compiler can neither move nor copy an operand
+// between the instructions.  Operands are "v": the solve kernel parks spills in AGPRs, which a DPP instruction cannot name.
+// Measured (tools/ubench/gj_bench.hip, profiles/dpp_fold_ubench.txt, five launches each): 2279 .. 2283 -> 1975 .. 1979
+// cycles at (NZL, NZE) = (12, 11), 2638 .. 2642 -> 2210 .. 2214 at (12, 12), 4160 -> 3100 at (16, 16), 1460 -> 1412 at (8, 8).
+// EXEC: row_newbcast reads another lane, so all 64 lanes must be active at every call (they are: every call site of
+// gj_factor and la_solve sits in wave-uniform control flow of a full wave).
+#define SRB_FJ(I) "v_fmac_f64_dpp %" #I ", %" #I ", -%[f] row_newbcast:%[k] row_mask:0xf bank_mask:0xf\n\t"
+#define SRB_FA(I) "+v"(A[(K + 1 + I) % NZE])
+#define SRB_FJ7 SRB_FJ(0) SRB_FJ(1) SRB_FJ(2) SRB_FJ(3) SRB_FJ(4) SRB_FJ(5) SRB_FJ(6)
+#define SRB_FJ10 SRB_FJ7 SRB_FJ(7) SRB_FJ(8) SRB_FJ(9)
+#define SRB_FJ11 SRB_FJ10 SRB_FJ(10)
+#define SRB_FJ15 SRB_FJ11 SRB_FJ(11) SRB_FJ(12) SRB_FJ(13) SRB_FJ(14)
+#define SRB_FA7 SRB_FA(0), SRB_FA(1), SRB_FA(2), SRB_FA(3), SRB_FA(4), SRB_FA(5), SRB_FA(6)
+#define SRB_FA10 SRB_FA7, SRB_FA(7), SRB_FA(8), SRB_FA(9)
+#define SRB_FA11 SRB_FA10, SRB_FA(10)
+#define SRB_FA15 SRB_FA11, SRB_FA(11), SRB_FA(12), SRB_FA(13), SRB_FA(14)
+#define SRB_FST(N) asm volatile("s_nop 1\n\t" SRB_FJ##N "s_nop 1" : SRB_FA##N : [f] "v"(f), [k] "n"(K))
+template <int NZL, int NZE, int K>
+__device__ __forceinline__ void gj_fold_step(double (&A)[NZL], double f)
+{
+    static_assert(NZE == 8 || NZE == 11 || NZE == 12 || NZE == 16, "gj_fold_step: the reduced sizes of the shipped instances");
+    if constexpr (NZE == 8) SRB_FST(7);
+    else if constexpr (NZE == 11) SRB_FST(10);
+    else if constexpr (NZE == 12) SRB_FST(11);
+    else SRB_FST(15);
+}
+#undef SRB_FJ
+#undef SRB_FA
+#undef SRB_FJ7
+#undef SRB_FJ10
+#undef SRB_FJ11
+#undef SRB_FJ15
+#undef SRB_FA7
+#undef SRB_FA10
+#undef SRB_FA11
+#undef SRB_FA15
+#undef SRB_FST
+template <int NZL, int NZE = NZL>
+__device__ __forceinline__ int gj_invert_dpp_fold(double (&A)[NZL], int lane, int regularise)
+{
+    static_assert(NZL <= 16, "row_newbcast reaches within 16 lanes");
+    static_assert(NZE <= NZL, "NZE");
+    const int r = lane & 15;
+    unsigned long long fail = 0;
+    double cs = 1.0;
+    srb_static_for(std::make_integer_sequence<int, NZE>{}, [&](auto ic) {
+        constexpr int k = decltype(ic)::value;
+        double piv = bc16(A[k], k);
+        if (regularise && piv <= 1e-14 && piv == piv) piv = 1e-7;
+        fail |= __ballot(!(piv > 0.0));
+        const double inv = rcp_d(piv);
+        const bool me = r == k;
+        const double f = me ? 0.0 : A[k] * inv;
+        gj_fold_step<NZL, NZE, k>(A, f);
+        A[k] = me ? 1.0 : -f;
+        cs = me ? inv : cs;
+    });
+#pragma unroll
+    for (int j = 0; j < NZL; j++) A[j] *= cs;
+    return fail != 0;
+}
+
 // The inverse of the solve kernels' reduced Newton matrix: the DPP form where the rows are replicated in every
 // 16-lane row of the wave (NZL <= 16 under SRB_USE_DPP, gj_load / mrow), else the readlane form.  With
-// row_newbcast as one v_mov_b64_dpp (bc16) the DPP form is the faster one: 2638 against 3062 cycles for
+// row_newbcast as one v_mov_b64_dpp (bc16) the DPP form is the faster one: 2638 against 3114 cycles for
 // NZL = 12 (tools/ubench/gj_bench.hip, profiles/factor_chain_ubench.txt), and it holds no pivot row in SGPRs.
-template <int NZL, int NZE = NZL>
+// FOLD: the folded form of it (gj_invert_dpp_fold), per instance (srb_dpp_fold, srb_wave.h).
+template <int NZL, int NZE = NZL, bool FOLD = srb_dpp_fold(NZL, NZE)>
 __device__ __forceinline__ int gj_factor(double (&A)[NZL], int nz, int lane, int regularise)
 {
-    if constexpr (NZL <= 16 && SRB_USE_DPP) return gj_invert_dpp<NZL, NZE>(A, lane, regularise);
-    else return gj_invert<NZL, NZE>(A, nz, lane, regularise);
+    if constexpr (NZL <= 16 && SRB_USE_DPP) {
+        if constexpr (FOLD) return gj_invert_dpp_fold<NZL, NZE>(A, lane, regularise);
+        else return gj_invert_dpp<NZL, NZE>(A, lane, regularise);
+    } else {
+        return gj_invert<NZL, NZE>(A, nz, lane, regularise);
+    }
 }

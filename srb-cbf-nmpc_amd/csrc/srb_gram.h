@@ -363,12 +363,7 @@ __device__ __forceinline__ void gram_batch(double (&hv)[12], double &ps, const d
     SRB_GG(0) SRB_GG(1) SRB_GG(2) SRB_GG(3)
 #undef SRB_GG
 }
-// f(integral_constant<int, I>) for I = 0 .. n - 1 in turn
-template <class F, int... I>
-__device__ __forceinline__ void srb_static_for(std::integer_sequence<int, I...>, F &&f)
-{
-    (f(std::integral_constant<int, I>{}), ...);
-}
+// (srb_static_for: srb_wave.h)
 
 // {x over lanes l and l ^ 32 summed} in lanes 0 .. 31, {y likewise} in lanes 32 .. 63: v_permlane32_swap exchanges
 // lanes 32 .. 63 of its first operand with lanes 0 .. 31 of its second; W = 16 the same over the 16-lane rows

@@ -46,6 +46,7 @@
 #define WAVE 64
 #include "srb_wave.h"
 #include "srb_gj.h"
+#include "srb_solve.h"
 #include "srb_gram.h"
 #define SYNC() srb_sync<NW>()       // the workgroup barrier of srb_wave.h (every SYNC site sits in a function templated on NW)
 
@@ -147,133 +148,6 @@ __device__ __forceinline__ void obs_relin(double *R, double *OJ, int rO, int o, 
     } else {
         OJ[2 * o] = jx; OJ[2 * o + 1] = jy;
     }
-}
-
-// dot of LDS term row (lane-parallel rows) with a wave-uniform vector held in registers: the whole row
-// first (row_load: its loads in flight together, one LDS round trip a row -- written element by element into
-// the FMAs, the compiler ran every pair of elements through one shared temporary, a round trip a pair), then
-// the sums in their fixed order (row_sum)
-template <int NZE>
-__device__ __forceinline__ void row_load(const double *row, double (&a)[NZE])
-{
-#pragma unroll
-    for (int j = 0; j < NZE; j++) a[j] = row[j];
-}
-template <int NZL, int NZE = NZL>
-__device__ __forceinline__ double row_sum(const double (&a)[NZE], const double (&v)[NZL])
-{
-    double s0 = 0.0, s1 = 0.0;
-#pragma unroll
-    for (int j = 0; j + 1 < NZE; j += 2) { s0 = fma(a[j], v[j], s0); s1 = fma(a[j + 1], v[j + 1], s1); }
-    if (NZE & 1) s0 = fma(a[NZE - 1], v[NZE - 1], s0);
-    return s0 + s1;
-}
-template <int NZL, int NZE = NZL>
-__device__ __forceinline__ double row_dot(const double *row, const double (&v)[NZL])
-{
-    double a[NZE];
-    row_load<NZE>(row, a);
-    __builtin_amdgcn_sched_barrier(0);
-    return row_sum<NZL, NZE>(a, v);
-}
-
-// row of the reduced matrix a lane holds: lane (NZL > 16, readlane Gauss-Jordan) or lane & 15
-// (NZL <= 16: every 16-lane row of the wave holds the whole matrix, DPP broadcasts)
-template <int NZL>
-__device__ __forceinline__ int mrow(int lane) { return (NZL <= 16 && SRB_USE_DPP) ? (lane & 15) : lane; }
-
-// lane i (< NZL) loads row i of H (+ delta * Z'Z) with identity padding
-template <int NZL, int NZE = NZL>
-__device__ __forceinline__ void gj_load(double (&A)[NZL], const double *H, const double *ZtZ, double delta, int nz, int lane)
-{
-    constexpr int LDH = NZL + 1;
-    lane = mrow<NZL>(lane);
-    const int i = (lane < NZL) ? lane : 0;
-#pragma unroll
-    for (int j = 0; j < NZL; j++) {
-        if (j >= NZE) { A[j] = (lane == j) ? 1.0 : 0.0; continue; }
-        double v = H[i * LDH + j];
-        if (delta != 0.0) v = fma(delta, ZtZ[i * LDH + j], v);
-        A[j] = (lane < nz && j < nz) ? v : ((lane == j) ? 1.0 : 0.0);
-    }
-}
-
-// Newton solve in the reduced space: out = (Hs + dl Zs)^-1 g with one step of iterative refinement
-// (y = M g; y += M (g - Hs y)): the explicit inverse alone is not backward stable, and near
-// the end of an interior-point solve Hs carries barrier weights of 1e8..1e12.
-// g, y, r, out: LDS vectors (zero beyond nz).  Returns out in registers (uniform).
-// KF (the fp32-factor instances, configs[4] "fp32 KKT with fp64 iterative-refine residuals"): `nref` steps of
-// refinement instead of SRB_REFINE, run-time (more while M is the fp32 inverse); the product instances (KF = 0)
-// keep the compile-time count and are unchanged.
-template <int NZL, int NW, int NZE = NZL, int KF = 0>
-__device__ __forceinline__ void la_solve(const double (&M)[NZL], const double *Hs, const double *Zs, double dl, const double *g,
-                                         double *y, double *r, double *out, double (&res)[NZL], int nz, int lane, int nref = SRB_REFINE)
-{
-    constexpr int LDH = NZL + 1;
-    if constexpr (NZL <= 16 && SRB_USE_DPP) {
-        // rows replicated per 16-lane row: the three vector broadcasts are DPP moves, no LDS
-        // round trip or barrier
-        const int i = lane & 15;
-        const double gi = (i < nz) ? g[i] : 0.0;         // g is zero beyond nz
-        // this lane's row of the matrix the refinement multiplies by (independent of y): loaded once, ahead of
-        // the first product, instead of one element per FMA of the residual
-        double hr[NZE];
-#pragma unroll
-        for (int j = 0; j < NZE; j++) hr[j] = Hs[i * LDH + j];
-        if (dl != 0.0) {                     // the NLP's inertia shift, applied on the fly (H stays unshifted)
-#pragma unroll
-            for (int j = 0; j < NZE; j++) hr[j] = fma(dl, Zs[i * LDH + j], hr[j]);
-        }
-        double y0 = 0.0;
-#pragma unroll
-        for (int j = 0; j < NZE; j++) y0 = fma(M[j], bc16(gi, j), y0);
-        // SRB_REFINE steps of iterative refinement with fp64 residuals (the KF instances: nref)
-        double y1 = y0;
-        const int nr = KF ? nref : SRB_REFINE;
-#pragma unroll
-        for (int it = 0; it < (KF ? 8 : SRB_REFINE); it++) {
-            if (KF && it >= nr) break;
-            double rr = gi;
-#pragma unroll
-            for (int j = 0; j < NZE; j++) rr = fma(-hr[j], bc16(y1, j), rr);
-            if (i >= nz) rr = 0.0;
-#pragma unroll
-            for (int j = 0; j < NZE; j++) y1 = fma(M[j], bc16(rr, j), y1);
-        }
-#pragma unroll
-        for (int j = 0; j < NZL; j++) res[j] = (j < NZE) ? bc16(y1, j) : 0.0;
-        return;
-    }
-    const int i = (lane < NZL) ? lane : 0;
-    double gv[NZL];
-#pragma unroll
-    for (int j = 0; j < NZE; j++) gv[j] = g[j];
-    double y0 = 0.0;
-#pragma unroll
-    for (int j = 0; j < NZE; j++) y0 = fma(M[j], gv[j], y0);
-    double y1 = y0;
-    const int nr = KF ? nref : SRB_REFINE;
-    for (int it = 0; it < nr; it++) {
-        if (it > 0) SYNC();                      // every lane has read the previous r
-        if (lane < nz) y[lane] = y1;
-        SYNC();
-        double rr = (lane < nz) ? g[lane] : 0.0;
-        if (dl != 0.0) {
-#pragma unroll
-            for (int j = 0; j < NZE; j++) rr = fma(-fma(dl, Zs[i * LDH + j], Hs[i * LDH + j]), y[j], rr);
-        } else {
-#pragma unroll
-            for (int j = 0; j < NZE; j++) rr = fma(-Hs[i * LDH + j], y[j], rr);
-        }
-        if (lane < nz) r[lane] = rr;
-        SYNC();
-#pragma unroll
-        for (int j = 0; j < NZE; j++) y1 = fma(M[j], r[j], y1);
-    }
-    if (lane < nz) out[lane] = y1;
-    SYNC();
-#pragma unroll
-    for (int j = 0; j < NZL; j++) res[j] = (j < NZE) ? out[j] : 0.0;
 }
 
 // --------------------------------------------------------------------------- null space

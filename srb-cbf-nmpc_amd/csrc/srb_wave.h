@@ -3,6 +3,8 @@
 // row_newbcast broadcasts, a refined reciprocal.  Header-only, device code.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
+#include <utility>
 
 #ifndef WAVE
 #define WAVE 64
@@ -10,8 +12,31 @@
 #ifndef SRB_USE_DPP     // DPP row_newbcast broadcasts in the reduced solve (0: readlane / LDS forms)
 #define SRB_USE_DPP 1
 #endif
+// The row broadcast folded into the FMA (one v_fmac_f64_dpp row_newbcast instead of v_mov_b64_dpp + v_fma_f64) in the
+// DPP Gauss-Jordan (srb_gj.h) and the DPP reduced solve (srb_solve.h); 0 keeps the bc16() + fma() text everywhere.
+// Only under SRB_USE_DPP and NZL <= 16; which instances take it: srb_dpp_fold below (2, a diagnostic build: the
+// run-time NZL <= 16 instances too -- the comparison of profiles/dpp_fold_static.txt).
+#ifndef SRB_DPP_FOLD
+#define SRB_DPP_FOLD 1
+#endif
 
 typedef double d4 __attribute__((ext_vector_type(4)));
+
+// f(integral_constant<int, I>) for I = 0 .. n - 1 in turn
+template <class F, int... I>
+__device__ __forceinline__ void srb_static_for(std::integer_sequence<int, I...>, F &&f)
+{
+    (f(std::integral_constant<int, I>{}), ...);
+}
+
+// Whether the reduced matrix of bound NZL with NZE steps compiled in takes the folded forms: the one-block shapes whose
+// reduced size is compiled in (NZE < NZL: 12_4_1_10_2_11, 12_1_4_10_2_3 and their f32, table and polish kernels).  The
+// run-time instances (NZE = NZL) keep the bc16() + fma() text (profiles/dpp_fold_static.txt).
+constexpr bool srb_dpp_fold(int NZL, int NZE)
+{
+    return SRB_DPP_FOLD && SRB_USE_DPP && NZL <= 16 && (NZE == 8 || NZE == 11 || NZE == 12 || NZE == 16) &&
+           (NZE < NZL || SRB_DPP_FOLD == 2);
+}
 
 // Agent of workgroup b in a grid of n one-agent workgroups, XCD-aware: the dispatcher deals
 // workgroups round-robin over the 8 XCDs (MI355X_MICROARCH.md, "Workgroup dispatch"; observed, not

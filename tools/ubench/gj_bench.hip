@@ -6,6 +6,11 @@
 // NZE = NZL - 1.  Checks that all three give bit-identical inverses.
 // Two latency chains go with it: a dependent chain of fp64 FMAs, and a chain of
 // FMA -> v_readlane (both halves) -> FMA, in cycles per link.
+// The DPP form with the row broadcast folded into the FMA (srb_gj.h gj_invert_dpp_fold, one v_fmac_f64_dpp row_newbcast
+// an entry) against the DPP form at (NZL, NZE) = (12, 11), (12, 12), (16, 16), (8, 8), and the reduced solve (srb_solve.h
+// la_solve) folded against unfolded at NZE = 11 and 12: five launches each in this one process, fastest and slowest;
+// the inverses and the solve results checked bit-equal.  Gate of the folded forms (profiles/dpp_fold_ubench.txt): the
+// folded form's slowest launch below the unfolded form's fastest at NZE 11 and at NZE 12.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/ubench/gj_bench.hip -o tools/ubench/gj_bench
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -14,6 +19,7 @@
 #define WAVE 64
 #include "../../srb-cbf-nmpc_amd/csrc/srb_kernel_params.h"
 #include "../../srb-cbf-nmpc_amd/csrc/srb_gj.h"
+#include "../../srb-cbf-nmpc_amd/csrc/srb_solve.h"
 
 // The readlane form with a step's dependent chain -- pivot k's reciprocal (v_rcp_f64 and the two Newton steps of
 // rcp_d), the multiplier, the update of entry A[k+1] and its broadcast, pivot k + 1 -- issued one link at a time:
@@ -84,13 +90,13 @@ __device__ __forceinline__ int gj_interleaved(double (&A)[NZL], int nz, int lane
     return fail;
 }
 
-// MODE 0 readlane, 1 DPP, 2 interleaved readlane; NZE: the steps run (the matrix is
+// MODE 0 readlane, 1 DPP, 2 interleaved readlane, 3 DPP with the broadcast folded; NZE: the steps run (the matrix is
 // NZE x NZE, identity beyond)
 template <int NZL, int NZE, int MODE>
 __global__ void kern(const double *M, double *out, unsigned long long *cyc, int reps)
 {
     const int lane = threadIdx.x;
-    const int row = MODE == 1 ? (lane & 15) : lane;
+    const int row = (MODE == 1 || MODE == 3) ? (lane & 15) : lane;
     double A[NZL];
     unsigned long long t0 = 0, t1 = 0;
     for (int rep = 0; rep < reps; rep++) {
@@ -99,7 +105,8 @@ __global__ void kern(const double *M, double *out, unsigned long long *cyc, int 
         __builtin_amdgcn_sched_barrier(0);
         if (rep == 1) t0 = __builtin_amdgcn_s_memtime();
         __builtin_amdgcn_sched_barrier(0);
-        if (MODE == 1) gj_invert_dpp<NZL, NZE>(A, lane, 0);
+        if constexpr (MODE == 3) gj_invert_dpp_fold<NZL, NZE>(A, lane, 0);
+        else if (MODE == 1) gj_invert_dpp<NZL, NZE>(A, lane, 0);
         else if (MODE == 2) gj_interleaved<NZL, NZE>(A, NZE, lane, 0);
         else gj_invert<NZL, NZE>(A, NZE, lane, 0);
         __builtin_amdgcn_sched_barrier(0);
@@ -132,6 +139,77 @@ __global__ void chain(const double *M, double *out, unsigned long long *cyc, int
     t1 = __builtin_amdgcn_s_memtime();
     out[threadIdx.x] = x;
     if (threadIdx.x == 0) cyc[0] = (t1 - t0) / (unsigned long long)((reps - 1) * LINKS);
+}
+
+// la_solve (delta = 0, one refinement step) with M the matrix in `Mg` as the "inverse", H and g in LDS; every
+// repetition perturbs g by its result, so that no solve can be hoisted out of the loop
+template <int NZL, int NZE, bool FOLD>
+__global__ void skern(const double *Mg, double *out, unsigned long long *cyc, int reps)
+{
+    constexpr int LDH = NZL + 1;
+    __shared__ double H[16 * LDH], g[16], vy[16], vr[16], vd[16];
+    const int lane = threadIdx.x, row = lane & 15;
+    for (int e = lane; e < 16 * LDH; e += 64) H[e] = (e / LDH < NZE && e % LDH < NZE) ? Mg[(e / LDH) * NZL + e % LDH] : 0.0;
+    if (lane < 16) g[lane] = lane < NZE ? 1.0 / (1 + lane) : 0.0;
+    __syncthreads();
+    double A[NZL], res[NZL];
+#pragma unroll
+    for (int j = 0; j < NZL; j++) A[j] = (row < NZE && j < NZE) ? 1e-2 * Mg[row * NZL + j] : 0.0;
+    unsigned long long t0 = 0, t1 = 0;
+    for (int rep = 0; rep < reps; rep++) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (rep == 1) t0 = __builtin_amdgcn_s_memtime();
+        __builtin_amdgcn_sched_barrier(0);
+        la_solve<NZL, 1, NZE, 0, FOLD>(A, H, H, 0.0, g, vy, vr, vd, res, NZE, lane);
+        __builtin_amdgcn_sched_barrier(0);
+        if (lane < NZE) g[lane] += 1e-3 * res[0];
+        __syncthreads();
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    t1 = __builtin_amdgcn_s_memtime();
+    if (lane == 0) for (int j = 0; j < NZL; j++) out[j] = res[j];
+    if (lane == 0) cyc[0] = (t1 - t0) / (reps - 1);
+}
+
+// five launches: fastest and slowest; r: the last launch's output
+struct MinMax { unsigned long long lo, hi; };
+template <class L>
+static MinMax launches(L launch, double *dO, unsigned long long *dC, double *r, int nout)
+{
+    MinMax m{~0ull, 0};
+    for (int t = 0; t < 6; t++) {
+        launch();
+        hipDeviceSynchronize();
+        unsigned long long c = 0;
+        hipMemcpy(r, dO, nout * sizeof(double), hipMemcpyDeviceToHost);
+        hipMemcpy(&c, dC, 8, hipMemcpyDeviceToHost);
+        if (t == 0) continue;                         // the first launch loads the code
+        m.lo = c < m.lo ? c : m.lo; m.hi = c > m.hi ? c : m.hi;
+    }
+    return m;
+}
+// folded against unfolded at one size: the Gauss-Jordan, and (SOLVE) la_solve; returns false on a bit difference;
+// gate: set false where the folded form's slowest launch is not below the unfolded form's fastest
+template <int NZL, int NZE, bool SOLVE>
+static bool fold_ab(const double *dM, double *dO, unsigned long long *dC, bool &gate_gj, bool &gate_solve)
+{
+    double r0[NZL * NZL], r1[NZL * NZL];
+    const MinMax a = launches([&] { hipLaunchKernelGGL((kern<NZL, NZE, 1>), dim3(1), dim3(64), 0, 0, dM, dO, dC, 64); }, dO, dC, r0, NZL * NZL);
+    const MinMax b = launches([&] { hipLaunchKernelGGL((kern<NZL, NZE, 3>), dim3(1), dim3(64), 0, 0, dM, dO, dC, 64); }, dO, dC, r1, NZL * NZL);
+    bool eq = !memcmp(r0, r1, sizeof r0);
+    gate_gj = b.hi < a.lo;
+    printf("NZL=%d NZE=%d GJ: dpp %llu .. %llu cyc, folded %llu .. %llu cyc; folded slowest < dpp fastest: %s; bit-equal: %s\n", NZL, NZE,
+           a.lo, a.hi, b.lo, b.hi, gate_gj ? "yes" : "NO", eq ? "yes" : "NO");
+    if constexpr (SOLVE) {
+        const MinMax c = launches([&] { hipLaunchKernelGGL((skern<NZL, NZE, false>), dim3(1), dim3(64), 0, 0, dM, dO, dC, 64); }, dO, dC, r0, NZL);
+        const MinMax d = launches([&] { hipLaunchKernelGGL((skern<NZL, NZE, true>), dim3(1), dim3(64), 0, 0, dM, dO, dC, 64); }, dO, dC, r1, NZL);
+        const bool eqs = !memcmp(r0, r1, NZL * sizeof(double));
+        gate_solve = d.hi < c.lo;
+        printf("NZL=%d NZE=%d la_solve (with the repetition's LDS update): unfolded %llu .. %llu cyc, folded %llu .. %llu cyc; folded slowest < "
+               "unfolded fastest: %s; bit-equal: %s\n", NZL, NZE, c.lo, c.hi, d.lo, d.hi, gate_solve ? "yes" : "NO", eqs ? "yes" : "NO");
+        eq = eq && eqs;
+    }
+    return eq;
 }
 
 template <int NZL, int NZE, int MODE>
@@ -173,6 +251,22 @@ int main()
                "interleaved %s, dpp %s\n", NZL, NZL - e, c[e][0], c[e][2], c[e][1], eq2 ? "yes" : "NO", eq1 ? "yes" : "NO");
     }
     printf("|M inv - I| %.3e\n", res);
+    // the folded forms (the 12 x 12 matrix above; NZL 16 and 8 take their own)
+    bool g11 = false, g12 = false, s11 = false, s12 = false, gx = false, sx = false;
+    ok = fold_ab<12, 11, true>(dM, dO, dC, g11, s11) && ok;
+    ok = fold_ab<12, 12, true>(dM, dO, dC, g12, s12) && ok;
+    {
+        double h16[256], h8[64];
+        for (int i = 0; i < 16; i++) for (int j = 0; j < 16; j++) h16[i * 16 + j] = 1.0 / (1 + i + j) + (i == j ? 2.0 + i : 0.0);
+        for (int i = 0; i < 8; i++) for (int j = 0; j < 8; j++) h8[i * 8 + j] = h16[i * 16 + j];
+        double *dM2; hipMalloc(&dM2, sizeof h16);
+        hipMemcpy(dM2, h16, sizeof h16, hipMemcpyHostToDevice);
+        ok = fold_ab<16, 16, false>(dM2, dO, dC, gx, sx) && ok;
+        hipMemcpy(dM2, h8, sizeof h8, hipMemcpyHostToDevice);
+        ok = fold_ab<8, 8, false>(dM2, dO, dC, gx, sx) && ok;
+    }
+    printf("gate (folded slowest < unfolded fastest at NZE 11 and 12): factor %s, solve %s\n", (g11 && g12) ? "passed" : "FAILED",
+           (s11 && s12) ? "passed" : "FAILED");
     unsigned long long l0 = 0, l1 = 0;
     const double hc[10] = {0.5, 0.25, 0.125, 0.75, 0.3, 0.6, 0.9, 0.1, 0.5, 0.25};
     hipMemcpy(dM, hc, sizeof hc, hipMemcpyHostToDevice);
