@@ -8,6 +8,7 @@
 #include <utility>
 #include "srb_kernel_params.h"
 #include "srb_wave.h"
+#include "srb_solve.h"
 
 // --------------------------------------------------------------------------- term rows
 // Term row t (Z row of a variable, M_e) at R + t * LDR; LDR = NZL + 1 (odd: lane-parallel row reads stay
@@ -844,5 +845,63 @@ __device__ __forceinline__ void rhs_only(const double *R, const double *CF, int 
         }
         __syncthreads();
         ul_add<NZL, false, true>(R, nullptr, CF, F, nullptr, g, nz, tid, 64 * NW);
+    }
+}
+
+// The corrector's right-hand side from slot-owned rows (SRB_RHS_SLOTS; 0 keeps rhs_only everywhere).  Every term row
+// with a coefficient belongs to a slot -- VAR, CoM-CoP and obstacle slots their own row, a VEL slot the Z row of its
+// variable -- and the slot's lane has just formed that coefficient in a register (set_rhs, polish_stationary).  So
+// g = sum_slots cf_slot R[row_slot] needs no CF store, no atomic for the VEL rows and no barrier: each lane adds
+// cf * (its slot's row) to NZE private accumulators, and the 64 lanes' partials are summed.  Which instances: one
+// wave, one column block of at most 12 columns, stored obstacle rows and the shape compiled in (the conditions of
+// the Gram's vector form); every other instance keeps rhs_only.  SRB_RHS_SLOTS_QP 1: the QP stage's copy as well --
+// off: with two slot trips and no obstacle rows the sum over the lanes costs more than the shorter pass saves
+// (tools/ubench/rhs_bench.hip, profiles/rhs_slots_ubench.txt: the gate passes at the NLP size and fails at the QP size).
+#ifndef SRB_RHS_SLOTS
+#define SRB_RHS_SLOTS 1
+#endif
+#ifndef SRB_RHS_SLOTS_QP
+#define SRB_RHS_SLOTS_QP 0
+#endif
+constexpr bool srb_rhs_slots(bool compiled, int NW, int NZL, int NZE)
+{
+    return SRB_RHS_SLOTS && compiled && NW == 1 && NZL <= 12 && SRB_OBS_STORED(NZL) && NZE > 1 && NZE <= NZL;
+}
+
+// g[a] = sum_{t < nts} cfs[t] R[rows[t]][a], a < nz, over the slots of all 64 lanes (one wave).  A slot without a row
+// of its own (beyond the last slot, or switched off in the stage) carries cf = 0 and a finite row in range, as in the
+// J dx pass.  Rows come through row_load with that pass's two buffers: slot t + 1's row is loaded before slot t's
+// FMAs.  The partials are reduced in a fixed order: gram_scatter sums the four 16-lane rows and leaves lane (kq, li)
+// with columns kq, kq + 4, kq + 8 at position li, then four DPP butterflies sum the 16 positions; every lane of a
+// 16-lane row ends with the same bits, lane li = 0 stores them.  g is left in LDS where rhs_only leaves it.
+template <int NZL, int NZE, int TS>
+__device__ __forceinline__ void rhs_slots(const double *R, const double (&cfs)[TS], const int (&rows)[TS], int nts, double *g,
+                                          int nz, int lane)
+{
+    static_assert(NZE <= 12 && NZE <= NZL, "rhs_slots: one column block of at most 12 columns");
+    constexpr int LDR = NZL + 1;
+    const int li = lane & 15, kq = lane >> 4;
+    double acc[12];
+#pragma unroll
+    for (int j = 0; j < 12; j++) acc[j] = 0.0;
+    double rw[2][NZE];
+    if (0 < nts) row_load<NZE>(R + rows[0] * LDR, rw[0]);
+#pragma unroll
+    for (int t = 0; t < TS; t++)
+        if (t < nts) {
+            if (t + 1 < TS && t + 1 < nts) row_load<NZE>(R + rows[(t + 1) % TS] * LDR, rw[(t + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < NZE; j++) acc[j] = fma(cfs[t], rw[t & 1][j], acc[j]);
+        }
+    d4 d = gram_scatter(acc);
+#define SRB_RS_STAGE(CTRL) { const double t0_ = dpp_d<CTRL>(d[0]), t1_ = dpp_d<CTRL>(d[1]), t2_ = dpp_d<CTRL>(d[2]); \
+                             d[0] += t0_; d[1] += t1_; d[2] += t2_; }
+    SRB_RS_STAGE(0xB1) SRB_RS_STAGE(0x4E) SRB_RS_STAGE(0x141) SRB_RS_STAGE(0x140)
+#undef SRB_RS_STAGE
+    if (li == 0) {
+#pragma unroll
+        for (int q = 0; q < 3; q++)
+            if (kq + 4 * q < nz) g[kq + 4 * q] = d[q];
     }
 }

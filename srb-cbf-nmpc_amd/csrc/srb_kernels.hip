@@ -455,6 +455,29 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
     // active rows then hold to 1e-10, ran on rows taken before it: J'z would be off by 2 |dx| |z| there)
     polish_rows<NZL, TS, NW, TK>(Q, nts, xs, OJ, zo, n, rO, R, nz);
     SYNC();
+    if constexpr (srb_rhs_slots(TK::compiled, NW, NZL, NZE)) {
+        // the coefficients stay in the registers of the lanes that own the slots (rhs_slots): a VEL slot's on the Z row
+        // of its variable, a slot of no kind 0 on row 0
+        double cfs[TS];
+        int rr[TS];
+#pragma unroll
+        for (int t = 0; t < TS; t++) {
+            const Slot &q = Q[t];
+            cfs[t] = 0.0; rr[t] = q.r;
+            if (t < nts) {
+                const double zj = SK_TWO(t) ? q.ds[0] * q.dz[0] - q.ds[1] * q.dz[1] : q.ds[0] * q.dz[0];
+                const int kd = SK_KIND(q, t);
+                if (SK_EQ(t, kd, K_VAR)) {
+                    const int v = q.i0;
+                    const double a0 = var_weight(prm, v), gf = fma(a0, xs[v], (v < 4 * N) ? -a0 * ref[v] : 0.0);
+                    cfs[t] = gf + zj;
+                } else if (SK_EQ(t, kd, K_COP) || SK_EQ(t, kd, K_OBS) || SK_EQ(t, kd, K_VEL)) {
+                    cfs[t] = zj;
+                }
+            }
+        }
+        rhs_slots<NZL, NZE, TS>(R, cfs, rr, nts, vg, nz, tid & 63);
+    } else {
 #pragma unroll
     for (int t = 0; t < TS; t++)
         if (t < nts) {
@@ -477,6 +500,7 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
                                    __HIP_MEMORY_SCOPE_WORKGROUP);
     SYNC();
     rhs_only<NZL, NW>(R, CF, cnt, OF, nko, vg, nz, tid, part, bmask);
+    }
     SYNC();
     // the Newton correction g implies, with the last step's inverse (Mi) and matrix (H0): the distance to the
     // stationary point in the reduced coordinates, whatever the scale of the gradient (oracle: the same test)
@@ -535,6 +559,8 @@ __device__ __forceinline__ double polish_stationary(Slot (&Q)[TS], int nts, cons
     constexpr bool GVEC = SRB_GRAM_FORM != SRB_GRAM_MFMA && srb_shape_compiled(NC, CC, KC) && NW == 1 && NZL <= 12 && \
                           SRB_OBS_STORED(NZL) && CC > 1 && NZE <= NZL; \
     using GSH = GramShape<GVEC ? NC : 0, GVEC ? CC : 0, GVEC ? KC : 0>; \
+    /* the corrector's right-hand side from slot-owned rows (srb_gram.h rhs_slots): the same instances */ \
+    constexpr bool RSL = srb_rhs_slots(srb_shape_compiled(NC, CC, KC), NW, NZL, NZE); \
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6; \
     /* the compiled shape (NC, CC, KC > 0) or the run-time one; n = (6 + C) N + 1, nz = N (C - 1) + 1 */ \
     const int N = NC > 0 ? NC : prm.N, C = CC > 0 ? CC : prm.C, K = KC > 0 ? KC : prm.K_obs + prm.K_nbr; \

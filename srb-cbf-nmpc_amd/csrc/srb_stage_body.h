@@ -333,6 +333,11 @@
             double delta = 0.0;
             // right-hand side of pass (0 predictor, 1 corrector / centring):
             //   dsT, r3 = rz - dsT / z, w = om r3, coefficient of term row r = rx + J'w
+            // RSL (srb_rhs_slots; with SPLIT the stage is a compile-time fact): pass 1 keeps each slot's coefficient in a
+            // register for rhs_slots -- no CF store, no VEL atomic; pass 0 keeps its stores: the Gram reads them.  The
+            // register is the slot's q.jd, which holds nothing between here and the J dx pass that rewrites it (so the
+            // instances that keep rhs_only declare nothing new, and compile to the code they had)
+            constexpr bool RSLS = RSL && (nl || SRB_RHS_SLOTS_QP);
             auto set_rhs = [&](int pass) {
                 const double smu = (pass == 0) ? 0.0 : (pc ? sigma * mu : sigma_d * mu);
                 const bool corr = pass == 1 && pc;
@@ -364,9 +369,11 @@
                                 cf = fma((r ? -SK_M(q, t, 1) : SK_M(q, t, 0)) * q.z[r] * IS(q, r), r3, cf);
                             }
                         cfs[t] = cf;
+                        if constexpr (RSLS) { if (pass != 0) { q.jd = cf; continue; } }
                         CF[q.wr] = cf;
                     }
                 }
+                if constexpr (RSLS) { if (pass != 0) return; }
                 if (NW > 1) SYNC();             // other waves' plain stores land before the VEL adds
                 if (nl)
 #pragma unroll
@@ -450,10 +457,20 @@
 #pragma clang loop unroll(disable)
             for (int pass = (pc ? 0 : 1); pass < 2; pass++) {
                 if (pass == 1 || !pc) {
-                    set_rhs(pass);
-                    SYNC();
-                    STAMP_END(6 + 4 * pass);
-                    rhs_only<NZL, NW>(R, CF, cnt, OF, nko, vg, nz, tid, part, bmask);
+                    if constexpr (RSLS) {
+                        set_rhs(1);                           // (pass is 1 here: without a predictor the loop starts at 1)
+                        STAMP_END(6 + 4 * pass);
+                        double cfr[TS];
+                        int rr[TS];
+#pragma unroll
+                        for (int t = 0; t < TS; t++) { cfr[t] = Q[t].jd; rr[t] = Q[t].r; }
+                        rhs_slots<NZL, NZE, TS>(R, cfr, rr, nts, vg, nz, lane);
+                    } else {
+                        set_rhs(pass);
+                        SYNC();
+                        STAMP_END(6 + 4 * pass);
+                        rhs_only<NZL, NW>(R, CF, cnt, OF, nko, vg, nz, tid, part, bmask);
+                    }
                     SYNC();
                     STAMP_END(7 + 4 * pass);
                 }
