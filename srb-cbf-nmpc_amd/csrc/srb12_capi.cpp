@@ -265,22 +265,20 @@ static int check_plans12(const srb12_batch *b, const srb12_plans *pl, bool rollo
     return SRB_OK;
 }
 
-// the checks of srb_moving that need no context (srb_host.h), with this mode's names in the messages
-static int check_moving12(const srb_moving *mv, const srb12_batch *b, bool rollout)
+// the checks of srb_moving, srb_sizes and srb_agent_sizes that need no context (srb_host.h), with this mode's names in
+// the messages
+static int check_tables12(const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag, const srb12_batch *b,
+                          bool rollout)
 {
-    return srb_check_moving(mv, b, rollout, "srb12_rollout_moving_device", "srb12_batch");
+    return srb_check_tables(mv, sz, ag, b, rollout, "srb12_rollout_moving_device", "srb12_batch");
 }
 
-// pl: the plan members of this launch (NULL: none, the launch of srb12_solve_batch[_device] as ever); obs_vel /
-// obs_horizon: the members of srb_moving (null / 0: static obstacles, every launch as before); obs_eps / obs_clear:
-// those of srb_sizes (null / 0: eps_obs for every row, the selection as before); agent_rad / agent_pad / nbr_clear:
-// those of srb_agent_sizes (null / 0: eps_nbr and the levels as they are, the selection as before); own_plan
+// pl: the plan members of this launch (NULL: none, the launch of srb12_solve_batch[_device] as ever); t: the tables of
+// srb_moving, srb_sizes and srb_agent_sizes (SrbTables{}: none, every launch as without them); own_plan
 // [n_agents][N][2]: with pl->plan_selection the agent's own plan of the horizon-aware selection (null: row
 // agent_offset + a of pl->nbr_plan, the launch as before)
-static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_t s, const srb12_plans *pl = nullptr,
-                    const double *obs_vel = nullptr, int obs_horizon = 0, const double *obs_eps = nullptr,
-                    int obs_clear = 0, const double *agent_rad = nullptr, const double *agent_pad = nullptr,
-                    int nbr_clear = 0, const double *own_plan = nullptr)
+static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_t s, const srb12_plans *pl,
+                    const SrbTables &t, const double *own_plan = nullptr)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return srb_internal_fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -294,7 +292,7 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     if (pl && pl->nbr_plan && p->K_nbr > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return srb_internal_fail(SRB_ERR_ARG, "nbr_plan: agent_offset + n_agents exceeds n_all (the plan table's rows)");
     // (the kernel reads row agent_offset + agent of the agent tables unchecked)
-    if (p->use_nlp && (agent_rad || agent_pad) && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
+    if (p->use_nlp && (t.agent_rad || t.agent_pad) && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes: agent_offset + n_agents exceeds n_all (the agent tables' rows)");
     if (pl && pl->plan) {
         const size_t rows = (size_t)n_agents * 2 * p->N;
@@ -310,12 +308,10 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     clamp_rows(c, d, &Ko, &Kn);
     // (the table is read by the NLP stage's neighbour rows only: without them it is never touched)
     const double *nbr_plan = (pl && p->use_nlp && Kn > 0 && d->nbr_state) ? pl->nbr_plan : nullptr;
-    // (the velocities are read by the NLP stage's static rows only, through sel)
-    const double *vel = (p->use_nlp && Ko > 0) ? obs_vel : nullptr;
-    const double *eps = (p->use_nlp && Ko > 0) ? obs_eps : nullptr;   // likewise (the QP-only solve ignores both)
-    const double *pad = (p->use_nlp && Ko > 0) ? agent_pad : nullptr; // likewise
-    // (the radii are read by the NLP stage's neighbour columns only, through sel and at the agent's own row)
-    const double *rad = (p->use_nlp && Kn > 0) ? agent_rad : nullptr;
+    // (the velocities, levels and pads are read by the NLP stage's static rows only, through sel; the radii by its
+    // neighbour columns only, through sel and at the agent's own row; the QP-only solve reads none)
+    const SrbTables g = t.gated(p->use_nlp && Ko > 0, p->use_nlp && Kn > 0);
+    const double *vel = g.obs_vel, *eps = g.obs_eps, *rad = g.agent_rad, *pad = g.agent_pad;
     Srb12KParams k = make_k12(p, Ko, Kn);
     k.dbg_agent = c->dbg_agent; k.dbg = c->dbg;
     const srb12_inst *in = pick12(p->N, Ko + Kn);
@@ -326,11 +322,16 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     if (Ko + Kn > 0) {
         hipLaunchKernelGGL(srb12_pos_kernel, dim3((n_agents + 255) / 256), dim3(256), 0, s, n_agents, d->x0, c->pos);
         HIPCHK(hipGetLastError());
-        int rc = srb_internal_select(c->sel_ctx, n_agents, c->pos, d->obstacles, Ko > 0 ? d->n_obs : 0, d->nbr_state,
-                                     Kn > 0 ? d->n_all : 0, d->agent_offset, Ko, Kn, d->obstacles_version, sel, s,
-                                     pl && pl->plan_selection ? nbr_plan : nullptr, p->N, vel, vel ? obs_horizon : 0, p->Ts,
-                                     eps, eps ? obs_clear : 0, rad, rad ? nbr_clear : 0,
-                                     pl && pl->plan_selection && nbr_plan ? own_plan : nullptr);
+        SrbSelect q = {};
+        q.n_agents = n_agents; q.x0 = c->pos; q.agent_offset = d->agent_offset;
+        q.obstacles = d->obstacles; q.n_obs = Ko > 0 ? d->n_obs : 0; q.obstacles_version = d->obstacles_version;
+        q.nbr_state = d->nbr_state; q.n_all = Kn > 0 ? d->n_all : 0;
+        q.K_obs = Ko; q.K_nbr = Kn; q.sel = sel; q.s = s;
+        q.N = p->N; q.Ts = p->Ts;
+        q.nbr_plan = pl && pl->plan_selection ? nbr_plan : nullptr;
+        q.own_plan = q.nbr_plan ? own_plan : nullptr;
+        q.t = g;
+        int rc = srb_internal_select(c->sel_ctx, q);
         if (rc) return rc;
         // the selection context's own ordering event: its grid buffers are reallocated only after
         // this launch (grid_reserve waits on it)
@@ -338,8 +339,8 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     }
     if (c->timing) HIPCHK(hipEventRecord(c->ev[1], s));
     // with any of the four tables the instance's table kernel (five more arguments); without, the launch as ever
-    c->last_solve_name = (vel || eps || rad || pad) ? in->fn_mv_name : in->fn_name;
-    if (vel || eps || rad || pad)
+    c->last_solve_name = g.any_solve_table() ? in->fn_mv_name : in->fn_name;
+    if (g.any_solve_table())
         hipLaunchKernelGGL(in->fn_mv, dim3(n_agents), dim3(64), lds, s, k, n_agents, d->x0, d->xref, d->foot, d->contact,
                            d->obstacles, d->nbr_state, (const int *)sel, d->x_qp, d->x, d->obj, d->status, d->iters,
                            nbr_plan, pl ? pl->plan : nullptr, vel, eps, rad, pad, d->agent_offset);
@@ -351,12 +352,6 @@ static int launch12(srb12_ctx *c, int n_agents, const srb12_batch *d, hipStream_
     if (c->timing) HIPCHK(hipEventRecord(c->ev[2], s));
     c->timed = c->timing != 0;
     return SRB_OK;
-}
-
-// the batch has a neighbour table (what srb_agent_sizes.agent_rad / agent_body need)
-static bool has_nbr12(const srb12_batch *b)
-{
-    return b && b->struct_size == (int)sizeof(srb12_batch) && b->nbr_state && b->n_all > 0;
 }
 
 // The argument errors of an own plan that need no context (srb12_solve_batch_link_device; the driver hands over
@@ -376,34 +371,24 @@ static int check_own_plan12(const double *own_plan, const srb12_plans *pl, const
     return SRB_OK;
 }
 
-static int solve_device12(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl, bool plans, void *stream,
-                          const srb_moving *mv = nullptr, const srb_sizes *sz = nullptr,
-                          const srb_agent_sizes *ag = nullptr, const double *own_plan = nullptr)
+// pl, mv, sz and ag may be NULL; own_plan NULL: srb12_solve_batch_agents_device itself.  (Every device solve comes
+// this way: one path.)
+extern "C" int srb12_solve_batch_link_device(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl,
+                                             const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
+                                             const double *own_plan, void *stream)
 {
     if (int rc = srb_check_struct(d, "srb12_batch")) return rc;
-    if (int rc0 = check_moving12(mv, d, false)) return rc0;
-    if (int rc0 = srb_check_sizes(sz)) return rc0;
-    if (int rc0 = srb_check_agent_sizes(ag, has_nbr12(d))) return rc0;
-    if (plans)
+    if (int rc0 = check_tables12(mv, sz, ag, d, false)) return rc0;
+    if (pl)
         if (int rc = check_plans12(d, pl, false)) return rc;
     if (int rc0 = check_own_plan12(own_plan, pl, ag)) return rc0;
     if (!c || !d) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t s = (hipStream_t)stream;
     int rc = c->order.order_after_last(s);
-    if (!rc) rc = launch12(c, n_agents, d, s, pl, mv ? mv->obs_vel : nullptr, mv ? mv->horizon_selection : 0,
-                           sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0, ag ? ag->agent_rad : nullptr,
-                           ag ? ag->agent_pad : nullptr, ag ? ag->clearance_selection : 0, own_plan);
+    if (!rc) rc = launch12(c, n_agents, d, s, pl, srb_tables(mv, sz, ag), own_plan);
     if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
-}
-
-// pl, mv, sz and ag may be NULL, as in srb12_solve_batch_agents_device; own_plan NULL: that entry point itself
-extern "C" int srb12_solve_batch_link_device(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl,
-                                             const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
-                                             const double *own_plan, void *stream)
-{
-    return solve_device12(c, n_agents, d, pl, pl != nullptr, stream, mv, sz, ag, own_plan);
 }
 
 // pl, mv and sz may be NULL, as in srb12_solve_batch_sized_device; ag NULL (or without a table): that entry point itself.
@@ -426,10 +411,13 @@ extern "C" int srb12_solve_batch_device(srb12_ctx *c, int n_agents, const srb12_
     return srb12_solve_batch_sized_device(c, n_agents, d, nullptr, nullptr, nullptr, stream);
 }
 
+// (this entry point needs its struct)
 extern "C" int srb12_solve_batch_plans_device(srb12_ctx *c, int n_agents, const srb12_batch *d, const srb12_plans *pl,
                                               void *stream)
 {
-    return solve_device12(c, n_agents, d, pl, true, stream);
+    if (int rc = srb_check_struct(d, "srb12_batch")) return rc;
+    if (!pl) return srb_internal_fail(SRB_ERR_ARG, "null argument");
+    return srb12_solve_batch_sized_device(c, n_agents, d, pl, nullptr, nullptr, stream);
 }
 
 // pl may be NULL (srb12_solve_batch_device with the table), else srb12_solve_batch_plans_device with it
@@ -445,9 +433,7 @@ static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const 
                         const srb_agent_sizes *hag = nullptr)
 {
     if (int rc = srb_check_struct(h, "srb12_batch")) return rc;
-    if (int rc0 = check_moving12(hmv, h, false)) return rc0;
-    if (int rc0 = srb_check_sizes(hsz)) return rc0;
-    if (int rc0 = srb_check_agent_sizes(hag, has_nbr12(h))) return rc0;
+    if (int rc0 = check_tables12(hmv, hsz, hag, h, false)) return rc0;
     if (plans)
         if (int rc = check_plans12(h, hp, false)) return rc;
     if (!c || !h) return srb_internal_fail(SRB_ERR_ARG, "null argument");
@@ -472,13 +458,13 @@ static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const 
     d.sel = h->sel ? c->sel : nullptr;
     d.obstacles = nullptr; d.nbr_state = nullptr;
     if (h->n_obs > 0 && h->obstacles) {
-        if (int rc = srb_stage_reserve(c->order, c->obstacles, c->cap_obs, (size_t)h->n_obs * 2 * sizeof(double))) return rc;
-        HIPCHK(hipMemcpyAsync(c->obstacles, h->obstacles, (size_t)h->n_obs * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+        if (int rc = srb_stage_copy(c->order, c->obstacles, c->cap_obs, h->obstacles, (size_t)h->n_obs * 2 * sizeof(double), s))
+            return rc;
         d.obstacles = c->obstacles;
     }
     if (h->n_all > 0 && h->nbr_state) {
-        if (int rc = srb_stage_reserve(c->order, c->nbr, c->cap_nbr, (size_t)h->n_all * 4 * sizeof(double))) return rc;
-        HIPCHK(hipMemcpyAsync(c->nbr, h->nbr_state, (size_t)h->n_all * 4 * sizeof(double), hipMemcpyHostToDevice, s));
+        if (int rc = srb_stage_copy(c->order, c->nbr, c->cap_nbr, h->nbr_state, (size_t)h->n_all * 4 * sizeof(double), s))
+            return rc;
         d.nbr_state = c->nbr;
     }
     d.obstacles_version = 0;               // staging copies: no grid reuse across calls
@@ -490,9 +476,8 @@ static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const 
         if (hp->nbr_plan && d.nbr_state) {
             if (c->p.K_nbr > 0 && (h->agent_offset < 0 || h->agent_offset + n_agents > h->n_all))
                 return srb_internal_fail(SRB_ERR_ARG, "nbr_plan: agent_offset + n_agents exceeds n_all (the plan table's rows)");
-            const size_t bytes = (size_t)h->n_all * 2 * N * sizeof(double);
-            if (int rc = srb_stage_reserve(c->order, c->nbr_plan, c->cap_plan, bytes)) return rc;
-            HIPCHK(hipMemcpyAsync(c->nbr_plan, hp->nbr_plan, bytes, hipMemcpyHostToDevice, s));
+            if (int rc = srb_stage_copy(c->order, c->nbr_plan, c->cap_plan, hp->nbr_plan, (size_t)h->n_all * 2 * N * sizeof(double), s))
+                return rc;
             dp.nbr_plan = c->nbr_plan;
         }
         if (hp->plan) {
@@ -500,41 +485,38 @@ static int solve_host12(srb12_ctx *c, int n_agents, const srb12_batch *h, const 
             dp.plan = c->plan;
         }
     }
-    // the velocity table, staged like the obstacle rows it belongs to (none without them)
-    const double *vel = nullptr;
-    if (hmv && hmv->obs_vel && d.obstacles) {
-        const size_t bytes = (size_t)h->n_obs * 2 * sizeof(double);
-        if (int rc = srb_stage_reserve(c->order, c->obs_vel, c->cap_vel, bytes)) return rc;
-        HIPCHK(hipMemcpyAsync(c->obs_vel, hmv->obs_vel, bytes, hipMemcpyHostToDevice, s));
-        vel = c->obs_vel;
+    // The tables: ht the caller's (host), t their staged copies.  The velocity and the level table are staged like
+    // the obstacle rows they belong to (none without them), the agent tables with n_all rows each.  (Only the agent
+    // tables ask for the NLP stage here, all four in the LIP mode's solve_host: without it launch12 hands no table to
+    // a kernel and selects no rows, so nothing observable depends on the difference.)
+    const SrbTables ht = srb_tables(hmv, hsz, hag);
+    SrbTables t = {};
+    t.obs_horizon = ht.obs_horizon; t.obs_clear = ht.obs_clear; t.nbr_clear = ht.nbr_clear;
+    if (ht.obs_vel && d.obstacles) {
+        if (int rc = srb_stage_copy(c->order, c->obs_vel, c->cap_vel, ht.obs_vel, (size_t)h->n_obs * 2 * sizeof(double), s))
+            return rc;
+        t.obs_vel = c->obs_vel;
     }
-    // the level table likewise (srb12_solve_batch_sized)
-    const double *eps = nullptr;
-    if (hsz && hsz->obs_eps && d.obstacles) {
-        const size_t bytes = (size_t)h->n_obs * sizeof(double);
-        if (int rc = srb_stage_reserve(c->order, c->obs_eps, c->cap_eps, bytes)) return rc;
-        HIPCHK(hipMemcpyAsync(c->obs_eps, hsz->obs_eps, bytes, hipMemcpyHostToDevice, s));
-        eps = c->obs_eps;
+    if (ht.obs_eps && d.obstacles) {
+        if (int rc = srb_stage_copy(c->order, c->obs_eps, c->cap_eps, ht.obs_eps, (size_t)h->n_obs * sizeof(double), s))
+            return rc;
+        t.obs_eps = c->obs_eps;
     }
-    // the agent tables likewise, n_all rows each (srb12_solve_batch_agents); the QP-only solve reads neither
-    const double *rad = nullptr, *pad = nullptr;
-    if (c->p.use_nlp && hag && (hag->agent_rad || hag->agent_pad)) {
+    if (c->p.use_nlp && (ht.agent_rad || ht.agent_pad)) {
         if (h->agent_offset < 0 || h->agent_offset + n_agents > h->n_all)    // launch12's refusal, before the copies
             return srb_internal_fail(SRB_ERR_ARG, "srb_agent_sizes: agent_offset + n_agents exceeds n_all (the agent tables' rows)");
         const size_t bytes = (size_t)h->n_all * sizeof(double);
-        if (hag->agent_rad) {
-            if (int rc = srb_stage_reserve(c->order, c->agent_rad, c->cap_rad, bytes)) return rc;
-            HIPCHK(hipMemcpyAsync(c->agent_rad, hag->agent_rad, bytes, hipMemcpyHostToDevice, s));
-            rad = c->agent_rad;
+        if (ht.agent_rad) {
+            if (int rc = srb_stage_copy(c->order, c->agent_rad, c->cap_rad, ht.agent_rad, bytes, s)) return rc;
+            t.agent_rad = c->agent_rad;
         }
-        if (hag->agent_pad) {
-            if (int rc = srb_stage_reserve(c->order, c->agent_pad, c->cap_pad, bytes)) return rc;
-            HIPCHK(hipMemcpyAsync(c->agent_pad, hag->agent_pad, bytes, hipMemcpyHostToDevice, s));
-            pad = c->agent_pad;
+        if (ht.agent_pad) {
+            if (int rc = srb_stage_copy(c->order, c->agent_pad, c->cap_pad, ht.agent_pad, bytes, s)) return rc;
+            t.agent_pad = c->agent_pad;
         }
     }
-    int rc = launch12(c, n_agents, &d, s, hp ? &dp : nullptr, vel, vel ? hmv->horizon_selection : 0, eps,
-                      eps ? hsz->clearance_selection : 0, rad, pad, rad ? hag->clearance_selection : 0);
+    t.normalise();                         // (a table that was not staged takes its flag with it)
+    int rc = launch12(c, n_agents, &d, s, hp ? &dp : nullptr, t);
     if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->x_qp) HIPCHK(hipMemcpyAsync(h->x_qp, c->x_qp, A * nv * sizeof(double), hipMemcpyDeviceToHost, s));
@@ -698,10 +680,9 @@ static int launch_advance12(srb12_ctx *c, int n_agents, const srb12_sim *d, int 
 }
 
 // the metrics of the LIP rollout (srb_sim_metrics_kernel, with scenes srb_sim_scene_metrics_kernel) on the com rows;
-// radius: srb_sizes.obs_radius (null: the centre distances and the 0.5 m fail test, the kernels as ever); body /
-// collide: srb_agent_sizes.agent_body and collide_cycle (body null: d_agent by centres, the kernels as ever)
-static int launch_metrics12(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, hipStream_t s,
-                            const double *radius = nullptr, const double *body = nullptr, int *collide = nullptr)
+// t.obs_radius (srb_sizes; null: the centre distances and the 0.5 m fail test, the kernels as ever); t.agent_body and
+// t.collide_cycle (srb_agent_sizes; body null: d_agent by centres, the kernels as ever)
+static int launch_metrics12(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, hipStream_t s, const SrbTables &t)
 {
     if (!d->com) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim: missing buffer (com)");
     if (d->n_obs < 0 || d->n_all < 0 || (d->n_obs > 0 && !d->obstacles) || (d->n_all > 0 && !d->nbr_state))
@@ -714,11 +695,12 @@ static int launch_metrics12(srb12_ctx *c, int n_agents, const srb12_sim *d, int 
     m.n_obs = d->n_obs; m.n_all = d->n_all; m.agent_offset = d->agent_offset;
     m.d_obs = d->d_obs; m.d_agent = d->d_agent; m.min_d_obs = d->min_d_obs; m.min_d_agent = d->min_d_agent;
     m.fail_cycle = d->fail_cycle; m.distance_to_fail = d->distance_to_fail;
-    return srb_internal_sim_metrics(c->sel_ctx, n_agents, &m, cycle, s, radius, body, collide);
+    return srb_internal_sim_metrics(c->sel_ctx, n_agents, &m, cycle, s, t);
 }
 
-static int sim12_call(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream, bool advance,
-                      const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr, const srb12_plant *pl = nullptr)
+template <bool advance>
+static int sim12_call(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream, const srb_sizes *sz,
+                      const srb_agent_sizes *ag, const srb12_plant *pl)
 {
     if (int rc = check_sim12(d, cycle, advance)) return rc;
     if (int rc = check_plant12(pl, d)) return rc;
@@ -731,26 +713,25 @@ static int sim12_call(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle,
     hipStream_t s = (hipStream_t)stream;
     return c->order.run(c->device, s, [&] {
         return advance ? launch_advance12(c, n_agents, d, cycle, s, pl)
-                       : launch_metrics12(c, n_agents, d, cycle, s, sz ? sz->obs_radius : nullptr,
-                                          ag ? ag->agent_body : nullptr, ag ? ag->collide_cycle : nullptr);
+                       : launch_metrics12(c, n_agents, d, cycle, s, srb_tables(nullptr, sz, ag));
     });
-}
-
-extern "C" int srb12_sim_advance_device(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream)
-{
-    return sim12_call(c, n_agents, d, cycle, stream, true);
 }
 
 extern "C" int srb12_sim_advance_plant_device(srb12_ctx *c, int n_agents, const srb12_sim *d, const srb12_plant *pl,
                                               int cycle, void *stream)
 {
-    return sim12_call(c, n_agents, d, cycle, stream, true, nullptr, nullptr, pl);
+    return sim12_call<true>(c, n_agents, d, cycle, stream, nullptr, nullptr, pl);
+}
+
+extern "C" int srb12_sim_advance_device(srb12_ctx *c, int n_agents, const srb12_sim *d, int cycle, void *stream)
+{
+    return srb12_sim_advance_plant_device(c, n_agents, d, nullptr, cycle, stream);
 }
 
 extern "C" int srb12_sim_metrics_agents_device(srb12_ctx *c, int n_agents, const srb12_sim *d, const srb_sizes *sz,
                                                const srb_agent_sizes *ag, int cycle, void *stream)
 {
-    return sim12_call(c, n_agents, d, cycle, stream, false, sz, ag);
+    return sim12_call<false>(c, n_agents, d, cycle, stream, sz, ag, nullptr);
 }
 
 extern "C" int srb12_sim_metrics_sized_device(srb12_ctx *c, int n_agents, const srb12_sim *d, const srb_sizes *sz,
@@ -854,25 +835,24 @@ extern "C" int srb12_link_update_device(srb12_ctx *c, int n_all, const srb_link 
 // NULL; ag: the agent sizes (srb12_rollout_agents_device), or NULL; pt: the disturbed plant
 // (srb12_rollout_plant_device), or NULL; ln: the degraded link (srb12_rollout_link_device), or NULL -- the tables do
 // not change over a rollout: the same pointers serve every cycle
-static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, const srb12_plans *pl,
-                     bool plans, int cycles, void *stream, const srb_moving *mv = nullptr, const srb_sizes *sz = nullptr,
-                     const srb_agent_sizes *ag = nullptr, const srb12_plant *pt = nullptr, const srb_link *ln = nullptr)
+// (Every rollout entry point comes this way: one path.)
+extern "C" int srb12_rollout_link_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d,
+                                         const srb12_plans *pl, const srb_moving *mv, const srb_sizes *sz,
+                                         const srb_agent_sizes *ag, const srb12_plant *pt, const srb_link *ln, int cycles,
+                                         void *stream)
 {
     if (int rc = srb_check_struct(b, "srb12_batch")) return rc;
-    if (int rc0 = check_moving12(mv, b, true)) return rc0;
-    if (int rc0 = srb_check_sizes(sz)) return rc0;
-    if (int rc0 = srb_check_agent_sizes(ag, true)) return rc0;    // (the driver's neighbour table is the team itself)
+    if (int rc0 = check_tables12(mv, sz, ag, b, true)) return rc0;
     if (int rc0 = check_plant12(pt, nullptr)) return rc0;         // (a missing buffer of the roll is reported below, as ever)
     if (!plant12_on(pt)) pt = nullptr;
-    if (plans)
-        if (int rc = srb_check_struct(pl, "srb12_plans")) return rc;
+    if (int rc = srb_check_struct(pl, "srb12_plans")) return rc;
     // (the layout and null checks of check_sim12 only: the driver's first cycle is c_first itself)
     if (int rc = check_sim12(d, d && d->struct_size == (int)sizeof(srb12_sim) ? d->c_first : 0, false)) return rc;
     // (the truth plan table of the link is the plans' plan_table, whose struct_size was checked above)
-    if (int rc0 = srb_check_link(ln, n_agents, d->last_state, plans && pl ? pl->plan_table : nullptr)) return rc0;
+    if (int rc0 = srb_check_link(ln, n_agents, d->last_state, pl ? pl->plan_table : nullptr)) return rc0;
     if (!b) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (!d->goal) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.goal missing");
-    if (plans)
+    if (pl)
         if (int rc = check_plans12(b, pl, true)) return rc;
     if (!c) return srb_internal_fail(SRB_ERR_ARG, "null argument");
     if (cycles < 0) return srb_internal_fail(SRB_ERR_ARG, "negative cycles");
@@ -913,23 +893,17 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
     if (rc) return rc;
     // moving obstacles: the table advances one cycle between the agents' advance and the metrics, from the second
     // cycle on, so d_obs / fail_cycle and the solve see the agents and the obstacles at matching times
-    const double *vel = (mv && b->n_obs > 0) ? mv->obs_vel : nullptr;
-    const int hsel = mv ? mv->horizon_selection : 0;
-    const double *eps = sz ? sz->obs_eps : nullptr, *radius = sz ? sz->obs_radius : nullptr;
-    const int csel = sz ? sz->clearance_selection : 0;
-    const double *rad = ag ? ag->agent_rad : nullptr, *pad = ag ? ag->agent_pad : nullptr;
-    const double *body = ag ? ag->agent_body : nullptr;
-    int *collide = ag ? ag->collide_cycle : nullptr;
-    const int nsel = ag ? ag->clearance_selection : 0;
+    SrbTables t = srb_tables(mv, sz, ag);
+    if (b->n_obs <= 0) { t.obs_vel = nullptr; t.normalise(); }   // (no rows: nothing moves)
     for (int i = 0; i <= cycles && !rc; i++) {
         const int cyc = d->c_first + i;
         rc = launch_advance12(c, n_agents, &sim, cyc, s, pt);
         if (rc || i == cycles) break;
-        if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
-        if (!rc) rc = launch_metrics12(c, n_agents, &sim, cyc, s, radius, body, collide);
+        if (i > 0 && t.obs_vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, t.obs_vel, s);
+        if (!rc) rc = launch_metrics12(c, n_agents, &sim, cyc, s, t);
         if (!rc && ln) rc = launch_link12(c, n_agents, ln, d->last_state, pl ? pl->plan_table : nullptr, cyc, d->c_first, s);
         if (!pl) {
-            if (!rc) rc = launch12(c, n_agents, &bat, s, nullptr, vel, hsel, eps, csel, rad, pad, nsel);
+            if (!rc) rc = launch12(c, n_agents, &bat, s, nullptr, t);
             continue;
         }
         // the first solve against the caller's table (or none), every later one against last cycle's shifted plans
@@ -938,7 +912,7 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
         if (i > 0) cur.nbr_plan = ln ? ln->seen_plan : pl->plan_table;
         if (!cur.nbr_plan) cur.plan_selection = 0;
         const double *own = (ln && i > 0 && cur.plan_selection) ? pl->plan_table : nullptr;
-        if (!rc) rc = launch12(c, n_agents, &bat, s, &cur, vel, hsel, eps, csel, rad, pad, nsel, own);
+        if (!rc) rc = launch12(c, n_agents, &bat, s, &cur, t, own);
         if (!rc) rc = launch_shift12(c, n_agents, pl->plan, SRB12_SIM_NDOMAIN, pl->plan_table, s);
     }
     const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier cycles run
@@ -948,13 +922,19 @@ static int rollout12(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb
 extern "C" int srb12_rollout_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d, int cycles,
                                     void *stream)
 {
-    return rollout12(c, n_agents, b, d, nullptr, false, cycles, stream);
+    return srb12_rollout_sized_device(c, n_agents, b, d, nullptr, nullptr, nullptr, cycles, stream);
 }
 
 extern "C" int srb12_rollout_plans_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d,
                                           const srb12_plans *pl, int cycles, void *stream)
 {
-    return rollout12(c, n_agents, b, d, pl, true, cycles, stream);
+    if (!pl) {      // this entry point needs its struct: the driver's refusals that stand before that one, then it
+        if (int rc = srb_check_struct(b, "srb12_batch")) return rc;
+        if (int rc = check_sim12(d, d && d->struct_size == (int)sizeof(srb12_sim) ? d->c_first : 0, false)) return rc;
+        if (b && !d->goal) return srb_internal_fail(SRB_ERR_ARG, "srb12_sim.goal missing");
+        return srb_internal_fail(SRB_ERR_ARG, "null argument");
+    }
+    return srb12_rollout_sized_device(c, n_agents, b, d, pl, nullptr, nullptr, cycles, stream);
 }
 
 // pl may be NULL (srb12_rollout_device with the table moved), else srb12_rollout_plans_device with it
@@ -986,16 +966,6 @@ extern "C" int srb12_rollout_plant_device(srb12_ctx *c, int n_agents, const srb1
                                           const srb_agent_sizes *ag, const srb12_plant *pt, int cycles, void *stream)
 {
     return srb12_rollout_link_device(c, n_agents, b, d, pl, mv, sz, ag, pt, nullptr, cycles, stream);
-}
-
-// pl, mv, sz, ag and pt may be NULL, as in srb12_rollout_plant_device; ln NULL (or with no table set): that entry point
-// itself
-extern "C" int srb12_rollout_link_device(srb12_ctx *c, int n_agents, const srb12_batch *b, const srb12_sim *d,
-                                         const srb12_plans *pl, const srb_moving *mv, const srb_sizes *sz,
-                                         const srb_agent_sizes *ag, const srb12_plant *pt, const srb_link *ln, int cycles,
-                                         void *stream)
-{
-    return rollout12(c, n_agents, b, d, pl, pl != nullptr, cycles, stream, mv, sz, ag, pt, ln);
 }
 
 // diagnostics (not in the public header): agent >= 0 records a per-iteration trace on the next

@@ -406,28 +406,25 @@ static int check_scenes(const srb_ctx *c, int n_agents, int n_obs, bool has_nbr,
 }
 
 // Obstacle / neighbour selection for a batch (srb_knn_kernel; with a uniform grid per long table,
-// srb_grid_build_kernel): K_obs, K_nbr already clamped to the tables.  x0 rows are [x, ., y, .]
-// (stride 4); shared with the SRB-12 mode (srb12_capi.cpp), which hands over its CoM positions so.
-static int launch_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
-                         const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                         int obstacles_version, int *sel, hipStream_t s, int sel_stride = -1,
-                         const double *nbr_plan = nullptr, int N = 0, const double *own_plan = nullptr)
+// srb_grid_build_kernel); shared with the SRB-12 mode (srb12_capi.cpp), which hands over its CoM positions as x0.
+static int launch_select(srb_ctx *c, const SrbSelect &q)
 {
-    if (sel_stride < 0) sel_stride = K_obs + K_nbr;
+    const int sel_stride = q.stride();
+    hipStream_t s = q.s;
     // scenes: every agent's scene sub-tables brute force, no grid built or consulted (the cached static grid of
     // obstacles_version stays for a later call with scenes off); the plan selection on the scene's rows
     if (c->scene_agents > 0) {
-        const bool by_plan = nbr_plan && K_nbr > 0;
-        if (K_obs > 0 || !by_plan) {
-            hipLaunchKernelGGL(srb_knn_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_WAVES), 0, s, n_agents, x0, obstacles,
-                               nbr_state, agent_offset, c->scene_agents, c->scene_obs, K_obs, by_plan ? 0 : K_nbr, sel,
-                               sel_stride);
+        const bool by_plan = q.nbr_plan && q.K_nbr > 0;
+        if (q.K_obs > 0 || !by_plan) {
+            hipLaunchKernelGGL(srb_knn_scene_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_WAVES), 0, s, q.n_agents, q.x0,
+                               q.obstacles, q.nbr_state, q.agent_offset, c->scene_agents, c->scene_obs, q.K_obs,
+                               by_plan ? 0 : q.K_nbr, q.sel, sel_stride);
             HIPCHK(hipGetLastError());
         }
         if (by_plan) {
-            hipLaunchKernelGGL(srb_knn_plan_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents, x0,
-                               nbr_state, nbr_plan, N, agent_offset, c->scene_agents, K_nbr, sel + K_obs, sel_stride,
-                               own_plan);
+            hipLaunchKernelGGL(srb_knn_plan_scene_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, q.n_agents,
+                               q.x0, q.nbr_state, q.nbr_plan, q.N, q.agent_offset, c->scene_agents, q.K_nbr,
+                               q.sel + q.K_obs, sel_stride, q.own_plan);
             HIPCHK(hipGetLastError());
         }
         return SRB_OK;
@@ -435,14 +432,12 @@ static int launch_select(srb_ctx *c, int n_agents, const double *x0, const doubl
     // SRB_OPT_PLAN_SELECTION (the caller hands over nbr_plan only then): the neighbour columns by closest predicted
     // approach (srb_knn_plan_kernel, brute force, no grid); the static columns from srb_knn_kernel as ever.
     // own_plan (the SRB-12 mode under a srb_link; else null): the agent's own plan rows, not row g of the table
-    if (nbr_plan && K_nbr > 0) {
-        if (K_obs > 0) {
-            int rc = launch_select(c, n_agents, x0, obstacles, n_obs, nullptr, 0, agent_offset, K_obs, 0, obstacles_version,
-                                   sel, s, sel_stride);
-            if (rc) return rc;
-        }
-        hipLaunchKernelGGL(srb_knn_plan_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents, x0, nbr_state, nbr_plan,
-                           n_all, N, agent_offset, K_nbr, sel + K_obs, sel_stride, own_plan);
+    if (q.nbr_plan && q.K_nbr > 0) {
+        if (q.K_obs > 0)
+            if (int rc = launch_select(c, q.obs_only())) return rc;
+        hipLaunchKernelGGL(srb_knn_plan_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, q.n_agents, q.x0,
+                           q.nbr_state, q.nbr_plan, q.n_all, q.N, q.agent_offset, q.K_nbr, q.sel + q.K_obs, sel_stride,
+                           q.own_plan);
         HIPCHK(hipGetLastError());
         return SRB_OK;
     }
@@ -451,74 +446,104 @@ static int launch_select(srb_ctx *c, int n_agents, const double *x0, const doubl
     // (a versioned static obstacle table builds its grid once, so it pays off at fewer rows;
     // SRB_OPT_GRID_MIN_ROWS / _STATIC set the thresholds)
     const int min_rows = c->grid_min_rows, min_rows_static = c->grid_min_rows_static;
-    const bool go = K_obs > 0 && n_obs >= (obstacles_version != 0 ? min_rows_static : min_rows);
-    const bool gn = K_nbr > 0 && n_all >= min_rows;
-    if (go) { int rc = grid_reserve(c, 0, n_obs); if (rc) return rc; }
-    if (gn) { int rc = grid_reserve(c, 1, n_all); if (rc) return rc; }
+    const bool go = q.K_obs > 0 && q.n_obs >= (q.obstacles_version != 0 ? min_rows_static : min_rows);
+    const bool gn = q.K_nbr > 0 && q.n_all >= min_rows;
+    if (go) { int rc = grid_reserve(c, 0, q.n_obs); if (rc) return rc; }
+    if (gn) { int rc = grid_reserve(c, 1, q.n_all); if (rc) return rc; }
     const srb_ctx::grid_buf &G0 = c->grid[0], &G1 = c->grid[1];
     // a static obstacle table (same version, pointer and size) keeps its grid
-    const bool go_build = go && !(obstacles_version != 0 && obstacles_version == c->grid_ver &&
-                                  obstacles == c->grid_src && n_obs == c->grid_n);
+    const bool go_build = go && !(q.obstacles_version != 0 && q.obstacles_version == c->grid_ver &&
+                                  q.obstacles == c->grid_src && q.n_obs == c->grid_n);
     if (go_build || gn) {
         hipLaunchKernelGGL(srb_grid_build_kernel, dim3(2), dim3(1024), 0, s,
-                           obstacles, 2, n_obs, go_build ? G0.g : nullptr, G0.off, G0.spos, G0.sidx,
-                           nbr_state, 4, n_all, gn ? G1.g : nullptr, G1.off, G1.spos, G1.sidx);
+                           q.obstacles, 2, q.n_obs, go_build ? G0.g : nullptr, G0.off, G0.spos, G0.sidx,
+                           q.nbr_state, 4, q.n_all, gn ? G1.g : nullptr, G1.off, G1.spos, G1.sidx);
         HIPCHK(hipGetLastError());
     }
-    if (go_build) { c->grid_src = obstacles; c->grid_n = n_obs; c->grid_ver = obstacles_version; }
-    hipLaunchKernelGGL(srb_knn_kernel, dim3(n_agents), dim3(64 * SRB_KNN_WAVES), 0, s, n_agents, x0, obstacles, n_obs,
-                       nbr_state, n_all, agent_offset, K_obs, K_nbr, sel, sel_stride,
+    if (go_build) { c->grid_src = q.obstacles; c->grid_n = q.n_obs; c->grid_ver = q.obstacles_version; }
+    hipLaunchKernelGGL(srb_knn_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_WAVES), 0, s, q.n_agents, q.x0, q.obstacles,
+                       q.n_obs, q.nbr_state, q.n_all, q.agent_offset, q.K_obs, q.K_nbr, q.sel, sel_stride,
                        go ? G0.g : nullptr, G0.off, G0.spos, G0.sidx,
                        gn ? G1.g : nullptr, G1.off, G1.spos, G1.sidx);
     HIPCHK(hipGetLastError());
     return SRB_OK;
 }
 
-static int launch_obs_horizon(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
-                              int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride, hipStream_t s, int N,
-                              double Ts);
-static int launch_obs_clear(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
-                            const double *obs_eps, int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride,
-                            hipStream_t s, int N, double Ts);
-static int launch_nbr_clear(srb_ctx *c, int n_agents, const double *x0, const double *nbr_state, const double *nbr_plan,
-                            const double *agent_rad, int n_all, int agent_offset, int K_nbr, int *sel, int sel_stride,
-                            hipStream_t s, int N);
-
-// The selection of a solve, both modes.  obs_vel with obs_horizon (srb_moving.horizon_selection): the static columns by
-// closest predicted approach over the caller's grid (N, Ts), the neighbour columns as without.  obs_eps with
-// obs_clear (srb_sizes.clearance_selection): the static columns by clearance to the level set -- over the horizon
-// when obs_vel and obs_horizon say so, else now -- and the neighbour columns as without.  agent_rad with nbr_clear
-// (srb_agent_sizes.clearance_selection): the neighbour columns by clearance -- over the horizon when the caller hands
-// over nbr_plan, else now -- and the static columns as without.  own_plan with nbr_plan (srb12_solve_batch_link_device):
-// the plan selection takes the agent's own plan from own_plan[agent]; the caller refuses it together with nbr_clear
-int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
-                        const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                        int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan, int N,
-                        const double *obs_vel, int obs_horizon, double Ts, const double *obs_eps, int obs_clear,
-                        const double *agent_rad, int nbr_clear, const double *own_plan)
+// The horizon-aware obstacle selection (srb_moving.horizon_selection; srb_moving.hip) into the static columns
+// 0 .. K_obs - 1 of sel: brute force, with scenes over the agent's scene.  q.N, q.Ts: the grid of the horizon (the
+// SRB-12 mode hands over its own).
+static int launch_obs_horizon(srb_ctx *c, const SrbSelect &q)
 {
-    const bool clear = obs_eps && obs_clear, horizon = obs_vel && obs_horizon, nclear = agent_rad && nbr_clear;
-    if (clear || horizon || nclear) {
-        if (K_nbr > 0) {
-            const int rc = nclear ? launch_nbr_clear(c, n_agents, x0, nbr_state, nbr_plan, agent_rad, n_all, agent_offset,
-                                                     K_nbr, sel + K_obs, K_obs + K_nbr, s, N)
-                                  : launch_select(c, n_agents, x0, obstacles, 0, nbr_state, n_all, agent_offset, 0, K_nbr,
-                                                  0, sel + K_obs, s, K_obs + K_nbr, nbr_plan, N, own_plan);
-            if (rc) return rc;
-        }
-        if (K_obs > 0 && clear)
-            return launch_obs_clear(c, n_agents, x0, obstacles, obs_horizon ? obs_vel : nullptr, obs_eps, n_obs,
-                                    agent_offset, K_obs, sel, K_obs + K_nbr, s, N, Ts);
-        if (K_obs > 0 && horizon)
-            return launch_obs_horizon(c, n_agents, x0, obstacles, obs_vel, n_obs, agent_offset, K_obs, sel, K_obs + K_nbr,
-                                      s, N, Ts);
-        if (K_obs > 0)                        // the static columns alone, by centres (the pass of the plan selection)
-            return launch_select(c, n_agents, x0, obstacles, n_obs, nullptr, 0, agent_offset, K_obs, 0, obstacles_version,
-                                 sel, s, K_obs + K_nbr);
-        return SRB_OK;
-    }
-    return launch_select(c, n_agents, x0, obstacles, n_obs, nbr_state, n_all, agent_offset, K_obs, K_nbr,
-                         obstacles_version, sel, s, -1, nbr_plan, N, own_plan);
+    if (c->scene_agents > 0)
+        hipLaunchKernelGGL(srb_knn_obs_horizon_scene_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, q.s,
+                           q.n_agents, q.x0, q.obstacles, q.t.obs_vel, q.N, q.Ts, q.agent_offset, c->scene_agents,
+                           c->scene_obs, q.K_obs, q.sel, q.stride());
+    else
+        hipLaunchKernelGGL(srb_knn_obs_horizon_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, q.s, q.n_agents,
+                           q.x0, q.obstacles, q.t.obs_vel, q.n_obs, q.N, q.Ts, q.K_obs, q.sel, q.stride());
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+// The clearance selection (srb_sizes.clearance_selection; srb_sizes.hip) into the static columns 0 .. K_obs - 1 of sel:
+// launch_obs_horizon's geometry.  Without the horizon flag the key's distance is the one now (the kernel gets no
+// velocities); with it the horizon's minimum.
+static int launch_obs_clear(srb_ctx *c, const SrbSelect &q)
+{
+    const double *obs_vel = q.t.obs_horizon ? q.t.obs_vel : nullptr;
+    if (c->scene_agents > 0)
+        hipLaunchKernelGGL(srb_knn_obs_clear_scene_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, q.s,
+                           q.n_agents, q.x0, q.obstacles, obs_vel, q.t.obs_eps, q.N, q.Ts, q.agent_offset, c->scene_agents,
+                           c->scene_obs, q.K_obs, q.sel, q.stride());
+    else
+        hipLaunchKernelGGL(srb_knn_obs_clear_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, q.s, q.n_agents,
+                           q.x0, q.obstacles, obs_vel, q.t.obs_eps, q.n_obs, q.N, q.Ts, q.K_obs, q.sel, q.stride());
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+// The neighbour clearance selection (srb_agent_sizes.clearance_selection; srb_agents.hip) of a neighbour-only request
+// (SrbSelect::nbr_only: q.sel points at the neighbour columns): brute force, with scenes over the agent's scene.
+// q.nbr_plan null: the key's distance is the snapshot's; else the horizon's minimum.
+static int launch_nbr_clear(srb_ctx *c, const SrbSelect &q)
+{
+    if (c->scene_agents > 0)
+        hipLaunchKernelGGL(srb_knn_nbr_clear_scene_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, q.s,
+                           q.n_agents, q.x0, q.nbr_state, q.nbr_plan, q.t.agent_rad, q.N, q.agent_offset, c->scene_agents,
+                           q.K_nbr, q.sel, q.stride());
+    else
+        hipLaunchKernelGGL(srb_knn_nbr_clear_kernel, dim3(q.n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, q.s, q.n_agents,
+                           q.x0, q.nbr_state, q.nbr_plan, q.t.agent_rad, q.n_all, q.N, q.agent_offset, q.K_nbr, q.sel,
+                           q.stride());
+    HIPCHK(hipGetLastError());
+    return SRB_OK;
+}
+
+// The columns of one side by what q asks for them.  Static: with srb_sizes' flag by clearance to the level set (over
+// the horizon when srb_moving's flag is set too, else now), with srb_moving's flag alone by closest predicted
+// approach over the grid (q.N, q.Ts), else by centres.  Neighbours: with srb_agent_sizes' flag by clearance (over the
+// horizon with q.nbr_plan, else now), else launch_select's (by q.nbr_plan or the snapshot).
+static int select_obs(srb_ctx *c, const SrbSelect &q)
+{
+    if (q.K_obs == 0) return SRB_OK;
+    if (q.t.obs_clear) return launch_obs_clear(c, q);
+    if (q.t.obs_horizon) return launch_obs_horizon(c, q);
+    return launch_select(c, q.obs_only());
+}
+
+static int select_nbr(srb_ctx *c, const SrbSelect &q)
+{
+    if (q.K_nbr == 0) return SRB_OK;
+    return q.t.nbr_clear ? launch_nbr_clear(c, q.nbr_only()) : launch_select(c, q.nbr_only());
+}
+
+// The selection of a solve, both modes: with any flag of q.t the two sides one after the other, without one the one
+// launch of launch_select.  q.own_plan (srb12_solve_batch_link_device): the caller refuses it together with nbr_clear
+int srb_internal_select(srb_ctx *c, const SrbSelect &q)
+{
+    if (!q.t.obs_clear && !q.t.obs_horizon && !q.t.nbr_clear) return launch_select(c, q);
+    if (int rc = select_nbr(c, q)) return rc;
+    return select_obs(c, q);
 }
 
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s) { return c->order.mark_done(s); }
@@ -533,62 +558,12 @@ void srb_internal_clamp_K(const srb_ctx *c, int n_obs, bool has_nbr, int n_all, 
     clamp_K(c, n_obs, has_nbr, n_all, Ko, Kn);
 }
 
-// The horizon-aware obstacle selection (srb_moving.horizon_selection; srb_moving.hip) into the static columns
-// 0 .. K_obs - 1 of sel (rows of stride sel_stride): brute force, with scenes over the agent's scene.  K_obs is
-// already clamped to the table (or the scene).  N, Ts: the grid of the horizon (the SRB-12 mode hands over its own).
-static int launch_obs_horizon(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
-                              int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride, hipStream_t s, int N,
-                              double Ts)
+// the checks of srb_moving, srb_sizes and srb_agent_sizes that need no context (srb_host.h), with this mode's names in
+// the messages
+static int check_tables(const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag, const srb_batch *b,
+                        bool rollout)
 {
-    if (c->scene_agents > 0)
-        hipLaunchKernelGGL(srb_knn_obs_horizon_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents,
-                           x0, obstacles, obs_vel, N, Ts, agent_offset, c->scene_agents, c->scene_obs, K_obs, sel,
-                           sel_stride);
-    else
-        hipLaunchKernelGGL(srb_knn_obs_horizon_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents, x0,
-                           obstacles, obs_vel, n_obs, N, Ts, K_obs, sel, sel_stride);
-    HIPCHK(hipGetLastError());
-    return SRB_OK;
-}
-
-// The clearance selection (srb_sizes.clearance_selection; srb_sizes.hip) into the static columns 0 .. K_obs - 1 of sel:
-// launch_obs_horizon's geometry.  obs_vel null: the key's distance is the one now; else the horizon's minimum.
-static int launch_obs_clear(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, const double *obs_vel,
-                            const double *obs_eps, int n_obs, int agent_offset, int K_obs, int *sel, int sel_stride,
-                            hipStream_t s, int N, double Ts)
-{
-    if (c->scene_agents > 0)
-        hipLaunchKernelGGL(srb_knn_obs_clear_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents,
-                           x0, obstacles, obs_vel, obs_eps, N, Ts, agent_offset, c->scene_agents, c->scene_obs, K_obs, sel,
-                           sel_stride);
-    else
-        hipLaunchKernelGGL(srb_knn_obs_clear_kernel, dim3(n_agents), dim3(64 * SRB_KNN_OBS_WAVES), 0, s, n_agents, x0,
-                           obstacles, obs_vel, obs_eps, n_obs, N, Ts, K_obs, sel, sel_stride);
-    HIPCHK(hipGetLastError());
-    return SRB_OK;
-}
-
-// The neighbour clearance selection (srb_agent_sizes.clearance_selection; srb_agents.hip) into sel (which points at
-// the neighbour columns; rows of stride sel_stride): brute force, with scenes over the agent's scene.  nbr_plan null:
-// the key's distance is the snapshot's; else the horizon's minimum.  K_nbr is already clamped to the table.
-static int launch_nbr_clear(srb_ctx *c, int n_agents, const double *x0, const double *nbr_state, const double *nbr_plan,
-                            const double *agent_rad, int n_all, int agent_offset, int K_nbr, int *sel, int sel_stride,
-                            hipStream_t s, int N)
-{
-    if (c->scene_agents > 0)
-        hipLaunchKernelGGL(srb_knn_nbr_clear_scene_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents,
-                           x0, nbr_state, nbr_plan, agent_rad, N, agent_offset, c->scene_agents, K_nbr, sel, sel_stride);
-    else
-        hipLaunchKernelGGL(srb_knn_nbr_clear_kernel, dim3(n_agents), dim3(64 * SRB_KNN_PLAN_WAVES), 0, s, n_agents, x0,
-                           nbr_state, nbr_plan, agent_rad, n_all, N, agent_offset, K_nbr, sel, sel_stride);
-    HIPCHK(hipGetLastError());
-    return SRB_OK;
-}
-
-// the checks of srb_moving that need no context (srb_host.h), with this mode's names in the messages
-static int check_moving(const srb_moving *mv, const srb_batch *b, bool rollout)
-{
-    return srb_check_moving(mv, b, rollout, "srb_rollout_moving_device", "srb_batch");
+    return srb_check_tables(mv, sz, ag, b, rollout, "srb_rollout_moving_device", "srb_batch");
 }
 
 // The argument errors of the plan members (srb_batch.nbr_plan / plan), before anything is launched.  select: the
@@ -607,13 +582,8 @@ static int check_plans(srb_ctx *c, int n_agents, const srb_batch *d, bool select
     return SRB_OK;
 }
 
-// obs_vel / obs_horizon: the members of srb_moving (null / 0: static obstacles, every launch as before);
-// obs_eps / obs_clear: those of srb_sizes (null / 0: eps_obs for every row, the selection as before);
-// agent_rad / agent_pad / nbr_clear: those of srb_agent_sizes (null / 0: eps_nbr and the levels as they are, the
-// selection as before)
-static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, int use_nlp,
-                  const double *obs_vel = nullptr, int obs_horizon = 0, const double *obs_eps = nullptr, int obs_clear = 0,
-                  const double *agent_rad = nullptr, const double *agent_pad = nullptr, int nbr_clear = 0)
+// t: the tables of srb_moving, srb_sizes and srb_agent_sizes (SrbTables{}: none, every launch as without them)
+static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, int use_nlp, const SrbTables &t)
 {
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -628,7 +598,7 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
         return fail(SRB_ERR_ARG, "obstacles missing");
     if (use_nlp && p->K_nbr > 0 && d->nbr_state && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
-    if (use_nlp && (agent_rad || agent_pad) && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
+    if (use_nlp && (t.agent_rad || t.agent_pad) && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return fail(SRB_ERR_ARG, "srb_agent_sizes: agent_offset + n_agents exceeds n_all (the agent tables' rows)");
     // (the QP-only solve ignores nbr_plan: it has no obstacle rows)
     if (use_nlp)
@@ -658,16 +628,20 @@ static int launch(srb_ctx *c, int n_agents, const srb_batch *d, hipStream_t s, i
     // around a collective, bench.py's multi-GPU step)
     // (with srb_moving.horizon_selection the static columns by closest predicted approach: srb_internal_select)
     if (use_nlp && k.K_obs + k.K_nbr > 0 && c->selection) {
-        int rc = srb_internal_select(c, n_agents, d->x0, d->obstacles, n_obs, d->nbr_state, n_all, d->agent_offset, k.K_obs,
-                                     k.K_nbr, d->obstacles_version, sel, s, c->plan_selection ? nbr_plan : nullptr, k.N,
-                                     obs_vel, obs_horizon, p->Ts, obs_eps, obs_clear, agent_rad, nbr_clear);
-        if (rc) return rc;
+        SrbSelect q = {};
+        q.n_agents = n_agents; q.x0 = d->x0; q.agent_offset = d->agent_offset;
+        q.obstacles = d->obstacles; q.n_obs = n_obs; q.obstacles_version = d->obstacles_version;
+        q.nbr_state = d->nbr_state; q.n_all = n_all;
+        q.K_obs = k.K_obs; q.K_nbr = k.K_nbr; q.sel = sel; q.s = s;
+        q.N = k.N; q.Ts = p->Ts;
+        q.nbr_plan = c->plan_selection ? nbr_plan : nullptr;
+        q.t = t;
+        if (int rc = srb_internal_select(c, q)) return rc;
     }
-    const double *vel = (use_nlp && k.K_obs > 0) ? obs_vel : nullptr;   // read only for the static columns of sel
-    const double *eps = (use_nlp && k.K_obs > 0) ? obs_eps : nullptr;   // likewise (the QP-only solve ignores both)
-    const double *pad = (use_nlp && k.K_obs > 0) ? agent_pad : nullptr; // likewise
-    const double *rad = (use_nlp && k.K_nbr > 0) ? agent_rad : nullptr; // read only for the neighbour columns of sel
-    const bool tabled = vel || eps || rad || pad;
+    // (the QP-only solve reads no table)
+    const SrbTables g = t.gated(use_nlp && k.K_obs > 0, use_nlp && k.K_nbr > 0);
+    const double *vel = g.obs_vel, *eps = g.obs_eps, *rad = g.agent_rad, *pad = g.agent_pad;
+    const bool tabled = g.any_solve_table();
     if (c->timing) HIPCHK(hipEventRecord(c->ev[2], s));
     // the solve kernel, then (NLP stage) the active-set polish of its result: fused into the solve
     // kernel's end (SRB_OPT_POLISH_FUSED, instances up to SRB_FUSED_POLISH_MAX = NZL 24), else srb_polish_kernel (same instance
@@ -866,32 +840,19 @@ extern "C" int srb_ctx_set_qp_init(srb_ctx *c, int mode)
     return SRB_OK;
 }
 
-// the batch has a neighbour table (what srb_agent_sizes.agent_rad / agent_body need)
-static bool has_nbr(const srb_batch *b) { return b && b->struct_size == (int)sizeof(srb_batch) && b->nbr_state && b->n_all > 0; }
-
-static int solve_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv, const srb_sizes *sz,
-                        const srb_agent_sizes *ag, void *stream)
+// (the plain, the _moving and the _sized entry points are this one without a table: one path)
+extern "C" int srb_solve_batch_agents_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
+                                             const srb_sizes *sz, const srb_agent_sizes *ag, void *stream)
 {
     if (int rc0 = srb_check_struct(dev_io, "srb_batch")) return rc0;   // first: it needs no context
-    if (int rc0 = check_moving(mv, dev_io, false)) return rc0;
-    if (int rc0 = srb_check_sizes(sz)) return rc0;
-    if (int rc0 = srb_check_agent_sizes(ag, has_nbr(dev_io))) return rc0;
+    if (int rc0 = check_tables(mv, sz, ag, dev_io, false)) return rc0;
     if (!c || !dev_io) return fail(SRB_ERR_ARG, "null argument");
     hipStream_t s = (hipStream_t)stream;          // NULL: the HIP null stream (ordered with blocking streams)
     HIPCHK(hipSetDevice(c->device));
     int rc = c->order.order_after_last(s);
-    if (!rc) rc = launch(c, n_agents, dev_io, s, c->p.use_nlp, mv ? mv->obs_vel : nullptr, mv ? mv->horizon_selection : 0,
-                         sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0, ag ? ag->agent_rad : nullptr,
-                         ag ? ag->agent_pad : nullptr, ag ? ag->clearance_selection : 0);
+    if (!rc) rc = launch(c, n_agents, dev_io, s, c->p.use_nlp, srb_tables(mv, sz, ag));
     if (!rc && n_agents > 0) rc = c->order.mark_done(s);
     return rc;
-}
-
-// (the plain, the _moving and the _sized entry points are the _agents ones without a table: one path)
-extern "C" int srb_solve_batch_agents_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
-                                             const srb_sizes *sz, const srb_agent_sizes *ag, void *stream)
-{
-    return solve_device(c, n_agents, dev_io, mv, sz, ag, stream);
 }
 
 extern "C" int srb_solve_batch_sized_device(srb_ctx *c, int n_agents, const srb_batch *dev_io, const srb_moving *mv,
@@ -911,103 +872,65 @@ extern "C" int srb_solve_batch_moving_device(srb_ctx *c, int n_agents, const srb
     return srb_solve_batch_sized_device(c, n_agents, dev_io, mv, nullptr, stream);
 }
 
-// One or both tables of the selection into dev_io->sel (required; [A][Ko + Kn], the layout the solve reads):
+// One or both tables of the selection into d->sel (required; [A][Ko + Kn], the layout the solve reads):
 // tables bit 0 the static obstacles (its columns 0 .. Ko - 1), bit 1 the neighbour snapshot (Ko .. Ko + Kn - 1).
 // With SRB_OPT_SELECTION = 0 the solve then uses sel as it is, so a caller can select the static obstacles
 // while the neighbour all-gather is in flight and the neighbours after it (bench.py).
-extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, int tables, void *stream)
+// A flag of mv, sz or ag chooses the launcher of its side, as in the solve's own selection (select_obs, select_nbr:
+// srb_moving.horizon_selection, srb_sizes.clearance_selection for tables & 1, srb_agent_sizes.clearance_selection for
+// tables & 2); an entry point whose struct or flag is absent is the one below it, since the snapshot selection reads
+// no table.
+extern "C" int srb_select_agents_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv,
+                                        const srb_sizes *sz, const srb_agent_sizes *ag, int tables, void *stream)
 {
     if (int rc0 = srb_check_struct(d, "srb_batch")) return rc0;
+    if (int rc0 = check_tables(mv, sz, ag, d, false)) return rc0;
     if (!c || !d) return fail(SRB_ERR_ARG, "null argument");
     if (tables < 1 || tables > 3) return fail(SRB_ERR_ARG, "tables: 1 (static obstacles), 2 (neighbours) or 3 (both)");
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (!d->x0 || !d->sel) return fail(SRB_ERR_ARG, "missing buffer (x0, sel)");
     if (n_agents == 0) return SRB_OK;
-    const srb_params *p = &c->p;
-    int Ko = p->K_obs, Kn = p->K_nbr;                     // clamped exactly as the solve does
+    int Ko = c->p.K_obs, Kn = c->p.K_nbr;                 // clamped exactly as the solve does
     clamp_K(c, d->n_obs, d->nbr_state != nullptr, d->n_all, &Ko, &Kn);
     if (int rc0 = check_scenes(c, n_agents, d->n_obs, d->nbr_state != nullptr, d->n_all, d->agent_offset)) return rc0;
-    if ((tables & 1) && Ko > 0 && !d->obstacles) return fail(SRB_ERR_ARG, "obstacles missing");
+    SrbSelect q = {};
+    q.n_agents = n_agents; q.x0 = d->x0; q.agent_offset = d->agent_offset;
+    q.obstacles = d->obstacles; q.n_obs = Ko > 0 ? d->n_obs : 0; q.obstacles_version = d->obstacles_version;
+    q.nbr_state = d->nbr_state; q.n_all = Kn > 0 ? d->n_all : 0;
+    q.K_obs = Ko; q.K_nbr = Kn; q.sel = d->sel; q.s = (hipStream_t)stream;
+    q.N = c->p.N; q.Ts = c->p.Ts;
+    q.nbr_plan = (c->plan_selection && (tables & 2)) ? d->nbr_plan : nullptr;
+    q.t = srb_tables(mv, sz, ag);
+    // only the flags of the sides that this call selects count
+    if (!(tables & 1)) q.t.obs_horizon = q.t.obs_clear = 0;
+    if (!(tables & 2)) q.t.nbr_clear = 0;
+    const bool obs_flag = q.t.obs_horizon || q.t.obs_clear, nbr_flag = q.t.nbr_clear != 0;
+    // The refusals of the two sides, in the order they have always had: the neighbour side's first where its flag
+    // is set; and a call for the static columns alone under their flag never looked at the plan members.
+    const bool no_obstacles = (tables & 1) && Ko > 0 && !d->obstacles;
+    if (no_obstacles && !nbr_flag) return fail(SRB_ERR_ARG, "obstacles missing");
     if ((tables & 2) && Kn > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
         return fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
-    if (int rc0 = check_plans(c, n_agents, d, (tables & 2) != 0)) return rc0;
-    const double *nbr_plan = (c->plan_selection && (tables & 2)) ? d->nbr_plan : nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    const int ko = (tables & 1) ? Ko : 0, kn = (tables & 2) ? Kn : 0;
-    return c->order.run(c->device, s, [&] {
-        if (ko + kn == 0) return (int)SRB_OK;
-        return launch_select(c, n_agents, d->x0, d->obstacles, ko ? d->n_obs : 0, d->nbr_state, kn ? d->n_all : 0,
-                             d->agent_offset, ko, kn, d->obstacles_version, d->sel + (ko ? 0 : Ko), s, Ko + Kn, nbr_plan, p->N);
+    if ((tables & 2) || !obs_flag)
+        if (int rc0 = check_plans(c, n_agents, d, (tables & 2) != 0)) return rc0;
+    if (no_obstacles) return fail(SRB_ERR_ARG, "obstacles missing");
+    // Without a flag one launch serves both sides; with one, a launch per side (the flagged side last, the neighbour
+    // side's flag before the static side's)
+    return c->order.run(c->device, q.s, [&] {
+        int rc = SRB_OK;
+        if (nbr_flag) {
+            if (tables & 1) rc = select_obs(c, q);
+            return rc ? rc : select_nbr(c, q);
+        }
+        if (obs_flag) {
+            if (tables & 2) rc = select_nbr(c, q);
+            return rc ? rc : select_obs(c, q);
+        }
+        return tables == 1 ? select_obs(c, q) : tables == 2 ? select_nbr(c, q) : Ko + Kn > 0 ? launch_select(c, q) : rc;
     });
 }
 
-// srb_select_device with the static columns by closest predicted approach (srb_moving.horizon_selection = 1) or by
-// clearance to the level set (srb_sizes.clearance_selection = 1, over the horizon with both); any other srb_moving
-// and srb_sizes is srb_select_device itself (the snapshot selection reads neither the velocities nor the levels).
-static int select_sized(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv, const srb_sizes *sz,
-                        int tables, void *stream);
-
-// With srb_agent_sizes.clearance_selection = 1, tables & 2 is the neighbour clearance selection (over the horizon
-// with SRB_OPT_PLAN_SELECTION = 1 and a plan table); the static columns as the _sized call selects them.
-extern "C" int srb_select_agents_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv,
-                                        const srb_sizes *sz, const srb_agent_sizes *ag, int tables, void *stream)
-{
-    if (int rc0 = srb_check_struct(d, "srb_batch")) return rc0;
-    if (int rc0 = check_moving(mv, d, false)) return rc0;
-    if (int rc0 = srb_check_sizes(sz)) return rc0;
-    if (int rc0 = srb_check_agent_sizes(ag, has_nbr(d))) return rc0;
-    const bool nclear = ag && ag->agent_rad && ag->clearance_selection;
-    if (!nclear || !(tables & 2) || tables < 1 || tables > 3 || !c || !d)
-        return select_sized(c, n_agents, d, mv, sz, tables, stream);
-    if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
-    if (!d->x0 || !d->sel) return fail(SRB_ERR_ARG, "missing buffer (x0, sel)");
-    if (n_agents == 0) return SRB_OK;
-    int Ko = c->p.K_obs, Kn = c->p.K_nbr;                 // clamped exactly as the solve does
-    clamp_K(c, d->n_obs, d->nbr_state != nullptr, d->n_all, &Ko, &Kn);
-    if (int rc0 = check_scenes(c, n_agents, d->n_obs, d->nbr_state != nullptr, d->n_all, d->agent_offset)) return rc0;
-    if (Kn > 0 && (d->agent_offset < 0 || d->agent_offset + n_agents > d->n_all))
-        return fail(SRB_ERR_ARG, "agent_offset out of range of the neighbour table");
-    if (int rc0 = check_plans(c, n_agents, d, true)) return rc0;
-    if (tables & 1)                                       // the static columns: the pass of the _sized call
-        if (int rc0 = select_sized(c, n_agents, d, mv, sz, 1, stream)) return rc0;
-    hipStream_t s = (hipStream_t)stream;
-    return c->order.run(c->device, s, [&] {
-        if (Kn == 0) return (int)SRB_OK;
-        return launch_nbr_clear(c, n_agents, d->x0, d->nbr_state, c->plan_selection ? d->nbr_plan : nullptr, ag->agent_rad,
-                                d->n_all, d->agent_offset, Kn, d->sel + Ko, Ko + Kn, s, c->p.N);
-    });
-}
-
-static int select_sized(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv, const srb_sizes *sz,
-                        int tables, void *stream)
-{
-    if (int rc0 = srb_check_struct(d, "srb_batch")) return rc0;
-    if (int rc0 = check_moving(mv, d, false)) return rc0;
-    if (int rc0 = srb_check_sizes(sz)) return rc0;
-    const bool horizon = mv && mv->obs_vel && mv->horizon_selection, clear = sz && sz->obs_eps && sz->clearance_selection;
-    if ((!horizon && !clear) || !(tables & 1) || tables < 1 || tables > 3 || !c || !d)
-        return srb_select_device(c, n_agents, d, tables, stream);
-    if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
-    if (!d->x0 || !d->sel) return fail(SRB_ERR_ARG, "missing buffer (x0, sel)");
-    if (n_agents == 0) return SRB_OK;
-    int Ko = c->p.K_obs, Kn = c->p.K_nbr;                 // clamped exactly as the solve does
-    clamp_K(c, d->n_obs, d->nbr_state != nullptr, d->n_all, &Ko, &Kn);
-    if (int rc0 = check_scenes(c, n_agents, d->n_obs, d->nbr_state != nullptr, d->n_all, d->agent_offset)) return rc0;
-    if (Ko > 0 && !d->obstacles) return fail(SRB_ERR_ARG, "obstacles missing");
-    if (tables & 2)                                       // the neighbour columns: the pass of srb_select_device
-        if (int rc0 = srb_select_device(c, n_agents, d, 2, stream)) return rc0;
-    hipStream_t s = (hipStream_t)stream;
-    return c->order.run(c->device, s, [&] {
-        if (Ko == 0) return (int)SRB_OK;
-        if (clear)
-            return launch_obs_clear(c, n_agents, d->x0, d->obstacles, horizon ? mv->obs_vel : nullptr, sz->obs_eps, d->n_obs,
-                                    d->agent_offset, Ko, d->sel, Ko + Kn, s, c->p.N, c->p.Ts);
-        return launch_obs_horizon(c, n_agents, d->x0, d->obstacles, mv->obs_vel, d->n_obs, d->agent_offset, Ko, d->sel,
-                                  Ko + Kn, s, c->p.N, c->p.Ts);
-    });
-}
-
-// (the _sized and the _moving entry points are the _agents one without a table: one path)
+// (the _sized, the _moving and the plain entry points are the _agents one without a table: one path)
 extern "C" int srb_select_sized_device(srb_ctx *c, int n_agents, const srb_batch *d, const srb_moving *mv,
                                        const srb_sizes *sz, int tables, void *stream)
 {
@@ -1018,6 +941,11 @@ extern "C" int srb_select_moving_device(srb_ctx *c, int n_agents, const srb_batc
                                         void *stream)
 {
     return srb_select_sized_device(c, n_agents, d, mv, nullptr, tables, stream);
+}
+
+extern "C" int srb_select_device(srb_ctx *c, int n_agents, const srb_batch *d, int tables, void *stream)
+{
+    return srb_select_sized_device(c, n_agents, d, nullptr, nullptr, tables, stream);
 }
 
 extern "C" int srb_obstacles_advance_device(srb_ctx *c, int n_obs, double *obstacles, const double *obs_vel, void *stream)
@@ -1111,12 +1039,13 @@ static int launch_advance(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
     return SRB_OK;
 }
 
-// radius: srb_sizes.obs_radius (null: the centre distances and the 0.5 m fail test, the kernels as ever);
-// body / collide: srb_agent_sizes.agent_body and collide_cycle (body null: d_agent by centres, the kernels as ever;
-// else the kernels of srb_agents.hip, which take radius null or not)
-static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s,
-                          const double *radius = nullptr, const double *body = nullptr, int *collide = nullptr)
+// t.obs_radius (srb_sizes; null: the centre distances and the 0.5 m fail test, the kernels as ever); t.agent_body and
+// t.collide_cycle (srb_agent_sizes; body null: d_agent by centres, the kernels as ever; else the kernels of
+// srb_agents.hip, which take the radius null or not)
+static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s, const SrbTables &t)
 {
+    const double *radius = t.obs_radius, *body = t.agent_body;
+    int *collide = t.collide_cycle;
     if (!d->state) return fail(SRB_ERR_ARG, "srb_sim: missing buffer (state)");
     if (d->n_obs < 0 || d->n_all < 0 || (d->n_obs > 0 && !d->obstacles) || (d->n_all > 0 && !d->nbr_state))
         return fail(SRB_ERR_ARG, "srb_sim: obstacles / nbr_state missing for n_obs / n_all rows");
@@ -1169,14 +1098,14 @@ static int launch_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle,
     return SRB_OK;
 }
 
-int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s, const double *radius,
-                             const double *agent_body, int *collide_cycle)
+int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s, const SrbTables &t)
 {
-    return launch_metrics(c, n_agents, d, cycle, s, radius, agent_body, collide_cycle);
+    return launch_metrics(c, n_agents, d, cycle, s, t);
 }
 
-static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream, bool advance,
-                    const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr, const srb_plant *pl = nullptr)
+template <bool advance>
+static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream, const srb_sizes *sz,
+                    const srb_agent_sizes *ag, const srb_plant *pl)
 {
     if (int rc = check_sim(d, cycle, advance)) return rc;
     if (int rc = check_plant(pl, d->x != nullptr)) return rc;
@@ -1189,26 +1118,25 @@ static int sim_call(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void 
     hipStream_t s = (hipStream_t)stream;
     return c->order.run(c->device, s, [&] {
         return advance ? launch_advance(c, n_agents, d, cycle, s, pl)
-                       : launch_metrics(c, n_agents, d, cycle, s, sz ? sz->obs_radius : nullptr,
-                                        ag ? ag->agent_body : nullptr, ag ? ag->collide_cycle : nullptr);
+                       : launch_metrics(c, n_agents, d, cycle, s, srb_tables(nullptr, sz, ag));
     });
-}
-
-extern "C" int srb_sim_advance_device(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream)
-{
-    return sim_call(c, n_agents, d, cycle, stream, true);
 }
 
 extern "C" int srb_sim_advance_plant_device(srb_ctx *c, int n_agents, const srb_sim *d, const srb_plant *pl, int cycle,
                                             void *stream)
 {
-    return sim_call(c, n_agents, d, cycle, stream, true, nullptr, nullptr, pl);
+    return sim_call<true>(c, n_agents, d, cycle, stream, nullptr, nullptr, pl);
+}
+
+extern "C" int srb_sim_advance_device(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, void *stream)
+{
+    return srb_sim_advance_plant_device(c, n_agents, d, nullptr, cycle, stream);
 }
 
 extern "C" int srb_sim_metrics_agents_device(srb_ctx *c, int n_agents, const srb_sim *d, const srb_sizes *sz,
                                              const srb_agent_sizes *ag, int cycle, void *stream)
 {
-    return sim_call(c, n_agents, d, cycle, stream, false, sz, ag);
+    return sim_call<false>(c, n_agents, d, cycle, stream, sz, ag, nullptr);
 }
 
 extern "C" int srb_sim_metrics_sized_device(srb_ctx *c, int n_agents, const srb_sim *d, const srb_sizes *sz, int cycle,
@@ -1286,14 +1214,14 @@ extern "C" int srb_link_update_device(srb_ctx *c, int n_all, const srb_link *ln,
     return srb_link_update_lanes_device(c, n_all, ln, last_state, plan_table, cycle, c_first, SRB_LINK_LANES, stream);
 }
 
-static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d, const srb_moving *mv,
-                   const srb_sizes *sz, const srb_agent_sizes *ag, const srb_plant *pl, const srb_link *ln, int cycles,
-                   void *stream)
+// The driver.  The tables of srb_sizes, srb_agent_sizes, srb_plant and srb_link do not change over a rollout: the same
+// pointers serve every cycle.  (The entry points below are this one without a struct: one path.)
+extern "C" int srb_rollout_link_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
+                                       const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
+                                       const srb_plant *pl, const srb_link *ln, int cycles, void *stream)
 {
     if (int rc0 = srb_check_struct(b, "srb_batch")) return rc0;
-    if (int rc0 = check_moving(mv, b, true)) return rc0;
-    if (int rc0 = srb_check_sizes(sz)) return rc0;
-    if (int rc0 = srb_check_agent_sizes(ag, true)) return rc0;    // (the driver's neighbour table is the team itself)
+    if (int rc0 = check_tables(mv, sz, ag, b, true)) return rc0;
     if (int rc0 = check_plant(pl, true)) return rc0;              // (batch.x missing is reported below, as ever)
     if (!plant_on(pl)) pl = nullptr;
     // (the layout and null checks of check_sim only: the driver's first cycle is c_first itself)
@@ -1337,31 +1265,20 @@ static int rollout(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *
     if (rc) return rc;
     // moving obstacles: the table advances one cycle between the agents' advance and the metrics, from the second
     // cycle on, so d_obs / fail_cycle and the solve see the agents and the obstacles at matching times
-    const double *vel = (mv && b->n_obs > 0) ? mv->obs_vel : nullptr;
+    SrbTables t = srb_tables(mv, sz, ag);
+    if (b->n_obs <= 0) { t.obs_vel = nullptr; t.normalise(); }   // (no rows: nothing moves)
     for (int i = 0; i <= cycles && !rc; i++) {
         const int cyc = d->c_first + i;
         rc = launch_advance(c, n_agents, &sim, cyc, s, pl);
         if (rc || i == cycles) break;
-        if (i > 0 && vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, vel, s);
-        if (!rc) rc = launch_metrics(c, n_agents, &sim, cyc, s, sz ? sz->obs_radius : nullptr,
-                                     ag ? ag->agent_body : nullptr, ag ? ag->collide_cycle : nullptr);
+        if (i > 0 && t.obs_vel) rc = srb_launch_obstacles_advance(b->n_obs, c->p.Ts, mv->obstacles, t.obs_vel, s);
+        if (!rc) rc = launch_metrics(c, n_agents, &sim, cyc, s, t);
         if (!rc && ln) rc = launch_link(c, n_agents, ln, d->last_state, d->plan_table, cyc, d->c_first, s);
         if (i > 0 && d->plan_table) bat.nbr_plan = ln ? ln->seen_plan : d->plan_table;
-        if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp, vel, mv ? mv->horizon_selection : 0,
-                             sz ? sz->obs_eps : nullptr, sz ? sz->clearance_selection : 0, ag ? ag->agent_rad : nullptr,
-                             ag ? ag->agent_pad : nullptr, ag ? ag->clearance_selection : 0);
+        if (!rc) rc = launch(c, n_agents, &bat, s, c->p.use_nlp, t);
     }
     const int rc_mark = c->order.mark_done(s);            // also after a refusal inside the loop: earlier launches run
     return rc ? rc : rc_mark;
-}
-
-// the tables of srb_sizes, srb_agent_sizes, srb_plant and srb_link do not change over a rollout: the same pointers
-// serve every cycle
-extern "C" int srb_rollout_link_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
-                                       const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag,
-                                       const srb_plant *pl, const srb_link *ln, int cycles, void *stream)
-{
-    return rollout(c, n_agents, b, d, mv, sz, ag, pl, ln, cycles, stream);
 }
 
 extern "C" int srb_rollout_plant_device(srb_ctx *c, int n_agents, const srb_batch *b, const srb_sim *d,
@@ -1496,9 +1413,7 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp,
                       const srb_sizes *sz = nullptr, const srb_agent_sizes *ag = nullptr)
 {
     if (int rc0 = srb_check_struct(h, "srb_batch")) return rc0;   // first: it needs no context
-    if (int rc0 = check_moving(mv, h, false)) return rc0;
-    if (int rc0 = srb_check_sizes(sz)) return rc0;
-    if (int rc0 = srb_check_agent_sizes(ag, has_nbr(h))) return rc0;
+    if (int rc0 = check_tables(mv, sz, ag, h, false)) return rc0;
     if (!c || !h) return fail(SRB_ERR_ARG, "null argument");
     if (n_agents < 0 || n_agents > c->max_agents) return fail(SRB_ERR_ARG, "n_agents exceeds max_agents");
     if (n_agents == 0) return SRB_OK;
@@ -1527,15 +1442,13 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp,
     }
     d.obstacles = nullptr; d.nbr_state = nullptr;
     if (h->n_obs > 0 && h->obstacles) {
-        const size_t bytes = (size_t)h->n_obs * 2 * sizeof(double);
-        if (int rc0 = srb_stage_reserve(c->order, c->obstacles, c->cap_obs, bytes)) return rc0;
-        HIPCHK(hipMemcpyAsync(c->obstacles, h->obstacles, bytes, hipMemcpyHostToDevice, s));
+        if (int rc0 = srb_stage_copy(c->order, c->obstacles, c->cap_obs, h->obstacles, (size_t)h->n_obs * 2 * sizeof(double), s))
+            return rc0;
         d.obstacles = c->obstacles;
     }
     if (h->n_all > 0 && h->nbr_state) {
-        const size_t bytes = (size_t)h->n_all * 4 * sizeof(double);
-        if (int rc0 = srb_stage_reserve(c->order, c->nbr, c->cap_nbr, bytes)) return rc0;
-        HIPCHK(hipMemcpyAsync(c->nbr, h->nbr_state, bytes, hipMemcpyHostToDevice, s));
+        if (int rc0 = srb_stage_copy(c->order, c->nbr, c->cap_nbr, h->nbr_state, (size_t)h->n_all * 4 * sizeof(double), s))
+            return rc0;
         d.nbr_state = c->nbr;
     }
     // the plan members: the table staged like nbr_state (NLP stage only), the plans like x
@@ -1543,49 +1456,45 @@ static int solve_host(srb_ctx *c, int n_agents, const srb_batch *h, int use_nlp,
     if (use_nlp)                           // the overlap rule holds for the caller's own (host) buffers
         if (int rc0 = check_plans(c, n_agents, h, false)) return rc0;
     if (use_nlp && h->nbr_plan && d.nbr_state) {
-        const size_t bytes = (size_t)h->n_all * 2 * N * sizeof(double);
-        if (int rc0 = srb_stage_reserve(c->order, c->nbr_plan, c->cap_plan, bytes)) return rc0;
-        HIPCHK(hipMemcpyAsync(c->nbr_plan, h->nbr_plan, bytes, hipMemcpyHostToDevice, s));
+        if (int rc0 = srb_stage_copy(c->order, c->nbr_plan, c->cap_plan, h->nbr_plan, (size_t)h->n_all * 2 * N * sizeof(double), s))
+            return rc0;
         d.nbr_plan = c->nbr_plan;
     }
     d.plan = h->plan ? c->plan : nullptr;
-    // the velocity table staged like the obstacle table it belongs to (srb_solve_batch_moving)
-    const double *vel = nullptr;
-    if (use_nlp && mv && mv->obs_vel && d.obstacles) {
-        const size_t bytes = (size_t)h->n_obs * 2 * sizeof(double);
-        if (int rc0 = srb_stage_reserve(c->order, c->obs_vel, c->cap_vel, bytes)) return rc0;
-        HIPCHK(hipMemcpyAsync(c->obs_vel, mv->obs_vel, bytes, hipMemcpyHostToDevice, s));
-        vel = c->obs_vel;
+    // The tables: ht the caller's (host), t their staged copies.  The velocity and the level table are staged like
+    // the obstacle table they belong to, the agent tables with n_all rows each.  All four only with the NLP stage:
+    // srb_solve_qp comes this way and reads none.  (solve_host12 leaves that test out for the first two; there the
+    // QP-only solve selects no rows, launch12 then hands neither to a kernel, and nothing observable depends on it.)
+    const SrbTables ht = srb_tables(mv, sz, ag);
+    SrbTables t = {};
+    t.obs_horizon = ht.obs_horizon; t.obs_clear = ht.obs_clear; t.nbr_clear = ht.nbr_clear;
+    if (use_nlp && ht.obs_vel && d.obstacles) {
+        if (int rc0 = srb_stage_copy(c->order, c->obs_vel, c->cap_vel, ht.obs_vel, (size_t)h->n_obs * 2 * sizeof(double), s))
+            return rc0;
+        t.obs_vel = c->obs_vel;
     }
-    // the level table likewise (srb_solve_batch_sized)
-    const double *eps = nullptr;
-    if (use_nlp && sz && sz->obs_eps && d.obstacles) {
-        const size_t bytes = (size_t)h->n_obs * sizeof(double);
-        if (int rc0 = srb_stage_reserve(c->order, c->obs_eps, c->cap_eps, bytes)) return rc0;
-        HIPCHK(hipMemcpyAsync(c->obs_eps, sz->obs_eps, bytes, hipMemcpyHostToDevice, s));
-        eps = c->obs_eps;
+    if (use_nlp && ht.obs_eps && d.obstacles) {
+        if (int rc0 = srb_stage_copy(c->order, c->obs_eps, c->cap_eps, ht.obs_eps, (size_t)h->n_obs * sizeof(double), s))
+            return rc0;
+        t.obs_eps = c->obs_eps;
     }
-    // the agent tables likewise, n_all rows each (srb_solve_batch_agents); the QP-only solve reads neither
-    const double *rad = nullptr, *pad = nullptr;
-    if (use_nlp && ag && (ag->agent_rad || ag->agent_pad)) {
+    if (use_nlp && (ht.agent_rad || ht.agent_pad)) {
         if (h->agent_offset < 0 || h->agent_offset + n_agents > h->n_all)    // launch()'s refusal, before the copies
             return fail(SRB_ERR_ARG, "srb_agent_sizes: agent_offset + n_agents exceeds n_all (the agent tables' rows)");
         const size_t bytes = (size_t)h->n_all * sizeof(double);
-        if (ag->agent_rad) {
-            if (int rc0 = srb_stage_reserve(c->order, c->agent_rad, c->cap_rad, bytes)) return rc0;
-            HIPCHK(hipMemcpyAsync(c->agent_rad, ag->agent_rad, bytes, hipMemcpyHostToDevice, s));
-            rad = c->agent_rad;
+        if (ht.agent_rad) {
+            if (int rc0 = srb_stage_copy(c->order, c->agent_rad, c->cap_rad, ht.agent_rad, bytes, s)) return rc0;
+            t.agent_rad = c->agent_rad;
         }
-        if (ag->agent_pad) {
-            if (int rc0 = srb_stage_reserve(c->order, c->agent_pad, c->cap_pad, bytes)) return rc0;
-            HIPCHK(hipMemcpyAsync(c->agent_pad, ag->agent_pad, bytes, hipMemcpyHostToDevice, s));
-            pad = c->agent_pad;
+        if (ht.agent_pad) {
+            if (int rc0 = srb_stage_copy(c->order, c->agent_pad, c->cap_pad, ht.agent_pad, bytes, s)) return rc0;
+            t.agent_pad = c->agent_pad;
         }
     }
+    t.normalise();                         // (a table that was not staged takes its flag with it)
     d.sel = nullptr;                       // the context's scratch; copied out below when asked for
     d.obstacles_version = 0;               // staged copy: rebuilt every call
-    int rc = launch(c, n_agents, &d, s, use_nlp, vel, vel && mv ? mv->horizon_selection : 0, eps,
-                    eps && sz ? sz->clearance_selection : 0, rad, pad, rad && ag ? ag->clearance_selection : 0);
+    int rc = launch(c, n_agents, &d, s, use_nlp, t);
     if (!rc) rc = c->order.mark_done(s);
     if (rc) return rc;
     if (h->sel && use_nlp) {

@@ -1,39 +1,113 @@
 // Host plumbing shared by the three C-ABI files (srb_capi.cpp, srb12_capi.cpp, srb_ll_capi.cpp): the error
 // channel, the HIP-error macros, the submission-order chaining of a context, and what the LIP and the SRB-12 mode
-// check and launch alike (the struct-size refusal, the range-overlap test, the srb_moving, srb_sizes and srb_agent_sizes checks,
-// the growth of a staging buffer, the obstacle-advance launch).  Internal, host only.
+// check and launch alike (the struct-size refusal, the range-overlap test, the srb_moving, srb_sizes and srb_agent_sizes
+// checks, the two values that carry the optional tables and a selection past those checks -- SrbTables, SrbSelect --
+// the staging of a host table, the obstacle-advance launch).  Internal, host only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
 #include "srbnmpc.h"
 #include "srb_kernel_decls.h"
 
+// What the launches need of the three optional structs (srb_moving, srb_sizes, srb_agent_sizes; each may be null),
+// resolved once by srb_tables() below.  A new table is a new member here, not a new argument of every launcher.
+struct SrbTables {
+    const double *obs_vel;         // srb_moving.obs_vel [n_obs][2] (null: static obstacles, every launch as without)
+    int obs_horizon;               // ... horizon_selection: the static columns by closest predicted approach
+    const double *obs_eps;         // srb_sizes.obs_eps [n_obs] (null: eps_obs for every row)
+    int obs_clear;                 // ... clearance_selection: the static columns by clearance to the level set
+    const double *agent_rad, *agent_pad;   // srb_agent_sizes [n_all] each (null: eps_nbr and the levels as they are)
+    int nbr_clear;                 // ... clearance_selection: the neighbour columns by clearance
+    // the drivers' metrics: srb_sizes.obs_radius (null: centre distances and the 0.5 m fail test), srb_agent_sizes
+    // .agent_body and its collide_cycle (body null: d_agent by centres)
+    const double *obs_radius, *agent_body;
+    int *collide_cycle;
+    // a flag whose table is null is 0 (the selection ignores such a flag anyway: srb_internal_select)
+    void normalise()
+    {
+        if (!obs_vel) obs_horizon = 0;
+        if (!obs_eps) obs_clear = 0;
+        if (!agent_rad) nbr_clear = 0;
+    }
+    // What a solve kernel is handed: vel, eps and pad are read for the static columns of sel only, rad for the
+    // neighbour columns only (obs_rows, nbr_rows: the NLP stage has such columns after the clamp)
+    SrbTables gated(bool obs_rows, bool nbr_rows) const
+    {
+        SrbTables g = *this;
+        if (!obs_rows) g.obs_vel = g.obs_eps = g.agent_pad = nullptr;
+        if (!nbr_rows) g.agent_rad = nullptr;
+        g.normalise();
+        return g;
+    }
+    bool any_solve_table() const { return obs_vel || obs_eps || agent_rad || agent_pad; }
+};
+
+static inline SrbTables srb_tables(const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag)
+{
+    SrbTables t = {};
+    if (mv) { t.obs_vel = mv->obs_vel; t.obs_horizon = mv->horizon_selection; }
+    if (sz) { t.obs_eps = sz->obs_eps; t.obs_clear = sz->clearance_selection; t.obs_radius = sz->obs_radius; }
+    if (ag) {
+        t.agent_rad = ag->agent_rad; t.agent_pad = ag->agent_pad; t.nbr_clear = ag->clearance_selection;
+        t.agent_body = ag->agent_body; t.collide_cycle = ag->collide_cycle;
+    }
+    t.normalise();
+    return t;
+}
+
+// One selection: what srb_internal_select and the launchers under it share.  K_obs, K_nbr are already clamped to
+// the tables; x0 rows are [x, ., y, .] (stride 4).  Row a of sel holds the static columns 0 .. K_obs - 1, then the
+// neighbour columns.  Callers start from SrbSelect{} and assign the members by name.
+struct SrbSelect {
+    int n_agents;
+    const double *x0;
+    int agent_offset;
+    const double *obstacles;       // [n_obs][2]; obstacles_version != 0: a static table that keeps its grid
+    int n_obs, obstacles_version;
+    const double *nbr_state;       // [n_all][4]
+    int n_all;
+    int K_obs, K_nbr;
+    int *sel;
+    int sel_stride;                // 0: K_obs + K_nbr
+    hipStream_t s;
+    int N;                         // the horizon's grid (N, Ts) of the plan, horizon and clearance selections
+    double Ts;
+    const double *nbr_plan;        // [n_all][N][2] != null: the neighbour columns by closest predicted approach
+    const double *own_plan;        // [n_agents][N][2] with nbr_plan: the agent's own plan there, not row g of the table
+    SrbTables t;
+    int stride() const { return sel_stride ? sel_stride : K_obs + K_nbr; }
+    // the passes over one side alone, into the same rows of sel
+    SrbSelect obs_only() const
+    {
+        SrbSelect q = *this;
+        q.sel_stride = stride();
+        q.nbr_state = nullptr; q.n_all = 0; q.K_nbr = 0;
+        return q;
+    }
+    SrbSelect nbr_only() const     // (sel then points at the neighbour columns; no grid of the static table is kept)
+    {
+        SrbSelect q = *this;
+        q.sel_stride = stride(); q.sel = sel + K_obs;
+        q.n_obs = 0; q.obstacles_version = 0; q.K_obs = 0;
+        return q;
+    }
+};
+
 // defined in srb_capi.cpp: the thread's last-error message (srb_last_error), and the LIP-mode context's selection
-// launch and ordering mark, which the SRB-12 mode reuses (nbr_plan [n_all][N][2] != NULL: the neighbour columns by
-// the horizon-aware selection of SRB_OPT_PLAN_SELECTION, whatever that option of the context says; obs_vel
-// [n_obs][2] with obs_horizon != 0: the static columns by srb_moving.horizon_selection over the grid (N, Ts);
-// obs_eps [n_obs] with obs_clear != 0: the static columns by srb_sizes.clearance_selection; agent_rad [n_all] with
-// nbr_clear != 0: the neighbour columns by srb_agent_sizes.clearance_selection, over the horizon with nbr_plan;
-// own_plan [n_agents][N][2] with nbr_plan: the horizon-aware selection reads the agent's own plan there, not in row
-// g of the table)
+// launch (q.t with its flags: the static columns by srb_moving.horizon_selection or srb_sizes.clearance_selection, the
+// neighbour columns by srb_agent_sizes.clearance_selection; q.nbr_plan: the neighbour columns by the horizon-aware
+// selection of SRB_OPT_PLAN_SELECTION, whatever that option of the context says) and ordering mark, which the SRB-12
+// mode reuses
 int srb_internal_fail(int code, const char *msg);
-int srb_internal_select(srb_ctx *c, int n_agents, const double *x0, const double *obstacles, int n_obs,
-                        const double *nbr_state, int n_all, int agent_offset, int K_obs, int K_nbr,
-                        int obstacles_version, int *sel, hipStream_t s, const double *nbr_plan = nullptr, int N = 0,
-                        const double *obs_vel = nullptr, int obs_horizon = 0, double Ts = 0.0,
-                        const double *obs_eps = nullptr, int obs_clear = 0, const double *agent_rad = nullptr,
-                        int nbr_clear = 0, const double *own_plan = nullptr);
+int srb_internal_select(srb_ctx *c, const SrbSelect &q);
 int srb_internal_mark_done(srb_ctx *c, hipStream_t s);
 // ... and its scene partition (srb_ctx_set_scenes): the per-call refusals, the "up to K nearest" clamp, and the
 // metrics launch (srb_sim_metrics_kernel, or with scenes srb_sim_scene_metrics_kernel) on d->state rows
-// [x, xdot, y, ydot] -- launches only, the caller orders the stream.  radius [n_obs] != NULL: srb_sizes.obs_radius, the
-// sized kernels of srb_sizes.hip; agent_body [n_all] != NULL: srb_agent_sizes.agent_body (and its collide_cycle), the
-// kernels of srb_agents.hip
+// [x, xdot, y, ydot] -- launches only, the caller orders the stream.  t.obs_radius: the sized kernels of
+// srb_sizes.hip; t.agent_body (and t.collide_cycle): the kernels of srb_agents.hip
 int srb_internal_check_scenes(const srb_ctx *c, int n_agents, int n_obs, bool has_nbr, int n_all, int agent_offset);
 void srb_internal_clamp_K(const srb_ctx *c, int n_obs, bool has_nbr, int n_all, int *Ko, int *Kn);
-int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s,
-                             const double *radius = nullptr, const double *agent_body = nullptr,
-                             int *collide_cycle = nullptr);
+int srb_internal_sim_metrics(srb_ctx *c, int n_agents, const srb_sim *d, int cycle, hipStream_t s, const SrbTables &t);
 
 // a failed HIP call returns SRB_ERR_HIP with "<expression>: <HIP's message>"; HIPCHK_UNWIND_ first runs `cleanup`
 // (a create function's local CREATE_CHK names its destroy there once).  `text`: the expression stringified by the
@@ -168,6 +242,23 @@ static inline int srb_check_agent_sizes(const srb_agent_sizes *ag, bool has_nbr)
     return SRB_OK;
 }
 
+// the batch has a neighbour table (what srb_agent_sizes.agent_rad / agent_body need)
+template <class Batch> static inline bool srb_has_nbr(const Batch *b)
+{
+    return b && b->struct_size == (int)sizeof(Batch) && b->nbr_state && b->n_all > 0;
+}
+
+// The three checks above in the order every entry point runs them, after its own srb_check_struct(batch).  rollout:
+// the driver's rules (srb_check_moving), and its neighbour table is the team itself.
+template <class Batch>
+static int srb_check_tables(const srb_moving *mv, const srb_sizes *sz, const srb_agent_sizes *ag, const Batch *b,
+                            bool rollout, const char *entry, const char *batch)
+{
+    if (int rc = srb_check_moving(mv, b, rollout, entry, batch)) return rc;
+    if (int rc = srb_check_sizes(sz)) return rc;
+    return srb_check_agent_sizes(ag, rollout || srb_has_nbr(b));
+}
+
 // ---- degraded neighbour link (srb_link; srb_link.hip), both modes.  The struct degrades the link at all (else every
 // entry point is the one it extends and nothing is launched; age_log alone is not written)
 static inline bool srb_link_on(const srb_link *ln) { return ln && (ln->delay || ln->drop || ln->noise_p || ln->noise_v); }
@@ -207,6 +298,16 @@ template <class T> static int srb_stage_reserve(SrbCallOrder &order, T *&buf, si
     void *fresh = nullptr;                 // (a failed hipMalloc is not promised to leave its argument null)
     HIPCHK(hipMalloc(&fresh, bytes));
     buf = (T *)fresh; cap = bytes;
+    return SRB_OK;
+}
+
+// A host table staged into such a buffer on s: reserve, then the copy (after a failure the context is as
+// srb_stage_reserve leaves it)
+template <class T>
+static int srb_stage_copy(SrbCallOrder &order, T *&buf, size_t &cap, const T *host_src, size_t bytes, hipStream_t s)
+{
+    if (int rc = srb_stage_reserve(order, buf, cap, bytes)) return rc;
+    HIPCHK(hipMemcpyAsync(buf, host_src, bytes, hipMemcpyHostToDevice, s));
     return SRB_OK;
 }
 
